@@ -8,9 +8,10 @@ Default workload (BASELINE.json configs[1]): synthetic random pairs, N = M = 204
 i.e. GraphDeformLoss_Neural.deform() x2 without the dumps (reference models/loss.py:1401-1411).
 A "step" is one pass over a resident batch of pairs; inputs are in HBM before the timed region.  The timed form is a
 two-stage pipeline over two alternating resident batches (ops.PairPipeline: the graphs of batch t + 1 are built while
-the feature half of batch t runs; nothing is cached); `single_call` reports the one-call form beside it.
+the feature half of batch t runs; nothing is cached); `single_call` (`--full`) reports the one-call form beside it.
 
   python bench.py [--gpus N --steps K --warmup W --pairs P | --pairs-total T] [--workload pair|train|partial]
+                  [--full] [--dump-outputs DIR]
 
 One process per GPU.  `--gpus N` with N > 1 STARTS the N ranks itself: the parent process — which never
 imports torch and never touches the GPU — spawns N children of this script with RANK / LOCAL_RANK /
@@ -21,9 +22,16 @@ sharded over the ranks with no data-path collective (barrier + MAX-over-ranks ti
   --pairs P        P pairs per GPU per step: per-GPU work fixed, "scaling": "weak" (default, P = 512)
   --pairs-total T  T pairs per step over ALL GPUs (T/N per rank): total work fixed, "scaling": "strong"
 --workload train / partial time the training step of BASELINE configs[2] / configs[3] (train_driver.py's
-timing mode: forward + criterion + backward + all-reduce + Adam), one JSON line in the same format.
+timing mode: forward + criterion + backward + all-reduce + Adam), one JSON line in the same format (`--dump-outputs`: the
+last step's loss terms; `--full` changes nothing there: that line holds only what the timed steps give).
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (the soft-correspondence sweep, pass A
+Prints ONE JSON line (rank 0): `value` (pairs/s over the K timed steps), `ms_per_step`, `median_ms_per_step`, the
+configuration.  A plain run does only that: set up, warm up, time K steps, print.  `--dump-outputs DIR` then also writes
+what the last timed step computed (both directions' warped / verts12 / T12 / losses, float32, DIR/out12_<name>.npy and
+DIR/out21_<name>.npy; a fixed seeded sample of the pairs if they exceed 64 MB); the inputs are seeded, so two builds run
+with the same arguments can be compared output for output.  Everything below is measured with `--full` only.
+
+`--full`: `roofline` is for the dominant kernel (the soft-correspondence sweep, pass A
 of K1), its launch time measured with HIP events on the launch stream inside the timed region; `frac` =
 flops performed on the f16 matrix pipe / its dense peak, `algorithmic_frac_f16` = SURVEY §8d's flops against the
 same peak; `roofline.kernels` = the other kernels of the step, event-timed the same way over 3 extra steps
@@ -51,6 +59,8 @@ N_PTS, M_PTS, DIM, ALPHA = 2048, 2048, 128, 100.0
 PEAK_F16_MFMA_TFLOPS = 2500.0  # dense f16 / bf16 matrix peak (same guide)
 PEAK_HBM_GBS = 8000.0          # HBM3E peak (same guide; 6.3 TB/s achievable)
 CHECK_PAIRS = 4
+DUMP_BYTES = 64 * 1000 * 1000  # --dump-outputs: at most this many bytes in all
+DUMP_SEED = 20261
 TRAFFIC_FILE = "r6_k1_traffic.json"   # PMC passes of this round's dominant kernel (tools/k1_traffic.py)
 
 
@@ -64,8 +74,13 @@ def parse_args(argv=None):
     ap.add_argument("--workload", default="pair", choices=["pair", "train", "partial"],
                     help="pair: configs[1] (default); train: configs[2] training step B=8/GPU N=2048; partial: configs[3] "
                          "training step B=2/GPU 4995 x 2200")
-    ap.add_argument("--cpu-sample", type=int, default=48, help="pairs timed for cpu_baseline (0 = skip; rank 0 at N = 1 only)")
-    ap.add_argument("--no-check", action="store_true", help="skip the oracle check of 4 pairs of the timed batches")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: roofline + per-kernel figures, the one-call and "
+                         "graph-cached forms, the oracle check of the timed batches and the CPU baselines")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
+    ap.add_argument("--cpu-sample", type=int, default=48, help="--full: pairs timed for cpu_baseline (0 = skip; rank 0 at N = 1 only)")
+    ap.add_argument("--no-check", action="store_true", help="--full: skip the oracle check of 4 pairs of the timed batches")
     ap.add_argument("--no-pipeline", action="store_true",
                     help="time the one-call form (dvm_pair_fwd_f32 on ONE resident batch, rounds 1-5) instead of the two-stage "
                          "pipeline over two alternating batches")
@@ -74,9 +89,12 @@ def parse_args(argv=None):
     ap.add_argument("--dist-always", action="store_true", help="initialise the process group at world size 1 too (runs the RCCL "
                     "branch on a 1-GPU box; tests/test_gpu_ddp.py)")
     ap.add_argument("--traffic-bytes", type=float, default=None,
-                    help="per-launch HBM bytes of the dominant kernel from the PMC passes (default: profiles/r6_k1_traffic.json, "
+                    help="--full: per-launch HBM bytes of the dominant kernel from the PMC passes (default: profiles/r6_k1_traffic.json, "
                          "used only if it was taken on this kernel source, for the kernel the timed launches ran, at this --pairs)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def rank_env():
@@ -170,6 +188,36 @@ def checked_pair_ids(P, n, seed=20260):
     """`n` pairs of a batch of P chosen by a seeded draw ("checked on 4 random pairs per run")."""
     import random
     return sorted(random.Random(seed + P).sample(range(P), min(n, P)))
+
+
+def host_outputs(out12, out21):
+    """The arrays one pair step hands its caller, on the host: {"out12_warped": (P, N, 3) float32, ...}.  T12 (int32 indices
+    < N) becomes float32, exact below 2^24."""
+    res = {}
+    for tag, o in (("out12", out12), ("out21", out21)):
+        for k in ("warped", "verts12", "T12", "losses"):
+            t = o[k].detach()
+            if k == "T12":
+                assert int(t.max()) < (1 << 24)
+            res["%s_%s" % (tag, k)] = t.float().cpu().numpy()
+    return res
+
+
+def dump_outputs(path, arrays):
+    """`arrays` (name -> numpy array, pairs along axis 0) to path/<name>.npy; over DUMP_BYTES in all, the same fixed seeded
+    sample of pairs of every array (their indices in path/sampled_pairs.npy)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES:
+        P = next(iter(arrays.values())).shape[0]
+        keep = max(1, int(P * DUMP_BYTES // (total + 8 * P)))   # (+ 8 bytes per kept pair for its index)
+        ids = np.sort(np.random.default_rng(DUMP_SEED).choice(P, keep, replace=False))
+        arrays = {k: a[ids] for k, a in arrays.items()}
+        arrays["sampled_pairs"] = ids.astype(np.float64)
+    for k, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (k, a.dtype)
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def oracle_legs(timed, sample_pairs, check_pairs):
@@ -310,6 +358,75 @@ def kernel_models(P):
     }
 
 
+def full_fields(args, P, pairs_per_step, lib, routes, k1_name, k1_total_ms, k1_launches, alone_ms, alone_n, slots, local_dt, single,
+                pipe_same, dtc, cached_same):
+    """--full: the fields of the result line beyond the headline, from what run_pair measured after its timed region."""
+    traffic, traffic_src = args.traffic_bytes, {"file": None, "why": "--traffic-bytes"}
+    if traffic is None:
+        traffic, traffic_src = load_traffic(P, k1_name)
+    k1_ms = k1_total_ms / max(k1_launches, 1)
+    k1_alone = alone_ms / max(alone_n, 1)
+    flops_launch = P * (2.0 * N_PTS * M_PTS * DIM)   # SURVEY §8d: the distance tile counted once per pair
+    tf = lambda ms_: flops_launch / (ms_ * 1e-3) / 1e12 if ms_ > 0 else 0.0  # noqa: E731
+    # fp16 products of the N x M contraction pass A PERFORMED per direction, from the routes the library reports for the last
+    # timed launch: coarse screen 1 (hh), first forms 3 (hh + hm + mh); None when the launch was mixed or partly swept twice
+    nprod = (1 if routes["coarse"] == routes["entries"] and routes["reswept_lean"] == 0
+             else 3 if routes["coarse"] == 0 else None)
+    perf = (lambda ms_: 2.0 * nprod * tf(ms_)) if nprod else (lambda ms_: None)  # noqa: E731
+    frac16 = lambda x: None if x is None else x / PEAK_F16_MFMA_TFLOPS  # noqa: E731
+    kernels = []
+    for k, (ms_tot, n) in sorted(slots.items()):
+        if n == 0:
+            continue
+        m = kernel_models(P)[k]
+        per_launch = ms_tot / n
+        per_step = ms_tot / 3.0
+        work = m["work"]
+        if m["bound"] == "mfma":
+            ach, peak, unit = work / (per_launch * 1e-3) / 1e12, m["peak"], "TFLOP/s"
+        else:
+            ach, peak, unit = work / (per_launch * 1e-3) / 1e9, PEAK_HBM_GBS, "GB/s"
+        kernels.append({"kernel": lib.dvm_profile_kernel_name(k).decode(), "bound": m["bound"], "achieved": ach, "peak": peak,
+                        "unit": unit, "frac": ach / peak, "launch_ms": per_launch, "launches_per_step": n / 3.0,
+                        "ms_per_step": per_step, "algorithmic_per_launch": work, "note": m["note"]})
+    pmc = load_pmc(P, k1_name)
+    return {
+        # the one-call form (geometry and features of the SAME batch inside one call; rounds 1-5 timed this)
+        "single_call": (None if single is None else
+                        {"value": pairs_per_step * args.steps / single, "unit": "pairs/s", "ms_per_step": single / args.steps * 1e3,
+                         "bit_identical_to_pipelined": bool(pipe_same)}),
+        # the same steps with the per-shape graph cache on (opt-in; NOT `value`: the reference rebuilds the graphs per call)
+        "graph_cached": {"value": pairs_per_step * args.steps / dtc, "unit": "pairs/s", "ms_per_step": dtc / args.steps * 1e3,
+                         "hits": args.steps, "bit_identical_to_uncached": bool(cached_same),
+                         "what": "graphs (FPS nodes, rings, skinning), uniform grids and xyz kNN of both clouds reused from a first "
+                                 "call (dvm_pair_fwd_cached_f32); everything feature-dependent recomputed"},
+        # The dominant kernel runs the N x M contraction on the 16-bit matrix pipe.  ONE denominator: the dense f16 matrix peak.
+        #   achieved / frac      = flops the kernel PERFORMS (`products_per_direction` fp16 products x 2 directions x B*2NMd; the norm
+        #                          instruction not counted) / launch time            -> the pipe's utilisation
+        #   algorithmic_frac_f16 = SURVEY §8d's formulation-independent count (B*2NMd: the distance tile once per pair) / launch time,
+        #                          against the same peak
+        #   mfma_busy, valu_per_mfma, l2_hit_rate, traffic = PMC passes of this kernel (profiles/r6_k1_traffic.json; null unless
+        #                          taken on this kernel source, for this kernel, at this --pairs): why the pipe is not busier
+        "roofline": {"bound": "mfma", "kernel": k1_name + " (K1 pass A: the N x M sweep on the f16 matrix pipe; named by the library "
+                                                         "from what the timed launches ran)",
+                     "routes_last_timed_launch": routes, "products_per_direction": nprod,
+                     "achieved": perf(k1_ms), "peak": PEAK_F16_MFMA_TFLOPS, "unit": "TFLOP/s",
+                     "frac": frac16(perf(k1_ms)), "pipe": "f16 matrix (v_mfma_f32_32x32x16_f16)",
+                     "algorithmic_flops_per_launch": flops_launch, "algorithmic_frac_f16": frac16(tf(k1_ms)),
+                     "traffic": traffic, "traffic_source": traffic_src, "launch_ms": k1_ms, "launches_timed": k1_launches,
+                     "flops_per_launch": (2.0 * nprod * flops_launch) if nprod else None,
+                     "mfma_busy": pmc.get("mfma_busy"), "valu_per_mfma": pmc.get("valu_per_mfma"), "l2_hit_rate": pmc.get("l2_hit_rate"),
+                     "algorithmic_bytes_per_launch": pmc.get("algorithmic_bytes_per_launch"),
+                     "share_of_step": (k1_total_ms * 1e-3) / local_dt if local_dt > 0 else None,
+                     # in the timed region the sweep shares the CUs with the geometry chain of the NEXT batch (FPS / graph / kNN)
+                     # and this batch's pooling on the helper streams, which stretches its launch; alone (one-call form, helper
+                     # streams off, 3 launches after the timed region) it takes `launch_ms` below
+                     "standalone": {"launch_ms": k1_alone, "achieved": perf(k1_alone), "frac": frac16(perf(k1_alone)),
+                                    "algorithmic_frac_f16": frac16(tf(k1_alone))},
+                     "kernels": kernels},
+    }
+
+
 def run_pair(args):
     import torch
     import torch.distributed as dist
@@ -390,7 +507,8 @@ def run_pair(args):
     if dist_on:
         dist.barrier()
     torch.cuda.synchronize()
-    ops.check(lib.dvm_profile_enable(args.steps + 4), "dvm_profile_enable")   # slot 0 (the sweep) only
+    if args.full:
+        ops.check(lib.dvm_profile_enable(args.steps + 4), "dvm_profile_enable")   # slot 0 (the sweep) only
     # per-step durations for the median: one event between steps on the caller's stream (pair_forward joins its helper
     # streams back into it before returning, so consecutive events bracket whole steps)
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
@@ -404,72 +522,76 @@ def run_pair(args):
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    # which pass-A kernel the last timed launch's (direction, pair) entries went to (the probe and the gate decide on the device)
-    routes = (ctypes.c_int * 5)()
-    ops.check(lib.dvm_k1_last_routes(routes), "dvm_k1_last_routes")
-    routes = dict(zip(("full", "lean", "coarse", "reswept_lean", "entries"), list(routes)))
+    # what the last timed step handed back; copied to the host before any later call can rewrite its buffers
+    last = pouts[(tstep - 1) % 2] if pipelined else outs
+    dumped = host_outputs(*last) if (args.dump_outputs and rank == 0) else None
     step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
     median_ms = step_ms[len(step_ms) // 2] if len(step_ms) % 2 else 0.5 * (step_ms[len(step_ms) // 2 - 1] + step_ms[len(step_ms) // 2])
-    k1_total_ms, k1_launches = read_slot(0)
-    k1_name = lib.dvm_profile_kernel_name(0).decode()     # what the timed launches actually ran (the probe / alpha routes pass A)
-    lib.dvm_profile_disable()
-    # the other kernels of the step, bracketed the same way, over 3 extra steps (outside the timed region: 16 more event
-    # records per step)
-    ops.check(lib.dvm_profile_select((1 << 8) - 1), "dvm_profile_select")
-    ops.check(lib.dvm_profile_enable(3 * 16), "dvm_profile_enable")
-    for _ in range(3):
+    if args.full:
+        # which pass-A kernel the last timed launch's (direction, pair) entries went to (the probe and the gate decide on the device)
+        routes = (ctypes.c_int * 5)()
+        ops.check(lib.dvm_k1_last_routes(routes), "dvm_k1_last_routes")
+        routes = dict(zip(("full", "lean", "coarse", "reswept_lean", "entries"), list(routes)))
+        k1_total_ms, k1_launches = read_slot(0)
+        k1_name = lib.dvm_profile_kernel_name(0).decode()     # what the timed launches actually ran (the probe / alpha routes pass A)
+        lib.dvm_profile_disable()
+        # the other kernels of the step, bracketed the same way, over 3 extra steps (outside the timed region: 16 more event
+        # records per step)
+        ops.check(lib.dvm_profile_select((1 << 8) - 1), "dvm_profile_select")
+        ops.check(lib.dvm_profile_enable(3 * 16), "dvm_profile_enable")
+        for _ in range(3):
+            step()
+        torch.cuda.synchronize()
+        slots = {k: read_slot(k) for k in range(1, 8)}
+        lib.dvm_profile_disable()
+        # the sweep kernel alone: the same launches with the helper-stream overlap switched off
+        lib.dvm_pair_set_overlap(0)
         step()
-    torch.cuda.synchronize()
-    slots = {k: read_slot(k) for k in range(1, 8)}
-    lib.dvm_profile_disable()
-    # the sweep kernel alone: the same launches with the helper-stream overlap switched off
-    lib.dvm_pair_set_overlap(0)
-    step()
-    torch.cuda.synchronize()
-    ops.check(lib.dvm_profile_enable(8), "dvm_profile_enable")
-    for _ in range(3):
-        step()
-    torch.cuda.synchronize()
-    alone_ms, alone_n = read_slot(0)
-    lib.dvm_profile_disable()
-    lib.dvm_pair_set_overlap(1)
-    # the one-call form of rounds 1-5 (dvm_pair_fwd_f32 on ONE resident batch: geometry and features of the same batch inside one
-    # call, the geometry chain on the call's helper streams), timed over the same number of steps
-    single = None
-    if pipelined:
+        torch.cuda.synchronize()
+        ops.check(lib.dvm_profile_enable(8), "dvm_profile_enable")
+        for _ in range(3):
+            step()
+        torch.cuda.synchronize()
+        alone_ms, alone_n = read_slot(0)
+        lib.dvm_profile_disable()
+        lib.dvm_pair_set_overlap(1)
+        # the one-call form of rounds 1-5 (dvm_pair_fwd_f32 on ONE resident batch: geometry and features of the same batch inside one
+        # call, the geometry chain on the call's helper streams), timed over the same number of steps
+        single = None
+        if pipelined:
+            for _ in range(max(1, args.warmup)):
+                step()
+            torch.cuda.synchronize()
+            ts0 = time.perf_counter()
+            for _ in range(args.steps):
+                step()
+            torch.cuda.synchronize()
+            single = time.perf_counter() - ts0
+            if dist_on:
+                t = torch.tensor([single], dtype=torch.float64, device=dev)
+                dist.all_reduce(t, op=dist.ReduceOp.MAX)
+                single = float(t.item())
+            pipe_same = all(torch.equal(pouts[0][sd][k], outs[sd][k]) for sd in (0, 1) for k in outs[sd])   # batch 0: both forms, same bits
+        # "graph build reported with and without caching".  The timed region above rebuilds both clouds' deformation graphs
+        # every step, as the reference does (models/loss.py:1325-1337); here the same steps reuse the graphs / grids / xyz kNN of a
+        # first call through the opt-in per-shape cache (dvm_pair_fwd_cached_f32: bit-identical outputs, checked below)
+        gcache = ops.GeometryCache()
+        ref12 = {k: v.clone() for k, v in out12.items()}
+        couts = ops.pair_forward(wl, f1, f2, v1, v2, ALPHA, s1, s2, with_map=True, cache=gcache, key="bench-batch")   # builds
         for _ in range(max(1, args.warmup)):
-            step()
+            couts = ops.pair_forward(wl, f1, f2, v1, v2, ALPHA, s1, s2, with_map=True, out=couts, cache=gcache, key="bench-batch")
         torch.cuda.synchronize()
-        ts0 = time.perf_counter()
+        tc0 = time.perf_counter()
         for _ in range(args.steps):
-            step()
+            couts = ops.pair_forward(wl, f1, f2, v1, v2, ALPHA, s1, s2, with_map=True, out=couts, cache=gcache, key="bench-batch")
         torch.cuda.synchronize()
-        single = time.perf_counter() - ts0
+        dtc = time.perf_counter() - tc0
+        cached_same = all(torch.equal(couts[0][k], ref12[k]) for k in ref12)
         if dist_on:
-            t = torch.tensor([single], dtype=torch.float64, device=dev)
+            t = torch.tensor([dtc], dtype=torch.float64, device=dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            single = float(t.item())
-        pipe_same = all(torch.equal(pouts[0][sd][k], outs[sd][k]) for sd in (0, 1) for k in outs[sd])   # batch 0: both forms, same bits
-    # "graph build reported with and without caching".  The timed region above rebuilds both clouds' deformation graphs
-    # every step, as the reference does (models/loss.py:1325-1337); here the same steps reuse the graphs / grids / xyz kNN of a
-    # first call through the opt-in per-shape cache (dvm_pair_fwd_cached_f32: bit-identical outputs, checked below)
-    gcache = ops.GeometryCache()
-    ref12 = {k: v.clone() for k, v in out12.items()}
-    couts = ops.pair_forward(wl, f1, f2, v1, v2, ALPHA, s1, s2, with_map=True, cache=gcache, key="bench-batch")   # builds
-    for _ in range(max(1, args.warmup)):
-        couts = ops.pair_forward(wl, f1, f2, v1, v2, ALPHA, s1, s2, with_map=True, out=couts, cache=gcache, key="bench-batch")
-    torch.cuda.synchronize()
-    tc0 = time.perf_counter()
-    for _ in range(args.steps):
-        couts = ops.pair_forward(wl, f1, f2, v1, v2, ALPHA, s1, s2, with_map=True, out=couts, cache=gcache, key="bench-batch")
-    torch.cuda.synchronize()
-    dtc = time.perf_counter() - tc0
-    cached_same = all(torch.equal(couts[0][k], ref12[k]) for k in ref12)
-    if dist_on:
-        t = torch.tensor([dtc], dtype=torch.float64, device=dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dtc = float(t.item())
-    del gcache
+            dtc = float(t.item())
+        del gcache
     local_dt = dt
     if dist_on:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
@@ -477,39 +599,12 @@ def run_pair(args):
         dt = float(t.item())
 
     # sanity: finite outputs (a bench number over garbage is worthless)
-    assert torch.isfinite(out12["losses"]).all() and torch.isfinite(out21["warped"]).all()
+    assert torch.isfinite(last[0]["losses"]).all() and torch.isfinite(last[1]["warped"]).all()
+    if args.full:
+        assert torch.isfinite(out12["losses"]).all() and torch.isfinite(out21["warped"]).all()
 
     if rank == 0:
         value = pairs_per_step * args.steps / dt
-        traffic, traffic_src = args.traffic_bytes, {"file": None, "why": "--traffic-bytes"}
-        if traffic is None:
-            traffic, traffic_src = load_traffic(P, k1_name)
-        k1_ms = k1_total_ms / max(k1_launches, 1)
-        k1_alone = alone_ms / max(alone_n, 1)
-        flops_launch = P * (2.0 * N_PTS * M_PTS * DIM)   # the distance tile counted once per pair
-        tf = lambda ms_: flops_launch / (ms_ * 1e-3) / 1e12 if ms_ > 0 else 0.0  # noqa: E731
-        # fp16 products of the N x M contraction pass A PERFORMED per direction, from the routes the library reports for the last
-        # timed launch: coarse screen 1 (hh), first forms 3 (hh + hm + mh); None when the launch was mixed or partly swept twice
-        nprod = (1 if routes["coarse"] == routes["entries"] and routes["reswept_lean"] == 0
-                 else 3 if routes["coarse"] == 0 else None)
-        perf = (lambda ms_: 2.0 * nprod * tf(ms_)) if nprod else (lambda ms_: None)  # noqa: E731
-        frac16 = lambda x: None if x is None else x / PEAK_F16_MFMA_TFLOPS  # noqa: E731
-        kernels = []
-        for k, (ms_tot, n) in sorted(slots.items()):
-            if n == 0:
-                continue
-            m = kernel_models(P)[k]
-            per_launch = ms_tot / n
-            per_step = ms_tot / 3.0
-            work = m["work"]
-            if m["bound"] == "mfma":
-                ach, peak, unit = work / (per_launch * 1e-3) / 1e12, m["peak"], "TFLOP/s"
-            else:
-                ach, peak, unit = work / (per_launch * 1e-3) / 1e9, PEAK_HBM_GBS, "GB/s"
-            kernels.append({"kernel": lib.dvm_profile_kernel_name(k).decode(), "bound": m["bound"], "achieved": ach, "peak": peak,
-                            "unit": unit, "frac": ach / peak, "launch_ms": per_launch, "launches_per_step": n / 3.0,
-                            "ms_per_step": per_step, "algorithmic_per_launch": work, "note": m["note"]})
-        pmc = load_pmc(P, k1_name)
         res = {
             "metric": "point-cloud pairs/sec (N=2048, d=128)", "value": value, "unit": "pairs/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "median_ms_per_step": median_ms,
@@ -525,50 +620,23 @@ def run_pair(args):
                                     "nothing is cached" if pipelined else
                                     "one call per step on one resident batch (dvm_pair_fwd_f32)")},
             "per_gpu": {"pairs_per_s": value / world, "rank0_ms_per_step": local_dt / args.steps * 1e3},
-            # the one-call form (geometry and features of the SAME batch inside one call; rounds 1-5 timed this)
-            "single_call": (None if single is None else
-                            {"value": pairs_per_step * args.steps / single, "unit": "pairs/s", "ms_per_step": single / args.steps * 1e3,
-                             "bit_identical_to_pipelined": bool(pipe_same)}),
-            # the same steps with the per-shape graph cache on (opt-in; NOT `value`: the reference rebuilds the graphs per call)
-            "graph_cached": {"value": pairs_per_step * args.steps / dtc, "unit": "pairs/s", "ms_per_step": dtc / args.steps * 1e3,
-                             "hits": args.steps, "bit_identical_to_uncached": bool(cached_same),
-                             "what": "graphs (FPS nodes, rings, skinning), uniform grids and xyz kNN of both clouds reused from a first "
-                                     "call (dvm_pair_fwd_cached_f32); everything feature-dependent recomputed"},
             "process_group": (dist.get_backend() if dist_on else None),
-            # The dominant kernel runs the N x M contraction on the 16-bit matrix pipe.  ONE denominator: the dense f16 matrix peak.
-            #   achieved / frac      = flops the kernel PERFORMS (`products_per_direction` fp16 products x 2 directions x B*2NMd; the norm
-            #                          instruction not counted) / launch time            -> the pipe's utilisation
-            #   algorithmic_frac_f16 = SURVEY §8d's formulation-independent count (B*2NMd: the distance tile once per pair) / launch time,
-            #                          against the same peak
-            #   mfma_busy, valu_per_mfma, l2_hit_rate, traffic = PMC passes of this kernel (profiles/r6_k1_traffic.json; null unless
-            #                          taken on this kernel source, for this kernel, at this --pairs): why the pipe is not busier
-            "roofline": {"bound": "mfma", "kernel": k1_name + " (K1 pass A: the N x M sweep on the f16 matrix pipe; named by the library "
-                                                             "from what the timed launches ran)",
-                         "routes_last_timed_launch": routes, "products_per_direction": nprod,
-                         "achieved": perf(k1_ms), "peak": PEAK_F16_MFMA_TFLOPS, "unit": "TFLOP/s",
-                         "frac": frac16(perf(k1_ms)), "pipe": "f16 matrix (v_mfma_f32_32x32x16_f16)",
-                         "algorithmic_flops_per_launch": flops_launch, "algorithmic_frac_f16": frac16(tf(k1_ms)),
-                         "traffic": traffic, "traffic_source": traffic_src, "launch_ms": k1_ms, "launches_timed": k1_launches,
-                         "flops_per_launch": (2.0 * nprod * flops_launch) if nprod else None,
-                         "mfma_busy": pmc.get("mfma_busy"), "valu_per_mfma": pmc.get("valu_per_mfma"), "l2_hit_rate": pmc.get("l2_hit_rate"),
-                         "algorithmic_bytes_per_launch": pmc.get("algorithmic_bytes_per_launch"),
-                         "share_of_step": (k1_total_ms * 1e-3) / local_dt if local_dt > 0 else None,
-                         # in the timed region the sweep shares the CUs with the geometry chain of the NEXT batch (FPS / graph / kNN)
-                         # and this batch's pooling on the helper streams, which stretches its launch; alone (one-call form, helper
-                         # streams off, 3 launches after the timed region) it takes `launch_ms` below
-                         "standalone": {"launch_ms": k1_alone, "achieved": perf(k1_alone), "frac": frac16(perf(k1_alone)),
-                                        "algorithmic_frac_f16": frac16(tf(k1_alone))},
-                         "kernels": kernels},
+            "full": bool(args.full),
         }
-        if args.no_check and not (world == 1 and args.cpu_sample > 0):
-            res["checked_pairs"], res["check"], res["cpu_baseline"] = 0, None, None
-        else:
-            ncheck = 0 if args.no_check else min(CHECK_PAIRS, P)
-            timed = [(batches[i], pouts[i][0], pouts[i][1]) for i in range(2)] if pipelined else [(batch, out12, out21)]
-            check, cpu = oracle_legs(timed, args.cpu_sample if world == 1 else 0, ncheck)
-            res["checked_pairs"], res["check"], res["cpu_baseline"] = ncheck, (check if ncheck else None), cpu
+        if args.full:
+            res.update(full_fields(args, P, pairs_per_step, lib, routes, k1_name, k1_total_ms, k1_launches, alone_ms, alone_n, slots,
+                                   local_dt, single, pipe_same if single is not None else None, dtc, cached_same))
+            if args.no_check and not (world == 1 and args.cpu_sample > 0):
+                res["checked_pairs"], res["check"], res["cpu_baseline"] = 0, None, None
+            else:
+                ncheck = 0 if args.no_check else min(CHECK_PAIRS, P)
+                timed = [(batches[i], pouts[i][0], pouts[i][1]) for i in range(2)] if pipelined else [(batch, out12, out21)]
+                check, cpu = oracle_legs(timed, args.cpu_sample if world == 1 else 0, ncheck)
+                res["checked_pairs"], res["check"], res["cpu_baseline"] = ncheck, (check if ncheck else None), cpu
+        if dumped is not None:
+            dump_outputs(args.dump_outputs, dumped)
         print(json.dumps(res))
-        if res["check"] is not None and not res["check"]["ok"]:
+        if res.get("check") is not None and not res["check"]["ok"]:
             print("bench.py: the GPU outputs of the timed batch differ from the oracle: %s" % res["check"], file=sys.stderr)
             if dist_on:
                 dist.destroy_process_group()
@@ -608,6 +676,9 @@ def run_train(args):
                "host_enqueue_ms_per_step": tr["host_enqueue_ms_per_step"], "roofline": tr["roofline"], "cpu_baseline": None,
                "process_group": tr.get("process_group"),
                "first_losses": tr["first_losses"], "last_losses": tr["last_losses"]}
+        if args.dump_outputs:
+            import numpy as np   # what the timed step hands back: the loss terms of its last step (float32 values, exactly in float64)
+            dump_outputs(args.dump_outputs, {"last_losses": np.asarray(tr["last_losses"], dtype=np.float64)})
         print(json.dumps(res))
     return rc
 

@@ -120,7 +120,7 @@ def test_bench_gpus_2_starts_its_own_ranks():
     the 8-GPU run belongs to the driver), barriers, MAX-over-ranks time, one JSON line from rank 0, whole-job value, the
     oracle check of 4 pairs of the timed batch."""
     res = _bench_line([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--pairs", "16",
-                       "--backend", "gloo"])
+                       "--backend", "gloo", "--full"])
     assert res["n_gpus"] == 2 and res["steps"] == 2 and res["scaling"] == "weak" and res["cpu_baseline"] is None
     assert abs(res["value"] - 2 * 16 * 2 / (res["ms_per_step"] * 2e-3)) < 1e-6 * res["value"]   # pairs of BOTH ranks / time
     assert res["roofline"]["frac"] > 0 and len(res["roofline"]["kernels"]) >= 6
@@ -131,7 +131,7 @@ def test_bench_gpus_2_starts_its_own_ranks():
 def test_bench_strong_scaling_two_ranks():
     """--pairs-total: the total work is fixed and split over the ranks (24 pairs -> 12 + 12), "scaling": "strong"."""
     res = _bench_line([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--pairs-total", "24",
-                       "--backend", "gloo", "--no-check"])
+                       "--backend", "gloo", "--no-check", "--full"])
     assert res["n_gpus"] == 2 and res["scaling"] == "strong" and res["config"]["pairs_per_gpu_per_step"] == 12
     assert abs(res["value"] - 24 * 2 / (res["ms_per_step"] * 2e-3)) < 1e-6 * res["value"]
     assert res["checked_pairs"] == 0 and res["check"] is None
@@ -150,7 +150,7 @@ def test_bench_under_an_external_launcher():
 def test_bench_single_gpu_line_and_check():
     """N = 1, in-process (what `rocprofv3 ... -- python3 bench.py` profiles): roofline + kernels[] + oracle check + cpu_baseline
     on pairs of the timed batch."""
-    res = _bench_line([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--pairs", "8", "--cpu-sample", "4"])
+    res = _bench_line([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--pairs", "8", "--cpu-sample", "4", "--full"])
     assert res["n_gpus"] == 1 and res["checked_pairs"] == 4 and res["check"]["ok"]
     assert res["cpu_baseline"]["kind"] == "port" and res["cpu_baseline"]["value"] > 0 and "timed batch" in res["cpu_baseline"]["sample"]
     aten = res["cpu_baseline"]["aten"]      # the same pairs in the reference's dense ATen / MKL formulation
@@ -313,7 +313,8 @@ def test_rccl_branch_runs_at_world_size_one():
     env.update(WORLD_SIZE="1", RANK="0", LOCAL_RANK="0", LOCAL_WORLD_SIZE="1", MASTER_ADDR="127.0.0.1",
                HSA_ENABLE_IPC_MODE_LEGACY="0")
     runs = [
-        ([os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--pairs", "8", "--cpu-sample", "0", "--backend", "nccl", "--dist-always"], None),
+        ([os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--pairs", "8", "--cpu-sample", "0", "--backend", "nccl", "--dist-always",
+          "--full"], None),
         ([os.path.join(ROOT, "bench.py"), "--workload", "train", "--steps", "2", "--warmup", "1", "--backend", "nccl", "--dist-always"], 2122644),
         ([os.path.join(ROOT, "dv-matcher_amd", "train_driver.py"), "--steps", "2", "--warmup", "1", "--batch", "2", "--points", "256",
           "--backend", "nccl", "--dist-always"], 2122644),

@@ -6,12 +6,12 @@
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r6p; rm -rf "$O"; mkdir -p $O
 cd $R
-python bench.py --steps 20 --warmup 5 > $O/bench_pairs512.json 2> $O/bench.err
+python bench.py --full --steps 20 --warmup 5 > $O/bench_pairs512.json 2> $O/bench.err
 python bench.py --workload train --steps 10 --warmup 3 > $O/bench_train.json 2> $O/bench_train.err
 python bench.py --workload partial --steps 10 --warmup 3 > $O/bench_partial.json 2> $O/bench_partial.err
 # strong-scaling proxy: what one rank of an 8-GPU strong-scaling run does alone (512 / 8 = 64 pairs), and the points around it
 for p in 32 64 128 256 512; do
-  python bench.py --pairs $p --steps 20 --warmup 5 --cpu-sample 0 --no-check 2>/dev/null | python3 -c "
+  python bench.py --full --pairs $p --steps 20 --warmup 5 --cpu-sample 0 --no-check 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']; s=d['single_call']
 print('pairs %4d: %8.0f pairs/s  %7.3f ms/step (median %7.3f)  | one-call form %8.0f pairs/s %7.3f ms (same bits: %s) | sweep %.3f ms | graph_cached %8.0f pairs/s' % ($p, d['value'], d['ms_per_step'], d['median_ms_per_step'], s['value'], s['ms_per_step'], s['bit_identical_to_pipelined'], r['launch_ms'], d['graph_cached']['value']))"
@@ -37,7 +37,7 @@ rocprofv3 --kernel-trace --stats -d /tmp/p_bench -o x --output-format csv -- pyt
 cp $(find /tmp/p_bench -name "*kernel_stats.csv" | head -1) $O/kernel_stats_bench_steps3_pairs512.csv
 rocprofv3 --kernel-trace --stats -d /tmp/p_train -o x --output-format csv -- python3 $R/dv-matcher_amd/train_driver.py --steps 3 --warmup 1 --batch 8 --points 2048 > /tmp/p_train.log 2>&1
 cp $(find /tmp/p_train -name "*kernel_stats.csv" | head -1) $O/kernel_stats_train_B8_N2048.csv
-B="python3 $R/bench.py --steps 2 --warmup 1 --cpu-sample 0 --no-check"
+B="python3 $R/bench.py --full --steps 2 --warmup 1 --cpu-sample 0 --no-check"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/pmc/fetch --output-format csv -- $B > $O/pmc_fetch.log 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/pmc/write --output-format csv -- $B > $O/pmc_write.log 2>&1
 rocprofv3 --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum -d $O/pmc/tcc --output-format csv -- $B > $O/pmc_tcc.log 2>&1
@@ -51,5 +51,5 @@ for k in softcorr_coarse softcorr_refine mlp_f16x2p pool_kernel grid_chamfer fps
 find $O/pmc -name "*.csv" -size +2M -delete
 # the bench line again, now that the traffic file of THIS source exists (it is picked up from profiles/ only: copy first)
 cp $O/k1_traffic.json $R/profiles/r6_k1_traffic.json
-python bench.py --steps 20 --warmup 5 > $O/bench_pairs512_with_traffic.json 2>> $O/bench.err
+python bench.py --full --steps 20 --warmup 5 > $O/bench_pairs512_with_traffic.json 2>> $O/bench.err
 cat $O/scaling_proxy.txt $O/sync_stats.txt; cut -c1-400 $O/bench_pairs512_with_traffic.json; python tools/kstats.py $O/kernel_stats_bench_steps3_pairs512.csv "" 14; python tools/kstats.py $O/kernel_stats_train_B8_N2048.csv "" 25

@@ -5,9 +5,9 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r6k; rm -rf "$O"; mkdir -p $O
 cd $R
 timeout 900 python -m pytest tests/test_gpu_k1_routes.py tests/test_gpu_parity.py -x -q -k "softcorr or k1 or pair_forward_full or argmin" 2>&1 | tail -3
-python bench.py --steps 20 --warmup 5 --cpu-sample 0 > $O/bench_pairs512.json 2> $O/bench.err
+python bench.py --full --steps 20 --warmup 5 --cpu-sample 0 > $O/bench_pairs512.json 2> $O/bench.err
 cd /tmp
-B="python3 $R/bench.py --steps 2 --warmup 1 --cpu-sample 0 --no-check"
+B="python3 $R/bench.py --full --steps 2 --warmup 1 --cpu-sample 0 --no-check"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/pmc/fetch --output-format csv -- $B > $O/pmc_fetch.log 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/pmc/write --output-format csv -- $B > $O/pmc_write.log 2>&1
 rocprofv3 --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum -d $O/pmc/tcc --output-format csv -- $B > $O/pmc_tcc.log 2>&1
@@ -20,7 +20,7 @@ python tools/k1_traffic.py $O/pmc $O/bench_pairs512.json $O/k1_traffic.json
 for k in softcorr_coarse softcorr_refine mlp_f16x2p pool_kernel grid_chamfer fps_kernel; do echo "== $k"; python tools/pmc_summary.py $O/pmc $k; done > $O/pmc_summary.txt 2>&1
 find $O/pmc -name "*.csv" -size +2M -delete
 cp $O/k1_traffic.json $R/profiles/r6_k1_traffic.json
-python bench.py --steps 20 --warmup 5 > $O/bench_pairs512_with_traffic.json 2>> $O/bench.err
+python bench.py --full --steps 20 --warmup 5 > $O/bench_pairs512_with_traffic.json 2>> $O/bench.err
 python3 -c "
 import json; d=json.load(open('$O/bench_pairs512_with_traffic.json')); r=d['roofline']
 print({k: d[k] for k in ('value','ms_per_step','single_call')}); print({k: r[k] for k in r if k not in ('kernels',)})"

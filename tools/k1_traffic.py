@@ -45,7 +45,7 @@ res = {
                    "a 256-pair one-direction run such as tools/gpu/r5_pmc_coarse.sh)",
     "SQ": {k: v for k, v in sorted(per.items()) if k.startswith("SQ_")},
     "kernels_in_bracket": sorted({k for ks in acc.values() for k in ks}),
-    "how": "rocprofv3 --kernel-trace --pmc <one group per pass> -- python3 bench.py --steps 2 --warmup 1 --cpu-sample 0 --no-check "
+    "how": "rocprofv3 --kernel-trace --pmc <one group per pass> -- python3 bench.py --full --steps 2 --warmup 1 --cpu-sample 0 --no-check "
            "(tools/gpu/profiles_r6.sh); FETCH_SIZE doubled per MI355X_MICROARCH.md; Infinity-Cache hits are counted in FETCH_SIZE",
 }
 json.dump(res, open(out, "w"), indent=1)
