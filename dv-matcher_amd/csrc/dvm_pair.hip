@@ -50,6 +50,14 @@ __global__ void fill_kernel(float *p, int n, float v) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) p[i] = v;
 }
+// out[b * stride + off] = v for b < B: a strided column written from nothing (no scratch read, no dependency on another stream)
+__global__ void fill_col_kernel(float *out, int B, int stride, int off, float v) {
+    int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < B) out[(size_t)b * stride + off] = v;
+}
+static void launch_fill_col(float *out, int B, int stride, int off, float v, hipStream_t s) {
+    hipLaunchKernelGGL(fill_col_kernel, dim3((B + 255) / 256), dim3(256), 0, s, out, B, stride, off, v);
+}
 
 struct PairWs {
     int32_t *nodes, *ring, *infl, *pidx, *idx11, *idx22;
@@ -160,8 +168,8 @@ DVM_EXPORT int dvm_pair_direction_fwd_f32(const float *feat1, const float *feat2
             launch_map_term(verts12, verts2, w.idx11, w.idx22, w.pval, w.pidx, B, N, M, k, topk, w.partial, s);
         launch_reduce_partials(w.partial, B, map_term_blocks(N, k), 1.f, losses, 6, 5, s);
     } else {
-        // losses[:,5] = 0 — a strided fill through the mean kernel's overwrite path
-        launch_mean(w.d1, B, 1, 0.f, losses, 6, 5, 0, s);
+        // losses[:,5] = 0 exactly (not a Chamfer value times 0, which is NaN when that value is not finite)
+        launch_fill_col(losses, B, 6, 5, 0.f, s);
     }
     DVM_CHECK_LAUNCH("pair_direction");
     return DVM_OK;
@@ -460,8 +468,9 @@ static int pair_fwd_impl(const float *feat1, const float *feat2, const float *ve
         launch_reduce_partials(w.partial[0], B, map_term_blocks(N, 10), 1.f, losses12, 6, 5, s2);
         launch_reduce_partials(w.partial[1], B, map_term_blocks(M, 10), 1.f, losses21, 6, 5, s2);
     } else {
-        launch_mean(w.cd[0], B, 1, 0.f, losses12, 6, 5, 0, s2);
-        launch_mean(w.cd[0], B, 1, 0.f, losses21, 6, 5, 0, s2);
+        // losses[:,5] = 0 exactly: read nothing — w.cd[0] is written later, on the caller's stream
+        launch_fill_col(losses12, B, 6, 5, 0.f, s2);
+        launch_fill_col(losses21, B, 6, 5, 0.f, s2);
     }
     if (overlap) (void)hipEventRecord(cx->ev_join2, cx->side);
     // ---- Deformer: z for both directions from the pooled features (made above), one MLP launch

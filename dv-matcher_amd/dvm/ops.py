@@ -74,6 +74,12 @@ def workspace(nbytes, device, tag="ws"):
     return buf
 
 
+def scratch(nbytes, device):
+    """A dedicated, uninitialised scratch buffer of `nbytes` bytes owned by the caller (training arenas, geometry-cache entries,
+    pipeline workspaces): with workspace() the only allocation of library scratch, so one replacement reaches all of it."""
+    return torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+
+
 def neg_alpha_f32(alpha):
     """`-alpha * distance`: ATen casts the python/numpy scalar to fp32 (models/loss.py:112)."""
     return float(torch.tensor(-float(alpha), dtype=torch.float32).item())
@@ -929,7 +935,7 @@ def uni3fc_train_forward(params, x, dino, k, eps, momentum, defer_stats=False, g
     feat = torch.empty(B, N, 128, dtype=torch.float32, device=dev)
     tmp = torch.empty(B, N, 64, dtype=torch.float32, device=dev)
     nb = lib.dvm_uni3fc_train_workspace_bytes(B, N, int(k))
-    arena = torch.empty(nb, dtype=torch.uint8, device=dev)
+    arena = scratch(nb, dev)
     _ensure_pair_ctx(dev)
     table = _ptr_table(params, U3_TRAIN_NPARAMS)
     tap = knn_tap()
@@ -982,7 +988,7 @@ def criterion_train_forward(params, feat, verts, g, knn_idx, alpha, topk=10, wit
                                  and tuple(d2.shape) == (P // 2, N, N) and a2.numel() == nA):
         raise DvmError("criterion_train_forward: dist term inputs must be contiguous fp32 (B,N,N) matrices and int32 anchor lists of one length")
     nb = lib.dvm_criterion_train_workspace_bytes(P // 2, N, k, topk, nA, int(kd))
-    arena = torch.empty(nb, dtype=torch.uint8, device=feat.device)
+    arena = scratch(nb, feat.device)
     if nA:
         _ensure_pair_ctx(feat.device)
     table = _ptr_table(params, CRIT_TRAIN_NPARAMS)
@@ -1025,7 +1031,7 @@ def criterion_dir_train_forward(params, feat_s, feat_t, verts_s, verts_t, g, knn
     lib = _lib.load()
     terms = torch.empty(P, 7, dtype=torch.float32, device=feat_s.device)
     nb = lib.dvm_criterion_dir_train_workspace_bytes(P, N, M, k, topk)
-    arena = torch.empty(nb, dtype=torch.uint8, device=feat_s.device)
+    arena = scratch(nb, feat_s.device)
     table = _ptr_table(params, CRIT_TRAIN_NPARAMS)
     check(lib.dvm_criterion_dir_train_fwd_f32(_p(feat_s), _p(feat_t), _p(verts_s), _p(verts_t), _p(g["nodes_idx"]), _p(g["one_ring"]), _p(g["infl_idx"]),
                                               _p(g["weights"]), _p(knn_s), _p(knn_t), P, N, M, C, k, topk, neg_alpha_f32(alpha),
@@ -1094,7 +1100,7 @@ class GeometryCache:
             self.entries.move_to_end(key)
             self.hits += 1
             return ent, 1
-        ent = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
+        ent = scratch(max(int(nbytes), 256), device)
         self.entries[key] = ent
         self.misses += 1
         while len(self.entries) > self.max_entries:
@@ -1174,7 +1180,7 @@ class PairPipeline:
         self.wl, self.B, self.N, self.M, self.with_map, self.dev = wl, int(B), int(N), int(M), bool(with_map), dev
         lib = _lib.load()
         self.nb = lib.dvm_pair_workspace_bytes(self.B, self.N, self.M)
-        self.ws = [torch.empty(max(int(self.nb), 256), dtype=torch.uint8, device=dev) for _ in range(depth)]
+        self.ws = [scratch(max(int(self.nb), 256), dev) for _ in range(depth)]
         self.free = [None] * depth           # event: the stage-2 call that last used the workspace has finished
         self.geo = torch.cuda.Stream(device=dev)
         with torch.cuda.stream(self.geo):
@@ -1201,6 +1207,11 @@ class PairPipeline:
         valid (e.g. recorded when the batch was loaded); None = behind everything enqueued on the current stream so far — which, called
         after a forward(), is the END of that forward: no overlap with it (pass `ready` to pipeline)."""
         _need_gpu(verts1, verts2, start1, start2)
+        cur = torch.cuda.current_stream(self.dev)
+        converted = not (all(t.dtype is torch.float32 and not t.requires_grad and t.is_contiguous() for t in (verts1, verts2))
+                         and all(t.dtype is torch.int32 and t.is_contiguous() for t in (start1, start2)))
+        if converted and ready is not None:
+            cur.wait_event(ready)                       # the conversions below read the inputs on the current stream
         verts1, verts2, start1, start2 = _f(verts1), _f(verts2), _i(start1), _i(start2)
         if tuple(verts1.shape) != (self.B, self.N, 3) or tuple(verts2.shape) != (self.B, self.M, 3):
             raise DvmError("PairPipeline.prefetch: coordinates %s / %s, built for B=%d N=%d M=%d"
@@ -1210,9 +1221,8 @@ class PairPipeline:
         slot = self.n % len(self.ws)
         self.n += 1
         self.slot_gen[slot] = self.n
-        cur = torch.cuda.current_stream(self.dev)
-        if ready is None:
-            self.geo.wait_stream(cur)                   # the coordinates were produced on the caller's stream
+        if ready is None or converted:
+            self.geo.wait_stream(cur)                   # the coordinates (or their fp32 / int32 copies) were produced on the caller's stream
         else:
             self.geo.wait_event(ready)
         if self.free[slot] is not None:
@@ -1222,7 +1232,7 @@ class PairPipeline:
                                                     int(self.with_map), _p(self.ws[slot]), self.nb, _stream()), "dvm_pair_geometry_f32")
             ready = torch.cuda.Event()
             ready.record()
-        return dict(slot=slot, gen=self.n, ready=ready, verts1=verts1, verts2=verts2, start1=start1, start2=start2)
+        return dict(pipe=self, slot=slot, gen=self.n, ready=ready, verts1=verts1, verts2=verts2, start1=start1, start2=start2)
 
     def forward(self, ticket, feat1, feat2, alpha, out=None):
         """Stage 2 of the ticket's batch on the current stream -> (out12, out21) as pair_forward."""
@@ -1238,6 +1248,8 @@ class PairPipeline:
                         verts12=torch.empty(B, n, 3, dtype=torch.float32, device=dev),
                         T12=torch.empty(B, n, dtype=torch.int32, device=dev),
                         losses=torch.empty(B, 6, dtype=torch.float32, device=dev))
+        if ticket.get("pipe") is not self:
+            raise DvmError("PairPipeline.forward: the ticket was issued by another pipeline (its geometry is in that pipeline's workspace)")
         slot = ticket["slot"]
         if self.slot_gen[slot] != ticket["gen"]:
             raise DvmError("PairPipeline.forward: this ticket's workspace has been rewritten by a later prefetch (%d workspaces rotate: "

@@ -416,6 +416,9 @@ def test_pair_pipeline_equals_pair_forward(ops, golden, shape, with_map):
     for f1, f2, v1, v2, s1, s2 in batches:
         o12, o21 = ops.pair_forward(wl, f1, f2, v1, v2, 50.0, s1, s2, with_map=with_map)
         ref.append(({k: v.clone() for k, v in o12.items()}, {k: v.clone() for k, v in o21.items()}))
+        if not with_map:   # no map term: losses[:,5] is an exact 0, read from nothing
+            for o in (o12, o21):
+                assert torch.equal(o["losses"][:, 5].view(torch.int32), torch.zeros(B, dtype=torch.int32, device="cuda")), o["losses"]
     torch.cuda.synchronize()
     loaded = torch.cuda.Event()
     loaded.record()
