@@ -351,8 +351,10 @@ __global__ __launch_bounds__(THREADS) void grid_knn_self_kernel(GridBuf gb, int 
     kb.init(INFINITY);
     grid_search<K, MetricMMQueryRow>(g, qp.x, qp.y, qp.z, met, kb);
     int32_t *o = idx + ((size_t)b * P + g.ids[t]) * k;
+    // (a slot the search left empty — fewer than k points, or a non-finite query whose every key is +inf — names row 0: the
+    // consumers gather through these indices unchecked)
     for (int q = 0; q < K; ++q)
-        if (q < k) o[q] = q < P ? kb.idx_at(q) : 0;
+        if (q < k) o[q] = (unsigned)kb.idx_at(q) < (unsigned)P ? kb.idx_at(q) : 0;
 }
 
 // node ring: 9-NN among nodes in fp64 (grid over the nodes, queries = nodes in cell order)
@@ -383,8 +385,10 @@ __global__ __launch_bounds__(THREADS) void grid_ring_kernel(GridBuf gb, int32_t 
     bool ambiguous = false;
 #pragma unroll
     for (int q = 0; q < 9; ++q) ambiguous = ambiguous || (ks.key_at(q) == ks.key_at(q + 1) && ks.key_at(q) < INFINITY);
+    // (a slot left empty — fewer than 9 nodes, or a non-finite node whose every fp64 distance is NaN — names the node itself:
+    // the ARAP kernels gather through the ring unchecked)
     if (!ambiguous) {
-        for (int q = 0; q < 9; ++q) o[q] = q < P ? ks.idx_at(q) : a;
+        for (int q = 0; q < 9; ++q) o[q] = (unsigned)ks.idx_at(q) < (unsigned)P ? ks.idx_at(q) : a;
         return;
     }
     MetricF64 met;
@@ -392,7 +396,7 @@ __global__ __launch_bounds__(THREADS) void grid_ring_kernel(GridBuf gb, int32_t 
     KBest<9, double> kb;
     kb.init((double)INFINITY);
     grid_search<9, MetricF64>(g, qp.x, qp.y, qp.z, met, kb);
-    for (int q = 0; q < 9; ++q) o[q] = q < P ? kb.idx[q] : a;
+    for (int q = 0; q < 9; ++q) o[q] = (unsigned)kb.idx[q] < (unsigned)P ? kb.idx[q] : a;
 }
 
 // influence nodes (3 nearest nodes, matmul form with the node as row operand) on the node grid, and
@@ -423,7 +427,7 @@ __global__ __launch_bounds__(THREADS) void grid_infl_kernel(const float *__restr
         grid_search<3, MetricMMCandRow>(gn, qp.x, qp.y, qp.z, met, kb);
         const size_t row = (size_t)b * N + i;
         for (int q = 0; q < 3; ++q) {
-            infl[row * 3 + q] = q < gnodes.P ? kb.idx_at(q) : 0;
+            infl[row * 3 + q] = (unsigned)kb.idx_at(q) < (unsigned)gnodes.P ? kb.idx_at(q) : 0;   // (empty slot: row 0, as above)
             dists[row * 3 + q] = kb.key_at(q);
         }
     }
