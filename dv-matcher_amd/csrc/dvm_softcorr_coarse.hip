@@ -33,8 +33,8 @@
 //    matrix instruction per slice of ~10 vector instructions, fenced (`fused`): what bounds the kernel is the SIMD's vector
 //    issue (4 cycles per instruction, shared by its two waves — 60 % busy over the kernel, the matrix pipe 27 %);
 //  * at the end the two half-lanes of a row merge into 16 entries; entries above lim = min of the two 12th entries (and of the
-//    larger of the two 8th) are dropped — each half-lane is complete only up to its own 12th —, so the largest entry written
-//    IS the completeness bound pass B certifies against.
+//    larger of the two 8th) are dropped — each half-lane is complete only up to its own 12th, taken again after the re-done
+//    sub-tiles have pushed entries out —, so the largest entry written IS the completeness bound pass B certifies against.
 #include <stdlib.h>
 #include <type_traits>
 
@@ -530,6 +530,16 @@ __global__ __launch_bounds__(64 * W, 8 / W) void softcorr_coarse_kernel(const HC
                 }
             }
         }
+    }
+    // The re-done keys went into lists of 12: a half-lane that took r of them dropped its r largest entries, some of which
+    // may lie at or below lim — and the merge below keeps the OTHER half-lane's entries up to lim, so a dropped column would
+    // lie below the largest entry written, which pass B takes for the completeness bound.  Each half-lane is complete up to
+    // its NEW 12th entry: the row's bound comes down to the smaller of the two.
+#pragma unroll
+    for (int qb = 0; qb < QB; ++qb) {
+        const unsigned wk = kb[qb].e[HC_KL - 1];
+        const auto sk = __builtin_amdgcn_permlane32_swap(wk, wk, false, false);
+        lim[qb] = min(lim[qb], min(wk, h ? sk[0] : sk[1]));
     }
     stamp(3);
 
