@@ -7,12 +7,19 @@
 //     dL/dS_ij = [j = idx_t] gp_t  -  P_ij * G_i
 //     W_ij     = neg_alpha * dL/dS_ij / D_ij              (0 where D_ij = 0, like cdist's backward)
 //     df1_i    = sum_j W_ij (f1_i - f2_j)   ,   df2_j = sum_i W_ij (f2_j - f1_i)
-// The N x M matrices never exist in HBM: the dense term (-P*G) is recomputed tile by tile from row_smax /
-// row_sum, flash-attention style, once row-major (df1) and once column-major (df2); the k-sparse term is a
-// gather/scatter kernel.  Per 32x32 tile: 64 fp32 MFMAs (32x32x2) rebuild the distances, ~13 VALU per entry
-// turn them into W in the accumulator layout, and 64 more MFMAs apply W to the staged rows — W's C-layout
-// registers are fed straight back as the A operand (the contraction index is permuted consistently on the
-// B side), so W never touches LDS.
+// The row's top-k columns belong to the prep kernel, BOTH terms: W = neg_alpha * (gp_t - val_t * G) / D with the
+// exact-difference D and the forward's own val_t as P.  On a one-hot row the two terms cancel exactly; split over
+// two kernels they would each take their own D (and the dense one a P recomputed from it), and for a column much
+// closer than sqrt(eps) |f| the 1/D of the two differ by O(1): a gradient of order alpha * g where it is ~0.  The
+// prep kernel marks those columns in a bit matrix [B][N][ceil(M/32)] and the dense passes skip them.  (The
+// columns of a row's top-k are distinct, as the forward writes them; its padding slots at M < topk carry val 0.)
+// Every other column takes the dense term (-P*G), recomputed tile by tile from row_smax / row_sum, flash-attention
+// style, once row-major (df1) and once column-major (df2).  Per 32x32 tile: 64 fp32 MFMAs (32x32x2) rebuild the
+// distances by the norm expansion, ~15 VALU per entry turn them into W in the accumulator layout, and 64 more MFMAs
+// apply W to the staged rows — W's C-layout registers are fed straight back as the A operand (the contraction index
+// is permuted consistently on the B side), so W never touches LDS.  Where the expansion cancels
+// (v < BW_TAU (|f_o|^2 + |f_i|^2): a cluster of columns near one query, more than its top-k) the entry's D is
+// redone from the exact difference in a wave-uniform branch that ordinary features never take.
 #include <algorithm>
 
 #include "dvm_common.h"
@@ -34,7 +41,9 @@ constexpr int BW_WAVES = 4;
 constexpr int BW_OB = 32 * BW_WAVES;  // outer rows per workgroup
 constexpr int BW_THREADS = 64 * BW_WAVES;
 constexpr int BW_LD_PER_THREAD = BW_KT * BW_D / 4 / BW_THREADS;  // 8 float4 per thread per tile
-constexpr int BW_TILE_FLOATS = BW_KT * BW_LDK + 3 * BW_KT;       // rows + {norm, c2, coef}
+constexpr int BW_MASK = 256;                                      // skip-mask words per tile (see issue_loads)
+constexpr int BW_TILE_FLOATS = BW_KT * BW_LDK + 3 * BW_KT + BW_MASK;  // rows + {norm, c2, coef} + mask
+constexpr float BW_TAU = 1.f / 64.f;  // the norm expansion's v is redone exactly below this share of |f_o|^2 + |f_i|^2
 constexpr size_t BW_LDS_BYTES = ((size_t)2 * BW_TILE_FLOATS + BW_OB) * sizeof(float);
 
 
@@ -49,6 +58,8 @@ struct SBGroup {
 };
 struct SBArgs {
     SBGroup g[2];
+    const uint32_t *topk_bits;  // [B][N][wpr]: bit j of row i set for the row's top-k columns (the prep kernel owns them)
+    int wpr;                    // (M + 31) / 32
     int blocks0;  // B * g[0].tiles_o * split
     int split;    // the inner loop is cut into `split` pieces (small batches: fill the chip); outputs are atomics
     float a2;     // neg_alpha * log2(e)
@@ -96,6 +107,9 @@ __global__ __launch_bounds__(BW_THREADS, 2) void softcorr_bwd_mfma_kernel(const 
 
     f32x4 pre[BW_LD_PER_THREAD];
     float pres = 0.f;
+    uint32_t prem = 0;
+    const uint32_t *bits = args.topk_bits;
+    const int wpr = args.wpr;
     auto issue_loads = [&](int t) {
         const int j0 = t * BW_KT;
 #pragma unroll
@@ -113,6 +127,15 @@ __global__ __launch_bounds__(BW_THREADS, 2) void softcorr_bwd_mfma_kernel(const 
             else if (which == 1) pres = (ok && ic2) ? ic2[j] : 0.f;
             else pres = ok ? (icf ? icf[j] : 1.f) : 0.f;
         }
+        // the top-k skip mask of this tile x the workgroup's outer block, one word per thread.  df1 pass: word
+        // [outer row tid/2][32-column half tid%2]; df2 pass: word [inner row tid/4][32-column group tid%4 of the block]
+        if (grp == 0) {
+            const int mrow = ot * BW_OB + (tid >> 1), wc = (j0 >> 5) + (tid & 1);
+            prem = (mrow < No && wc < wpr) ? bits[((size_t)b * No + mrow) * wpr + wc] : 0u;
+        } else {
+            const int irow = j0 + (tid >> 2), wc = ot * (BW_OB / 32) + (tid & 3);
+            prem = (irow < Ni && wc < wpr) ? bits[((size_t)b * Ni + irow) * wpr + wc] : 0u;
+        }
     };
     auto commit_loads = [&](int buf) {
         float *kt = smem + buf * BW_TILE_FLOATS;
@@ -126,6 +149,7 @@ __global__ __launch_bounds__(BW_THREADS, 2) void softcorr_bwd_mfma_kernel(const 
             *(float2 *)(kt + r * BW_LDK + 64 + 2 * c) = od;
         }
         if (tid < 3 * BW_KT) kt[BW_KT * BW_LDK + tid] = pres;
+        ((uint32_t *)kt)[BW_KT * BW_LDK + 3 * BW_KT + tid] = prem;
     };
 
     f32x16 acc2[4];  // [position block cb] : out[outer row (C layout)][position 4*r32 + cb]
@@ -157,22 +181,60 @@ __global__ __launch_bounds__(BW_THREADS, 2) void softcorr_bwd_mfma_kernel(const 
             }
             // this lane's 16 inner rows: local row = (r&3) + 8*(r>>2) + 4*h
             const float *sc = kt + BW_KT * BW_LDK + sub * 32 + 4 * h;
-            float w[16];
+            const uint32_t *msk = (const uint32_t *)(kt + BW_KT * BW_LDK + 3 * BW_KT);
+            unsigned exact = 0;
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const f32x4 nb = *(const f32x4 *)(sc + 8 * g);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int r = 4 * g + u;
+                    acc[r] = (acc[r] + nrm_o) + nb[u];
+                    exact |= (acc[r] < BW_TAU * (nrm_o + nb[u]) ? 1u : 0u) << r;
+                }
+            }
+            if (__any(exact != 0)) {  // rare: redo v = |f_o - f_i|^2 from the difference where the expansion cancelled
+#pragma unroll 1
+                for (int r = 0; r < 16; ++r) {
+                    if (!__any((exact >> r) & 1u)) continue;
+                    // this lane's entry r: its outer row (op, from global, cached) against LDS row `er` of the tile
+                    // (position p < 64 holds channel 2p, 64 + p channel 2p + 1), all 128 channels by one lane
+                    const int er = sub * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                    const float *xr = kt + er * BW_LDK;
+                    float v = 0.f;
+#pragma unroll 4
+                    for (int c = 0; c < BW_D / 4; ++c) {
+                        const f32x4 o4 = *(const f32x4 *)(op + 4 * c);
+                        const float2 ev = *(const float2 *)(xr + 2 * c), od = *(const float2 *)(xr + 64 + 2 * c);
+                        const float d0 = ev.x - o4.x, d1 = od.x - o4.y, d2 = ev.y - o4.z, d3 = od.y - o4.w;
+                        v = fmaf(d0, d0, v);
+                        v = fmaf(d1, d1, v);
+                        v = fmaf(d2, d2, v);
+                        v = fmaf(d3, d3, v);
+                    }
+#pragma unroll
+                    for (int rr = 0; rr < 16; ++rr)
+                        if (rr == r && ((exact >> r) & 1u)) acc[rr] = v;
+                }
+            }
+            float w[16];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
                 const f32x4 cc = *(const f32x4 *)(sc + BW_KT + 8 * g);
                 const f32x4 cf = *(const f32x4 *)(sc + 2 * BW_KT + 8 * g);
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     const int r = 4 * g + u;
-                    const float v = fmaxf((acc[r] + nrm_o) + nb[u], 0.f);
+                    const int il = (r & 3) + 8 * (r >> 2) + 4 * h;  // inner row within the sub-tile
+                    const bool topk = grp == 0 ? ((msk[(wave * 32 + r32) * 2 + sub] >> il) & 1u)
+                                               : ((msk[(sub * 32 + il) * 4 + wave] >> r32) & 1u);
+                    const float v = fmaxf(acc[r], 0.f);
                     const float D = sqrt_rn(v);
                     const float e = __builtin_amdgcn_exp2f(fmaf(D, a2, -(c2_o + cc[u])));
                     const float wv = (coef_o * cf[u]) * e * __builtin_amdgcn_rcpf(D);
                     // padding rows of the last tile carry coef 0 but zero features: their "distance" |f_o| can be far
                     // below the row minimum, e overflows to +inf and 0 * inf would poison the whole output row
-                    w[r] = (v > 0.f && cf[u] != 0.f) ? wv : 0.f;
+                    w[r] = (v > 0.f && cf[u] != 0.f && !topk) ? wv : 0.f;
                     rl += w[r];
                 }
             }
@@ -216,6 +278,8 @@ __global__ __launch_bounds__(BW_THREADS, 2) void softcorr_bwd_mfma_kernel(const 
 // fallback and the cross-check for the MFMA kernel (variant 1).
 struct SBScalarArgs {
     SBGroup g[2];
+    const uint32_t *topk_bits;  // as in SBArgs
+    int wpr;
     long rows0;      // B * g[0].No
     long rows_total;  // rows0 + B * g[1].No
     int d;
@@ -252,8 +316,23 @@ __global__ __launch_bounds__(256) void softcorr_bwd_scalar_kernel(const SBScalar
             xv[u] = c < d ? fi[c] : 0.f;
             part = fmaf(ov[u], xv[u], part);
         }
+        // the row's top-k columns are the prep kernel's (grp 0: outer = f1 row, grp 1: inner j = f1 row)
+        const uint32_t *bw = args.topk_bits + (grp == 0 ? ((size_t)b * No + row) * args.wpr + (j >> 5)
+                                                         : ((size_t)b * Ni + j) * args.wpr + (row >> 5));
+        if ((*bw >> (grp == 0 ? (j & 31) : (row & 31))) & 1u) continue;  // uniform over the wave
         const float dot = wave_sum(part);
-        const float v = fmaxf((-2.f * dot + nrm_o) + G.ni[(size_t)b * Ni + j], 0.f);
+        const float ni = G.ni[(size_t)b * Ni + j];
+        float v = (-2.f * dot + nrm_o) + ni;
+        if (v < BW_TAU * (nrm_o + ni)) {  // uniform: the expansion cancelled, redo v from the difference
+            float p2 = 0.f;
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const float dd = ov[u] - xv[u];
+                p2 = fmaf(dd, dd, p2);
+            }
+            v = wave_sum(p2);
+        }
+        v = fmaxf(v, 0.f);
         const float D = sqrt_rn(v);
         const float c2 = c2_o + (G.c2i ? G.c2i[(size_t)b * Ni + j] : 0.f);
         const float cf = coef_o * (G.coefi ? G.coefi[(size_t)b * Ni + j] : 1.f);
@@ -270,8 +349,8 @@ __global__ __launch_bounds__(256) void softcorr_bwd_scalar_kernel(const SBScalar
     }
 }
 
-// Per f1 row: G = sum_t g_t*val_t, the row's dense-term coefficients, and the k-sparse term
-// (gathered rows of f2; scatter-add into df2).  One wave per row, lanes own channels lane + 64u.
+// Per f1 row: G = sum_t g_t*val_t, the row's dense-term coefficients, the top-k bits, and both terms of the top-k
+// entries (gathered rows of f2; scatter-add into df2).  One wave per row, lanes own channels lane + 64u.
 __global__ __launch_bounds__(256) void softcorr_bwd_prep_kernel(const float *__restrict__ f1, const float *__restrict__ f2,
                                                                 const float *__restrict__ pi_val,
                                                                 const int32_t *__restrict__ pi_idx,
@@ -279,8 +358,8 @@ __global__ __launch_bounds__(256) void softcorr_bwd_prep_kernel(const float *__r
                                                                 const float *__restrict__ row_smax,
                                                                 const float *__restrict__ row_sum, int B, int N, int M, int d,
                                                                 int topk, float neg_alpha, float *__restrict__ coef,
-                                                                float *__restrict__ c2, float *__restrict__ df1,
-                                                                float *__restrict__ df2) {
+                                                                float *__restrict__ c2, uint32_t *__restrict__ topk_bits,
+                                                                float *__restrict__ df1, float *__restrict__ df2) {
     const int lane = threadIdx.x & 63;
     const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= (long)B * N) return;
@@ -294,11 +373,17 @@ __global__ __launch_bounds__(256) void softcorr_bwd_prep_kernel(const float *__r
         own[u] = 0.f;
     }
     float G = 0.f;
+    for (int t = 0; t < topk; ++t) G += gval[(size_t)row * topk + t] * pi_val[(size_t)row * topk + t];
+    const int wpr = (M + 31) >> 5;
     for (int t = 0; t < topk; ++t) {
         const int j = pi_idx[(size_t)row * topk + t];
-        const float gp = gval[(size_t)row * topk + t] * pi_val[(size_t)row * topk + t];
-        G += gp;
-        if (j < 0 || j >= M || gp == 0.f) continue;  // uniform over the wave
+        if (j < 0 || j >= M) continue;  // uniform over the wave
+        if (lane == 0) atomicOr(topk_bits + (size_t)row * wpr + (j >> 5), 1u << (j & 31));
+        // both terms of the entry, on the forward's P: [j = idx_t] gp_t - val_t G = 0 where the row is one-hot
+        const float val = pi_val[(size_t)row * topk + t];
+        const float ds = fmaf(-val, G, gval[(size_t)row * topk + t] * val);
+        if (ds == 0.f) continue;
+        const float gp = ds;
         const float *x = f2 + ((size_t)b * M + j) * d;
         float dx[8], part = 0.f;
 #pragma unroll
@@ -337,7 +422,8 @@ using namespace dvm;
 
 DVM_EXPORT size_t dvm_softcorr_bwd_workspace_bytes(int B, int N, int M, int d) {
     (void)d;
-    return 3 * align_up((size_t)B * N * sizeof(float)) + align_up((size_t)B * M * sizeof(float));
+    return 3 * align_up((size_t)B * N * sizeof(float)) + align_up((size_t)B * M * sizeof(float)) +
+           align_up((size_t)B * N * ((M + 31) / 32) * sizeof(uint32_t));
 }
 
 DVM_EXPORT int dvm_softcorr_bwd_f32(const float *f1, const float *f2, int B, int N, int M, int d, float neg_alpha, int topk,
@@ -356,6 +442,8 @@ DVM_EXPORT int dvm_softcorr_bwd_f32(const float *f1, const float *f2, int B, int
     float *coef = ar.take<float>((size_t)B * N);
     float *c2 = ar.take<float>((size_t)B * N);
     float *n2 = ar.take<float>((size_t)B * M);
+    const int wpr = (M + 31) / 32;
+    uint32_t *bits = ar.take<uint32_t>((size_t)B * N * wpr);
     if (!ar.ok()) {
         set_error("dvm_softcorr_bwd_f32: workspace too small (%zu < %zu)", ws_bytes, ar.off);
         return DVM_ENOSPACE;
@@ -363,10 +451,11 @@ DVM_EXPORT int dvm_softcorr_bwd_f32(const float *f1, const float *f2, int B, int
     hipStream_t s = (hipStream_t)stream;
     (void)hipMemsetAsync(d_f1, 0, (size_t)B * N * d * sizeof(float), s);
     (void)hipMemsetAsync(d_f2, 0, (size_t)B * M * d * sizeof(float), s);
+    (void)hipMemsetAsync(bits, 0, (size_t)B * N * wpr * sizeof(uint32_t), s);
     launch_rownorm2(f1, B * N, d, n1, s);
     launch_rownorm2(f2, B * M, d, n2, s);
     hipLaunchKernelGGL(softcorr_bwd_prep_kernel, dim3((unsigned)(((size_t)B * N + 3) / 4)), dim3(256), 0, s, f1, f2, pi_val, pi_idx,
-                       g_val, row_smax, row_sum, B, N, M, d, topk, neg_alpha, coef, c2, d_f1, d_f2);
+                       g_val, row_smax, row_sum, B, N, M, d, topk, neg_alpha, coef, c2, bits, d_f1, d_f2);
     const float a2 = neg_alpha * LOG2E;
     const bool mfma = (variant == 2) || (variant == 0 && d == BW_D);
     if (mfma) {
@@ -378,6 +467,8 @@ DVM_EXPORT int dvm_softcorr_bwd_f32(const float *f1, const float *f2, int B, int
         const int min_tiles = (std::min(N, M) + BW_KT - 1) / BW_KT;
         while (base * split < 512 && split < 8 && min_tiles / (2 * split) >= 4) split *= 2;
         a.split = split;
+        a.topk_bits = bits;
+        a.wpr = wpr;
         a.blocks0 = B * a.g[0].tiles_o * split;
         a.a2 = a2;
         ensure_dyn_lds((const void *)softcorr_bwd_mfma_kernel, (int)BW_LDS_BYTES);
@@ -388,6 +479,8 @@ DVM_EXPORT int dvm_softcorr_bwd_f32(const float *f1, const float *f2, int B, int
         a.g[1] = SBGroup{f2, f1, n2, n1, nullptr, nullptr, c2, coef, d_f2, M, N, 0};
         a.rows0 = (long)B * N;
         a.rows_total = (long)B * N + (long)B * M;
+        a.topk_bits = bits;
+        a.wpr = wpr;
         a.d = d;
         a.a2 = a2;
         const size_t rows = (size_t)B * N + (size_t)B * M;

@@ -257,7 +257,9 @@ def softcorr(f1, f2, alpha, topk=10, variant=0, stats=True):
 
 
 def softcorr_bwd(f1, f2, alpha, val, idx, smax, ssum, gval, variant=0):
-    """Backward of softcorr: gval (B,N,topk) -> (d_f1 (B,N,d), d_f2 (B,M,d))."""
+    """Backward of softcorr: gval (B,N,topk) -> (d_f1 (B,N,d), d_f2 (B,M,d)).  val / idx / smax / ssum are softcorr's outputs for
+    the same f1, f2, alpha: a row's in-range columns must be distinct (repeated slots carry val 0, as softcorr writes them at
+    M < topk), since each slot's entry takes both terms of dL/dS."""
     _need_gpu(f1, f2, gval)
     f1, f2, gval, val = _f(f1), _f(f2), _f(gval), _f(val)
     B, N, d = f1.shape
