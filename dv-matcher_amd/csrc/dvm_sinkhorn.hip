@@ -1,0 +1,506 @@
+// dvm_sinkhorn.hip — Sinkhorn-normalised soft correspondence, forward, sparse top-k.
+//
+// NOT in the reference (the reference has a row softmax only).  With S_ij = cdist(f1, f2)_ij * neg_alpha,
+// formed exactly as dvm_softcorr_fwd_f32 forms it, the operator alternates
+//     u_i = -LSE_j(S_ij + v_j)                (rows of P = exp(S + u + v) sum to 1)
+//     v_j = log(N / M) - LSE_i(S_ij + u_i)    (columns sum to N / M)
+// n_iter times from v = 0 and ends with a row step that also keeps the top-k of L_ij = S_ij + v_j per row.  n_iter = 0
+// is the reference's operator (v = 0, one row softmax): that case is pinned to dvm_softcorr_fwd_f32, which is pinned to
+// the reference.
+//
+// One kernel does every step: a workgroup owns 256 "query" rows (8 waves x 32), streams all "key" rows through a
+// double-buffered, k-deinterleaved LDS tile together with the keys' |.|^2 and potential, forms the squared-distance tile
+// on the fp32 matrix cores (the k-ordered fma chain of torch.cdist's matmul form, as softcorr_mfma_kernel does) and keeps
+// an online (max, sum) of L per query row in registers.  The row step is (queries, keys, potential) = (f1, f2, v), the
+// column step the same kernel with (f2, f1, u): every potential is owned by one lane pair, so there are no float atomics
+// and two runs give the same bits.  The N x M matrix is never written to HBM; the potentials (4 (N + M) bytes per entry)
+// live in L2.
+//
+// Every candidate takes the exact path (correctly rounded sqrt, s = d * neg_alpha, L = s + v): the potentials are
+// compared against a float64 evaluation at a few fp32 roundings of max |S|, which leaves no room for the 1-ulp hardware
+// sqrt under alpha = 100.  The running sum is kept in fp64 (one add per 16 candidates), so that its error does not grow
+// with the number of key tiles.
+#include <float.h>
+#include <math.h>
+
+#include "dvm_common.h"
+
+namespace dvm {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+void launch_rownorm2(const float *x, int rows, int K, float *out, hipStream_t s);   // dvm_softcorr.hip
+
+namespace {
+
+constexpr float SK_LOG2E = 1.4426950408889634f;
+
+// running (max, sum exp(. - max)) of one row
+struct LseState {
+    float m;    // running max of L (-inf initially)
+    double l;   // sum exp(L - m)
+    __device__ __forceinline__ void init() {
+        m = -INFINITY;
+        l = 0.0;
+    }
+    __device__ __forceinline__ void rescale(float new_m) {
+        if (new_m > m) {
+            l = l * (double)__builtin_amdgcn_exp2f((m - new_m) * SK_LOG2E);   // m = -inf, l = 0 -> 0 * 0
+            m = new_m;
+        }
+    }
+    // the shift the terms are taken against: finite even while every L seen so far is -inf (padding columns only), so that
+    // L - shift is -inf and the term 0 instead of (-inf) - (-inf)
+    __device__ __forceinline__ float shift() const { return fmaxf(m, -FLT_MAX); }
+    __device__ __forceinline__ void merge(float om, double ol) {
+        const float mm = fmaxf(m, om);
+        const double a = (m == -INFINITY) ? 0.0 : l * (double)exp2f((m - mm) * SK_LOG2E);
+        const double b = (om == -INFINITY) ? 0.0 : ol * (double)exp2f((om - mm) * SK_LOG2E);
+        l = a + b;
+        m = mm;
+    }
+};
+
+// top-k list of a final row sweep.  With a potential the key is -L (ascending = descending logit, ties -> lowest column);
+// without one (n_iter = 0: L = d * neg_alpha, a monotone function of d) the key is the distance itself, as
+// dvm_softcorr_fwd_f32 ranks — two distances that round to one logit stay in distance order, which is what that
+// operator returns.
+template <int TOPK>
+__device__ __forceinline__ void store_final(const KBest<TOPK, float> &kb, bool hasv, const LseState &st, int topk, int M, float neg_alpha,
+                                            float *val, int32_t *idx, float *row_lmax, float *row_sum, float *u) {
+    const float lmax = hasv ? -kb.key[0] : kb.key[0] * neg_alpha;   // = st.m: every candidate went through the same L
+    const float lsum = (float)st.l;
+    const float inv = 1.0f / lsum;
+#pragma unroll
+    for (int t = 0; t < TOPK; ++t) {
+        if (t < topk) {
+            const bool live = t < M;
+            const float L = hasv ? -kb.key[t] : kb.key[t] * neg_alpha;
+            val[t] = live ? exp2f((L - lmax) * SK_LOG2E) * inv : 0.f;
+            idx[t] = live ? kb.idx[t] : 0;
+        }
+    }
+    if (row_lmax) *row_lmax = lmax;
+    if (row_sum) *row_sum = lsum;
+    if (u) *u = -(lmax + logf(lsum));
+}
+
+struct SKArgs {
+    const float *q, *k;     // queries [B][N][d], keys [B][M][d]
+    const float *nq, *nk;   // their |.|^2
+    const float *pot;       // the keys' potential [B][M]; NULL = 0
+    int N, M, d, tiles;     // tiles = query blocks per entry
+    float neg_alpha;
+    float add;              // potential sweep: out = add - LSE (0 for the row step, log(N / M) for the column step)
+    float *out;             // potential sweep: the queries' new potential [B][N]
+    int topk;               // final row sweep
+    float *val;
+    int32_t *idx;
+    float *lmax, *sum, *u;
+};
+
+// ------------------------------------------------------------ scalar variant
+// One thread per query row, keys staged through LDS in tiles of 32, the dot product an explicit k-ordered fmaf chain.
+// Any d % 4 == 0.  The cross-check form of the matrix-core kernel and the path for d != 128; not tuned.
+constexpr int SS_KT = 32;
+constexpr int SS_DC = 32;
+
+// SWAP: the queries are f2 (column step).  cdist adds |f1|^2 first: d2 = (acc + |f1_i|^2) + |f2_j|^2 in either direction,
+// so that a step and its transpose see the same S_ij bit for bit.
+template <bool FINAL, bool SWAP, int TOPK>
+__global__ __launch_bounds__(128) void sinkhorn_scalar_kernel(const SKArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];   // [SS_KT][d] keys + [SS_KT] norms + [SS_KT] potentials
+    const int N = a.N, M = a.M, d = a.d;
+    float *kt = smem;
+    float *kn = smem + SS_KT * d;
+    float *kp = kn + SS_KT;
+    const int b = blockIdx.y;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int ic = i < N ? i : N - 1;
+    const float *q = a.q + ((size_t)b * N + ic) * d;
+    const float na = a.nq[(size_t)b * N + ic];
+    const float *kbase = a.k + (size_t)b * M * d;
+    const bool hasv = a.pot != nullptr;
+    const float neg_alpha = a.neg_alpha;
+    LseState st;
+    st.init();
+    KBest<TOPK, float> kb;
+    if (FINAL) kb.init(INFINITY);
+    for (int j0 = 0; j0 < M; j0 += SS_KT) {
+        __syncthreads();
+        for (int e = threadIdx.x; e < SS_KT * d / 4; e += blockDim.x) {
+            int r = e / (d / 4), c = e % (d / 4);
+            f32x4 v = {0.f, 0.f, 0.f, 0.f};
+            if (j0 + r < M) v = *(const f32x4 *)(kbase + (size_t)(j0 + r) * d + 4 * c);
+            *(f32x4 *)(kt + r * d + 4 * c) = v;
+        }
+        if (threadIdx.x < SS_KT) {
+            const int j = j0 + threadIdx.x;
+            kn[threadIdx.x] = j < M ? a.nk[(size_t)b * M + j] : INFINITY;
+            kp[threadIdx.x] = (j < M && hasv) ? a.pot[(size_t)b * M + j] : 0.f;
+        }
+        __syncthreads();
+        float acc[SS_KT];
+#pragma unroll
+        for (int j = 0; j < SS_KT; ++j) acc[j] = 0.f;
+        for (int c0 = 0; c0 < d; c0 += SS_DC) {
+            float qr[SS_DC];
+            int cw = d - c0 < SS_DC ? d - c0 : SS_DC;
+#pragma unroll
+            for (int c = 0; c < SS_DC; c += 4) {
+                f32x4 v = {0.f, 0.f, 0.f, 0.f};
+                if (c < cw) v = *(const f32x4 *)(q + c0 + c);
+                qr[c] = -2.f * v.x, qr[c + 1] = -2.f * v.y, qr[c + 2] = -2.f * v.z, qr[c + 3] = -2.f * v.w;
+            }
+#pragma unroll
+            for (int j = 0; j < SS_KT; ++j) {
+#pragma unroll
+                for (int c = 0; c < SS_DC; c += 4) {
+                    if (c < cw) {
+                        f32x4 kv = *(const f32x4 *)(kt + j * d + c0 + c);
+                        acc[j] = fmaf(qr[c], kv.x, acc[j]);
+                        acc[j] = fmaf(qr[c + 1], kv.y, acc[j]);
+                        acc[j] = fmaf(qr[c + 2], kv.z, acc[j]);
+                        acc[j] = fmaf(qr[c + 3], kv.w, acc[j]);
+                    }
+                }
+            }
+        }
+        float Lv[SS_KT], dv[SS_KT];
+        float tmax = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < SS_KT; ++j) {
+            float d2 = SWAP ? (acc[j] + kn[j]) + na : (acc[j] + na) + kn[j];
+            d2 = d2 > 0.f ? d2 : 0.f;
+            dv[j] = sqrt_rn(d2);
+            Lv[j] = dv[j] * neg_alpha + kp[j];
+            tmax = fmaxf(tmax, Lv[j]);
+        }
+        st.rescale(tmax);
+        const float sh = st.shift();
+        float ls = 0.f;
+#pragma unroll
+        for (int j = 0; j < SS_KT; ++j) {
+            ls += __builtin_amdgcn_exp2f((Lv[j] - sh) * SK_LOG2E);
+            if (FINAL) kb.insert(hasv ? -Lv[j] : dv[j], j0 + j);
+        }
+        st.l += (double)ls;
+    }
+    if (i < N) {
+        const size_t row = (size_t)b * N + i;
+        if (FINAL)
+            store_final<TOPK>(kb, hasv, st, a.topk, M, neg_alpha, a.val + row * a.topk, a.idx + row * a.topk,
+                              a.lmax ? a.lmax + row : nullptr, a.sum ? a.sum + row : nullptr, a.u ? a.u + row : nullptr);
+        else
+            a.out[row] = a.add - (st.m + logf((float)st.l));
+    }
+}
+
+// -------------------------------------------------------------- matrix-core variant (d == 128)
+// Tile shapes, LDS layout and the two-role phase structure are those of softcorr_mfma_kernel (dvm_softcorr.hip): the
+// accumulator tile is [key][query], so a query's 16 candidates of a 32-key sub-tile sit in one lane's registers and the
+// online (max, sum) and the top-k list need no cross-lane traffic until the two half-lanes of a query merge at the end.
+constexpr int SK_D = 128;
+constexpr int SK_KT = 64;             // keys per LDS tile (two 32-key MFMA sub-tiles)
+constexpr int SK_LDK = SK_D + 4;      // padded row (floats): 528 B, keeps ds_read_b128 conflict-free
+constexpr int SK_QW = 32;             // queries per wave
+constexpr int SK_WAVES = 8;
+constexpr int SK_QB = SK_QW * SK_WAVES;   // 256 queries per workgroup
+constexpr int SK_THREADS = 64 * SK_WAVES;
+constexpr int SK_LD_PER_THREAD = SK_KT * SK_D / 4 / SK_THREADS;   // float4 loads per thread per tile = 8
+constexpr int SK_TILE_FLOATS = SK_KT * SK_LDK + 2 * SK_KT;        // keys + their norms + their potentials
+constexpr int SK_STAGE = 16 * 64;   // final row sweep, floats per wave: this sub-tile's 16 ranking keys of each lane, [r][lane]
+constexpr size_t SK_LDS_BYTES = (size_t)2 * SK_TILE_FLOATS * sizeof(float);
+constexpr size_t SK_LDS_BYTES_FINAL = SK_LDS_BYTES + (size_t)SK_WAVES * SK_STAGE * sizeof(float);
+
+// FINAL: the last row sweep (top-k, pi_val / pi_idx / row_lmax / row_sum / u); HASV (FINAL only): rank by -L, else by d.
+template <bool FINAL, bool HASV, bool SWAP, int TOPK>
+__global__ __launch_bounds__(SK_THREADS, 2) void sinkhorn_mfma_kernel(const SKArgs a) {
+    // [2] x { [SK_KT][SK_LDK] keys, [SK_KT] norms, [SK_KT] potentials }; FINAL: + [SK_WAVES][16][64] ranking keys
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float *const stage = smem + 2 * SK_TILE_FLOATS + (threadIdx.x >> 6) * SK_STAGE + (threadIdx.x & 63);   // this lane's column
+
+    const int lid = xcd_remap(blockIdx.x, gridDim.x);
+    const int N = a.N, M = a.M;
+    const int b = lid / a.tiles;
+    const int qt = lid % a.tiles;
+    const float neg_alpha = a.neg_alpha;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r32 = lane & 31, h = lane >> 5;
+
+    const float *kbase = a.k + (size_t)b * M * SK_D;
+    const float *knb = a.nk + (size_t)b * M;
+    const float *kpb = a.pot ? a.pot + (size_t)b * M : nullptr;
+
+    // this lane's query row and its B-operand fragment: q[s] = -2 * query[row][2s + h]
+    const int qrow = qt * SK_QB + wave * SK_QW + r32;
+    const int qrc = qrow < N ? qrow : N - 1;
+    const float *qp = a.q + ((size_t)b * N + qrc) * SK_D;
+    float q[SK_D / 2];
+#pragma unroll
+    for (int c = 0; c < SK_D / 4; ++c) {
+        f32x4 v = *(const f32x4 *)(qp + 4 * c);
+        q[2 * c] = -2.f * (h ? v.y : v.x);
+        q[2 * c + 1] = -2.f * (h ? v.w : v.z);
+    }
+    const float na = a.nq[(size_t)b * N + qrc];
+
+    LseState st;
+    st.init();
+    KBest<TOPK, float> kb;
+    if (FINAL) kb.init(INFINITY);
+
+    const int ntiles = (M + SK_KT - 1) / SK_KT;
+    f32x4 pre[SK_LD_PER_THREAD];
+    float pren = 0.f;   // threads 0..63: a key's norm; threads 64..127: a key's potential
+
+    auto issue_loads = [&](int t) {
+        const int j0 = t * SK_KT;
+#pragma unroll
+        for (int e = 0; e < SK_LD_PER_THREAD; ++e) {
+            int id = tid + e * SK_THREADS;
+            int r = id >> 5, c = id & 31;   // 32 float4 per 128-float row
+            f32x4 v = {0.f, 0.f, 0.f, 0.f};
+            if (j0 + r < M) v = *(const f32x4 *)(kbase + (size_t)(j0 + r) * SK_D + 4 * c);
+            pre[e] = v;
+        }
+        if (tid < SK_KT)
+            pren = (j0 + tid < M) ? knb[j0 + tid] : INFINITY;
+        else if (tid < 2 * SK_KT)
+            pren = (kpb && j0 + tid - SK_KT < M) ? kpb[j0 + tid - SK_KT] : 0.f;
+    };
+    auto commit_loads = [&](int buf) {
+        float *kt = smem + buf * SK_TILE_FLOATS;
+#pragma unroll
+        for (int e = 0; e < SK_LD_PER_THREAD; ++e) {
+            int id = tid + e * SK_THREADS;
+            int r = id >> 5, c = id & 31;
+            // k = 4c+{0,1,2,3} -> (h,s) = (0,2c) (1,2c) (0,2c+1) (1,2c+1)
+            float2 ev = {pre[e].x, pre[e].z}, od = {pre[e].y, pre[e].w};
+            *(float2 *)(kt + r * SK_LDK + 2 * c) = ev;
+            *(float2 *)(kt + r * SK_LDK + 64 + 2 * c) = od;
+        }
+        if (tid < 2 * SK_KT) kt[SK_KT * SK_LDK + tid] = pren;   // norms, then potentials
+    };
+
+    issue_loads(0);
+    commit_loads(0);
+    __syncthreads();
+
+    // Two waves share a SIMD (w and w + 4).  Both alternate a matrix phase (64 dependent MFMAs) with an epilogue of
+    // comparable length; waves 4-7 (role 1) defer the epilogue of each tile's second sub-tile across the barrier, so that
+    // after every barrier one wave of the SIMD starts on the matrix pipe and its partner in the epilogue.  Every wave
+    // still folds its sub-tiles in ascending key order: a row's result does not depend on the wave that owns it.
+    const int role = __builtin_amdgcn_readfirstlane(wave >> 2);
+
+    auto mfma_chain = [&](const float *kt, int sub, f32x16 &acc, float (&nbv)[16], float (&pv)[16]) {
+        const float *arow = kt + (sub * 32 + r32) * SK_LDK + h * 64;
+        acc = f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int c = 0; c < 16; ++c) {
+            f32x4 av = *(const f32x4 *)(arow + 4 * c);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, q[4 * c], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, q[4 * c + 1], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, q[4 * c + 2], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, q[4 * c + 3], acc, 0, 0, 0);
+        }
+        // |key|^2 and potential of this lane's 16 keys: local key = (r&3) + 8*(r>>2) + 4*h
+        const float *kn = kt + SK_KT * SK_LDK + sub * 32 + 4 * h;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            f32x4 nb = *(const f32x4 *)(kn + 8 * g);
+            nbv[4 * g] = nb.x, nbv[4 * g + 1] = nb.y, nbv[4 * g + 2] = nb.z, nbv[4 * g + 3] = nb.w;
+            f32x4 pb = *(const f32x4 *)(kn + SK_KT + 8 * g);
+            pv[4 * g] = pb.x, pv[4 * g + 1] = pb.y, pv[4 * g + 2] = pb.z, pv[4 * g + 3] = pb.w;
+        }
+    };
+
+    auto epilogue = [&](const f32x16 &acc, const float (&nbv)[16], const float (&pv)[16], int jbase) {
+        float Lv[16];
+        unsigned mask = 0;
+        const float worst = FINAL ? kb.key[TOPK - 1] : 0.f;
+        float tmax = -INFINITY;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            float d2 = SWAP ? (acc[r] + nbv[r]) + na : (acc[r] + na) + nbv[r];   // +inf for padding keys
+            d2 = d2 > 0.f ? d2 : 0.f;
+            const float de = sqrt_rn(d2);
+            const float L = de * neg_alpha + pv[r];   // (-ffp-contract=off: a product, then a sum)
+            Lv[r] = L;
+            if (FINAL) {   // the ranking keys are parked in LDS ([r][lane], conflict-free) for the dynamic pick below
+                const float key = HASV ? -L : de;
+                stage[r * 64] = key;
+                mask |= (key < worst) ? (1u << r) : 0u;
+            }
+            tmax = fmaxf(tmax, L);
+        }
+        st.rescale(tmax);
+        const float sh = st.shift();
+        float ls = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) ls += __builtin_amdgcn_exp2f((Lv[r] - sh) * SK_LOG2E);
+        st.l += (double)ls;
+        if (FINAL) {
+            // candidates that beat this lane's current worst, in ascending column order; a counted, wave-uniform loop
+            // with a branch-free body keeps the list in its registers
+            const int iters = (int)__reduce_max_sync(~0ull, (unsigned)__popc(mask));
+            for (int it = 0; it < iters; ++it) {
+                const bool act = mask != 0;
+                const int bpos = act ? (__ffs(mask) - 1) : 0;
+                mask &= mask - 1;
+                const float key = act ? stage[bpos * 64] : INFINITY;
+                kb.insert_nb(key, jbase + (bpos & 3) + 8 * (bpos >> 2));
+            }
+        }
+    };
+
+    // the 16-entry list leaves no room for the next tile's 32 prefetch registers next to it: that variant loads the tile after
+    // its epilogues (the other wave of the SIMD covers the latency) instead of spilling
+    constexpr bool LATE_LOADS = FINAL && TOPK > 10;
+    f32x16 acc;
+    float nbv[16], pv[16];
+    for (int t = 0; t < ntiles; ++t) {
+        const int buf = t & 1;
+        if (!LATE_LOADS && t + 1 < ntiles) issue_loads(t + 1);
+        const float *kt = smem + buf * SK_TILE_FLOATS;
+        if (role == 1 && t > 0) epilogue(acc, nbv, pv, (t - 1) * SK_KT + 32 + 4 * h);   // the previous tile's second sub-tile
+        mfma_chain(kt, 0, acc, nbv, pv);
+        epilogue(acc, nbv, pv, t * SK_KT + 4 * h);
+        mfma_chain(kt, 1, acc, nbv, pv);
+        if (role == 0) epilogue(acc, nbv, pv, t * SK_KT + 32 + 4 * h);
+        if (LATE_LOADS && t + 1 < ntiles) issue_loads(t + 1);
+        if (t + 1 < ntiles) commit_loads(buf ^ 1);
+        __syncthreads();
+    }
+    if (role == 1) epilogue(acc, nbv, pv, (ntiles - 1) * SK_KT + 32 + 4 * h);
+
+    // merge the two half-lanes that share a query (lane, lane ^ 32); the lower lane writes the row
+    {
+        const float om = __shfl_xor(st.m, 32, 64);
+        const double ol = __shfl_xor(st.l, 32, 64);
+        st.merge(om, ol);
+    }
+    if (FINAL) {
+        float ok[TOPK];
+        int oi[TOPK];
+#pragma unroll
+        for (int t = 0; t < TOPK; ++t) {
+            ok[t] = __shfl_xor(kb.key[t], 32, 64);
+            oi[t] = __shfl_xor(kb.idx[t], 32, 64);
+        }
+#pragma unroll
+        for (int t = 0; t < TOPK; ++t) kb.insert_lex(ok[t], oi[t]);
+    }
+    if (h == 0 && qrow < N) {
+        const size_t row = (size_t)b * N + qrow;
+        if (FINAL)
+            store_final<TOPK>(kb, HASV, st, a.topk, M, neg_alpha, a.val + row * a.topk, a.idx + row * a.topk,
+                              a.lmax ? a.lmax + row : nullptr, a.sum ? a.sum + row : nullptr, a.u ? a.u + row : nullptr);
+        else
+            a.out[row] = a.add - (st.m + logf((float)st.l));
+    }
+}
+
+template <bool FINAL, bool HASV, bool SWAP, int TOPK>
+void launch_mfma(const SKArgs &a, int B, hipStream_t s) {
+    const size_t lds = FINAL ? SK_LDS_BYTES_FINAL : SK_LDS_BYTES;
+    ensure_dyn_lds((const void *)sinkhorn_mfma_kernel<FINAL, HASV, SWAP, TOPK>, (int)lds);
+    hipLaunchKernelGGL((sinkhorn_mfma_kernel<FINAL, HASV, SWAP, TOPK>), dim3((unsigned)(B * a.tiles)), dim3(SK_THREADS), lds, s, a);
+}
+
+template <bool FINAL, bool SWAP, int TOPK>
+void launch_scalar(const SKArgs &a, int B, hipStream_t s) {
+    const size_t lds = (size_t)(SS_KT * a.d + 2 * SS_KT) * sizeof(float);
+    ensure_dyn_lds((const void *)sinkhorn_scalar_kernel<FINAL, SWAP, TOPK>, 66 * 1024);
+    hipLaunchKernelGGL((sinkhorn_scalar_kernel<FINAL, SWAP, TOPK>), dim3((a.N + 127) / 128, B), dim3(128), lds, s, a);
+}
+
+// one potential sweep: out [B][Nq] = add - LSE_keys(S + pot)
+void launch_sweep(bool mfma, bool swap, SKArgs a, int B, hipStream_t s) {
+    if (mfma) {
+        a.tiles = (a.N + SK_QB - 1) / SK_QB;
+        if (swap)
+            launch_mfma<false, true, true, 1>(a, B, s);
+        else
+            launch_mfma<false, true, false, 1>(a, B, s);
+    } else {
+        if (swap)
+            launch_scalar<false, true, 1>(a, B, s);
+        else
+            launch_scalar<false, false, 1>(a, B, s);
+    }
+}
+
+template <int TOPK>
+void launch_final(bool mfma, SKArgs a, int B, hipStream_t s) {
+    if (mfma) {
+        a.tiles = (a.N + SK_QB - 1) / SK_QB;
+        if (a.pot)
+            launch_mfma<true, true, false, TOPK>(a, B, s);
+        else
+            launch_mfma<true, false, false, TOPK>(a, B, s);
+    } else {
+        launch_scalar<true, false, TOPK>(a, B, s);
+    }
+}
+
+}  // namespace
+}  // namespace dvm
+
+using namespace dvm;
+
+DVM_EXPORT size_t dvm_sinkhorn_workspace_bytes(int B, int N, int M, int d) {
+    (void)d;
+    if (B < 1 || N < 1 || M < 1) return 0;
+    // |f1|^2, |f2|^2 and the two potentials (used when the caller does not ask for u / v)
+    return 2 * (align_up((size_t)B * N * sizeof(float)) + align_up((size_t)B * M * sizeof(float)));
+}
+
+DVM_EXPORT int dvm_sinkhorn_fwd_f32(const float *f1, const float *f2, int B, int N, int M, int d, float neg_alpha, int n_iter,
+                                    int topk, float *pi_val, int32_t *pi_idx, float *row_lmax, float *row_sum, float *u, float *v,
+                                    int variant, void *ws, size_t ws_bytes, void *stream) {
+    DVM_REQUIRE(f1 && f2 && pi_val && pi_idx, "dvm_sinkhorn_fwd_f32: null pointer");
+    DVM_REQUIRE(B >= 1 && N >= 1 && M >= 1, "dvm_sinkhorn_fwd_f32: empty input (B=%d N=%d M=%d)", B, N, M);
+    DVM_REQUIRE(d >= 4 && d % 4 == 0 && d <= 512, "dvm_sinkhorn_fwd_f32: d=%d unsupported (need d%%4==0, 4<=d<=512)", d);
+    DVM_REQUIRE(topk >= 1 && topk <= 16, "dvm_sinkhorn_fwd_f32: topk=%d unsupported (1..16)", topk);
+    DVM_REQUIRE(n_iter >= 0, "dvm_sinkhorn_fwd_f32: n_iter=%d must not be negative", n_iter);
+    DVM_REQUIRE(neg_alpha < 0.f, "dvm_sinkhorn_fwd_f32: neg_alpha must be negative (got %g)", (double)neg_alpha);
+    DVM_REQUIRE(variant == 0 || variant == 1, "dvm_sinkhorn_fwd_f32: bad variant %d (0 = auto, 1 = scalar)", variant);
+    Arena ar(ws, ws_bytes);
+    float *n1 = ar.take<float>((size_t)B * N);
+    float *n2 = ar.take<float>((size_t)B * M);
+    float *wu = ar.take<float>((size_t)B * N);
+    float *wv = ar.take<float>((size_t)B * M);
+    if (!ar.ok()) {
+        set_error("dvm_sinkhorn_fwd_f32: workspace too small (%zu < %zu)", ws_bytes, ar.off);
+        return DVM_ENOSPACE;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    float *ub = u ? u : wu, *vb = v ? v : wv;
+    const bool mfma = variant == 0 && d == SK_D;
+    launch_rownorm2(f1, B * N, d, n1, s);
+    launch_rownorm2(f2, B * M, d, n2, s);
+    if (n_iter == 0 && v) (void)hipMemsetAsync(v, 0, (size_t)B * M * sizeof(float), s);
+    const float log_ratio = (float)log((double)N / (double)M);
+    SKArgs row{}, col{};
+    row.q = f1, row.k = f2, row.nq = n1, row.nk = n2, row.N = N, row.M = M, row.d = d, row.neg_alpha = neg_alpha;
+    col.q = f2, col.k = f1, col.nq = n2, col.nk = n1, col.N = M, col.M = N, col.d = d, col.neg_alpha = neg_alpha;
+    for (int it = 0; it < n_iter; ++it) {
+        row.pot = it ? vb : nullptr;   // v = 0 before the first row step: nothing is read from the buffer
+        row.add = 0.f, row.out = ub;
+        launch_sweep(mfma, false, row, B, s);
+        col.pot = ub;
+        col.add = log_ratio, col.out = vb;
+        launch_sweep(mfma, true, col, B, s);
+    }
+    row.pot = n_iter ? vb : nullptr;
+    row.out = nullptr;
+    row.topk = topk, row.val = pi_val, row.idx = pi_idx, row.lmax = row_lmax, row.sum = row_sum, row.u = u;
+    if (topk <= 10)
+        launch_final<10>(mfma, row, B, s);
+    else
+        launch_final<16>(mfma, row, B, s);
+    DVM_CHECK_LAUNCH("sinkhorn");
+    return DVM_OK;
+}

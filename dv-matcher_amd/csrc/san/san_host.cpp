@@ -33,6 +33,7 @@ int main() {
                g = dvm_chamfer_workspace_bytes(B, N, M), h = dvm_dg_build_workspace_bytes(B, N), i = dvm_deformer_workspace_bytes(B, N, M, 10);
         EXPECT(a > 0 && b > 0 && c > 0 && d >= (size_t)B * N * M * 4 && e > 0 && f > 0 && g > 0 && h > 0 && i > 0);
         EXPECT(b >= c / 2);
+        EXPECT(dvm_sinkhorn_workspace_bytes(B, N, M, 128) >= (size_t)8 * B * ((size_t)N + M));   // norms + potentials of both sides
         (void)prev;
         prev = b;
     }
@@ -45,6 +46,23 @@ int main() {
     EXPECT(strlen(dvm_last_error()) > 0);
     EXPECT(dvm_softcorr_fwd_f32(dummy, dummy, 1, 8, 8, 128, +1.f, 10, dummy, idummy, dummy, dummy, 0, dummy, 64, nullptr) == DVM_EINVAL);   // alpha sign
     EXPECT(dvm_softcorr_fwd_f32(dummy, dummy, 1, 8, 8, 128, -1.f, 99, dummy, idummy, dummy, dummy, 0, dummy, 64, nullptr) == DVM_EINVAL);   // topk range
+    // dvm_sinkhorn_fwd_f32: every rejection path, then a workspace one byte short of what the query asks for
+    const size_t skb = dvm_sinkhorn_workspace_bytes(1, 8, 8, 128);
+    std::vector<char> skws(skb);
+    EXPECT(dvm_sinkhorn_workspace_bytes(0, 8, 8, 128) == 0);
+    EXPECT(dvm_sinkhorn_fwd_f32(nullptr, nullptr, 1, 8, 8, 128, -1.f, 5, 10, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr) == DVM_EINVAL);
+    EXPECT(strstr(dvm_last_error(), "null pointer") != nullptr);
+    EXPECT(dvm_sinkhorn_fwd_f32(dummy, dummy, 0, 8, 8, 128, -1.f, 5, 10, dummy, idummy, dummy, dummy, dummy, dummy, 0, skws.data(), skb, nullptr) == DVM_EINVAL);   // empty
+    EXPECT(dvm_sinkhorn_fwd_f32(dummy, dummy, 1, 8, 8, 130, -1.f, 5, 10, dummy, idummy, dummy, dummy, dummy, dummy, 0, skws.data(), skb, nullptr) == DVM_EINVAL);   // d
+    EXPECT(dvm_sinkhorn_fwd_f32(dummy, dummy, 1, 8, 8, 516, -1.f, 5, 10, dummy, idummy, dummy, dummy, dummy, dummy, 0, skws.data(), skb, nullptr) == DVM_EINVAL);   // d too large
+    EXPECT(dvm_sinkhorn_fwd_f32(dummy, dummy, 1, 8, 8, 128, -1.f, 5, 17, dummy, idummy, dummy, dummy, dummy, dummy, 0, skws.data(), skb, nullptr) == DVM_EINVAL);   // topk range
+    EXPECT(dvm_sinkhorn_fwd_f32(dummy, dummy, 1, 8, 8, 128, -1.f, 5, 0, dummy, idummy, dummy, dummy, dummy, dummy, 0, skws.data(), skb, nullptr) == DVM_EINVAL);
+    EXPECT(dvm_sinkhorn_fwd_f32(dummy, dummy, 1, 8, 8, 128, -1.f, -1, 10, dummy, idummy, dummy, dummy, dummy, dummy, 0, skws.data(), skb, nullptr) == DVM_EINVAL);  // n_iter
+    EXPECT(dvm_sinkhorn_fwd_f32(dummy, dummy, 1, 8, 8, 128, 0.f, 5, 10, dummy, idummy, dummy, dummy, dummy, dummy, 0, skws.data(), skb, nullptr) == DVM_EINVAL);    // alpha sign
+    EXPECT(dvm_sinkhorn_fwd_f32(dummy, dummy, 1, 8, 8, 128, -1.f, 5, 10, dummy, idummy, dummy, dummy, dummy, dummy, 7, skws.data(), skb, nullptr) == DVM_EINVAL);   // variant
+    EXPECT(dvm_sinkhorn_fwd_f32(dummy, dummy, 1, 8, 8, 128, -1.f, 5, 10, dummy, idummy, nullptr, nullptr, nullptr, nullptr, 0, skws.data(), skb - 1, nullptr) == DVM_ENOSPACE);
+    EXPECT(strstr(dvm_last_error(), "workspace") != nullptr);
+    EXPECT(dvm_sinkhorn_fwd_f32(dummy, dummy, 1, 8, 8, 128, -1.f, 5, 10, dummy, idummy, dummy, dummy, dummy, dummy, 0, nullptr, 0, nullptr) == DVM_ENOSPACE);
     EXPECT(dvm_linear_f32(nullptr, dummy, 1, 4, 4, 4, 0, nullptr, nullptr, nullptr, nullptr, 1.f, dummy, nullptr) == DVM_EINVAL);
     EXPECT(dvm_linear_f32(dummy, dummy, 1, 4, 4, 4, 0, nullptr, nullptr, dummy, nullptr, 1.f, dummy, nullptr) == DVM_EINVAL);               // alpha without beta
     EXPECT(dvm_linear_f32(dummy, dummy, 1, 4, 100000, 4, 0, nullptr, nullptr, nullptr, nullptr, 1.f, dummy, nullptr) == DVM_EINVAL);        // K too large

@@ -8,6 +8,8 @@
 Default: the fused C-ABI path (dvm_pair_direction_fwd_f32, nothing N x M in HBM).  --reference-sequence runs the
 same steps one by one through the reference-named module API (models.loss / models.model / lib.*), dense Pi
 included; both must give the same points (tests/test_gpu_backbone.py::test_deform_driver).
+--sinkhorn T replaces Pi_12 by the Sinkhorn-normalised correspondence (models.loss.sinkhorn_pi, T iterations; not in the
+reference) and runs the same steps through the per-op calls.
 Features come from --pairs (.npz with verts1, verts2, feat1, feat2, name1, name2) or are synthetic.
 """
 import argparse
@@ -48,6 +50,19 @@ def deform_reference_sequence(deformer, feat1, feat2, verts1, verts2, alpha, sta
     return torch.cat(pts, dim=0)
 
 
+def deform_sinkhorn(deformer, feat1, feat2, verts1, verts2, alpha, start, n_iter, k_deform=10):
+    """The same deformation with Pi_12 = sinkhorn_pi(feat1, feat2): the per-op chain of GraphDeformLoss_Neural._direction."""
+    g1 = ops.dg_build(verts1, start)
+    pi = ml.sinkhorn_pi(feat1, feat2, alpha=alpha, n_iter=n_iter, topk=10)
+    idx11, idx22 = ops.knn_cdist(verts1, verts1, k_deform), ops.knn_cdist(verts2, verts2, k_deform)
+    verts12 = ops.apply(pi.val, pi.idx, verts2)
+    def9 = ops.deformer(deformer.weight_list(feat1.device), feat1, feat2, verts1, verts12, idx11, idx22, pi.val, pi.idx, g1["nodes_idx"])
+    iden = torch.tensor([1, 0, 0, 0, 1, 0], dtype=torch.float32, device=verts1.device).view(1, 1, 6)
+    R = ops.rot6d(def9[..., 3:] + iden)
+    warped, _, _ = ops.dg_warp_arap(verts1, g1, R, def9[..., :3].contiguous())
+    return warped
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", nargs="*", default=None)
@@ -58,6 +73,8 @@ def main(argv=None):
     ap.add_argument("--deformer-weights", default=os.path.join(HERE, "..", "tests", "golden", "deformer_scape_r_weights.npz"),
                     help="npz of the Deformer state_dict ('.' -> '__') or a .pth state_dict")
     ap.add_argument("--reference-sequence", action="store_true")
+    ap.add_argument("--sinkhorn", type=int, default=None, metavar="T",
+                    help="Pi_12 from T Sinkhorn iterations (models.loss.sinkhorn_pi) through the per-op calls; default: the row softmax")
     ap.add_argument("--out", default="result/deform_amd")
     args = ap.parse_args(argv)
     assert torch.cuda.is_available(), "the deformation path needs a HIP device"
@@ -86,8 +103,11 @@ def main(argv=None):
         for name1, name2, v1, v2, f1, f2 in items:
             v1, v2, f1, f2 = (t.to(dev)[None] for t in (v1, v2, f1, f2))
             start = torch.randint(0, v1.shape[1], (1,), generator=g)   # deform.py draws it inside FPS
-            fn = deform_reference_sequence if args.reference_sequence else deform_fused
-            warped = fn(deformer, f1, f2, v1, v2, args.alpha, start.to(dev))
+            if args.sinkhorn is not None:
+                warped = deform_sinkhorn(deformer, f1, f2, v1, v2, args.alpha, start.to(dev), args.sinkhorn)
+            else:
+                fn = deform_reference_sequence if args.reference_sequence else deform_fused
+                warped = fn(deformer, f1, f2, v1, v2, args.alpha, start.to(dev))
             path = os.path.join(args.out, "deform_%s_%s.off" % (name1, name2))
             ml.save_off_file(path, warped[0].cpu().numpy())
             files.append(path)

@@ -256,6 +256,32 @@ def softcorr(f1, f2, alpha, topk=10, variant=0, stats=True):
     return val, idx, smax, ssum
 
 
+def sinkhorn(f1, f2, alpha, n_iter, topk=10, variant=0, potentials=False):
+    """Sinkhorn-normalised soft correspondence (dvm_sinkhorn_fwd_f32; not in the reference): n_iter row / column normalisations
+    of exp(-alpha * cdist(f1, f2)) in the log domain, a final row step, the top-k of every row.  n_iter = 0 is softcorr.
+    f1 (B,N,d), f2 (B,M,d) -> pi_val (B,N,topk), pi_idx (B,N,topk) int32, row_lmax (B,N), row_sum (B,N)[, u (B,N), v (B,M)].
+    Forward only: there is no backward kernel yet, so inputs that require grad are refused while grad mode is on."""
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (f1, f2)):
+        raise DvmError("sinkhorn is forward only (no backward kernel): detach the features or call it under torch.no_grad()")
+    _need_gpu(f1, f2)
+    f1, f2 = _f(f1), _f(f2)
+    B, N, d = f1.shape
+    M = f2.shape[1]
+    lib = _lib.load()
+    dev = f1.device
+    val = torch.empty(B, N, topk, dtype=torch.float32, device=dev)
+    idx = torch.empty(B, N, topk, dtype=torch.int32, device=dev)
+    lmax = torch.empty(B, N, dtype=torch.float32, device=dev)
+    lsum = torch.empty(B, N, dtype=torch.float32, device=dev)
+    u = torch.empty(B, N, dtype=torch.float32, device=dev) if potentials else None
+    v = torch.empty(B, M, dtype=torch.float32, device=dev) if potentials else None
+    nb = lib.dvm_sinkhorn_workspace_bytes(B, N, M, d)
+    ws = workspace(nb, dev, "sinkhorn")
+    check(lib.dvm_sinkhorn_fwd_f32(_p(f1), _p(f2), B, N, M, d, neg_alpha_f32(alpha), int(n_iter), topk, _p(val), _p(idx), _p(lmax),
+                                   _p(lsum), _p(u), _p(v), variant, _p(ws), nb, _stream()), "dvm_sinkhorn_fwd_f32")
+    return (val, idx, lmax, lsum, u, v) if potentials else (val, idx, lmax, lsum)
+
+
 def softcorr_bwd(f1, f2, alpha, val, idx, smax, ssum, gval, variant=0):
     """Backward of softcorr: gval (B,N,topk) -> (d_f1 (B,N,d), d_f2 (B,M,d)).  val / idx / smax / ssum are softcorr's outputs for
     the same f1, f2, alpha: a row's in-range columns must be distinct (repeated slots carry val 0, as softcorr writes them at

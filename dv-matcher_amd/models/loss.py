@@ -109,6 +109,13 @@ class SparsePi:
         return ops.apply(self.val, self.idx, V)
 
 
+def sinkhorn_pi(x, y, alpha=100, n_iter=5, topk=10):
+    """Sinkhorn-normalised counterpart of topk_pi(knnsearch_t_grad(x, y, alpha)) as a SparsePi (ops.sinkhorn; not in the
+    reference): n_iter row / column normalisations keep many source points from sharing one target point.  Forward only."""
+    val, idx, _, _ = ops.sinkhorn(x, y, alpha, n_iter, topk=topk)
+    return SparsePi(val, idx, y.shape[1])
+
+
 def rank_term(pval, pidx, M):
     """||P P^T - I||_F per batch element for the sparse top-k correspondence P (val/idx (B,N,k), M columns) —
     models/loss.py:1427-1433 — without the dense (B,N,M) P or the (B,N,N) product:

@@ -176,6 +176,24 @@ int dvm_softcorr_fwd_f32(const float *f1, const float *f2, int B, int N, int M, 
                          float *pi_val, int32_t *pi_idx, float *row_smax, float *row_sum, int variant, void *ws,
                          size_t ws_bytes, void *stream);
 
+/* Sinkhorn-normalised soft correspondence, forward, sparse top-k.  NOT in the reference (which has the row softmax above
+ * only); pinned instead to dvm_softcorr_fwd_f32 at n_iter = 0 and to a float64 evaluation of this definition otherwise.
+ * With D = cdist(f1,f2) formed exactly as above and S = D*neg_alpha, per batch entry:
+ *   v = 0;  repeat n_iter times:  u_i = -LSE_j(S_ij + v_j);  v_j = log(N/M) - LSE_i(S_ij + u_i)
+ *   L_ij = S_ij + v_j;  row_lmax_i = max_j L_ij;  row_sum_i = sum_j exp(L_ij - row_lmax_i)
+ *   P_ij = exp(L_ij - row_lmax_i) / row_sum_i  (the last step is always a row step: rows of P sum to 1, columns approach N/M)
+ *   u_i  = -(row_lmax_i + log(row_sum_i)),  so that P_ij = exp(S_ij + u_i + v_j)
+ * pi_val / pi_idx [B,N,topk]: the topk largest of each row of P ranked by the logit L (descending, ties -> lowest column;
+ * at n_iter = 0 by the distance, as dvm_softcorr_fwd_f32 ranks), no renormalisation, slots beyond M as (0, 0).
+ * row_lmax, row_sum [B,N], u [B,N], v [B,M] may each be NULL.  n_iter = 0 returns what dvm_softcorr_fwd_f32 returns (and v = 0).
+ * A fixed iteration count, no float atomics, no host synchronisation: capturable, and bit-reproducible from run to run.
+ * f1 [B,N,d], f2 [B,M,d]; neg_alpha = (float)(-alpha) < 0; n_iter >= 0; 1 <= topk <= 16; d % 4 == 0, d <= 512.
+ * variant: 0 = auto (fp32-MFMA sweeps for d == 128, else the scalar kernel), 1 = scalar-FMA kernel.  Forward only. */
+size_t dvm_sinkhorn_workspace_bytes(int B, int N, int M, int d);
+int dvm_sinkhorn_fwd_f32(const float *f1, const float *f2, int B, int N, int M, int d, float neg_alpha, int n_iter,
+                         int topk, float *pi_val, int32_t *pi_idx, float *row_lmax, float *row_sum, float *u, float *v,
+                         int variant, void *ws, size_t ws_bytes, void *stream);
+
 /* Backward of dvm_softcorr_fwd_f32 (autograd through models/loss.py:110-114 + the top-k keep of
  * 1339-1347): given g_val [B,N,topk] = dL/d pi_val and the forward's outputs (pi_val, pi_idx, row_smax,
  * row_sum), writes d_f1 [B,N,d] and d_f2 [B,M,d] (overwritten, not accumulated).  The dense N x M term is
