@@ -10,9 +10,12 @@
 //     the 512-wide hidden layer is produced in two halves that layer 1 consumes immediately (split-K, its
 //     accumulators stay in registers), which is what lets 64 nodes fit: LDS = z/h1 (70 KB) + h0-half/h2 (66 KB).
 //   -> 0.6 MB of weights per 32 nodes instead of 1.8 MB, half the matrix work.
-// fp16 has a narrow range: an activation or weight beyond +-60000/scale raises a flag and the caller re-runs the
-// launch with the bf16x3 kernel (gated on that flag, so it costs one empty launch otherwise).  Values below
-// 2^-3/scale lose relative — not absolute — precision in the m plane (<= 2^-24 of the scale).
+// fp16 has a narrow range: a weight beyond +-60000/scale (checked when the weights are packed) or an activation whose scaled
+// value rounds to an fp16 infinity (beyond +-65504/scale; it surfaces as NaN in the node's outputs, see below) raises a flag
+// and the caller re-runs the launch with the bf16x3 kernel (gated on that flag, so it costs one empty launch otherwise).
+// Values below 2^-3/scale lose relative — not absolute — precision in the m plane (<= 2^-24 of the scale); fp16 subnormals
+// survive the split, the LDS-DMA and the matrix cores.  All three are pinned per row by
+// tests/test_gpu_deformer_mlp_adversarial.py (profiles/notes_mlp_rows.md).
 // (reference models/model.py:433-452, 476-477; floats only, no integer output depends on it)
 #include <stdlib.h>
 

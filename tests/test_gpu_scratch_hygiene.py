@@ -534,6 +534,41 @@ def test_deformer_mlp_poisoned_scratch(ops, monkeypatch, weights, rows):
     got = hygiene(ops, monkeypatch, lambda poison: ops.deformer_mlp(wl, dz))
     x = _mlp64(weights, z.numpy())
     np.testing.assert_allclose(got["out"].numpy(), x, rtol=2e-5, atol=2e-5 * np.abs(x).max())
+    if rows == "fallback":   # the 150 ordinary rows at their own scale (tests/test_gpu_deformer_mlp_adversarial.py: the per-family bar)
+        plain = np.ones((2, 100), bool)
+        plain[0, :50] = False
+        noise = np.abs(_mlp32(weights, z.numpy()[plain]) - x[plain]).max()
+        assert noise > 0 and np.abs(got["out"].numpy()[plain] - x[plain]).max() <= 3 * noise
+
+
+def _mlp32(weights, z):
+    """the fp32 chain (numpy, exp(x) - 1): its error against _mlp64 is the yardstick of the per-row bars"""
+    x = z.astype(np.float32)
+    for n, i in enumerate((0, 2, 4, 6)):
+        x = (x @ weights["deformation_decoder_layer__linear__%d__weight" % i].T
+             + weights["deformation_decoder_layer__linear__%d__bias" % i]).astype(np.float32)
+        if n < 3:
+            x = np.where(x > 0, x, np.exp(np.minimum(x, np.float32(0))) - np.float32(1)).astype(np.float32)
+    return x
+
+
+def test_deformer_mlp_weight_flag_poisoned_scratch(ops, monkeypatch, weights):
+    """One weight of layer 1 beyond 60000 / 256: the range flag is raised by the PACKING kernel (no activation overflows on the
+    small rows), on poisoned scratch; the gated bf16x3 launch answers.  Every row within 3 x the fp32 chain's error against
+    float64 with these weights."""
+    w = dict(weights)
+    w["deformation_decoder_layer__linear__2__weight"] = w["deformation_decoder_layer__linear__2__weight"].copy()
+    w["deformation_decoder_layer__linear__2__weight"][7, 300] = 250.0
+    wl = ops.deformer_weight_list(w, "cuda")
+    g = torch.Generator().manual_seed(4)
+    z = torch.randn(200, 262, generator=g)
+    z[100:] *= 1e-4
+    dz = z.cuda()
+    got = hygiene(ops, monkeypatch, lambda poison: ops.deformer_mlp(wl, dz))
+    x = _mlp64(w, z.numpy())
+    for part in (slice(0, 100), slice(100, 200)):
+        noise = np.abs(_mlp32(w, z.numpy()[part]) - x[part]).max()
+        assert noise > 0 and np.abs(got["out"].numpy()[part] - x[part]).max() <= 3 * noise, (part, noise)
 
 
 # ------------------------------------------------------------------------------------------------------------------ backbone
