@@ -20,6 +20,9 @@
 // compared against a float64 evaluation at a few fp32 roundings of max |S|, which leaves no room for the 1-ulp hardware
 // sqrt under alpha = 100.  The running sum is kept in fp64 (one add per 16 candidates), so that its error does not grow
 // with the number of key tiles.
+//
+// dvm_sinkhorn_fwd_hist_f32 is the same run with every iterate's potentials left in memory (u_hist, v_hist) for the
+// backward, dvm_sinkhorn_bwd.hip: only the destination of each sweep's output changes.
 #include <float.h>
 #include <math.h>
 
@@ -89,7 +92,8 @@ __device__ __forceinline__ void store_final(const KBest<TOPK, float> &kb, bool h
 struct SKArgs {
     const float *q, *k;     // queries [B][N][d], keys [B][M][d]
     const float *nq, *nk;   // their |.|^2
-    const float *pot;       // the keys' potential [B][M]; NULL = 0
+    const float *pot;       // the keys' potential, entry b at pot + b * pot_bs; NULL = 0
+    long pot_bs, out_bs;    // batch strides (floats) of pot and of out / u: M and N, or a slice of a potential history
     int N, M, d, tiles;     // tiles = query blocks per entry
     float neg_alpha;
     float add;              // potential sweep: out = add - LSE (0 for the row step, log(N / M) for the column step)
@@ -138,7 +142,7 @@ __global__ __launch_bounds__(128) void sinkhorn_scalar_kernel(const SKArgs a) {
         if (threadIdx.x < SS_KT) {
             const int j = j0 + threadIdx.x;
             kn[threadIdx.x] = j < M ? a.nk[(size_t)b * M + j] : INFINITY;
-            kp[threadIdx.x] = (j < M && hasv) ? a.pot[(size_t)b * M + j] : 0.f;
+            kp[threadIdx.x] = (j < M && hasv) ? a.pot[(size_t)b * a.pot_bs + j] : 0.f;
         }
         __syncthreads();
         float acc[SS_KT];
@@ -191,9 +195,10 @@ __global__ __launch_bounds__(128) void sinkhorn_scalar_kernel(const SKArgs a) {
         const size_t row = (size_t)b * N + i;
         if (FINAL)
             store_final<TOPK>(kb, hasv, st, a.topk, M, neg_alpha, a.val + row * a.topk, a.idx + row * a.topk,
-                              a.lmax ? a.lmax + row : nullptr, a.sum ? a.sum + row : nullptr, a.u ? a.u + row : nullptr);
+                              a.lmax ? a.lmax + row : nullptr, a.sum ? a.sum + row : nullptr,
+                              a.u ? a.u + (size_t)b * a.out_bs + i : nullptr);
         else
-            a.out[row] = a.add - (st.m + logf((float)st.l));
+            a.out[(size_t)b * a.out_bs + i] = a.add - (st.m + logf((float)st.l));
     }
 }
 
@@ -231,7 +236,7 @@ __global__ __launch_bounds__(SK_THREADS, 2) void sinkhorn_mfma_kernel(const SKAr
 
     const float *kbase = a.k + (size_t)b * M * SK_D;
     const float *knb = a.nk + (size_t)b * M;
-    const float *kpb = a.pot ? a.pot + (size_t)b * M : nullptr;
+    const float *kpb = a.pot ? a.pot + (size_t)b * a.pot_bs : nullptr;
 
     // this lane's query row and its B-operand fragment: q[s] = -2 * query[row][2s + h]
     const int qrow = qt * SK_QB + wave * SK_QW + r32;
@@ -396,9 +401,10 @@ __global__ __launch_bounds__(SK_THREADS, 2) void sinkhorn_mfma_kernel(const SKAr
         const size_t row = (size_t)b * N + qrow;
         if (FINAL)
             store_final<TOPK>(kb, HASV, st, a.topk, M, neg_alpha, a.val + row * a.topk, a.idx + row * a.topk,
-                              a.lmax ? a.lmax + row : nullptr, a.sum ? a.sum + row : nullptr, a.u ? a.u + row : nullptr);
+                              a.lmax ? a.lmax + row : nullptr, a.sum ? a.sum + row : nullptr,
+                              a.u ? a.u + (size_t)b * a.out_bs + qrow : nullptr);
         else
-            a.out[row] = a.add - (st.m + logf((float)st.l));
+            a.out[(size_t)b * a.out_bs + qrow] = a.add - (st.m + logf((float)st.l));
     }
 }
 
@@ -445,6 +451,44 @@ void launch_final(bool mfma, SKArgs a, int B, hipStream_t s) {
     }
 }
 
+__global__ void sinkhorn_zero_slice_kernel(float *p, int n, long bs) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) p[(size_t)blockIdx.y * bs + i] = 0.f;
+}
+
+// The whole operator.  Iterate t = 1..n_iter reads v^(t-1) at V + (t-1) * v_step and writes u^t to U + (t-1) * u_step and
+// v^t to V + t * v_step (batch strides u_bs / v_bs); the final row step reads v^T and writes its u to uf (batch stride
+// u_bs, may be NULL).  dvm_sinkhorn_fwd_f32 runs it with steps 0 (one buffer per side), dvm_sinkhorn_fwd_hist_f32 with a
+// history slice per iterate: the same kernels on the same operands, so the same bits.
+int sinkhorn_run(const float *f1, const float *f2, int B, int N, int M, int d, float neg_alpha, int n_iter, int topk, float *pi_val,
+                 int32_t *pi_idx, float *row_lmax, float *row_sum, float *n1, float *n2, float *U, long u_step, long u_bs, float *V,
+                 long v_step, long v_bs, float *uf, bool mfma, hipStream_t s) {
+    launch_rownorm2(f1, B * N, d, n1, s);
+    launch_rownorm2(f2, B * M, d, n2, s);
+    const float log_ratio = (float)log((double)N / (double)M);
+    SKArgs row{}, col{};
+    row.q = f1, row.k = f2, row.nq = n1, row.nk = n2, row.N = N, row.M = M, row.d = d, row.neg_alpha = neg_alpha;
+    col.q = f2, col.k = f1, col.nq = n2, col.nk = n1, col.N = M, col.M = N, col.d = d, col.neg_alpha = neg_alpha;
+    row.pot_bs = v_bs, row.out_bs = u_bs, col.pot_bs = u_bs, col.out_bs = v_bs;
+    for (int it = 0; it < n_iter; ++it) {
+        row.pot = it ? V + it * v_step : nullptr;   // v = 0 before the first row step: nothing is read from the buffer
+        row.add = 0.f, row.out = U + it * u_step;
+        launch_sweep(mfma, false, row, B, s);
+        col.pot = row.out;
+        col.add = log_ratio, col.out = V + (it + 1) * v_step;
+        launch_sweep(mfma, true, col, B, s);
+    }
+    row.pot = n_iter ? V + n_iter * v_step : nullptr;
+    row.out = nullptr;
+    row.topk = topk, row.val = pi_val, row.idx = pi_idx, row.lmax = row_lmax, row.sum = row_sum, row.u = uf;
+    if (topk <= 10)
+        launch_final<10>(mfma, row, B, s);
+    else
+        launch_final<16>(mfma, row, B, s);
+    DVM_CHECK_LAUNCH("sinkhorn");
+    return DVM_OK;
+}
+
 }  // namespace
 }  // namespace dvm
 
@@ -479,28 +523,37 @@ DVM_EXPORT int dvm_sinkhorn_fwd_f32(const float *f1, const float *f2, int B, int
     hipStream_t s = (hipStream_t)stream;
     float *ub = u ? u : wu, *vb = v ? v : wv;
     const bool mfma = variant == 0 && d == SK_D;
-    launch_rownorm2(f1, B * N, d, n1, s);
-    launch_rownorm2(f2, B * M, d, n2, s);
     if (n_iter == 0 && v) (void)hipMemsetAsync(v, 0, (size_t)B * M * sizeof(float), s);
-    const float log_ratio = (float)log((double)N / (double)M);
-    SKArgs row{}, col{};
-    row.q = f1, row.k = f2, row.nq = n1, row.nk = n2, row.N = N, row.M = M, row.d = d, row.neg_alpha = neg_alpha;
-    col.q = f2, col.k = f1, col.nq = n2, col.nk = n1, col.N = M, col.M = N, col.d = d, col.neg_alpha = neg_alpha;
-    for (int it = 0; it < n_iter; ++it) {
-        row.pot = it ? vb : nullptr;   // v = 0 before the first row step: nothing is read from the buffer
-        row.add = 0.f, row.out = ub;
-        launch_sweep(mfma, false, row, B, s);
-        col.pot = ub;
-        col.add = log_ratio, col.out = vb;
-        launch_sweep(mfma, true, col, B, s);
+    return sinkhorn_run(f1, f2, B, N, M, d, neg_alpha, n_iter, topk, pi_val, pi_idx, row_lmax, row_sum, n1, n2, ub, 0, N, vb, 0, M, u,
+                        mfma, s);
+}
+
+DVM_EXPORT size_t dvm_sinkhorn_hist_workspace_bytes(int B, int N, int M, int d) {
+    (void)d;
+    if (B < 1 || N < 1 || M < 1) return 0;
+    return align_up((size_t)B * N * sizeof(float)) + align_up((size_t)B * M * sizeof(float));   // |f1|^2, |f2|^2
+}
+
+DVM_EXPORT int dvm_sinkhorn_fwd_hist_f32(const float *f1, const float *f2, int B, int N, int M, int d, float neg_alpha, int n_iter,
+                                         int topk, float *pi_val, int32_t *pi_idx, float *row_lmax, float *row_sum, float *u_hist,
+                                         float *v_hist, int variant, void *ws, size_t ws_bytes, void *stream) {
+    DVM_REQUIRE(f1 && f2 && pi_val && pi_idx && u_hist && v_hist, "dvm_sinkhorn_fwd_hist_f32: null pointer");
+    DVM_REQUIRE(B >= 1 && N >= 1 && M >= 1, "dvm_sinkhorn_fwd_hist_f32: empty input (B=%d N=%d M=%d)", B, N, M);
+    DVM_REQUIRE(d >= 4 && d % 4 == 0 && d <= 512, "dvm_sinkhorn_fwd_hist_f32: d=%d unsupported (need d%%4==0, 4<=d<=512)", d);
+    DVM_REQUIRE(topk >= 1 && topk <= 16, "dvm_sinkhorn_fwd_hist_f32: topk=%d unsupported (1..16)", topk);
+    DVM_REQUIRE(n_iter >= 0, "dvm_sinkhorn_fwd_hist_f32: n_iter=%d must not be negative", n_iter);
+    DVM_REQUIRE(neg_alpha < 0.f, "dvm_sinkhorn_fwd_hist_f32: neg_alpha must be negative (got %g)", (double)neg_alpha);
+    DVM_REQUIRE(variant == 0 || variant == 1, "dvm_sinkhorn_fwd_hist_f32: bad variant %d (0 = auto, 1 = scalar)", variant);
+    Arena ar(ws, ws_bytes);
+    float *n1 = ar.take<float>((size_t)B * N);
+    float *n2 = ar.take<float>((size_t)B * M);
+    if (!ar.ok()) {
+        set_error("dvm_sinkhorn_fwd_hist_f32: workspace too small (%zu < %zu)", ws_bytes, ar.off);
+        return DVM_ENOSPACE;
     }
-    row.pot = n_iter ? vb : nullptr;
-    row.out = nullptr;
-    row.topk = topk, row.val = pi_val, row.idx = pi_idx, row.lmax = row_lmax, row.sum = row_sum, row.u = u;
-    if (topk <= 10)
-        launch_final<10>(mfma, row, B, s);
-    else
-        launch_final<16>(mfma, row, B, s);
-    DVM_CHECK_LAUNCH("sinkhorn");
-    return DVM_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const long u_bs = (long)(n_iter + 1) * N, v_bs = (long)(n_iter + 1) * M;
+    hipLaunchKernelGGL(sinkhorn_zero_slice_kernel, dim3((M + 255) / 256, B), dim3(256), 0, s, v_hist, M, v_bs);   // v^0
+    return sinkhorn_run(f1, f2, B, N, M, d, neg_alpha, n_iter, topk, pi_val, pi_idx, row_lmax, row_sum, n1, n2, u_hist, N, u_bs, v_hist,
+                        M, v_bs, u_hist + (size_t)n_iter * N, variant == 0 && d == SK_D, s);
 }

@@ -63,6 +63,34 @@ int main() {
     EXPECT(dvm_sinkhorn_fwd_f32(dummy, dummy, 1, 8, 8, 128, -1.f, 5, 10, dummy, idummy, nullptr, nullptr, nullptr, nullptr, 0, skws.data(), skb - 1, nullptr) == DVM_ENOSPACE);
     EXPECT(strstr(dvm_last_error(), "workspace") != nullptr);
     EXPECT(dvm_sinkhorn_fwd_f32(dummy, dummy, 1, 8, 8, 128, -1.f, 5, 10, dummy, idummy, dummy, dummy, dummy, dummy, 0, nullptr, 0, nullptr) == DVM_ENOSPACE);
+    // dvm_sinkhorn_fwd_hist_f32 / dvm_sinkhorn_bwd_f32: the same rejection paths
+    const size_t shb = dvm_sinkhorn_hist_workspace_bytes(1, 8, 8, 128), sbb = dvm_sinkhorn_bwd_workspace_bytes(1, 8, 8, 128, 5);
+    std::vector<char> shws(shb), sbws(sbb);
+    EXPECT(shb >= (size_t)4 * (8 + 8) && sbb > shb);
+    EXPECT(dvm_sinkhorn_hist_workspace_bytes(0, 8, 8, 128) == 0 && dvm_sinkhorn_bwd_workspace_bytes(1, 8, 8, 128, 33) == 0);
+    EXPECT(dvm_sinkhorn_bwd_workspace_bytes(1, 8, 8, 128, 20) > sbb);   // grows with the history
+    EXPECT(dvm_sinkhorn_fwd_hist_f32(dummy, dummy, 1, 8, 8, 128, -1.f, 5, 10, dummy, idummy, dummy, dummy, nullptr, dummy, 0, shws.data(), shb, nullptr) == DVM_EINVAL);
+    EXPECT(strstr(dvm_last_error(), "null pointer") != nullptr);
+    EXPECT(dvm_sinkhorn_fwd_hist_f32(dummy, dummy, 0, 8, 8, 128, -1.f, 5, 10, dummy, idummy, dummy, dummy, dummy, dummy, 0, shws.data(), shb, nullptr) == DVM_EINVAL);   // empty
+    EXPECT(dvm_sinkhorn_fwd_hist_f32(dummy, dummy, 1, 8, 8, 130, -1.f, 5, 10, dummy, idummy, dummy, dummy, dummy, dummy, 0, shws.data(), shb, nullptr) == DVM_EINVAL);   // d
+    EXPECT(dvm_sinkhorn_fwd_hist_f32(dummy, dummy, 1, 8, 8, 128, -1.f, 5, 17, dummy, idummy, dummy, dummy, dummy, dummy, 0, shws.data(), shb, nullptr) == DVM_EINVAL);   // topk
+    EXPECT(dvm_sinkhorn_fwd_hist_f32(dummy, dummy, 1, 8, 8, 128, -1.f, -1, 10, dummy, idummy, dummy, dummy, dummy, dummy, 0, shws.data(), shb, nullptr) == DVM_EINVAL);  // n_iter
+    EXPECT(dvm_sinkhorn_fwd_hist_f32(dummy, dummy, 1, 8, 8, 128, 0.f, 5, 10, dummy, idummy, dummy, dummy, dummy, dummy, 0, shws.data(), shb, nullptr) == DVM_EINVAL);    // alpha sign
+    EXPECT(dvm_sinkhorn_fwd_hist_f32(dummy, dummy, 1, 8, 8, 128, -1.f, 5, 10, dummy, idummy, dummy, dummy, dummy, dummy, 7, shws.data(), shb, nullptr) == DVM_EINVAL);   // variant
+    EXPECT(dvm_sinkhorn_fwd_hist_f32(dummy, dummy, 1, 8, 8, 128, -1.f, 5, 10, dummy, idummy, nullptr, nullptr, dummy, dummy, 0, shws.data(), shb - 1, nullptr) == DVM_ENOSPACE);
+    EXPECT(strstr(dvm_last_error(), "workspace") != nullptr);
+    EXPECT(dvm_sinkhorn_bwd_f32(dummy, dummy, 1, 8, 8, 128, -1.f, 5, 10, dummy, idummy, dummy, dummy, dummy, dummy, nullptr, 0, sbws.data(), sbb, nullptr) == DVM_EINVAL);
+    EXPECT(strstr(dvm_last_error(), "null pointer") != nullptr);
+    EXPECT(dvm_sinkhorn_bwd_f32(dummy, dummy, 1, 0, 8, 128, -1.f, 5, 10, dummy, idummy, dummy, dummy, dummy, dummy, dummy, 0, sbws.data(), sbb, nullptr) == DVM_EINVAL);   // empty
+    EXPECT(dvm_sinkhorn_bwd_f32(dummy, dummy, 1, 8, 8, 516, -1.f, 5, 10, dummy, idummy, dummy, dummy, dummy, dummy, dummy, 0, sbws.data(), sbb, nullptr) == DVM_EINVAL);   // d
+    EXPECT(dvm_sinkhorn_bwd_f32(dummy, dummy, 1, 8, 8, 128, -1.f, 5, 0, dummy, idummy, dummy, dummy, dummy, dummy, dummy, 0, sbws.data(), sbb, nullptr) == DVM_EINVAL);     // topk
+    EXPECT(dvm_sinkhorn_bwd_f32(dummy, dummy, 1, 8, 8, 128, -1.f, 33, 10, dummy, idummy, dummy, dummy, dummy, dummy, dummy, 0, sbws.data(), sbb, nullptr) == DVM_EINVAL);   // n_iter limit
+    EXPECT(strstr(dvm_last_error(), "n_iter") != nullptr);
+    EXPECT(dvm_sinkhorn_bwd_f32(dummy, dummy, 1, 8, 8, 128, 1.f, 5, 10, dummy, idummy, dummy, dummy, dummy, dummy, dummy, 0, sbws.data(), sbb, nullptr) == DVM_EINVAL);     // alpha sign
+    EXPECT(dvm_sinkhorn_bwd_f32(dummy, dummy, 1, 8, 8, 128, -1.f, 5, 10, dummy, idummy, dummy, dummy, dummy, dummy, dummy, 2, sbws.data(), sbb, nullptr) == DVM_EINVAL);    // variant
+    EXPECT(dvm_sinkhorn_bwd_f32(dummy, dummy, 1, 8, 8, 128, -1.f, 5, 10, dummy, idummy, dummy, dummy, dummy, dummy, dummy, 0, sbws.data(), dvm_sinkhorn_bwd_workspace_bytes(1, 8, 8, 128, 0), nullptr) == DVM_ENOSPACE);
+    EXPECT(strstr(dvm_last_error(), "workspace") != nullptr);
+    EXPECT(dvm_sinkhorn_bwd_f32(dummy, dummy, 1, 8, 8, 128, -1.f, 5, 10, dummy, idummy, dummy, dummy, dummy, dummy, dummy, 0, nullptr, 0, nullptr) == DVM_ENOSPACE);
     EXPECT(dvm_linear_f32(nullptr, dummy, 1, 4, 4, 4, 0, nullptr, nullptr, nullptr, nullptr, 1.f, dummy, nullptr) == DVM_EINVAL);
     EXPECT(dvm_linear_f32(dummy, dummy, 1, 4, 4, 4, 0, nullptr, nullptr, dummy, nullptr, 1.f, dummy, nullptr) == DVM_EINVAL);               // alpha without beta
     EXPECT(dvm_linear_f32(dummy, dummy, 1, 4, 100000, 4, 0, nullptr, nullptr, nullptr, nullptr, 1.f, dummy, nullptr) == DVM_EINVAL);        // K too large

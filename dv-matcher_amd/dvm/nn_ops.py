@@ -492,6 +492,37 @@ def softcorr_topk(f1, f2, alpha, topk=10):
     return _SoftCorrTopK.apply(f1, f2, alpha, topk)
 
 
+class _SinkhornTopK(torch.autograd.Function):
+    """Top-k Sinkhorn-normalised correspondence with its HIP backward: the forward keeps the history of the potentials
+    (dvm_sinkhorn_fwd_hist_f32, (n_iter + 1)(N + M) floats per entry), the backward is the reverse sweep over it
+    (dvm_sinkhorn_bwd_f32: the exact gradient of the unrolled operator, no N x M array, no float atomics)."""
+
+    @staticmethod
+    def forward(ctx, f1, f2, alpha, n_iter, topk):
+        val, idx, _, _, u_hist, v_hist = ops.sinkhorn_hist(f1, f2, alpha, n_iter, topk=topk)
+        ctx.save_for_backward(f1.detach(), f2.detach(), val, idx, u_hist, v_hist)
+        ctx.alpha, ctx.n_iter = alpha, n_iter
+        ctx.mark_non_differentiable(idx)
+        return val, idx
+
+    @staticmethod
+    def backward(ctx, gval, _gidx):
+        f1, f2, val, idx, u_hist, v_hist = ctx.saved_tensors
+        df1, df2 = ops.sinkhorn_bwd(f1, f2, ctx.alpha, ctx.n_iter, val, idx, u_hist, v_hist, gval.contiguous())
+        return df1, df2, None, None, None
+
+
+def sinkhorn_topk(f1, f2, alpha, n_iter, topk=10):
+    """Differentiable (w.r.t. f1, f2) top-k Sinkhorn correspondence: (val (B,N,k), idx (B,N,k) int32).  Without grad it is
+    ops.sinkhorn (no history is kept); under grad with n_iter = 0 it is softcorr_topk."""
+    if not (torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (f1, f2))):
+        val, idx, _, _ = ops.sinkhorn(f1, f2, alpha, n_iter, topk=topk)
+        return val, idx
+    if int(n_iter) == 0:   # the operator IS the row softmax there: softcorr_topk's node, bit for bit (its backward sums with atomics)
+        return softcorr_topk(f1, f2, alpha, topk)
+    return _SinkhornTopK.apply(f1, f2, alpha, int(n_iter), topk)
+
+
 class _SparseApply(torch.autograd.Function):
     """out[i] = sum_t val[i,t] V[idx[i,t]] on the HIP kernels, both ways (no (B,N,k,C) gather in HBM)."""
 

@@ -260,9 +260,11 @@ def sinkhorn(f1, f2, alpha, n_iter, topk=10, variant=0, potentials=False):
     """Sinkhorn-normalised soft correspondence (dvm_sinkhorn_fwd_f32; not in the reference): n_iter row / column normalisations
     of exp(-alpha * cdist(f1, f2)) in the log domain, a final row step, the top-k of every row.  n_iter = 0 is softcorr.
     f1 (B,N,d), f2 (B,M,d) -> pi_val (B,N,topk), pi_idx (B,N,topk) int32, row_lmax (B,N), row_sum (B,N)[, u (B,N), v (B,M)].
-    Forward only: there is no backward kernel yet, so inputs that require grad are refused while grad mode is on."""
+    Forward only: this entry keeps no history of the potentials, so inputs that require grad are refused while grad mode is on;
+    the differentiable entry is nn_ops.sinkhorn_topk (sinkhorn_hist + sinkhorn_bwd)."""
     if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (f1, f2)):
-        raise DvmError("sinkhorn is forward only (no backward kernel): detach the features or call it under torch.no_grad()")
+        raise DvmError("sinkhorn is forward only (it keeps no history for a backward): use nn_ops.sinkhorn_topk to differentiate, "
+                       "or detach the features / call it under torch.no_grad()")
     _need_gpu(f1, f2)
     f1, f2 = _f(f1), _f(f2)
     B, N, d = f1.shape
@@ -280,6 +282,54 @@ def sinkhorn(f1, f2, alpha, n_iter, topk=10, variant=0, potentials=False):
     check(lib.dvm_sinkhorn_fwd_f32(_p(f1), _p(f2), B, N, M, d, neg_alpha_f32(alpha), int(n_iter), topk, _p(val), _p(idx), _p(lmax),
                                    _p(lsum), _p(u), _p(v), variant, _p(ws), nb, _stream()), "dvm_sinkhorn_fwd_f32")
     return (val, idx, lmax, lsum, u, v) if potentials else (val, idx, lmax, lsum)
+
+
+def sinkhorn_hist(f1, f2, alpha, n_iter, topk=10, variant=0):
+    """ops.sinkhorn with the history of its potentials kept for sinkhorn_bwd (dvm_sinkhorn_fwd_hist_f32): the same sweeps on the
+    same operands, so val / idx / lmax / lsum and the last slices of the histories carry ops.sinkhorn's bits.
+    -> pi_val, pi_idx, row_lmax, row_sum, u_hist (B,n_iter+1,N) = u^1..u^T, u^final, v_hist (B,n_iter+1,M) = v^0 (= 0)..v^T.
+    Takes no part in autograd itself (nn_ops.sinkhorn_topk is the node)."""
+    _need_gpu(f1, f2)
+    f1, f2 = _f(f1), _f(f2)
+    B, N, d = f1.shape
+    M = f2.shape[1]
+    n_iter = int(n_iter)
+    lib = _lib.load()
+    dev = f1.device
+    val = torch.empty(B, N, topk, dtype=torch.float32, device=dev)
+    idx = torch.empty(B, N, topk, dtype=torch.int32, device=dev)
+    lmax = torch.empty(B, N, dtype=torch.float32, device=dev)
+    lsum = torch.empty(B, N, dtype=torch.float32, device=dev)
+    u_hist = torch.empty(B, max(n_iter, 0) + 1, N, dtype=torch.float32, device=dev)
+    v_hist = torch.empty(B, max(n_iter, 0) + 1, M, dtype=torch.float32, device=dev)
+    nb = lib.dvm_sinkhorn_hist_workspace_bytes(B, N, M, d)
+    ws = workspace(nb, dev, "sinkhorn_hist")
+    check(lib.dvm_sinkhorn_fwd_hist_f32(_p(f1), _p(f2), B, N, M, d, neg_alpha_f32(alpha), n_iter, topk, _p(val), _p(idx), _p(lmax),
+                                        _p(lsum), _p(u_hist), _p(v_hist), variant, _p(ws), nb, _stream()), "dvm_sinkhorn_fwd_hist_f32")
+    return val, idx, lmax, lsum, u_hist, v_hist
+
+
+def sinkhorn_bwd(f1, f2, alpha, n_iter, val, idx, u_hist, v_hist, gval, variant=0):
+    """Backward of the unrolled Sinkhorn operator (dvm_sinkhorn_bwd_f32): gval (B,N,topk) -> (d_f1 (B,N,d), d_f2 (B,M,d)).
+    val / idx / u_hist / v_hist are sinkhorn_hist's outputs for the same f1, f2, alpha, n_iter.  No float atomics: two calls give
+    the same bits."""
+    _need_gpu(f1, f2, gval)
+    f1, f2, gval, val, u_hist, v_hist = _f(f1), _f(f2), _f(gval), _f(val), _f(u_hist), _f(v_hist)
+    B, N, d = f1.shape
+    M = f2.shape[1]
+    n_iter = int(n_iter)
+    topk = val.shape[-1]
+    if n_iter >= 0 and (tuple(u_hist.shape) != (B, n_iter + 1, N) or tuple(v_hist.shape) != (B, n_iter + 1, M)):
+        raise ValueError("sinkhorn_bwd: u_hist / v_hist must be (B, n_iter + 1, N) / (B, n_iter + 1, M), got %s / %s"
+                         % (tuple(u_hist.shape), tuple(v_hist.shape)))
+    lib = _lib.load()
+    df1, df2 = torch.empty_like(f1), torch.empty_like(f2)
+    nb = lib.dvm_sinkhorn_bwd_workspace_bytes(B, N, M, d, n_iter)
+    ws = workspace(nb, f1.device, "sinkhorn_bwd")
+    check(lib.dvm_sinkhorn_bwd_f32(_p(f1), _p(f2), B, N, M, d, neg_alpha_f32(alpha), n_iter, topk, _p(val), _p(idx.contiguous()),
+                                   _p(u_hist), _p(v_hist), _p(gval), _p(df1), _p(df2), variant, _p(ws), nb, _stream()),
+          "dvm_sinkhorn_bwd_f32")
+    return df1, df2
 
 
 def softcorr_bwd(f1, f2, alpha, val, idx, smax, ssum, gval, variant=0):

@@ -106,13 +106,17 @@ class SparsePi:
         return out.scatter_(-1, self.idx.long(), self.val)
 
     def matmul(self, V):
+        if torch.is_grad_enabled() and self.val.requires_grad:   # a differentiable correspondence (sinkhorn_pi under grad)
+            return nn_ops.sparse_apply(self.val, self.idx, V)
         return ops.apply(self.val, self.idx, V)
 
 
 def sinkhorn_pi(x, y, alpha=100, n_iter=5, topk=10):
-    """Sinkhorn-normalised counterpart of topk_pi(knnsearch_t_grad(x, y, alpha)) as a SparsePi (ops.sinkhorn; not in the
-    reference): n_iter row / column normalisations keep many source points from sharing one target point.  Forward only."""
-    val, idx, _, _ = ops.sinkhorn(x, y, alpha, n_iter, topk=topk)
+    """Sinkhorn-normalised counterpart of topk_pi(knnsearch_t_grad(x, y, alpha)) as a SparsePi (not in the reference): n_iter
+    row / column normalisations keep many source points from sharing one target point.  When x or y requires grad the
+    SparsePi's val carries the graph (nn_ops.sinkhorn_topk: the exact gradient of the unrolled iterations); otherwise it is
+    ops.sinkhorn."""
+    val, idx = nn_ops.sinkhorn_topk(x, y, alpha, n_iter, topk=topk)
     return SparsePi(val, idx, y.shape[1])
 
 
@@ -156,6 +160,10 @@ class GraphDeformLoss_Neural(nn.Module):
         # training, equal point counts: the deformation part as ONE native autograd node (nn_ops.criterion_train); False = the
         # autograd path over the per-op nodes (the two agree to fp32 rounding, tests/test_gpu_criterion_native.py)
         self.native_train = True
+        # opt-in: Pi from this many Sinkhorn iterations (ops.sinkhorn / nn_ops.sinkhorn_topk; not in the reference) in place of the
+        # row softmax.  0 = the reference's operator, on exactly the paths above; > 0 leaves the native nodes (they have the row
+        # softmax built in) for the per-op paths
+        self.sinkhorn_iters = 0
 
     def _identity6(self, device):
         """[1,0,0,0,1,0]: the identity rotation in the 6D parametrisation (models/loss.py:1258-1262), made once per device."""
@@ -192,7 +200,10 @@ class GraphDeformLoss_Neural(nn.Module):
 
     def _direction(self, feat1, feat2, verts1, verts2, alpha, g1, deformer, idx11, idx22):
         """deform() of the reference for one direction -> (map_sum (B,), cd_warp, arap_sum, cd_self, extras)."""
-        pval, pidx, _, _ = ops.softcorr(feat1, feat2, alpha, topk=10, stats=False)
+        if self.sinkhorn_iters > 0:
+            pval, pidx, _, _ = ops.sinkhorn(feat1, feat2, alpha, self.sinkhorn_iters, topk=10)
+        else:
+            pval, pidx, _, _ = ops.softcorr(feat1, feat2, alpha, topk=10, stats=False)
         verts12 = ops.apply(pval, pidx, verts2)
         def9 = deformer.forward_sparse(feat1, feat2, verts1, verts12, idx11, idx22, pval, pidx, g1["nodes_idx"])
         R = rotation_6d_to_matrix(def9[..., 3:] + self._identity6(def9.device))
@@ -219,7 +230,7 @@ class GraphDeformLoss_Neural(nn.Module):
         instead of batch scalars (for a caller that has merged several calls into one batch)."""
         B, N, _ = verts1.shape
         M = verts2.shape[1]
-        if (self.native_train and not per_pair and not self.dump and self.w_rank <= 0 and feat1.is_cuda and feat1.dtype == torch.float32
+        if (self.native_train and self.sinkhorn_iters <= 0 and not per_pair and not self.dump and self.w_rank <= 0 and feat1.is_cuda and feat1.dtype == torch.float32
                 and feat2.dtype == torch.float32 and feat1.shape[-1] == 128 and 64 <= N <= 8192 and 64 <= M <= 8192 and self.k_deform <= 16
                 and idx11.shape[-1] == self.k_deform and all(torch.is_tensor(g1[k]) for k in ("nodes_idx", "one_ring", "infl_idx", "weights"))
                 and all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() for p in deformer.parameters())):
@@ -236,7 +247,10 @@ class GraphDeformLoss_Neural(nn.Module):
             else:
                 cd_warp, cd_self = tm[1] + tm[2], tm[3] + tm[4]
             return (terms[:, 0] if with_map else None), cd_warp, terms[:, 5].sum(), cd_self, None
-        pval, pidx = nn_ops.softcorr_topk(feat1, feat2, alpha, 10)
+        if self.sinkhorn_iters > 0:
+            pval, pidx = nn_ops.sinkhorn_topk(feat1, feat2, alpha, self.sinkhorn_iters, 10)
+        else:
+            pval, pidx = nn_ops.softcorr_topk(feat1, feat2, alpha, 10)
         verts12 = nn_ops.sparse_apply(pval, pidx, verts2)
         g1p = nn_ops.pool_rows(feat1, idx11, deformer.conv_layer.weight, deformer.conv_layer.bias)
         g2p = nn_ops.pool_rows(feat2, idx22, deformer.conv_layer.weight, deformer.conv_layer.bias)
@@ -405,7 +419,7 @@ class GraphDeformLoss_Neural(nn.Module):
             g1, g2, idx11, idx22 = geometry if geometry is not None else self.geometry(verts1, verts2, fps_starts, shape_ids)
             merged = (train and N == M and not self.dump and not self.partial_variant and self.w_rank <= 0
                       and all(torch.is_tensor(g1[k]) for k in g1))
-            native = (merged and self.native_train and feat1.is_cuda and feat1.dtype == torch.float32 and feat1.shape[-1] == 128 and N % 4 == 0
+            native = (merged and self.native_train and self.sinkhorn_iters <= 0 and feat1.is_cuda and feat1.dtype == torch.float32 and feat1.shape[-1] == 128 and N % 4 == 0
                       and 64 <= N <= 8192 and self.k_deform <= 16 and idx11.shape[-1] == self.k_deform
                       and all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() for p in deformer.parameters()))
             # ... and the dist term of all 2B shapes inside the same node (on its helper stream)

@@ -219,6 +219,10 @@ def main(argv=None):
     ap.add_argument("--points", type=int, default=1024, help="source points N")
     ap.add_argument("--points-target", type=int, default=None, help="target points M (default: N; with --partial 0.44 N like 4995 / 2200)")
     ap.add_argument("--epoch", type=int, default=1, help="timing mode: which epoch's alpha / lr to use (1-based)")
+    ap.add_argument("--sinkhorn", type=int, default=0, metavar="T",
+                    help="train under the Sinkhorn-normalised correspondence: T row / column normalisations in place of the row softmax "
+                         "(criterion.sinkhorn_iters = T, nn_ops.sinkhorn_topk; not in the reference; the criterion leaves its native "
+                         "nodes for the per-op path).  0: the reference's operator")
     ap.add_argument("--graph", action="store_true", help="timing mode, one rank: capture the whole step (forward, criterion, backward, "
                     "Adam) into ONE HIP graph and replay it — ~2000 kernel launches per step become one graph launch")
     ap.add_argument("--sync-stats", action="store_true", help="DDP: BatchNorm statistics and the positional encoding's min/max "
@@ -314,6 +318,9 @@ def main(argv=None):
         train_set = SyntheticPairs(n_train, N, M, seed_data if timing else 1000, dev)   # full loop: every rank holds the same pairs
         val_set = train_set if timing else SyntheticPairs(args.val_pairs or Bg, N, M, 2000, dev)
     crit = build_criterion(cfg, partial, min(N, M))
+    if args.sinkhorn < 0:
+        ap.error("--sinkhorn must not be negative")
+    crit.sinkhorn_iters = int(args.sinkhorn)
     if args.graph_cache:
         import collections
         crit.graph_cache = collections.OrderedDict()   # least-recently-used shapes are dropped beyond crit.graph_cache_max
@@ -503,7 +510,7 @@ def main(argv=None):
                                            "note": "algorithmic matrix flops of the whole step per GPU over the step time; the step is "
                                                    "~900 small launches, bound by the latency of its kernel chain (network forward -> criterion -> backward), not by the matrix pipe"},
                               "points": N, "points_target": M, "criterion": type(crit).__name__, "alpha": float(alpha),
-                              "hip_graph": use_graph, "graph_cache": bool(args.graph_cache),
+                              "sinkhorn_iters": crit.sinkhorn_iters, "hip_graph": use_graph, "graph_cache": bool(args.graph_cache),
                               "sync_stats": (None if not (args.sync_stats and dist_on) else
                                              {"native_node": getattr(net, "sync_stats", None) is not None,
                                               "native_calls": net.__dict__.get("native_train_calls", 0),
@@ -560,6 +567,7 @@ def main(argv=None):
                 save_ckpt(net, dfm, args.ckpt_dir, cfg["expname"], "val_best")
     if rank == 0:
         print(json.dumps({"epochs": epochs, "history": history, "best_val": best_val, "criterion": type(crit).__name__,
+                          "sinkhorn_iters": crit.sinkhorn_iters,
                           "ckpt": list(ckpt_paths(args.ckpt_dir, cfg["expname"], "val_best"))}))
     if dist_on:
         dist.destroy_process_group()

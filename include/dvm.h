@@ -188,11 +188,33 @@ int dvm_softcorr_fwd_f32(const float *f1, const float *f2, int B, int N, int M, 
  * row_lmax, row_sum [B,N], u [B,N], v [B,M] may each be NULL.  n_iter = 0 returns what dvm_softcorr_fwd_f32 returns (and v = 0).
  * A fixed iteration count, no float atomics, no host synchronisation: capturable, and bit-reproducible from run to run.
  * f1 [B,N,d], f2 [B,M,d]; neg_alpha = (float)(-alpha) < 0; n_iter >= 0; 1 <= topk <= 16; d % 4 == 0, d <= 512.
- * variant: 0 = auto (fp32-MFMA sweeps for d == 128, else the scalar kernel), 1 = scalar-FMA kernel.  Forward only. */
+ * variant: 0 = auto (fp32-MFMA sweeps for d == 128, else the scalar kernel), 1 = scalar-FMA kernel.  This entry keeps no
+ * history; the differentiable pair follows. */
 size_t dvm_sinkhorn_workspace_bytes(int B, int N, int M, int d);
 int dvm_sinkhorn_fwd_f32(const float *f1, const float *f2, int B, int N, int M, int d, float neg_alpha, int n_iter,
                          int topk, float *pi_val, int32_t *pi_idx, float *row_lmax, float *row_sum, float *u, float *v,
                          int variant, void *ws, size_t ws_bytes, void *stream);
+
+/* The differentiable pair of the Sinkhorn operator: the forward that keeps every iterate, and the exact gradient of the
+ * unrolled, fixed-n_iter operator with respect to f1 and f2 (T = n_iter).
+ * dvm_sinkhorn_fwd_hist_f32 runs dvm_sinkhorn_fwd_f32's sweeps on the same operands and leaves
+ *   u_hist [B,T+1,N] = u^1 .. u^T, u^final      v_hist [B,T+1,M] = v^0 (= 0) .. v^T
+ * pi_val, pi_idx, row_lmax, row_sum and the last slices of the histories equal dvm_sinkhorn_fwd_f32's outputs bit for bit.
+ * dvm_sinkhorn_bwd_f32: given g_val [B,N,topk] = dL/d pi_val and the forward's pi_val, pi_idx, u_hist, v_hist, writes
+ * d_f1 [B,N,d] and d_f2 [B,M,d] (overwritten, not accumulated).  A reverse sweep over the saved potentials, 2 n_iter
+ * sweeps of the forward's kind for their adjoints and one row-major / column-major pair of passes for the features; no
+ * N x M array is stored.  Entries with distance exactly 0 contribute 0, like cdist's backward.  No float atomics and no
+ * host synchronisation (n_iter = 0 included): every output row is owned by one workgroup, two runs give the same bits,
+ * and the call can be captured.  0 <= n_iter <= 32; other limits and variant as in the forward. */
+size_t dvm_sinkhorn_hist_workspace_bytes(int B, int N, int M, int d);
+int dvm_sinkhorn_fwd_hist_f32(const float *f1, const float *f2, int B, int N, int M, int d, float neg_alpha, int n_iter,
+                              int topk, float *pi_val, int32_t *pi_idx, float *row_lmax, float *row_sum, float *u_hist,
+                              float *v_hist, int variant, void *ws, size_t ws_bytes, void *stream);
+size_t dvm_sinkhorn_bwd_workspace_bytes(int B, int N, int M, int d, int n_iter);
+int dvm_sinkhorn_bwd_f32(const float *f1, const float *f2, int B, int N, int M, int d, float neg_alpha, int n_iter, int topk,
+                         const float *pi_val, const int32_t *pi_idx, const float *u_hist, const float *v_hist,
+                         const float *g_val, float *d_f1, float *d_f2, int variant, void *ws, size_t ws_bytes,
+                         void *stream);
 
 /* Backward of dvm_softcorr_fwd_f32 (autograd through models/loss.py:110-114 + the top-k keep of
  * 1339-1347): given g_val [B,N,topk] = dL/d pi_val and the forward's outputs (pi_val, pi_idx, row_smax,

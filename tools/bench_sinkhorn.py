@@ -3,7 +3,11 @@ a lighter epilogue.  Both are timed in one process, alternating, with warm-up an
 least MIN_S seconds of work each; the per-sweep share of the fp32-matrix bound (2 N M d B flop over 157.3 TF) is derived
 from the shapes.  Prints one JSON line per alpha (and keeps it in --out).
 
-    python tools/bench_sinkhorn.py [--B 64] [--N 2048] [--M 2048] [--n-iter 5] [--alphas 100,10] [--rounds 3] [--out FILE]
+--backward times ops.sinkhorn_bwd (on a history made once by ops.sinkhorn_hist) and ops.sinkhorn_hist instead, beside the two
+yardsticks that do not depend on them, from the same run: t_fwd = ops.sinkhorn(n_iter) and t_scb = ops.softcorr_bwd(variant=2).
+The expectation t_bwd <= 1.25 (t_fwd + (1 + x) t_scb) is stated with x = 0.049 * 2 n_iter (profiles/notes_sinkhorn.md 2b).
+
+    python tools/bench_sinkhorn.py [--B 64] [--N 2048] [--M 2048] [--n-iter 5] [--alphas 100,10] [--rounds 3] [--backward] [--out FILE]
 """
 import argparse
 import json
@@ -40,6 +44,7 @@ def main(argv=None):
     ap.add_argument("--n-iter", type=int, default=5)
     ap.add_argument("--alphas", default="100,10")
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--backward", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
     assert torch.cuda.is_available(), "bench_sinkhorn needs the MI355X: there is no CPU path to time"
@@ -50,7 +55,33 @@ def main(argv=None):
     sweeps = 2 * args.n_iter + 1
     bound = 2.0 * args.N * args.M * 128 * args.B / (FP32_MATRIX_TFLOPS * 1e12)   # seconds per sweep at the matrix peak
     lines = []
-    for alpha in [float(x) for x in args.alphas.split(",")]:
+    for alpha in [float(x) for x in args.alphas.split(",")] if args.backward else []:
+        gv = torch.randn(args.B, args.N, 10, generator=g).to(dev)
+        val, idx, _, _, uh, vh = ops.sinkhorn_hist(f1, f2, alpha, args.n_iter)
+        sval, sidx, smax, ssum = ops.softcorr(f1, f2, alpha, variant=2)
+        fns = {"bwd": lambda: ops.sinkhorn_bwd(f1, f2, alpha, args.n_iter, val, idx, uh, vh, gv),
+               "hist": lambda: ops.sinkhorn_hist(f1, f2, alpha, args.n_iter),
+               "fwd": lambda: ops.sinkhorn(f1, f2, alpha, args.n_iter),
+               "scb": lambda: ops.softcorr_bwd(f1, f2, alpha, sval, sidx, smax, ssum, gv, variant=2)}
+        reps = {}
+        for k, fn in fns.items():
+            fn()
+            torch.cuda.synchronize()
+            reps[k] = max(3, int(MIN_S / window(fn, 3)) + 1)
+        best = {k: [] for k in fns}
+        for _ in range(args.rounds):
+            for k, fn in fns.items():
+                best[k].append(window(fn, reps[k]))
+        t = {k: min(v) for k, v in best.items()}
+        x = 0.049 * 2 * args.n_iter
+        expected = 1.25 * (t["fwd"] + (1 + x) * t["scb"])
+        line = dict(B=args.B, N=args.N, M=args.M, alpha=alpha, n_iter=args.n_iter, t_bwd_ms=t["bwd"] * 1e3, t_hist_ms=t["hist"] * 1e3,
+                    t_fwd_ms=t["fwd"] * 1e3, t_scb_ms=t["scb"] * 1e3, x=x, expected_t_bwd_max_ms=expected * 1e3,
+                    expectation_held=bool(t["bwd"] <= expected), rounds_ms={k: [round(v * 1e3, 3) for v in vs] for k, vs in best.items()},
+                    reps=reps)
+        print(json.dumps(line))
+        lines.append(line)
+    for alpha in [float(x) for x in args.alphas.split(",")] if not args.backward else []:
         fns = {"sinkhorn": lambda: ops.sinkhorn(f1, f2, alpha, args.n_iter), "sinkhorn0": lambda: ops.sinkhorn(f1, f2, alpha, 0),
                "softcorr_v2": lambda: ops.softcorr(f1, f2, alpha, variant=2)}
         reps = {}
