@@ -11,19 +11,24 @@
 // kernels bit for bit whatever order the cells are visited in.
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "dvm_common.h"
 
 namespace dvm {
 
 constexpr int GRID_T = 256;
 
-struct GridView {          // one shape's grid (device pointers already offset to the shape)
+template <class IndexT>
+struct GridViewT {         // one shape's grid (device pointers already offset to the shape)
     const float4 *pts;     // sorted points: x, y, z, |p|^2 (ATen order)
-    const int32_t *ids;    // original (candidate-local) index of each sorted point
-    const int32_t *start;  // [G^3 + 1]
+    const IndexT *ids;     // original (candidate-local) index of each sorted point
+    const IndexT *start;   // [G^3 + 1]
     float ox, oy, oz, h, scale2;
     int G;
 };
+typedef GridViewT<int32_t> GridView;      // the grid as built, in global memory
+typedef GridViewT<uint16_t> GridViewLds;  // a workgroup's copy in LDS (grid_stage_lds): indices and cell table in 16 bits
 
 // GridBuf (dvm_common.h): batched storage — pts [B][P], ids [B][P], start [B][G^3+1], params [B][8]
 
@@ -230,13 +235,58 @@ struct MetricDiff {  // chamfer: (dx^2 + dy^2) + dz^2 in fp32, no contraction
     __device__ __forceinline__ static float to_d2(float k) { return k; }
 };
 
+// One contiguous run [s0, s1) of sorted candidates into a search's list.  The general form ranks by (key, original index); the
+// K = 1 lists of the Chamfer walk below have forms of their own that do not read an index per candidate.
+template <class View, class Metric, class List>
+__device__ __forceinline__ void grid_row(const View &g, const Metric &met, List &kb, int s0, int s1) {
+    for (int s = s0; s < s1; ++s) kb.insert_lex(met(g.pts[s]), (int)g.ids[s]);
+}
+
+// Chamfer's walk, distance only: the minimum does not depend on which of several candidates at that distance wins, so the list
+// is the key alone — no index is read, there is no tie branch, and with nothing to wait for but the coordinates the candidates
+// go four to a round trip (as in the radius-1 cube of grid_chamfer_kernel).  A NaN distance never enters (fminf keeps `key`).
+struct ChamferMin {
+    float key;
+    __device__ __forceinline__ float worst() const { return key; }
+};
+template <class Metric>
+__device__ __forceinline__ void grid_row(const GridView &g, const Metric &met, ChamferMin &kb, int s0, int s1) {
+    for (; s0 < s1; s0 += 4) {
+        float4 pc[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) pc[u] = g.pts[s0 + u < s1 ? s0 + u : s1 - 1];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) kb.key = fminf(kb.key, s0 + u < s1 ? met(pc[u]) : INFINITY);
+    }
+}
+// Chamfer's walk with the index: the list holds the best candidate's SORTED POSITION; original indices are read only when a
+// candidate ties the best distance exactly (both positions' then), and once by the caller at the end.  Same ranking as
+// KBest<1>::insert_lex on (key, original index): smaller distance first, then lower original index; pos < 0 is the empty
+// list, which a candidate at +inf enters as it enters KBest's (index 0x7fffffff).
+struct ChamferMinPos {
+    float key;
+    int pos;
+    __device__ __forceinline__ float worst() const { return key; }
+};
+template <class Metric>
+__device__ __forceinline__ void grid_row(const GridView &g, const Metric &met, ChamferMinPos &kb, int s0, int s1) {
+    for (int s = s0; s < s1; ++s) {
+        const float v = met(g.pts[s]);
+        if (v < kb.key) {
+            kb.key = v, kb.pos = s;
+        } else if (v == kb.key && (kb.pos < 0 || g.ids[s] < g.ids[kb.pos])) {
+            kb.pos = s;
+        }
+    }
+}
+
 // Walk cubes of radius R = 1, 2, ... around the query's cell until the K-th best key is certified:
 // every unvisited point is at least `face` away (true distance), the reference-rounded squared
 // distance of such a point is >= face^2 - margin, so once kth_d2 < face^2*(1-1e-4) - margin nothing
 // outside can rank before the current K-th.
 // Returns true once the list is certified (always, unless Rmax stops the walk first).
-template <int K, class Metric, class List>
-__device__ __forceinline__ bool grid_search(const GridView &g, float qx, float qy, float qz, Metric &met, List &kb,
+template <int K, class Metric, class List, class View>
+__device__ __forceinline__ bool grid_search(const View &g, float qx, float qy, float qz, Metric &met, List &kb,
                                             int R0 = 1 /* cubes below R0: already in kb */, int Rmax = 1 << 30) {
     const int G = g.G;
     const float inv = 1.0f / g.h;
@@ -283,8 +333,8 @@ __device__ __forceinline__ bool grid_search(const GridView &g, float qx, float q
                     sa0 = g.start[rowbase + x0];
                     sa1 = g.start[rowbase + x1 + 1];
                 }
-                for (int s = sa0; s < sa1; ++s) kb.insert_lex(met(g.pts[s]), g.ids[s]);
-                for (int s = sb0; s < sb1; ++s) kb.insert_lex(met(g.pts[s]), g.ids[s]);
+                grid_row(g, met, kb, sa0, sa1);
+                grid_row(g, met, kb, sb0, sb1);
             }
         }
         // certification.  An unvisited point lies inside the grid's box but beyond one of the cube's
@@ -313,21 +363,28 @@ __device__ __forceinline__ bool grid_search(const GridView &g, float qx, float q
     return Rmax >= G;   // (walked the whole grid: certified by exhaustion)
 }
 
-// The workgroup copies a grid's sorted points and cell table into LDS and repoints the view at the copy: every candidate and
-// range-bound read of a search is then an LDS read instead of an L2 round trip (the original indices stay in global memory).
-// Returns the bytes used.  All threads of the workgroup must call it; the caller synchronises afterwards.
-__device__ __forceinline__ size_t grid_stage_lds(GridView &g, int P, char *lds, int threads) {
+// The workgroup copies a grid — sorted points, original indices and cell table — into LDS and returns a view of the copy: every
+// candidate, index and range-bound read of a search is then an LDS read instead of an L2 round trip (with the indices left in
+// global memory every candidate of the inner loop waited for a global load in front of its compare).  Indices and cell
+// bounds are values in [0, P] and a grid that fits LDS has P < 65536: both are kept in 16 bits, which holds the footprint at
+// P = 2048 to 40.3 KB (39.7 KB before the indices came along; 47.9 KB with 32-bit copies) — four 512-thread workgroups still
+// share a CU's 160 KiB.
+// All threads of the workgroup must call it; the caller synchronises afterwards.
+static __host__ __device__ __forceinline__ size_t grid_lds_bytes(int P, int G) {
+    return ((size_t)P * (sizeof(float4) + sizeof(uint16_t)) + ((size_t)G * G * G + 1) * sizeof(uint16_t) + 15) / 16 * 16;
+}
+static size_t grid_lds_bytes(const GridBuf &gb) { return gb.P < 65536 ? grid_lds_bytes(gb.P, gb.G) : ~(size_t)0; }
+__device__ __forceinline__ GridViewLds grid_stage_lds(const GridView &g, int P, char *lds, int threads) {
     const int G3 = g.G * g.G * g.G;
     float4 *lp = (float4 *)lds;
-    int32_t *ls = (int32_t *)(lds + (size_t)P * sizeof(float4));
-    for (int i = threadIdx.x; i < P; i += threads) lp[i] = g.pts[i];
-    for (int i = threadIdx.x; i <= G3; i += threads) ls[i] = g.start[i];
-    g.pts = lp;
-    g.start = ls;
-    return ((size_t)P * sizeof(float4) + (size_t)(G3 + 1) * sizeof(int32_t) + 15) / 16 * 16;
-}
-static size_t grid_lds_bytes(const GridBuf &gb) {
-    return ((size_t)gb.P * sizeof(float4) + ((size_t)gb.G * gb.G * gb.G + 1) * sizeof(int32_t) + 15) / 16 * 16;
+    uint16_t *li = (uint16_t *)(lds + (size_t)P * sizeof(float4));
+    uint16_t *ls = li + P;
+    for (int i = threadIdx.x; i < P; i += threads) lp[i] = g.pts[i], li[i] = (uint16_t)g.ids[i];
+    for (int i = threadIdx.x; i <= G3; i += threads) ls[i] = (uint16_t)g.start[i];
+    GridViewLds v;
+    v.pts = lp, v.ids = li, v.start = ls;
+    v.ox = g.ox, v.oy = g.oy, v.oz = g.oz, v.h = g.h, v.scale2 = g.scale2, v.G = g.G;
+    return v;
 }
 
 // ---------------------------------------------------------------- kernels on top of grid_search
@@ -338,10 +395,13 @@ __global__ __launch_bounds__(THREADS) void grid_knn_self_kernel(GridBuf gb, int 
     const int b = blockIdx.y;
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     const int P = gb.P;
-    GridView g = grid_view(gb, b);
-    if (LDS_GRID) {
-        grid_stage_lds(g, P, kn_lds, THREADS);
+    const GridView gg = grid_view(gb, b);
+    typename std::conditional<LDS_GRID, GridViewLds, GridView>::type g;
+    if constexpr (LDS_GRID) {
+        g = grid_stage_lds(gg, P, kn_lds, THREADS);
         __syncthreads();
+    } else {
+        g = gg;
     }
     if (t >= P) return;
     const float4 qp = g.pts[t];
@@ -364,10 +424,13 @@ __global__ __launch_bounds__(THREADS) void grid_ring_kernel(GridBuf gb, int32_t 
     const int b = blockIdx.y;
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     const int P = gb.P;
-    GridView g = grid_view(gb, b);
-    if (LDS_GRID) {
-        grid_stage_lds(g, P, rg_lds, THREADS);
+    const GridView gg = grid_view(gb, b);
+    typename std::conditional<LDS_GRID, GridViewLds, GridView>::type g;
+    if constexpr (LDS_GRID) {
+        g = grid_stage_lds(gg, P, rg_lds, THREADS);
         __syncthreads();
+    } else {
+        g = gg;
     }
     if (t >= P) return;
     const float4 qp = g.pts[t];
@@ -408,14 +471,23 @@ __global__ __launch_bounds__(THREADS) void grid_infl_kernel(const float *__restr
     extern __shared__ __attribute__((aligned(16))) char in_lds[];
     const int b = blockIdx.y;
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    GridView gv = grid_view(gverts, b);
-    GridView gn = grid_view(gnodes, b);
-    if (LDS_GRID) {   // the nodes' grid (three nearest nodes) and / or the vertices' (nearest other vertex)
-        size_t used = 0;
-        if (LDS_GRID & 2) used = grid_stage_lds(gv, gverts.P, in_lds, THREADS);
-        if (LDS_GRID & 1) grid_stage_lds(gn, gnodes.P, in_lds + used, THREADS);
-        __syncthreads();
+    const GridView gv0 = grid_view(gverts, b), gn0 = grid_view(gnodes, b);
+    typename std::conditional<(LDS_GRID & 2) != 0, GridViewLds, GridView>::type gv;
+    typename std::conditional<(LDS_GRID & 1) != 0, GridViewLds, GridView>::type gn;
+    // the nodes' grid (three nearest nodes) and / or the vertices' (nearest other vertex)
+    size_t used = 0;
+    if constexpr ((LDS_GRID & 2) != 0) {
+        gv = grid_stage_lds(gv0, gverts.P, in_lds, THREADS);
+        used = grid_lds_bytes(gverts.P, gverts.G);
+    } else {
+        gv = gv0;
     }
+    if constexpr ((LDS_GRID & 1) != 0) {
+        gn = grid_stage_lds(gn0, gnodes.P, in_lds + used, THREADS);
+    } else {
+        gn = gn0;
+    }
+    if (LDS_GRID) __syncthreads();
     if (t >= N) return;
     const float4 qp = gv.pts[t];  // vertices in cell order (coherent waves)
     const int i = gv.ids[t];
@@ -459,7 +531,8 @@ struct ChGridArgs {
 typedef float f32x16_g __attribute__((ext_vector_type(16)));
 
 // the target's points [s_begin, s_end) in storage order with the reference's arithmetic (difference form, lower original index on
-// exact ties)
+// exact ties; !WANT_IDX: the minimum alone, `bs` untouched)
+template <bool WANT_IDX>
 __device__ __forceinline__ void chamfer_exact_scan(const GridView &g, const MetricDiff &met, int s_begin, int s_end, float &best, int &bs) {
     for (int s0 = s_begin; s0 < s_end; s0 += 4) {
         float4 pc[4];
@@ -469,7 +542,9 @@ __device__ __forceinline__ void chamfer_exact_scan(const GridView &g, const Metr
         for (int u = 0; u < 4; ++u) {
             const int sidx = s0 + u;
             const float d = sidx < s_end ? met(pc[u]) : INFINITY;
-            if (d < best) {
+            if (!WANT_IDX) {
+                best = fminf(best, d);
+            } else if (d < best) {
                 best = d, bs = sidx;
             } else if (d == best && d < INFINITY && g.ids[sidx] < g.ids[bs]) {  // exact tie: lower original index
                 bs = sidx;
@@ -480,6 +555,7 @@ __device__ __forceinline__ void chamfer_exact_scan(const GridView &g, const Metr
 
 // One WAVE of queries against the WHOLE target, screened on the matrix cores (described in grid_chamfer_kernel); lanes with `done`
 // take part in the matrix instructions and write nothing.
+template <bool WANT_IDX>
 __device__ __forceinline__ void chamfer_scan_wave(const ChGridGroup &G, const GridView &g, int b, int Na, bool done, const float4 qp, int i,
                                                   const MetricDiff &met, float margin, unsigned long long *stats, int grp) {
     const int P = G.gb.P;
@@ -558,20 +634,20 @@ __device__ __forceinline__ void chamfer_scan_wave(const ChGridGroup &G, const Gr
     int bs = 0;
     bool cert = false;
     if (!done) {
-        chamfer_exact_scan(g, met, stile, stile + 32 < P ? stile + 32 : P, best, bs);
-        if (ssec < INFINITY) chamfer_exact_scan(g, met, stile2, stile2 + 32 < P ? stile2 + 32 : P, best, bs);
+        chamfer_exact_scan<WANT_IDX>(g, met, stile, stile + 32 < P ? stile + 32 : P, best, bs);
+        if (ssec < INFINITY) chamfer_exact_scan<WANT_IDX>(g, met, stile2, stile2 + 32 < P ? stile2 + 32 : P, best, bs);
         cert = sother - sbest > 2.f * margin;
     }
     if (__ballot(!done && !cert) != 0) {   // (rare: a near-tie between tiles, within the screening's error)
         if (!done && !cert) {
             if (stats) atomicAdd(stats + grp * 8 + 7, 1ull);
             best = INFINITY, bs = 0;
-            chamfer_exact_scan(g, met, 0, P, best, bs);
+            chamfer_exact_scan<WANT_IDX>(g, met, 0, P, best, bs);
         }
     }
     if (!done) {
         G.dout[(size_t)b * Na + i] = best;
-        if (G.iout) G.iout[(size_t)b * Na + i] = g.ids[bs];
+        if (WANT_IDX && G.iout) G.iout[(size_t)b * Na + i] = g.ids[bs];
     }
 }
 
@@ -579,7 +655,12 @@ __device__ __forceinline__ void chamfer_scan_wave(const ChGridGroup &G, const Gr
 // points) and every candidate / range-bound read of the searches below is an LDS read instead of an L2 round trip — the kernel
 // spent 58 % of its wave cycles parked on those (profiles/r3_pmc_summary.txt, r4_pmc_grid.txt).  Same arithmetic, same order,
 // same results; the original indices (one read per query, more on exact ties) stay in global memory.
-template <int THREADS, bool LDS_TARGET>
+// WANT_IDX = false (chosen by the launch when no group asks for indices — the pair forward never does): the distance is the
+// same whichever of several candidates at the best distance wins, so this form keeps the running minimum alone.  No position,
+// no tie flag, no tie resolution, no read of `ids` anywhere; "found a candidate" is best < inf, which is bs >= 0 of the form
+// with indices (a candidate is taken on d < best only, and an infinite or NaN distance never satisfies that).  Every
+// decision — rows skipped, certified, walked, scanned — rests on the same `best`, so the distances are equal bit for bit.
+template <int THREADS, bool LDS_TARGET, bool WANT_IDX>
 __global__ __launch_bounds__(THREADS) void grid_chamfer_kernel(const ChGridArgs args) {
     extern __shared__ __attribute__((aligned(16))) char ch_lds[];
     const ChGridGroup &G = args.g[blockIdx.z];
@@ -609,7 +690,7 @@ __global__ __launch_bounds__(THREADS) void grid_chamfer_kernel(const ChGridArgs 
     const float margin = 64.f * 1.1920929e-7f * (g.scale2 + q2) + 1e-30f;
     bool done = !inrange;
     float fbest = INFINITY;   // the radius-1 cube's result, kept for the walk below
-    int fid = 0x7fffffff;
+    int fpos = -1;            // (WANT_IDX) and its sorted position
     // K = 1 fast path: the radius-1 cube is 9 contiguous (z, y) rows.  All 18 range bounds are requested together
     // (the generic walk chases start -> pts -> ids one row at a time: a dependent-load chain per row), only the
     // coordinates are read per candidate, the original index once at the end (and on exact ties).
@@ -666,14 +747,18 @@ __global__ __launch_bounds__(THREADS) void grid_chamfer_kernel(const ChGridArgs 
                     asm volatile("" : "+v"(dm));   // (evaluated for every lane, then selected: no branch around eight instructions)
                     const bool inb = s < rend;
                     const float d = inb ? dm : INFINITY;
-                    const bool lt = d < best, eq = d == best && inb && d < INFINITY;   // (inf == inf while bs is still -1 is NOT a tie: there is no candidate to resolve)
-                    tie = lt ? false : (tie || eq);
-                    bs = lt ? s : bs;
-                    best = lt ? d : best;
+                    if (WANT_IDX) {
+                        const bool lt = d < best, eq = d == best && inb && d < INFINITY;   // (inf == inf while bs is still -1 is NOT a tie: there is no candidate to resolve)
+                        tie = lt ? false : (tie || eq);
+                        bs = lt ? s : bs;
+                        best = lt ? d : best;
+                    } else {
+                        best = fminf(best, d);
+                    }
                 }
             }
         }
-        if (tie && bs >= 0) {   // exact ties (duplicated target points): the lowest original index among the candidates at the best distance
+        if (WANT_IDX && tie && bs >= 0) {   // exact ties (duplicated target points): the lowest original index among the candidates at the best distance
             int bid = g.ids[bs];
 #pragma unroll 1
             for (int r = 0; r < 9; ++r) {
@@ -707,10 +792,11 @@ __global__ __launch_bounds__(THREADS) void grid_chamfer_kernel(const ChGridArgs 
             atomicAdd(args.stats + blockIdx.z * 8 + 0, 1ull);
             atomicAdd(args.stats + blockIdx.z * 8 + 1, (unsigned long long)ncand);
         }
-        if (bs >= 0) fbest = best, fid = g.ids[bs];
-        if (!done && bs >= 0 && (bound2 == INFINITY || best < bound2 * 0.9999f - margin)) {
+        const bool found = WANT_IDX ? bs >= 0 : best < INFINITY;
+        if (found) fbest = best, fpos = bs;
+        if (!done && found && (bound2 == INFINITY || best < bound2 * 0.9999f - margin)) {
             G.dout[(size_t)b * Na + i] = best;
-            if (G.iout) G.iout[(size_t)b * Na + i] = fid;
+            if (WANT_IDX && G.iout) G.iout[(size_t)b * Na + i] = g.ids[bs];
             done = true;
             if (args.stats) atomicAdd(args.stats + blockIdx.z * 8 + 2, 1ull);
         }
@@ -739,20 +825,22 @@ __global__ __launch_bounds__(THREADS) void grid_chamfer_kernel(const ChGridArgs 
         // time (tens of thousands of instructions for the whole wave); the wave scans the target for it instead
         if (!done) {
             if (args.stats) atomicAdd(args.stats + blockIdx.z * 8 + 3, 1ull);
-            KBest<1, float> kb;
-            kb.key[0] = fbest, kb.idx[0] = fid;
+            typename std::conditional<WANT_IDX, ChamferMinPos, ChamferMin>::type kb;
+            kb.key = fbest;
+            if constexpr (WANT_IDX) kb.pos = fpos;
             if (grid_search<1, MetricDiff>(g, qp.x, qp.y, qp.z, met, kb, 2, 3)) {
                 if (args.stats) atomicAdd(args.stats + blockIdx.z * 8 + 4, 1ull);
-                G.dout[(size_t)b * Na + i] = kb.key[0];
+                G.dout[(size_t)b * Na + i] = kb.key;
                 // (non-finite coordinates leave the list empty: keep the index a valid row, the backward pass gathers through it)
-                if (G.iout) G.iout[(size_t)b * Na + i] = (unsigned)kb.idx[0] < (unsigned)G.gb.P ? kb.idx[0] : 0;
+                if constexpr (WANT_IDX)
+                    if (G.iout) G.iout[(size_t)b * Na + i] = kb.pos >= 0 ? g.ids[kb.pos] : 0;
                 done = true;
             }
         }
         scan = __ballot(!done) != 0;
         if (!scan) return;
     }
-    chamfer_scan_wave(G, g, b, Na, done, qp, i, met, margin, args.stats, blockIdx.z);
+    chamfer_scan_wave<WANT_IDX>(G, g, b, Na, done, qp, i, met, margin, args.stats, blockIdx.z);
 }
 
 // ---------------------------------------------------------------- host side
@@ -847,6 +935,8 @@ void launch_grid_chamfer(const GridBuf *gq, const GridBuf *gb, float *const *dou
         args.g[q] = ChGridGroup{gq[r], gb[r], dout[r], iout ? iout[r] : nullptr};
         if (q < ngroups && gq[r].P > maxN) maxN = gq[r].P;
     }
+    bool want_idx = false;   // one form per launch: the index-free kernel only when NO group wants indices
+    for (int q = 0; q < ngroups; ++q) want_idx = want_idx || args.g[q].iout != nullptr;
     args.scan_min = 24;   // (round 3, matrix-core scan + seeded walk, bench regime: 8 / 16 / 24 / 32 / never = 2.75 / 2.32 / 2.22 / 2.30 / 2.81 ms)
     args.stats = nullptr;
     if ((options().debug & DVM_DEBUG_CHAMFER_STATS) && hipMalloc(&args.stats, 64 * sizeof(unsigned long long)) == hipSuccess)   // diagnostic: synchronous, allocates
@@ -859,11 +949,18 @@ void launch_grid_chamfer(const GridBuf *gq, const GridBuf *gb, float *const *dou
     }
     lds_bytes = (lds_bytes + 15) / 16 * 16;
     prof_begin(s, DVM_PROF_CHAMFER);
-    if (lds_bytes <= 64 * 1024) {
-        ensure_dyn_lds((const void *)grid_chamfer_kernel<512, true>, (int)lds_bytes);
-        hipLaunchKernelGGL((grid_chamfer_kernel<512, true>), dim3((maxN + 511) / 512, B, ngroups), dim3(512), lds_bytes, s, args);
-    } else
-        hipLaunchKernelGGL((grid_chamfer_kernel<128, false>), dim3((maxN + 127) / 128, B, ngroups), dim3(128), 0, s, args);
+    const dim3 grid_lds((maxN + 511) / 512, B, ngroups), grid_glb((maxN + 127) / 128, B, ngroups);
+    if (lds_bytes <= 64 * 1024 && want_idx) {
+        ensure_dyn_lds((const void *)grid_chamfer_kernel<512, true, true>, (int)lds_bytes);
+        hipLaunchKernelGGL((grid_chamfer_kernel<512, true, true>), grid_lds, dim3(512), lds_bytes, s, args);
+    } else if (lds_bytes <= 64 * 1024) {
+        ensure_dyn_lds((const void *)grid_chamfer_kernel<512, true, false>, (int)lds_bytes);
+        hipLaunchKernelGGL((grid_chamfer_kernel<512, true, false>), grid_lds, dim3(512), lds_bytes, s, args);
+    } else if (want_idx) {
+        hipLaunchKernelGGL((grid_chamfer_kernel<128, false, true>), grid_glb, dim3(128), 0, s, args);
+    } else {
+        hipLaunchKernelGGL((grid_chamfer_kernel<128, false, false>), grid_glb, dim3(128), 0, s, args);
+    }
     prof_end(s, DVM_PROF_CHAMFER);
     if (args.stats) {
         unsigned long long h[64];
