@@ -10,7 +10,7 @@
 //
 // One kernel does every step: a workgroup owns 256 "query" rows (8 waves x 32), streams all "key" rows through a
 // double-buffered, k-deinterleaved LDS tile together with the keys' |.|^2 and potential, forms the squared-distance tile
-// on the fp32 matrix cores (the k-ordered fma chain of torch.cdist's matmul form, as softcorr_mfma_kernel does) and keeps
+// on the fp32 matrix cores (the k-ordered fma chain of torch.cdist's matmul form: the tile of dvm_dist_tile.h) and keeps
 // an online (max, sum) of L per query row in registers.  The row step is (queries, keys, potential) = (f1, f2, v), the
 // column step the same kernel with (f2, f1, u): every potential is owned by one lane pair, so there are no float atomics
 // and two runs give the same bits.  The N x M matrix is never written to HBM; the potentials (4 (N + M) bytes per entry)
@@ -26,18 +26,12 @@
 #include <float.h>
 #include <math.h>
 
-#include "dvm_common.h"
+#include "dvm_dist_tile.h"
 
 namespace dvm {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-void launch_rownorm2(const float *x, int rows, int K, float *out, hipStream_t s);   // dvm_softcorr.hip
-
 namespace {
 
-constexpr float SK_LOG2E = 1.4426950408889634f;
+using namespace dtile;
 
 // running (max, sum exp(. - max)) of one row
 struct LseState {
@@ -49,7 +43,7 @@ struct LseState {
     }
     __device__ __forceinline__ void rescale(float new_m) {
         if (new_m > m) {
-            l = l * (double)__builtin_amdgcn_exp2f((m - new_m) * SK_LOG2E);   // m = -inf, l = 0 -> 0 * 0
+            l = l * (double)__builtin_amdgcn_exp2f((m - new_m) * LOG2E);   // m = -inf, l = 0 -> 0 * 0
             m = new_m;
         }
     }
@@ -58,8 +52,8 @@ struct LseState {
     __device__ __forceinline__ float shift() const { return fmaxf(m, -FLT_MAX); }
     __device__ __forceinline__ void merge(float om, double ol) {
         const float mm = fmaxf(m, om);
-        const double a = (m == -INFINITY) ? 0.0 : l * (double)exp2f((m - mm) * SK_LOG2E);
-        const double b = (om == -INFINITY) ? 0.0 : ol * (double)exp2f((om - mm) * SK_LOG2E);
+        const double a = (m == -INFINITY) ? 0.0 : l * (double)exp2f((m - mm) * LOG2E);
+        const double b = (om == -INFINITY) ? 0.0 : ol * (double)exp2f((om - mm) * LOG2E);
         l = a + b;
         m = mm;
     }
@@ -80,7 +74,7 @@ __device__ __forceinline__ void store_final(const KBest<TOPK, float> &kb, bool h
         if (t < topk) {
             const bool live = t < M;
             const float L = hasv ? -kb.key[t] : kb.key[t] * neg_alpha;
-            val[t] = live ? exp2f((L - lmax) * SK_LOG2E) * inv : 0.f;
+            val[t] = live ? exp2f((L - lmax) * LOG2E) * inv : 0.f;
             idx[t] = live ? kb.idx[t] : 0;
         }
     }
@@ -105,20 +99,15 @@ struct SKArgs {
 };
 
 // ------------------------------------------------------------ scalar variant
-// One thread per query row, keys staged through LDS in tiles of 32, the dot product an explicit k-ordered fmaf chain.
-// Any d % 4 == 0.  The cross-check form of the matrix-core kernel and the path for d != 128; not tuned.
-constexpr int SS_KT = 32;
-constexpr int SS_DC = 32;
-
-// SWAP: the queries are f2 (column step).  cdist adds |f1|^2 first: d2 = (acc + |f1_i|^2) + |f2_j|^2 in either direction,
-// so that a step and its transpose see the same S_ij bit for bit.
+// One thread per query row (the scalar sweep of dvm_dist_tile.h).  Any d % 4 == 0.  The cross-check form of the
+// matrix-core kernel and the path for d != 128; not tuned.  SWAP: the queries are f2 (column step), see sqdist.
 template <bool FINAL, bool SWAP, int TOPK>
 __global__ __launch_bounds__(128) void sinkhorn_scalar_kernel(const SKArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];   // [SS_KT][d] keys + [SS_KT] norms + [SS_KT] potentials
+    extern __shared__ __attribute__((aligned(16))) float smem[];   // [SC_KT][d] keys + [SC_KT] norms + [SC_KT] potentials
     const int N = a.N, M = a.M, d = a.d;
     float *kt = smem;
-    float *kn = smem + SS_KT * d;
-    float *kp = kn + SS_KT;
+    float *kn = smem + SC_KT * d;
+    float *kp = kn + SC_KT;
     const int b = blockIdx.y;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const int ic = i < N ? i : N - 1;
@@ -131,53 +120,22 @@ __global__ __launch_bounds__(128) void sinkhorn_scalar_kernel(const SKArgs a) {
     st.init();
     KBest<TOPK, float> kb;
     if (FINAL) kb.init(INFINITY);
-    for (int j0 = 0; j0 < M; j0 += SS_KT) {
+    for (int j0 = 0; j0 < M; j0 += SC_KT) {
         __syncthreads();
-        for (int e = threadIdx.x; e < SS_KT * d / 4; e += blockDim.x) {
-            int r = e / (d / 4), c = e % (d / 4);
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (j0 + r < M) v = *(const f32x4 *)(kbase + (size_t)(j0 + r) * d + 4 * c);
-            *(f32x4 *)(kt + r * d + 4 * c) = v;
-        }
-        if (threadIdx.x < SS_KT) {
+        scalar_stage_keys(kt, kbase, j0, M, d);
+        if (threadIdx.x < SC_KT) {
             const int j = j0 + threadIdx.x;
             kn[threadIdx.x] = j < M ? a.nk[(size_t)b * M + j] : INFINITY;
             kp[threadIdx.x] = (j < M && hasv) ? a.pot[(size_t)b * a.pot_bs + j] : 0.f;
         }
         __syncthreads();
-        float acc[SS_KT];
-#pragma unroll
-        for (int j = 0; j < SS_KT; ++j) acc[j] = 0.f;
-        for (int c0 = 0; c0 < d; c0 += SS_DC) {
-            float qr[SS_DC];
-            int cw = d - c0 < SS_DC ? d - c0 : SS_DC;
-#pragma unroll
-            for (int c = 0; c < SS_DC; c += 4) {
-                f32x4 v = {0.f, 0.f, 0.f, 0.f};
-                if (c < cw) v = *(const f32x4 *)(q + c0 + c);
-                qr[c] = -2.f * v.x, qr[c + 1] = -2.f * v.y, qr[c + 2] = -2.f * v.z, qr[c + 3] = -2.f * v.w;
-            }
-#pragma unroll
-            for (int j = 0; j < SS_KT; ++j) {
-#pragma unroll
-                for (int c = 0; c < SS_DC; c += 4) {
-                    if (c < cw) {
-                        f32x4 kv = *(const f32x4 *)(kt + j * d + c0 + c);
-                        acc[j] = fmaf(qr[c], kv.x, acc[j]);
-                        acc[j] = fmaf(qr[c + 1], kv.y, acc[j]);
-                        acc[j] = fmaf(qr[c + 2], kv.z, acc[j]);
-                        acc[j] = fmaf(qr[c + 3], kv.w, acc[j]);
-                    }
-                }
-            }
-        }
-        float Lv[SS_KT], dv[SS_KT];
+        float acc[SC_KT];
+        scalar_dist_chain(q, kt, d, acc);
+        float Lv[SC_KT], dv[SC_KT];
         float tmax = -INFINITY;
 #pragma unroll
-        for (int j = 0; j < SS_KT; ++j) {
-            float d2 = SWAP ? (acc[j] + kn[j]) + na : (acc[j] + na) + kn[j];
-            d2 = d2 > 0.f ? d2 : 0.f;
-            dv[j] = sqrt_rn(d2);
+        for (int j = 0; j < SC_KT; ++j) {
+            dv[j] = sqrt_rn(sqdist<SWAP>(acc[j], na, kn[j]));
             Lv[j] = dv[j] * neg_alpha + kp[j];
             tmax = fmaxf(tmax, Lv[j]);
         }
@@ -185,8 +143,8 @@ __global__ __launch_bounds__(128) void sinkhorn_scalar_kernel(const SKArgs a) {
         const float sh = st.shift();
         float ls = 0.f;
 #pragma unroll
-        for (int j = 0; j < SS_KT; ++j) {
-            ls += __builtin_amdgcn_exp2f((Lv[j] - sh) * SK_LOG2E);
+        for (int j = 0; j < SC_KT; ++j) {
+            ls += __builtin_amdgcn_exp2f((Lv[j] - sh) * LOG2E);
             if (FINAL) kb.insert(hasv ? -Lv[j] : dv[j], j0 + j);
         }
         st.l += (double)ls;
@@ -203,18 +161,14 @@ __global__ __launch_bounds__(128) void sinkhorn_scalar_kernel(const SKArgs a) {
 }
 
 // -------------------------------------------------------------- matrix-core variant (d == 128)
-// Tile shapes, LDS layout and the two-role phase structure are those of softcorr_mfma_kernel (dvm_softcorr.hip): the
-// accumulator tile is [key][query], so a query's 16 candidates of a 32-key sub-tile sit in one lane's registers and the
-// online (max, sum) and the top-k list need no cross-lane traffic until the two half-lanes of a query merge at the end.
-constexpr int SK_D = 128;
-constexpr int SK_KT = 64;             // keys per LDS tile (two 32-key MFMA sub-tiles)
-constexpr int SK_LDK = SK_D + 4;      // padded row (floats): 528 B, keeps ds_read_b128 conflict-free
+// Tile, LDS layout and the two-role phase structure: dvm_dist_tile.h.  The online (max, sum) and the top-k list need no
+// cross-lane traffic until the two half-lanes of a query merge at the end.
 constexpr int SK_QW = 32;             // queries per wave
 constexpr int SK_WAVES = 8;
 constexpr int SK_QB = SK_QW * SK_WAVES;   // 256 queries per workgroup
 constexpr int SK_THREADS = 64 * SK_WAVES;
-constexpr int SK_LD_PER_THREAD = SK_KT * SK_D / 4 / SK_THREADS;   // float4 loads per thread per tile = 8
-constexpr int SK_TILE_FLOATS = SK_KT * SK_LDK + 2 * SK_KT;        // keys + their norms + their potentials
+constexpr int SK_LD_PER_THREAD = KT * D / 4 / SK_THREADS;   // float4 loads per thread per tile = 8
+constexpr int SK_TILE_FLOATS = ROWS_FLOATS + 2 * KT;        // keys + their norms + their potentials
 constexpr int SK_STAGE = 16 * 64;   // final row sweep, floats per wave: this sub-tile's 16 ranking keys of each lane, [r][lane]
 constexpr size_t SK_LDS_BYTES = (size_t)2 * SK_TILE_FLOATS * sizeof(float);
 constexpr size_t SK_LDS_BYTES_FINAL = SK_LDS_BYTES + (size_t)SK_WAVES * SK_STAGE * sizeof(float);
@@ -222,7 +176,7 @@ constexpr size_t SK_LDS_BYTES_FINAL = SK_LDS_BYTES + (size_t)SK_WAVES * SK_STAGE
 // FINAL: the last row sweep (top-k, pi_val / pi_idx / row_lmax / row_sum / u); HASV (FINAL only): rank by -L, else by d.
 template <bool FINAL, bool HASV, bool SWAP, int TOPK>
 __global__ __launch_bounds__(SK_THREADS, 2) void sinkhorn_mfma_kernel(const SKArgs a) {
-    // [2] x { [SK_KT][SK_LDK] keys, [SK_KT] norms, [SK_KT] potentials }; FINAL: + [SK_WAVES][16][64] ranking keys
+    // [2] x { [KT][LDK] keys, [KT] norms, [KT] potentials }; FINAL: + [SK_WAVES][16][64] ranking keys
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *const stage = smem + 2 * SK_TILE_FLOATS + (threadIdx.x >> 6) * SK_STAGE + (threadIdx.x & 63);   // this lane's column
 
@@ -234,21 +188,15 @@ __global__ __launch_bounds__(SK_THREADS, 2) void sinkhorn_mfma_kernel(const SKAr
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r32 = lane & 31, h = lane >> 5;
 
-    const float *kbase = a.k + (size_t)b * M * SK_D;
+    const float *kbase = a.k + (size_t)b * M * D;
     const float *knb = a.nk + (size_t)b * M;
     const float *kpb = a.pot ? a.pot + (size_t)b * a.pot_bs : nullptr;
 
-    // this lane's query row and its B-operand fragment: q[s] = -2 * query[row][2s + h]
+    // this lane's query row and its B-operand fragment
     const int qrow = qt * SK_QB + wave * SK_QW + r32;
     const int qrc = qrow < N ? qrow : N - 1;
-    const float *qp = a.q + ((size_t)b * N + qrc) * SK_D;
-    float q[SK_D / 2];
-#pragma unroll
-    for (int c = 0; c < SK_D / 4; ++c) {
-        f32x4 v = *(const f32x4 *)(qp + 4 * c);
-        q[2 * c] = -2.f * (h ? v.y : v.x);
-        q[2 * c + 1] = -2.f * (h ? v.w : v.z);
-    }
+    float q[D / 2];
+    load_query_frag(a.q + ((size_t)b * N + qrc) * D, h, q);
     const float na = a.nq[(size_t)b * N + qrc];
 
     LseState st;
@@ -256,81 +204,42 @@ __global__ __launch_bounds__(SK_THREADS, 2) void sinkhorn_mfma_kernel(const SKAr
     KBest<TOPK, float> kb;
     if (FINAL) kb.init(INFINITY);
 
-    const int ntiles = (M + SK_KT - 1) / SK_KT;
+    const int ntiles = (M + KT - 1) / KT;
     f32x4 pre[SK_LD_PER_THREAD];
     float pren = 0.f;   // threads 0..63: a key's norm; threads 64..127: a key's potential
 
     auto issue_loads = [&](int t) {
-        const int j0 = t * SK_KT;
-#pragma unroll
-        for (int e = 0; e < SK_LD_PER_THREAD; ++e) {
-            int id = tid + e * SK_THREADS;
-            int r = id >> 5, c = id & 31;   // 32 float4 per 128-float row
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (j0 + r < M) v = *(const f32x4 *)(kbase + (size_t)(j0 + r) * SK_D + 4 * c);
-            pre[e] = v;
-        }
-        if (tid < SK_KT)
+        const int j0 = t * KT;
+        issue_tile<SK_THREADS>(kbase, j0, M, tid, pre);
+        if (tid < KT)
             pren = (j0 + tid < M) ? knb[j0 + tid] : INFINITY;
-        else if (tid < 2 * SK_KT)
-            pren = (kpb && j0 + tid - SK_KT < M) ? kpb[j0 + tid - SK_KT] : 0.f;
+        else if (tid < 2 * KT)
+            pren = (kpb && j0 + tid - KT < M) ? kpb[j0 + tid - KT] : 0.f;
     };
     auto commit_loads = [&](int buf) {
         float *kt = smem + buf * SK_TILE_FLOATS;
-#pragma unroll
-        for (int e = 0; e < SK_LD_PER_THREAD; ++e) {
-            int id = tid + e * SK_THREADS;
-            int r = id >> 5, c = id & 31;
-            // k = 4c+{0,1,2,3} -> (h,s) = (0,2c) (1,2c) (0,2c+1) (1,2c+1)
-            float2 ev = {pre[e].x, pre[e].z}, od = {pre[e].y, pre[e].w};
-            *(float2 *)(kt + r * SK_LDK + 2 * c) = ev;
-            *(float2 *)(kt + r * SK_LDK + 64 + 2 * c) = od;
-        }
-        if (tid < 2 * SK_KT) kt[SK_KT * SK_LDK + tid] = pren;   // norms, then potentials
+        commit_tile<SK_THREADS>(kt, tid, pre);
+        if (tid < 2 * KT) kt[ROWS_FLOATS + tid] = pren;   // norms, then potentials
     };
 
-    issue_loads(0);
-    commit_loads(0);
-    __syncthreads();
-
-    // Two waves share a SIMD (w and w + 4).  Both alternate a matrix phase (64 dependent MFMAs) with an epilogue of
-    // comparable length; waves 4-7 (role 1) defer the epilogue of each tile's second sub-tile across the barrier, so that
-    // after every barrier one wave of the SIMD starts on the matrix pipe and its partner in the epilogue.  Every wave
-    // still folds its sub-tiles in ascending key order: a row's result does not depend on the wave that owns it.
-    const int role = __builtin_amdgcn_readfirstlane(wave >> 2);
-
-    auto mfma_chain = [&](const float *kt, int sub, f32x16 &acc, float (&nbv)[16], float (&pv)[16]) {
-        const float *arow = kt + (sub * 32 + r32) * SK_LDK + h * 64;
-        acc = f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int c = 0; c < 16; ++c) {
-            f32x4 av = *(const f32x4 *)(arow + 4 * c);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, q[4 * c], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, q[4 * c + 1], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, q[4 * c + 2], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, q[4 * c + 3], acc, 0, 0, 0);
-        }
-        // |key|^2 and potential of this lane's 16 keys: local key = (r&3) + 8*(r>>2) + 4*h
-        const float *kn = kt + SK_KT * SK_LDK + sub * 32 + 4 * h;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            f32x4 nb = *(const f32x4 *)(kn + 8 * g);
-            nbv[4 * g] = nb.x, nbv[4 * g + 1] = nb.y, nbv[4 * g + 2] = nb.z, nbv[4 * g + 3] = nb.w;
-            f32x4 pb = *(const f32x4 *)(kn + SK_KT + 8 * g);
-            pv[4 * g] = pb.x, pv[4 * g + 1] = pb.y, pv[4 * g + 2] = pb.z, pv[4 * g + 3] = pb.w;
-        }
+    // the chain, |key|^2 and potential of this lane's 16 keys
+    f32x16 acc;
+    float nbv[16], pv[16];
+    auto mfma_chain = [&](int buf, int sub) {
+        const float *kt = smem + buf * SK_TILE_FLOATS;
+        dist_chain(kt, sub, r32, h, q, acc);
+        lane_scalars(kt + ROWS_FLOATS, sub, h, nbv);
+        lane_scalars(kt + ROWS_FLOATS + KT, sub, h, pv);
     };
 
-    auto epilogue = [&](const f32x16 &acc, const float (&nbv)[16], const float (&pv)[16], int jbase) {
+    auto epilogue = [&](int t, int sub) {
         float Lv[16];
         unsigned mask = 0;
         const float worst = FINAL ? kb.key[TOPK - 1] : 0.f;
         float tmax = -INFINITY;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            float d2 = SWAP ? (acc[r] + nbv[r]) + na : (acc[r] + na) + nbv[r];   // +inf for padding keys
-            d2 = d2 > 0.f ? d2 : 0.f;
-            const float de = sqrt_rn(d2);
+            const float de = sqrt_rn(sqdist<SWAP>(acc[r], na, nbv[r]));   // +inf for padding keys
             const float L = de * neg_alpha + pv[r];   // (-ffp-contract=off: a product, then a sum)
             Lv[r] = L;
             if (FINAL) {   // the ranking keys are parked in LDS ([r][lane], conflict-free) for the dynamic pick below
@@ -344,7 +253,7 @@ __global__ __launch_bounds__(SK_THREADS, 2) void sinkhorn_mfma_kernel(const SKAr
         const float sh = st.shift();
         float ls = 0.f;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) ls += __builtin_amdgcn_exp2f((Lv[r] - sh) * SK_LOG2E);
+        for (int r = 0; r < 16; ++r) ls += __builtin_amdgcn_exp2f((Lv[r] - sh) * LOG2E);
         st.l += (double)ls;
         if (FINAL) {
             // candidates that beat this lane's current worst, in ascending column order; a counted, wave-uniform loop
@@ -355,7 +264,7 @@ __global__ __launch_bounds__(SK_THREADS, 2) void sinkhorn_mfma_kernel(const SKAr
                 const int bpos = act ? (__ffs(mask) - 1) : 0;
                 mask &= mask - 1;
                 const float key = act ? stage[bpos * 64] : INFINITY;
-                kb.insert_nb(key, jbase + (bpos & 3) + 8 * (bpos >> 2));
+                kb.insert_nb(key, t * KT + sub * 32 + lane_key(bpos, h));
             }
         }
     };
@@ -363,22 +272,8 @@ __global__ __launch_bounds__(SK_THREADS, 2) void sinkhorn_mfma_kernel(const SKAr
     // the 16-entry list leaves no room for the next tile's 32 prefetch registers next to it: that variant loads the tile after
     // its epilogues (the other wave of the SIMD covers the latency) instead of spilling
     constexpr bool LATE_LOADS = FINAL && TOPK > 10;
-    f32x16 acc;
-    float nbv[16], pv[16];
-    for (int t = 0; t < ntiles; ++t) {
-        const int buf = t & 1;
-        if (!LATE_LOADS && t + 1 < ntiles) issue_loads(t + 1);
-        const float *kt = smem + buf * SK_TILE_FLOATS;
-        if (role == 1 && t > 0) epilogue(acc, nbv, pv, (t - 1) * SK_KT + 32 + 4 * h);   // the previous tile's second sub-tile
-        mfma_chain(kt, 0, acc, nbv, pv);
-        epilogue(acc, nbv, pv, t * SK_KT + 4 * h);
-        mfma_chain(kt, 1, acc, nbv, pv);
-        if (role == 0) epilogue(acc, nbv, pv, t * SK_KT + 32 + 4 * h);
-        if (LATE_LOADS && t + 1 < ntiles) issue_loads(t + 1);
-        if (t + 1 < ntiles) commit_loads(buf ^ 1);
-        __syncthreads();
-    }
-    if (role == 1) epilogue(acc, nbv, pv, (ntiles - 1) * SK_KT + 32 + 4 * h);
+    const int role = __builtin_amdgcn_readfirstlane(wave >> 2);
+    two_role_sweep<LATE_LOADS>(ntiles, role, issue_loads, commit_loads, mfma_chain, epilogue);
 
     // merge the two half-lanes that share a query (lane, lane ^ 32); the lower lane writes the row
     {
@@ -417,7 +312,7 @@ void launch_mfma(const SKArgs &a, int B, hipStream_t s) {
 
 template <bool FINAL, bool SWAP, int TOPK>
 void launch_scalar(const SKArgs &a, int B, hipStream_t s) {
-    const size_t lds = (size_t)(SS_KT * a.d + 2 * SS_KT) * sizeof(float);
+    const size_t lds = (size_t)(SC_KT * a.d + 2 * SC_KT) * sizeof(float);
     ensure_dyn_lds((const void *)sinkhorn_scalar_kernel<FINAL, SWAP, TOPK>, 66 * 1024);
     hipLaunchKernelGGL((sinkhorn_scalar_kernel<FINAL, SWAP, TOPK>), dim3((a.N + 127) / 128, B), dim3(128), lds, s, a);
 }
@@ -522,7 +417,7 @@ DVM_EXPORT int dvm_sinkhorn_fwd_f32(const float *f1, const float *f2, int B, int
     }
     hipStream_t s = (hipStream_t)stream;
     float *ub = u ? u : wu, *vb = v ? v : wv;
-    const bool mfma = variant == 0 && d == SK_D;
+    const bool mfma = variant == 0 && d == D;
     if (n_iter == 0 && v) (void)hipMemsetAsync(v, 0, (size_t)B * M * sizeof(float), s);
     return sinkhorn_run(f1, f2, B, N, M, d, neg_alpha, n_iter, topk, pi_val, pi_idx, row_lmax, row_sum, n1, n2, ub, 0, N, vb, 0, M, u,
                         mfma, s);
@@ -555,5 +450,5 @@ DVM_EXPORT int dvm_sinkhorn_fwd_hist_f32(const float *f1, const float *f2, int B
     const long u_bs = (long)(n_iter + 1) * N, v_bs = (long)(n_iter + 1) * M;
     hipLaunchKernelGGL(sinkhorn_zero_slice_kernel, dim3((M + 255) / 256, B), dim3(256), 0, s, v_hist, M, v_bs);   // v^0
     return sinkhorn_run(f1, f2, B, N, M, d, neg_alpha, n_iter, topk, pi_val, pi_idx, row_lmax, row_sum, n1, n2, u_hist, N, u_bs, v_hist,
-                        M, v_bs, u_hist + (size_t)n_iter * N, variant == 0 && d == SK_D, s);
+                        M, v_bs, u_hist + (size_t)n_iter * N, variant == 0 && d == D, s);
 }

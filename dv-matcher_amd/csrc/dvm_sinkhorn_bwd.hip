@@ -23,31 +23,28 @@
 //               query accumulates -sum_key coef_key exp(S + pot_query + pot_key) in fp64; the first sweep (vbar^T) skips
 //               the top-k entries' final-step term through the bit matrix and adds to what colgather left.
 //   pack        the 2(T+1) per-row and per-column scalars of phase B (potentials scaled by log2 e, coefficients) as planes.
-//   phase B     softcorr_bwd_mfma_kernel's structure, one launch per pass (df1 row-major, df2 column-major): outer
-//               rows in registers, inner rows and their scalar planes through LDS, distances by 64 fp32 MFMAs per 32x32
-//               tile with the BW_TAU exact-difference redo, the entry's weight the sum of 2T + 1 exp2 terms, W fed back as
+//   phase B     the phase-B pieces of dvm_dist_tile.h (shared with softcorr_bwd_mfma_kernel), one launch per pass (df1
+//               row-major, df2 column-major): outer rows in registers, inner rows and their scalar planes through LDS,
+//               distances by 64 fp32 MFMAs per 32x32 tile with the TAU exact-difference redo, the entry's weight the
+//               sum of 2T + 1 exp2 terms, W fed back as
 //               the A operand of the second product.  The inner loop is never split: an output row is owned by one
 //               workgroup and added to the slots' share with a plain read-modify-write.
 // No float atomics and no host synchronisation anywhere, n_iter = 0 included (it runs prep, colgather, pack and phase B
 // with one term; dvm_softcorr_bwd_f32's atomics are not used).  variant 1 runs scalar forms of phase A and B (any
 // d % 4 == 0, d <= 512; untuned): the cross-check of the matrix-core kernels and the path for d != 128.
+// Every kernel here forms its distances with dvm_dist_tile.h.
 #include <float.h>
 #include <math.h>
 
 #include <algorithm>
 
-#include "dvm_common.h"
+#include "dvm_dist_tile.h"
 
 namespace dvm {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-void launch_rownorm2(const float *x, int rows, int K, float *out, hipStream_t s);   // dvm_softcorr.hip
-
 namespace {
 
-constexpr float LOG2E = 1.4426950408889634f;
+using namespace dtile;
+
 constexpr int SKB_MAX_ITER = 32;
 
 // ------------------------------------------------------------------------------------------------ prep / colgather / pack
@@ -200,18 +197,15 @@ struct SAArgs {
     int wpr;
 };
 
-constexpr int SS_KT = 32;
-constexpr int SS_DC = 32;
-
-// scalar form: sinkhorn_scalar_kernel's distances (one thread per query row, keys through LDS in tiles of 32)
+// scalar form: the scalar sweep of dvm_dist_tile.h (one thread per query row, keys through LDS in tiles of 32)
 template <bool SWAP, bool MASKED>
 __global__ __launch_bounds__(128) void skb_sweep_scalar_kernel(const SAArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];   // [SS_KT][d] keys + norms + potentials + coefficients
+    extern __shared__ __attribute__((aligned(16))) float smem[];   // [SC_KT][d] keys + norms + potentials + coefficients
     const int N = a.N, M = a.M, d = a.d;
     float *kt = smem;
-    float *kn = smem + SS_KT * d;
-    float *kp = kn + SS_KT;
-    float *kc = kp + SS_KT;
+    float *kn = smem + SC_KT * d;
+    float *kp = kn + SC_KT;
+    float *kc = kp + SC_KT;
     const int b = blockIdx.y;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const int ic = i < N ? i : N - 1;
@@ -221,53 +215,22 @@ __global__ __launch_bounds__(128) void skb_sweep_scalar_kernel(const SAArgs a) {
     const float *kbase = a.k + (size_t)b * M * d;
     const float neg_alpha = a.neg_alpha;
     double sum = 0.0;
-    for (int j0 = 0; j0 < M; j0 += SS_KT) {
+    for (int j0 = 0; j0 < M; j0 += SC_KT) {
         __syncthreads();
-        for (int e = threadIdx.x; e < SS_KT * d / 4; e += blockDim.x) {
-            int r = e / (d / 4), c = e % (d / 4);
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (j0 + r < M) v = *(const f32x4 *)(kbase + (size_t)(j0 + r) * d + 4 * c);
-            *(f32x4 *)(kt + r * d + 4 * c) = v;
-        }
-        if (threadIdx.x < SS_KT) {
+        scalar_stage_keys(kt, kbase, j0, M, d);
+        if (threadIdx.x < SC_KT) {
             const int j = j0 + threadIdx.x;
             kn[threadIdx.x] = j < M ? a.nk[(size_t)b * M + j] : INFINITY;
             kp[threadIdx.x] = j < M ? a.potk[(size_t)b * a.potk_bs + j] : 0.f;
             kc[threadIdx.x] = j < M ? a.coefk[(size_t)b * a.coefk_bs + j] : 0.f;
         }
         __syncthreads();
-        float acc[SS_KT];
-#pragma unroll
-        for (int j = 0; j < SS_KT; ++j) acc[j] = 0.f;
-        for (int c0 = 0; c0 < d; c0 += SS_DC) {
-            float qr[SS_DC];
-            int cw = d - c0 < SS_DC ? d - c0 : SS_DC;
-#pragma unroll
-            for (int c = 0; c < SS_DC; c += 4) {
-                f32x4 v = {0.f, 0.f, 0.f, 0.f};
-                if (c < cw) v = *(const f32x4 *)(q + c0 + c);
-                qr[c] = -2.f * v.x, qr[c + 1] = -2.f * v.y, qr[c + 2] = -2.f * v.z, qr[c + 3] = -2.f * v.w;
-            }
-#pragma unroll
-            for (int j = 0; j < SS_KT; ++j) {
-#pragma unroll
-                for (int c = 0; c < SS_DC; c += 4) {
-                    if (c < cw) {
-                        f32x4 kv = *(const f32x4 *)(kt + j * d + c0 + c);
-                        acc[j] = fmaf(qr[c], kv.x, acc[j]);
-                        acc[j] = fmaf(qr[c + 1], kv.y, acc[j]);
-                        acc[j] = fmaf(qr[c + 2], kv.z, acc[j]);
-                        acc[j] = fmaf(qr[c + 3], kv.w, acc[j]);
-                    }
-                }
-            }
-        }
+        float acc[SC_KT];
+        scalar_dist_chain(q, kt, d, acc);
         float ls = 0.f;
 #pragma unroll
-        for (int j = 0; j < SS_KT; ++j) {
-            float d2 = SWAP ? (acc[j] + kn[j]) + na : (acc[j] + na) + kn[j];
-            d2 = d2 > 0.f ? d2 : 0.f;
-            const float L = sqrt_rn(d2) * neg_alpha + kp[j];
+        for (int j = 0; j < SC_KT; ++j) {
+            const float L = sqrt_rn(sqdist<SWAP>(acc[j], na, kn[j])) * neg_alpha + kp[j];
             float term = kc[j] * __builtin_amdgcn_exp2f((L + pq) * LOG2E);
             if (MASKED) {
                 const int key = j0 + j < M ? j0 + j : M - 1;
@@ -284,16 +247,13 @@ __global__ __launch_bounds__(128) void skb_sweep_scalar_kernel(const SAArgs a) {
     }
 }
 
-// matrix-core form (d == 128): tile shapes, LDS layout and the two-role phase structure of sinkhorn_mfma_kernel
-constexpr int SK_D = 128;
-constexpr int SK_KT = 64;
-constexpr int SK_LDK = SK_D + 4;
+// matrix-core form (d == 128): tile, LDS layout and the two-role phase structure of dvm_dist_tile.h
 constexpr int SK_QW = 32;
 constexpr int SK_WAVES = 8;
 constexpr int SK_QB = SK_QW * SK_WAVES;
 constexpr int SK_THREADS = 64 * SK_WAVES;
-constexpr int SK_LD_PER_THREAD = SK_KT * SK_D / 4 / SK_THREADS;
-constexpr int SA_TILE_FLOATS = SK_KT * SK_LDK + 3 * SK_KT + SK_KT * SK_WAVES;   // keys + {norm, potential, coefficient} + mask words [key][wave]
+constexpr int SK_LD_PER_THREAD = KT * D / 4 / SK_THREADS;
+constexpr int SA_TILE_FLOATS = ROWS_FLOATS + 3 * KT + KT * SK_WAVES;   // keys + {norm, potential, coefficient} + mask words [key][wave]
 constexpr size_t SA_LDS_BYTES = (size_t)2 * SA_TILE_FLOATS * sizeof(float);
 
 template <bool SWAP, bool MASKED>
@@ -307,7 +267,7 @@ __global__ __launch_bounds__(SK_THREADS, 2) void skb_sweep_mfma_kernel(const SAA
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r32 = lane & 31, h = lane >> 5;
 
-    const float *kbase = a.k + (size_t)b * M * SK_D;
+    const float *kbase = a.k + (size_t)b * M * D;
     const float *knb = a.nk + (size_t)b * M;
     const float *kpb = a.potk + (size_t)b * a.potk_bs;
     const float *kcb = a.coefk + (size_t)b * a.coefk_bs;
@@ -316,120 +276,59 @@ __global__ __launch_bounds__(SK_THREADS, 2) void skb_sweep_mfma_kernel(const SAA
 
     const int qrow = qt * SK_QB + wave * SK_QW + r32;
     const int qrc = qrow < N ? qrow : N - 1;
-    const float *qp = a.q + ((size_t)b * N + qrc) * SK_D;
-    float q[SK_D / 2];
-#pragma unroll
-    for (int c = 0; c < SK_D / 4; ++c) {
-        f32x4 v = *(const f32x4 *)(qp + 4 * c);
-        q[2 * c] = -2.f * (h ? v.y : v.x);
-        q[2 * c + 1] = -2.f * (h ? v.w : v.z);
-    }
+    float q[D / 2];
+    load_query_frag(a.q + ((size_t)b * N + qrc) * D, h, q);
     const float na = a.nq[(size_t)b * N + qrc];
     const float pq = a.potq[(size_t)b * a.potq_bs + qrc] + a.add;
     double sum = 0.0;
 
-    const int ntiles = (M + SK_KT - 1) / SK_KT;
+    const int ntiles = (M + KT - 1) / KT;
     f32x4 pre[SK_LD_PER_THREAD];
     float pren = 0.f;   // threads 0..63: a key's norm; 64..127: its potential; 128..191: its coefficient
     uint32_t prem = 0;  // MASKED: the word of key tid / 8 for the 32 queries of wave tid % 8
 
     auto issue_loads = [&](int t) __attribute__((always_inline)) {
-        const int j0 = t * SK_KT;
-#pragma unroll
-        for (int e = 0; e < SK_LD_PER_THREAD; ++e) {
-            int id = tid + e * SK_THREADS;
-            int r = id >> 5, c = id & 31;
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (j0 + r < M) v = *(const f32x4 *)(kbase + (size_t)(j0 + r) * SK_D + 4 * c);
-            pre[e] = v;
-        }
-        if (tid < SK_KT)
+        const int j0 = t * KT;
+        issue_tile<SK_THREADS>(kbase, j0, M, tid, pre);
+        if (tid < KT)
             pren = (j0 + tid < M) ? knb[j0 + tid] : INFINITY;
-        else if (tid < 2 * SK_KT)
-            pren = (j0 + tid - SK_KT < M) ? kpb[j0 + tid - SK_KT] : 0.f;
-        else if (tid < 3 * SK_KT)
-            pren = (j0 + tid - 2 * SK_KT < M) ? kcb[j0 + tid - 2 * SK_KT] : 0.f;
-        if (MASKED) {
-            const int key = j0 + (tid >> 3), wc = qt * SK_WAVES + (tid & 7);
-            prem = (key < M && wc < wpr) ? bits[((size_t)b * M + key) * wpr + wc] : 0u;
-        }
+        else if (tid < 2 * KT)
+            pren = (j0 + tid - KT < M) ? kpb[j0 + tid - KT] : 0.f;
+        else if (tid < 3 * KT)
+            pren = (j0 + tid - 2 * KT < M) ? kcb[j0 + tid - 2 * KT] : 0.f;
+        if (MASKED) prem = skip_mask_load<SK_WAVES>(1, bits, wpr, b, qt, j0, N, M, tid);   // queries = columns: the df2 layout
     };
     auto commit_loads = [&](int buf) __attribute__((always_inline)) {
         float *kt = smem + buf * SA_TILE_FLOATS;
-#pragma unroll
-        for (int e = 0; e < SK_LD_PER_THREAD; ++e) {
-            int id = tid + e * SK_THREADS;
-            int r = id >> 5, c = id & 31;
-            float2 ev = {pre[e].x, pre[e].z}, od = {pre[e].y, pre[e].w};
-            *(float2 *)(kt + r * SK_LDK + 2 * c) = ev;
-            *(float2 *)(kt + r * SK_LDK + 64 + 2 * c) = od;
-        }
-        if (tid < 3 * SK_KT) kt[SK_KT * SK_LDK + tid] = pren;
-        if (MASKED) ((uint32_t *)kt)[SK_KT * SK_LDK + 3 * SK_KT + tid] = prem;
+        commit_tile<SK_THREADS>(kt, tid, pre);
+        if (tid < 3 * KT) kt[ROWS_FLOATS + tid] = pren;
+        if (MASKED) ((uint32_t *)kt)[ROWS_FLOATS + 3 * KT + tid] = prem;
     };
 
-    issue_loads(0);
-    commit_loads(0);
-    __syncthreads();
-
-    const int role = __builtin_amdgcn_readfirstlane(wave >> 2);   // see sinkhorn_mfma_kernel
-
-    // everything the epilogue needs leaves LDS here: role 1 runs a sub-tile's epilogue after the barrier that frees its buffer
-    auto mfma_chain = [&](const float *kt, int sub, f32x16 &acc, float (&nbv)[16], float (&pv)[16], float (&cv)[16], unsigned &skip) __attribute__((always_inline)) {
-        const float *arow = kt + (sub * 32 + r32) * SK_LDK + h * 64;
-        acc = f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int c = 0; c < 16; ++c) {
-            f32x4 av = *(const f32x4 *)(arow + 4 * c);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, q[4 * c], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, q[4 * c + 1], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, q[4 * c + 2], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, q[4 * c + 3], acc, 0, 0, 0);
-        }
-        const float *kn = kt + SK_KT * SK_LDK + sub * 32 + 4 * h;   // local key = (r&3) + 8*(r>>2) + 4*h
-        const uint32_t *msk = (const uint32_t *)(kt + SK_KT * SK_LDK + 3 * SK_KT);
-        skip = 0;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            f32x4 nb = *(const f32x4 *)(kn + 8 * g);
-            f32x4 pb = *(const f32x4 *)(kn + SK_KT + 8 * g);
-            f32x4 cb = *(const f32x4 *)(kn + 2 * SK_KT + 8 * g);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                nbv[4 * g + u] = nb[u], pv[4 * g + u] = pb[u], cv[4 * g + u] = cb[u];
-                if (MASKED) skip |= ((msk[(sub * 32 + 4 * h + 8 * g + u) * SK_WAVES + wave] >> r32) & 1u) << (4 * g + u);
-            }
-        }
+    f32x16 acc;
+    float nbv[16], pv[16], cv[16];
+    unsigned skip = 0;
+    auto mfma_chain = [&](int buf, int sub) __attribute__((always_inline)) {
+        const float *kt = smem + buf * SA_TILE_FLOATS;
+        dist_chain(kt, sub, r32, h, q, acc);
+        lane_scalars(kt + ROWS_FLOATS, sub, h, nbv);
+        lane_scalars(kt + ROWS_FLOATS + KT, sub, h, pv);
+        lane_scalars(kt + ROWS_FLOATS + 2 * KT, sub, h, cv);
+        if (MASKED) skip = skip_mask_lane<SK_WAVES>(1, (const uint32_t *)(kt + ROWS_FLOATS + 3 * KT), wave, r32, sub, h);
     };
-    auto epilogue = [&](const f32x16 &acc, const float (&nbv)[16], const float (&pv)[16], const float (&cv)[16], unsigned skip) __attribute__((always_inline)) {
+    auto epilogue = [&](int, int) __attribute__((always_inline)) {
         float ls = 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            float d2 = SWAP ? (acc[r] + nbv[r]) + na : (acc[r] + na) + nbv[r];   // +inf for padding keys
-            d2 = d2 > 0.f ? d2 : 0.f;
-            const float L = sqrt_rn(d2) * neg_alpha + pv[r];
+            const float L = sqrt_rn(sqdist<SWAP>(acc[r], na, nbv[r])) * neg_alpha + pv[r];   // -inf for padding keys
             const float term = cv[r] * __builtin_amdgcn_exp2f((L + pq) * LOG2E);
             ls += (MASKED && ((skip >> r) & 1u)) ? 0.f : term;
         }
         sum += (double)ls;
     };
 
-    f32x16 acc;
-    float nbv[16], pv[16], cv[16];
-    unsigned skip = 0;
-    for (int t = 0; t < ntiles; ++t) {
-        const int buf = t & 1;
-        if (t + 1 < ntiles) issue_loads(t + 1);
-        const float *kt = smem + buf * SA_TILE_FLOATS;
-        if (role == 1 && t > 0) epilogue(acc, nbv, pv, cv, skip);   // the previous tile's second sub-tile
-        mfma_chain(kt, 0, acc, nbv, pv, cv, skip);
-        epilogue(acc, nbv, pv, cv, skip);
-        mfma_chain(kt, 1, acc, nbv, pv, cv, skip);
-        if (role == 0) epilogue(acc, nbv, pv, cv, skip);
-        if (t + 1 < ntiles) commit_loads(buf ^ 1);
-        __syncthreads();
-    }
-    if (role == 1) epilogue(acc, nbv, pv, cv, skip);
+    const int role = __builtin_amdgcn_readfirstlane(wave >> 2);
+    two_role_sweep<false>(ntiles, role, issue_loads, commit_loads, mfma_chain, epilogue);
 
     sum += __shfl_xor(sum, 32, 64);
     if (h == 0 && qrow < N) {
@@ -445,23 +344,19 @@ void launch_sweep_t(bool mfma, SAArgs a, int B, hipStream_t s) {
         ensure_dyn_lds((const void *)skb_sweep_mfma_kernel<SWAP, MASKED>, (int)SA_LDS_BYTES);
         hipLaunchKernelGGL((skb_sweep_mfma_kernel<SWAP, MASKED>), dim3((unsigned)(B * a.tiles)), dim3(SK_THREADS), SA_LDS_BYTES, s, a);
     } else {
-        const size_t lds = (size_t)(SS_KT * a.d + 3 * SS_KT) * sizeof(float);
+        const size_t lds = (size_t)(SC_KT * a.d + 3 * SC_KT) * sizeof(float);
         ensure_dyn_lds((const void *)skb_sweep_scalar_kernel<SWAP, MASKED>, 66 * 1024);
         hipLaunchKernelGGL((skb_sweep_scalar_kernel<SWAP, MASKED>), dim3((a.N + 127) / 128, B), dim3(128), lds, s, a);
     }
 }
 
 // ------------------------------------------------------------------------------------------------ phase B
-constexpr int BW_D = 128;
-constexpr int BW_KT = 64;
-constexpr int BW_LDK = BW_D + 4;
 constexpr int BW_WAVES = 4;
 constexpr int BW_OB = 32 * BW_WAVES;
 constexpr int BW_THREADS = 64 * BW_WAVES;
-constexpr int BW_LD_PER_THREAD = BW_KT * BW_D / 4 / BW_THREADS;
-constexpr int BW_MASK = 256;
-constexpr int BW_FIXED_FLOATS = BW_KT * BW_LDK + BW_KT + BW_MASK;   // rows + norms + mask; the K2 planes [K2][BW_KT] follow
-constexpr float BW_TAU = 1.f / 64.f;
+constexpr int BW_LD_PER_THREAD = KT * D / 4 / BW_THREADS;
+constexpr int BW_MASK = 64 * BW_WAVES;   // skip-mask words per tile (skip_mask_load)
+constexpr int BW_FIXED_FLOATS = ROWS_FLOATS + KT + BW_MASK;   // rows + norms + mask; the K2 planes [K2][KT] follow
 
 // group 0: df1 (outer = f1 rows, inner = f2 rows); group 1: df2 (outer = f2 rows, inner = f1 rows)
 struct PBGroup {
@@ -491,64 +386,39 @@ __global__ __launch_bounds__(BW_THREADS, 2) void skb_apply_mfma_kernel(const PBA
     const int r32 = lane & 31, h = lane >> 5;
     const float a2 = args.a2;
 
-    const float *ibase = G.fi + (size_t)b * Ni * BW_D;
+    const float *ibase = G.fi + (size_t)b * Ni * D;
     const float *inb = G.ni + (size_t)b * Ni;
     const float *itab = G.tabi + (size_t)b * K2 * Ni;
 
     const int orow = ot * BW_OB + wave * 32 + r32;
     const int orc = orow < No ? orow : No - 1;
-    const float *op = G.fo + ((size_t)b * No + orc) * BW_D;
+    const float *op = G.fo + ((size_t)b * No + orc) * D;
     const float *to = G.tabo + (size_t)b * K2 * No + orc;   // plane kk at to[kk * No]
-    float q[BW_D / 2];
-#pragma unroll
-    for (int c = 0; c < BW_D / 4; ++c) {
-        f32x4 v = *(const f32x4 *)(op + 4 * c);
-        q[2 * c] = -2.f * (h ? v.y : v.x);
-        q[2 * c + 1] = -2.f * (h ? v.w : v.z);
-    }
+    float q[D / 2];
+    load_query_frag(op, h, q);
     const float nrm_o = G.no[(size_t)b * No + orc];
 
-    const int ntiles = (Ni + BW_KT - 1) / BW_KT;
+    const int ntiles = (Ni + KT - 1) / KT;
     f32x4 pre[BW_LD_PER_THREAD];
     float pres = 0.f;
     uint32_t prem = 0;
     const uint32_t *bits = args.topk_bits;
     const int wpr = args.wpr;
     auto issue_loads = [&](int t) __attribute__((always_inline)) {
-        const int j0 = t * BW_KT;
-#pragma unroll
-        for (int e = 0; e < BW_LD_PER_THREAD; ++e) {
-            int id = tid + e * BW_THREADS;
-            int r = id >> 5, c = id & 31;
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (j0 + r < Ni) v = *(const f32x4 *)(ibase + (size_t)(j0 + r) * BW_D + 4 * c);
-            pre[e] = v;
-        }
-        if (tid < BW_KT) pres = (j0 + tid < Ni) ? inb[j0 + tid] : 0.f;
-        if (grp == 0) {   // as softcorr_bwd_mfma_kernel
-            const int mrow = ot * BW_OB + (tid >> 1), wc = (j0 >> 5) + (tid & 1);
-            prem = (mrow < No && wc < wpr) ? bits[((size_t)b * No + mrow) * wpr + wc] : 0u;
-        } else {
-            const int irow = j0 + (tid >> 2), wc = ot * (BW_OB / 32) + (tid & 3);
-            prem = (irow < Ni && wc < wpr) ? bits[((size_t)b * Ni + irow) * wpr + wc] : 0u;
-        }
+        const int j0 = t * KT;
+        issue_tile<BW_THREADS>(ibase, j0, Ni, tid, pre);
+        if (tid < KT) pres = (j0 + tid < Ni) ? inb[j0 + tid] : 0.f;
+        prem = skip_mask_load<BW_WAVES>(grp, bits, wpr, b, ot, j0, No, Ni, tid);
     };
     // the planes go from L2 to LDS without a register stage (their count depends on T); padding rows: potential -inf
     // (every term exp2(-inf) = 0), coefficient 0
     auto commit_loads = [&](int buf, int t) __attribute__((always_inline)) {
         float *kt = smem + buf * TF;
-        const int j0 = t * BW_KT;
-#pragma unroll
-        for (int e = 0; e < BW_LD_PER_THREAD; ++e) {
-            int id = tid + e * BW_THREADS;
-            int r = id >> 5, c = id & 31;
-            float2 ev = {pre[e].x, pre[e].z}, od = {pre[e].y, pre[e].w};
-            *(float2 *)(kt + r * BW_LDK + 2 * c) = ev;
-            *(float2 *)(kt + r * BW_LDK + 64 + 2 * c) = od;
-        }
-        if (tid < BW_KT) kt[BW_KT * BW_LDK + tid] = pres;
-        ((uint32_t *)kt)[BW_KT * BW_LDK + BW_KT + tid] = prem;
-        for (int e = tid; e < K2 * BW_KT; e += BW_THREADS) {
+        const int j0 = t * KT;
+        commit_tile<BW_THREADS>(kt, tid, pre);
+        if (tid < KT) kt[ROWS_FLOATS + tid] = pres;
+        ((uint32_t *)kt)[ROWS_FLOATS + KT + tid] = prem;
+        for (int e = tid; e < K2 * KT; e += BW_THREADS) {
             const int kk = e >> 6, j = j0 + (e & 63);
             kt[BW_FIXED_FLOATS + e] = j < Ni ? itab[(size_t)kk * Ni + j] : (kk <= T ? -INFINITY : 0.f);
         }
@@ -571,72 +441,28 @@ __global__ __launch_bounds__(BW_THREADS, 2) void skb_apply_mfma_kernel(const PBA
         if (t + 1 < ntiles) issue_loads(t + 1);
 #pragma unroll 1
         for (int sub = 0; sub < 2; ++sub) {
-            const float *arow = kt + (sub * 32 + r32) * BW_LDK + h * 64;
-            f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int c = 0; c < 16; ++c) {
-                f32x4 a = *(const f32x4 *)(arow + 4 * c);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, q[4 * c], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, q[4 * c + 1], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, q[4 * c + 2], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, q[4 * c + 3], acc, 0, 0, 0);
-            }
-            const float *sc = kt + BW_KT * BW_LDK + sub * 32 + 4 * h;   // this lane's 16 inner rows: (r&3) + 8*(r>>2) + 4*h
-            const uint32_t *msk = (const uint32_t *)(kt + BW_KT * BW_LDK + BW_KT);
-            const float *tb = kt + BW_FIXED_FLOATS + sub * 32 + 4 * h;   // plane kk of those rows: tb[kk * 64 + 8 * g + u]
-            unsigned exact = 0;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const f32x4 nb = *(const f32x4 *)(sc + 8 * g);
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int r = 4 * g + u;
-                    acc[r] = (acc[r] + nrm_o) + nb[u];
-                    exact |= (acc[r] < BW_TAU * (nrm_o + nb[u]) ? 1u : 0u) << r;
-                }
-            }
-            if (__any(exact != 0)) {   // rare: redo v = |f_o - f_i|^2 from the difference where the expansion cancelled
-#pragma unroll 1
-                for (int r = 0; r < 16; ++r) {
-                    if (!__any((exact >> r) & 1u)) continue;
-                    const int er = sub * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                    const float *xr = kt + er * BW_LDK;
-                    float v = 0.f;
-#pragma unroll 4
-                    for (int c = 0; c < BW_D / 4; ++c) {
-                        const f32x4 o4 = *(const f32x4 *)(op + 4 * c);
-                        const float2 ev = *(const float2 *)(xr + 2 * c), od = *(const float2 *)(xr + 64 + 2 * c);
-                        const float d0 = ev.x - o4.x, d1 = od.x - o4.y, d2 = ev.y - o4.z, d3 = od.y - o4.w;
-                        v = fmaf(d0, d0, v);
-                        v = fmaf(d1, d1, v);
-                        v = fmaf(d2, d2, v);
-                        v = fmaf(d3, d3, v);
-                    }
-#pragma unroll
-                    for (int rr = 0; rr < 16; ++rr)
-                        if (rr == r && ((exact >> r) & 1u)) acc[rr] = v;
-                }
-            }
-            // acc becomes D; w the sum of the entry's 2T + 1 terms
+            f32x16 acc;
+            outer_inner_sqdist(kt, kt + ROWS_FLOATS, sub, r32, h, q, op, nrm_o, acc);
+            const uint32_t *msk = (const uint32_t *)(kt + ROWS_FLOATS + KT);
+            const float *tb = kt + BW_FIXED_FLOATS + sub * 32 + 4 * h;   // plane kk of this lane's 16 inner rows: tb[kk * 64 + 8 * g + u]
+            // acc becomes the distance; w the sum of the entry's 2T + 1 terms
             float w[16];
             {   // the final row step's term, skipped on the row's top-k columns (prep / colgather own it there)
+                const unsigned skip = skip_mask_lane<BW_WAVES>(grp, msk, wave, r32, sub, h);
                 const float po = to[(size_t)(grp == 0 ? 0 : T) * No];
                 const float co = grp == 0 ? to[(size_t)(T + 1) * No] : 1.f;
-                const float *pin = tb + (grp == 0 ? T : 0) * BW_KT;
+                const float *pin = tb + (grp == 0 ? T : 0) * KT;
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     const f32x4 pi = *(const f32x4 *)(pin + 8 * g);
                     f32x4 ci = {1.f, 1.f, 1.f, 1.f};
-                    if (grp == 1) ci = *(const f32x4 *)(tb + (T + 1) * BW_KT + 8 * g);
+                    if (grp == 1) ci = *(const f32x4 *)(tb + (T + 1) * KT + 8 * g);
 #pragma unroll
                     for (int u = 0; u < 4; ++u) {
                         const int r = 4 * g + u;
-                        const int il = (r & 3) + 8 * (r >> 2) + 4 * h;
-                        const bool topk = grp == 0 ? ((msk[(wave * 32 + r32) * 2 + sub] >> il) & 1u)
-                                                   : ((msk[(sub * 32 + il) * 4 + wave] >> r32) & 1u);
                         acc[r] = sqrt_rn(fmaxf(acc[r], 0.f));
                         const float e = __builtin_amdgcn_exp2f(fmaf(acc[r], a2, po + pi[u]));
-                        w[r] = topk ? 0.f : (co * ci[u]) * e;
+                        w[r] = ((skip >> r) & 1u) ? 0.f : (co * ci[u]) * e;
                     }
                 }
             }
@@ -647,10 +473,10 @@ __global__ __launch_bounds__(BW_THREADS, 2) void skb_apply_mfma_kernel(const PBA
                 const float co = to[(size_t)(T + 1 + tt) * No];
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
-                    const f32x4 pi = *(const f32x4 *)(tb + tt * BW_KT + 8 * g);
+                    const f32x4 pi = *(const f32x4 *)(tb + tt * KT + 8 * g);
                     f32x4 pix = pi;
-                    if (grp == 0) pix = *(const f32x4 *)(tb + (tt - 1) * BW_KT + 8 * g);
-                    const f32x4 ci = *(const f32x4 *)(tb + (T + 1 + tt) * BW_KT + 8 * g);
+                    if (grp == 0) pix = *(const f32x4 *)(tb + (tt - 1) * KT + 8 * g);
+                    const f32x4 ci = *(const f32x4 *)(tb + (T + 1 + tt) * KT + 8 * g);
 #pragma unroll
                     for (int u = 0; u < 4; ++u) {
                         const int r = 4 * g + u;
@@ -668,43 +494,17 @@ __global__ __launch_bounds__(BW_THREADS, 2) void skb_apply_mfma_kernel(const PBA
                 w[r] = acc[r] > 0.f ? wv : 0.f;
                 rl += w[r];
             }
-            // apply: out[o][pos] += sum_t W[t][o] * X[t][pos]; step r contracts t = (r&3)+8*(r>>2)+4*h
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int trow = sub * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                const f32x4 x = *(const f32x4 *)(kt + trow * BW_LDK + 4 * r32);
-                acc2[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[r], x.x, acc2[0], 0, 0, 0);
-                acc2[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[r], x.y, acc2[1], 0, 0, 0);
-                acc2[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[r], x.z, acc2[2], 0, 0, 0);
-                acc2[3] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[r], x.w, acc2[3], 0, 0, 0);
-            }
+            apply_chain(kt, sub, r32, h, w, acc2);
         }
         if (t + 1 < ntiles) commit_loads(buf ^ 1, t + 1);
         __syncthreads();
     }
 
-    // d_out[o] += (sum_t W[t][o]) * f_o - acc2[o]: this workgroup owns the rows, on top of the top-k slots' share
-    const float rtot = rl + __shfl_xor(rl, 32, 64);
-    if (h == 0) rsum[wave * 32 + r32] = rtot;
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int o = (r & 3) + 8 * (r >> 2) + 4 * h;
-        const int row = ot * BW_OB + wave * 32 + o;
-        if (row >= No) continue;
-        const float rr = rsum[wave * 32 + o];
-        const float *fo = G.fo + ((size_t)b * No + row) * BW_D;
-        float *dst = G.dout + ((size_t)b * No + row) * BW_D;
-#pragma unroll
-        for (int cb = 0; cb < 4; ++cb) {
-            const int pos = 4 * r32 + cb;
-            const int ch = pos < 64 ? 2 * pos : 2 * (pos - 64) + 1;
-            dst[ch] += rr * fo[ch] - acc2[cb][r];
-        }
-    }
+    // this workgroup owns the rows: a plain add on top of the top-k slots' share
+    store_outer_rows<false>(rsum, rl, G.fo, G.dout, b, ot * BW_OB + wave * 32, No, wave, r32, h, acc2);
 }
 
-// scalar form: one wave per outer row, lanes own channels lane + 64u (softcorr_bwd_scalar_kernel's distances)
+// scalar form: one wave per outer row, lanes own channels lane + 64u (the scalar phase B of dvm_dist_tile.h)
 struct PBScalarArgs {
     const float *f1, *f2, *n1, *n2, *tabR, *tabC;
     float *df1, *df2;
@@ -738,28 +538,11 @@ __global__ __launch_bounds__(256) void skb_apply_scalar_kernel(const PBScalarArg
     float rsum = 0.f;
     for (int j = 0; j < Ni; ++j) {
         const float *fi = fib + ((size_t)b * Ni + j) * d;
-        float xv[8], part = 0.f;
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int c = lane + 64 * u;
-            xv[u] = c < d ? fi[c] : 0.f;
-            part = fmaf(ov[u], xv[u], part);
-        }
+        float xv[8];
+        const float part = wave_row_load_dot(fi, d, lane, ov, xv);
         const int ri = grp ? j : row, ci = grp ? row : j;   // the entry's f1 row and f2 row (column)
         const bool topk = (args.topk_bits[((size_t)b * N + ri) * args.wpr + (ci >> 5)] >> (ci & 31)) & 1u;
-        const float dot = wave_sum(part);
-        const float ni = nib[(size_t)b * Ni + j];
-        float v = (-2.f * dot + nrm_o) + ni;
-        if (v < BW_TAU * (nrm_o + ni)) {   // uniform: the expansion cancelled, redo v from the difference
-            float p2 = 0.f;
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const float dd = ov[u] - xv[u];
-                p2 = fmaf(dd, dd, p2);
-            }
-            v = wave_sum(p2);
-        }
-        v = fmaxf(v, 0.f);
+        const float v = wave_row_sqdist(part, ov, xv, nrm_o, nib[(size_t)b * Ni + j]);
         if (!(v > 0.f)) continue;
         const float D = sqrt_rn(v);
         float sum = topk ? 0.f : tr[(size_t)(T + 1) * N + ri] * exp2f(fmaf(D, args.a2, tr[ri] + tc[(size_t)T * M + ci]));
@@ -832,7 +615,7 @@ DVM_EXPORT int dvm_sinkhorn_bwd_f32(const float *f1, const float *f2, int B, int
     }
     hipStream_t s = (hipStream_t)stream;
     const int T = n_iter, wpr = (M + 31) / 32;
-    const bool mfma = variant == 0 && d == SK_D;
+    const bool mfma = variant == 0 && d == D;
     const long u_bs = (long)(T + 1) * N, v_bs = (long)(T + 1) * M;
     (void)hipMemsetAsync(w.bits, 0, (size_t)B * N * wpr * sizeof(uint32_t), s);
     launch_rownorm2(f1, B * N, d, w.n1, s);
@@ -876,9 +659,9 @@ DVM_EXPORT int dvm_sinkhorn_bwd_f32(const float *f1, const float *f2, int B, int
         a.g[0] = PBGroup{f1, f2, w.n1, w.n2, w.tabR, w.tabC, d_f1, N, M, (N + BW_OB - 1) / BW_OB};
         a.g[1] = PBGroup{f2, f1, w.n2, w.n1, w.tabC, w.tabR, d_f2, M, N, (M + BW_OB - 1) / BW_OB};
         a.topk_bits = w.bits, a.wpr = wpr, a.T = T, a.a2 = a2, a.nalpha = -neg_alpha;
-        a.tile_floats = BW_FIXED_FLOATS + 2 * (T + 1) * BW_KT;
+        a.tile_floats = BW_FIXED_FLOATS + 2 * (T + 1) * KT;
         const size_t lds = ((size_t)2 * a.tile_floats + BW_OB) * sizeof(float);
-        const int lds_max = (int)(((size_t)2 * (BW_FIXED_FLOATS + 2 * (SKB_MAX_ITER + 1) * BW_KT) + BW_OB) * sizeof(float));
+        const int lds_max = (int)(((size_t)2 * (BW_FIXED_FLOATS + 2 * (SKB_MAX_ITER + 1) * KT) + BW_OB) * sizeof(float));
         ensure_dyn_lds((const void *)skb_apply_mfma_kernel<0>, lds_max);
         ensure_dyn_lds((const void *)skb_apply_mfma_kernel<1>, lds_max);
         hipLaunchKernelGGL(skb_apply_mfma_kernel<0>, dim3(B * a.g[0].tiles_o), dim3(BW_THREADS), lds, s, a);

@@ -7,20 +7,15 @@
 // distances equal the reference's CPU (MKL sgemm) values bit for bit and the top-k columns /
 // arg-max map are bit-exact integers.
 //
-// Data layout: features row-major [B][N][d] fp32 in HBM; one workgroup owns 128 query rows
-// (4 waves x 32) and sweeps all M keys through a double-buffered, k-deinterleaved LDS tile;
-// the accumulator tile is [key][query] so that a query's candidates sit in one lane's
-// registers (top-k insertion and online softmax need no cross-lane traffic until the end).
+// One workgroup owns 256 query rows (8 waves x 32) and sweeps all M keys through the distance tile of
+// dvm_dist_tile.h, which defines the layout, the chain and the two-role phase structure.
 #include <stdlib.h>
 
-#include "dvm_common.h"
+#include "dvm_dist_tile.h"
 
 namespace dvm {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr float LOG2E = 1.4426950408889634f;
+using namespace dtile;
 
 
 // ------------------------------------------------------------------ row norms
@@ -135,11 +130,8 @@ __device__ __forceinline__ void store_row(const RowState<TOPK> &st, int topk, in
 }
 
 // ------------------------------------------------------------ scalar variant
-// One thread per query row; keys staged through LDS in tiles of 32; the dot product is an
-// explicit k-ordered fmaf chain.  Any d % 4 == 0.  Reference kernel for the MFMA variant and
-// the fallback for d != 128.
-constexpr int SC_KT = 32;   // keys per tile
-constexpr int SC_DC = 32;   // feature chunk held in registers
+// One thread per query row (the scalar sweep of dvm_dist_tile.h).  Any d % 4 == 0.  Reference kernel for the
+// MFMA variant and the fallback for d != 128.
 
 template <int TOPK>
 __global__ __launch_bounds__(128) void softcorr_scalar_kernel(const float *__restrict__ f1, const float *__restrict__ f2,
@@ -160,48 +152,17 @@ __global__ __launch_bounds__(128) void softcorr_scalar_kernel(const float *__res
     st.init();
     for (int j0 = 0; j0 < M; j0 += SC_KT) {
         __syncthreads();
-        for (int e = threadIdx.x; e < SC_KT * d / 4; e += blockDim.x) {
-            int r = e / (d / 4), c = e % (d / 4);
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (j0 + r < M) v = *(const f32x4 *)(kbase + (size_t)(j0 + r) * d + 4 * c);
-            *(f32x4 *)(kt + r * d + 4 * c) = v;
-        }
+        scalar_stage_keys(kt, kbase, j0, M, d);
         if (threadIdx.x < SC_KT) kn[threadIdx.x] = (j0 + threadIdx.x < M) ? n2[(size_t)b * M + j0 + threadIdx.x] : INFINITY;
         __syncthreads();
         float acc[SC_KT];
-#pragma unroll
-        for (int j = 0; j < SC_KT; ++j) acc[j] = 0.f;
-        for (int c0 = 0; c0 < d; c0 += SC_DC) {
-            float qr[SC_DC];
-            int cw = d - c0 < SC_DC ? d - c0 : SC_DC;
-#pragma unroll
-            for (int c = 0; c < SC_DC; c += 4) {
-                f32x4 v = {0.f, 0.f, 0.f, 0.f};
-                if (c < cw) v = *(const f32x4 *)(q + c0 + c);
-                qr[c] = -2.f * v.x, qr[c + 1] = -2.f * v.y, qr[c + 2] = -2.f * v.z, qr[c + 3] = -2.f * v.w;
-            }
-#pragma unroll
-            for (int j = 0; j < SC_KT; ++j) {
-#pragma unroll
-                for (int c = 0; c < SC_DC; c += 4) {
-                    if (c < cw) {
-                        f32x4 kv = *(const f32x4 *)(kt + j * d + c0 + c);
-                        acc[j] = fmaf(qr[c], kv.x, acc[j]);
-                        acc[j] = fmaf(qr[c + 1], kv.y, acc[j]);
-                        acc[j] = fmaf(qr[c + 2], kv.z, acc[j]);
-                        acc[j] = fmaf(qr[c + 3], kv.w, acc[j]);
-                    }
-                }
-            }
-        }
+        scalar_dist_chain(q, kt, d, acc);
         // epilogue: distances, online softmax, top-k
         float dd[SC_KT];
         float tmin = INFINITY;
 #pragma unroll
         for (int j = 0; j < SC_KT; ++j) {
-            float d2 = (acc[j] + na) + kn[j];
-            d2 = d2 > 0.f ? d2 : 0.f;
-            dd[j] = sqrt_rn(d2);
+            dd[j] = sqrt_rn(sqdist<false>(acc[j], na, kn[j]));
             tmin = fminf(tmin, dd[j]);
         }
         st.rescale(tmin * neg_alpha);
@@ -241,12 +202,7 @@ __global__ __launch_bounds__(128) void softcorr_dense_kernel(const float *__rest
     const float *kbase = f2 + (size_t)b * M * d;
     for (int j0 = 0; j0 < M; j0 += SC_KT) {
         __syncthreads();
-        for (int e = threadIdx.x; e < SC_KT * d / 4; e += blockDim.x) {
-            int r = e / (d / 4), c = e % (d / 4);
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (j0 + r < M) v = *(const f32x4 *)(kbase + (size_t)(j0 + r) * d + 4 * c);
-            *(f32x4 *)(kt + r * d + 4 * c) = v;
-        }
+        scalar_stage_keys(kt, kbase, j0, M, d);
         if (threadIdx.x < SC_KT) kn[threadIdx.x] = (j0 + threadIdx.x < M) ? n2[(size_t)b * M + j0 + threadIdx.x] : INFINITY;
         __syncthreads();
         for (int j = 0; j < SC_KT && j0 + j < M; ++j) {
@@ -258,25 +214,20 @@ __global__ __launch_bounds__(128) void softcorr_dense_kernel(const float *__rest
                 acc = fmaf(-2.f * qv.z, kv.z, acc);
                 acc = fmaf(-2.f * qv.w, kv.w, acc);
             }
-            float d2 = (acc + na) + kn[j];
-            d2 = d2 > 0.f ? d2 : 0.f;
-            float s = sqrt_rn(d2) * neg_alpha;
+            float s = sqrt_rn(sqdist<false>(acc, na, kn[j])) * neg_alpha;
             if (i < N) P[((size_t)b * N + i) * M + j0 + j] = exp2f((s - smax) * LOG2E) * inv;
         }
     }
 }
 
 // -------------------------------------------------------------- MFMA variant
-constexpr int MF_D = 128;
-constexpr int MF_KT = 64;              // keys per LDS tile (two 32-key MFMA sub-tiles)
-constexpr int MF_LDK = MF_D + 4;       // padded row (floats): 528 B, keeps ds_read_b128 conflict-free
 constexpr int MF_QW = 32;              // queries per wave
 constexpr int MF_WAVES = 8;             // waves 0-3 and 4-7 pair up on the 4 SIMDs (two per SIMD)
 constexpr int MF_QB = MF_QW * MF_WAVES;  // 256 queries per workgroup
 constexpr int MF_THREADS = 64 * MF_WAVES;
-constexpr int MF_LD_PER_THREAD = MF_KT * MF_D / 4 / MF_THREADS;  // float4 loads per thread per tile = 8
+constexpr int MF_LD_PER_THREAD = KT * D / 4 / MF_THREADS;  // float4 loads per thread per tile = 8
 constexpr int MF_STAGE = 16 * 64;  // floats per wave: this sub-tile's 16 squared distances of each lane, [r][lane]
-constexpr size_t MF_LDS_BYTES = ((size_t)2 * (MF_KT * MF_LDK + MF_KT) + (size_t)MF_WAVES * MF_STAGE) * sizeof(float);
+constexpr size_t MF_LDS_BYTES = ((size_t)2 * (ROWS_FLOATS + KT) + (size_t)MF_WAVES * MF_STAGE) * sizeof(float);
 
 __device__ __forceinline__ float select16(const float (&v)[16], int b) {
     float a0 = (b & 1) ? v[1] : v[0], a1 = (b & 1) ? v[3] : v[2], a2 = (b & 1) ? v[5] : v[4], a3 = (b & 1) ? v[7] : v[6];
@@ -286,11 +237,6 @@ __device__ __forceinline__ float select16(const float (&v)[16], int b) {
     float c0 = (b & 4) ? b1 : b0, c1 = (b & 4) ? b3 : b2;
     return (b & 8) ? c1 : c0;
 }
-
-// XCD-aware block remap (bijective for any grid): blocks that share `orig % 8` share an L2;
-// give each XCD a contiguous range of logical ids so the row tiles of one pair reuse its keys
-// from that L2.
-
 
 // One launch covers up to two "groups" (the two directions of a pair batch: (f1 -> f2) and
 // (f2 -> f1)), each with its own query/key tensors and outputs.
@@ -318,9 +264,9 @@ template <int TOPK, bool LEAN>
 __global__ __launch_bounds__(MF_THREADS, 2) void softcorr_mfma_kernel(const SCArgs args) {
     // __launch_bounds__(512, 2): two waves per SIMD, i.e. ONE 512-thread workgroup per CU
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float *const ktile0 = smem;                       // [2][MF_KT][MF_LDK]
-    float *const knorm0 = smem + 2 * MF_KT * MF_LDK;  // [2][MF_KT]
-    float *const stage = knorm0 + 2 * MF_KT + (threadIdx.x >> 6) * MF_STAGE + (threadIdx.x & 63);  // this lane's column
+    float *const ktile0 = smem;                    // [2][KT][LDK]
+    float *const knorm0 = smem + 2 * ROWS_FLOATS;  // [2][KT]
+    float *const stage = knorm0 + 2 * KT + (threadIdx.x >> 6) * MF_STAGE + (threadIdx.x & 63);  // this lane's column
 
     int lid = xcd_remap(blockIdx.x, gridDim.x);
     const int grp = lid >= args.blocks0 ? 1 : 0;
@@ -333,20 +279,14 @@ __global__ __launch_bounds__(MF_THREADS, 2) void softcorr_mfma_kernel(const SCAr
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r32 = lane & 31, h = lane >> 5;
 
-    const float *kbase = G.k + (size_t)b * M * MF_D;
+    const float *kbase = G.k + (size_t)b * M * D;
     const float *knb = G.nk + (size_t)b * M;
 
-    // this lane's query row and its B-operand fragment: q[s] = -2 * f1[row][2s + h]
+    // this lane's query row and its B-operand fragment
     const int qrow = qt * MF_QB + wave * MF_QW + r32;
     const int qrc = qrow < N ? qrow : N - 1;
-    const float *qp = G.q + ((size_t)b * N + qrc) * MF_D;
-    float q[MF_D / 2];
-#pragma unroll
-    for (int c = 0; c < MF_D / 4; ++c) {
-        f32x4 v = *(const f32x4 *)(qp + 4 * c);
-        q[2 * c] = -2.f * (h ? v.y : v.x);
-        q[2 * c + 1] = -2.f * (h ? v.w : v.z);
-    }
+    float q[D / 2];
+    load_query_frag(G.q + ((size_t)b * N + qrc) * D, h, q);
     const float na = G.nq[(size_t)b * N + qrc];
 
     KBest<TOPK, float> kb;  // keyed on the correctly rounded distance
@@ -356,66 +296,26 @@ __global__ __launch_bounds__(MF_THREADS, 2) void softcorr_mfma_kernel(const SCAr
     float thr2 = INFINITY;   // conservative squared-distance bound for "may enter the top-k"
     const float a2 = neg_alpha * LOG2E;
 
-    const int ntiles = (M + MF_KT - 1) / MF_KT;
+    const int ntiles = (M + KT - 1) / KT;
     f32x4 pre[MF_LD_PER_THREAD];
     float pren = 0.f;
 
     auto issue_loads = [&](int t) {
-        int j0 = t * MF_KT;
-#pragma unroll
-        for (int e = 0; e < MF_LD_PER_THREAD; ++e) {
-            int id = tid + e * MF_THREADS;
-            int r = id >> 5, c = id & 31;  // 32 float4 per 128-float row
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (j0 + r < M) v = *(const f32x4 *)(kbase + (size_t)(j0 + r) * MF_D + 4 * c);
-            pre[e] = v;
-        }
-        if (tid < MF_KT) pren = (j0 + tid < M) ? knb[j0 + tid] : INFINITY;
+        const int j0 = t * KT;
+        issue_tile<MF_THREADS>(kbase, j0, M, tid, pre);
+        if (tid < KT) pren = (j0 + tid < M) ? knb[j0 + tid] : INFINITY;
     };
     auto commit_loads = [&](int buf) {
-        float *kt = ktile0 + buf * (MF_KT * MF_LDK);
-#pragma unroll
-        for (int e = 0; e < MF_LD_PER_THREAD; ++e) {
-            int id = tid + e * MF_THREADS;
-            int r = id >> 5, c = id & 31;
-            // k = 4c+{0,1,2,3} -> (h,s) = (0,2c) (1,2c) (0,2c+1) (1,2c+1)
-            float2 ev = {pre[e].x, pre[e].z}, od = {pre[e].y, pre[e].w};
-            *(float2 *)(kt + r * MF_LDK + 2 * c) = ev;
-            *(float2 *)(kt + r * MF_LDK + 64 + 2 * c) = od;
-        }
-        if (tid < MF_KT) knorm0[buf * MF_KT + tid] = pren;
+        commit_tile<MF_THREADS>(ktile0 + buf * ROWS_FLOATS, tid, pre);
+        if (tid < KT) knorm0[buf * KT + tid] = pren;
     };
 
-    issue_loads(0);
-    commit_loads(0);
-    __syncthreads();
-
-    // Phase structure.  Every wave alternates an MFMA phase M (64 dependent MFMAs, 4096 matrix-pipe
-    // cycles) with a VALU phase V (the epilogue) of about the same length.  The two waves that
-    // share a SIMD (w and w+4) would run them in lockstep — matrix pipe contended, then idle — so
-    // waves 4-7 (role 1) defer the epilogue of each tile's second sub-tile across the barrier:
-    //     role 0:   M0 V0 M1 V1 | barrier        role 1:   V1' M0 V0 M1 | barrier
-    // After every barrier one wave of the SIMD starts in M and its partner in V.
-    const int role = __builtin_amdgcn_readfirstlane(wave >> 2);
-
-    auto mfma_chain = [&](const float *kt, int sub, f32x16 &acc, float (&nbv)[16], int buf) {
-        const float *arow = kt + (sub * 32 + r32) * MF_LDK + h * 64;
-        acc = f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int c = 0; c < 16; ++c) {
-            f32x4 a = *(const f32x4 *)(arow + 4 * c);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, q[4 * c], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, q[4 * c + 1], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, q[4 * c + 2], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, q[4 * c + 3], acc, 0, 0, 0);
-        }
-        // |key|^2 of this lane's 16 keys: local key = (r&3) + 8*(r>>2) + 4*h
-        const float *kn = knorm0 + buf * MF_KT + sub * 32 + 4 * h;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            f32x4 nb = *(const f32x4 *)(kn + 8 * g);
-            nbv[4 * g] = nb.x, nbv[4 * g + 1] = nb.y, nbv[4 * g + 2] = nb.z, nbv[4 * g + 3] = nb.w;
-        }
+    // the chain and |key|^2 of this lane's 16 keys
+    f32x16 acc;
+    float nbv[16];
+    auto mfma_chain = [&](int buf, int sub) {
+        dist_chain(ktile0 + buf * ROWS_FLOATS, sub, r32, h, q, acc);
+        lane_scalars(knorm0 + buf * KT, sub, h, nbv);
     };
 
     // Epilogue.  fp32 MFMA executes on the same ALUs as VALU code (tools/probe_interleave.hip: every
@@ -427,13 +327,13 @@ __global__ __launch_bounds__(MF_THREADS, 2) void softcorr_mfma_kernel(const SCAr
     // The 16 squared distances are parked in LDS ([r][lane], conflict-free) for the dynamic pick.
     float lim2 = INFINITY;
     const float cutw = args.cutw;
-    auto epilogue = [&](const f32x16 &acc, const float (&nbv)[16], int jbase) {
+    auto epilogue = [&](int t, int sub) {
         unsigned mask = 0;
         float c2 = 0.f;
         if (LEAN) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                float v = (acc[r] + na) + nbv[r];
+                float v = sqdist_sum<false>(acc[r], na, nbv[r]);
                 stage[r * 64] = v;
                 mask |= (v <= lim2) ? (1u << r) : 0u;
             }
@@ -442,7 +342,7 @@ __global__ __launch_bounds__(MF_THREADS, 2) void softcorr_mfma_kernel(const SCAr
             float tminf = INFINITY;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                float v = (acc[r] + na) + nbv[r];
+                float v = sqdist_sum<false>(acc[r], na, nbv[r]);
                 stage[r * 64] = v;
                 mask |= (v <= lim2) ? (1u << r) : 0u;
                 float f = __builtin_amdgcn_sqrtf(fabsf(v));
@@ -488,7 +388,7 @@ __global__ __launch_bounds__(MF_THREADS, 2) void softcorr_mfma_kernel(const SCAr
                 // replace this term's fast value by the reference-rounded one (both 0 for +inf)
                 l += __builtin_amdgcn_exp2f((s - cref) * LOG2E) - __builtin_amdgcn_exp2f(fmaf(dfast, a2, -c2));
             }
-            kb.insert_nb(de, jbase + (bpos & 3) + 8 * (bpos >> 2));
+            kb.insert_nb(de, t * KT + sub * 32 + lane_key(bpos, h));
         }
         // bounds for the next sub-tile.  Top-k: the row's k-th best is at most min(a_k, b_k, max(a_m, b_m))
         // with a, b the sorted lists of the two half-lanes and m = k/2 (2m elements lie below that max).
@@ -507,21 +407,8 @@ __global__ __launch_bounds__(MF_THREADS, 2) void softcorr_mfma_kernel(const SCAr
         }
     };
 
-    f32x16 acc;
-    float nbv[16];
-    for (int t = 0; t < ntiles; ++t) {
-        const int buf = t & 1;
-        if (t + 1 < ntiles) issue_loads(t + 1);
-        const float *kt = ktile0 + buf * (MF_KT * MF_LDK);
-        if (role == 1 && t > 0) epilogue(acc, nbv, (t - 1) * MF_KT + 32 + 4 * h);  // V1' of the previous tile
-        mfma_chain(kt, 0, acc, nbv, buf);
-        epilogue(acc, nbv, t * MF_KT + 4 * h);
-        mfma_chain(kt, 1, acc, nbv, buf);
-        if (role == 0) epilogue(acc, nbv, t * MF_KT + 32 + 4 * h);
-        if (t + 1 < ntiles) commit_loads(buf ^ 1);
-        __syncthreads();
-    }
-    if (role == 1) epilogue(acc, nbv, (ntiles - 1) * MF_KT + 32 + 4 * h);
+    const int role = __builtin_amdgcn_readfirstlane(wave >> 2);
+    two_role_sweep<false>(ntiles, role, issue_loads, commit_loads, mfma_chain, epilogue);
 
     // merge the two half-lanes that share a query (lane, lane^32)
     {
@@ -568,7 +455,7 @@ constexpr float LEAN_MIN_ALPHA = 32.f;
 template <int TOPK>
 static void launch_softcorr_mfma(SCArgs &a, int blocks, hipStream_t s) {
     ensure_dyn_lds((const void *)softcorr_mfma_kernel<TOPK, true>, (int)MF_LDS_BYTES);
-ensure_dyn_lds((const void *)softcorr_mfma_kernel<TOPK, false>, (int)MF_LDS_BYTES);
+    ensure_dyn_lds((const void *)softcorr_mfma_kernel<TOPK, false>, (int)MF_LDS_BYTES);
     const float alpha = -a.neg_alpha;
     a.cutw = 20.f / alpha;
     if (alpha >= LEAN_MIN_ALPHA)
@@ -616,8 +503,6 @@ void launch_absmax_finalize(const int *slots, int nt, int *out, hipStream_t s) {
     hipLaunchKernelGGL(absmax_finalize_kernel, dim3(nt), dim3(64), 0, s, slots, out);
 }
 
-void launch_rownorm2(const float *x, int rows, int K, float *out, hipStream_t s);
-
 // norms of both sides + soft correspondence in both directions for the fused pair path (d = 128, top-10)
 size_t softcorr_pair_ws_bytes(int B, int N, int M) { return align_up(514 * sizeof(int)) + softcorr_f16_ws_bytes(B, N, M, true); }
 int launch_softcorr_pair(const float *f1, const float *f2, float *n1, float *n2, int B, int N, int M, float neg_alpha, float *val12,
@@ -657,7 +542,7 @@ DVM_EXPORT int dvm_rownorm2_f32(const float *x, int rows, int K, float *out, voi
 
 DVM_EXPORT size_t dvm_softcorr_workspace_bytes(int B, int N, int M, int d) {
     return align_up((size_t)B * N * sizeof(float)) + align_up((size_t)B * M * sizeof(float)) +
-           (d == MF_D ? align_up(514 * sizeof(int)) + softcorr_f16_ws_bytes(B, N, M, false) : 0);
+           (d == D ? align_up(514 * sizeof(int)) + softcorr_f16_ws_bytes(B, N, M, false) : 0);
 }
 
 DVM_EXPORT int dvm_softcorr_fwd_f32(const float *f1, const float *f2, int B, int N, int M, int d, float neg_alpha,
@@ -669,7 +554,7 @@ DVM_EXPORT int dvm_softcorr_fwd_f32(const float *f1, const float *f2, int B, int
     DVM_REQUIRE(topk >= 1 && topk <= 16, "dvm_softcorr_fwd_f32: topk=%d unsupported (1..16)", topk);
     DVM_REQUIRE(neg_alpha < 0.f, "dvm_softcorr_fwd_f32: neg_alpha must be negative (got %g)", (double)neg_alpha);
     DVM_REQUIRE(variant >= 0 && variant <= 3, "dvm_softcorr_fwd_f32: bad variant %d", variant);
-    DVM_REQUIRE(variant < 2 || d == MF_D, "dvm_softcorr_fwd_f32: the matrix-core variants need d == 128");
+    DVM_REQUIRE(variant < 2 || d == D, "dvm_softcorr_fwd_f32: the matrix-core variants need d == 128");
     DVM_REQUIRE(variant != 3 || topk <= 10, "dvm_softcorr_fwd_f32: the bf16 variant keeps 12 candidates (topk <= 10)");
     Arena ar(ws, ws_bytes);
     float *n1 = ar.take<float>((size_t)B * N);
@@ -679,7 +564,7 @@ DVM_EXPORT int dvm_softcorr_fwd_f32(const float *f1, const float *f2, int B, int
         return DVM_ENOSPACE;
     }
     hipStream_t s = (hipStream_t)stream;
-    if (variant == 0 && d == MF_D && topk <= 10) variant = 3;   // auto: the fp16-split sweep (variants 1 / 2: the `variant` argument)
+    if (variant == 0 && d == D && topk <= 10) variant = 3;   // auto: the fp16-split sweep (variants 1 / 2: the `variant` argument)
     if (variant == 3) {
         int *slots = ar.take<int>(2 * 256 + 2);
         int *amax = slots + 512;
@@ -700,7 +585,7 @@ DVM_EXPORT int dvm_softcorr_fwd_f32(const float *f1, const float *f2, int B, int
     }
     launch_rownorm2(f1, B * N, d, n1, s);
     launch_rownorm2(f2, B * M, d, n2, s);
-    bool mfma = (variant == 2) || (variant == 0 && d == MF_D);
+    bool mfma = (variant == 2) || (variant == 0 && d == D);
     prof_note(DVM_PROF_K1_SWEEP, mfma ? "softcorr_mfma_kernel" : "softcorr_scalar_kernel");
     prof_begin(s);
     if (mfma) {

@@ -18,32 +18,24 @@
 // distances by the norm expansion, ~15 VALU per entry turn them into W in the accumulator layout, and 64 more MFMAs
 // apply W to the staged rows — W's C-layout registers are fed straight back as the A operand (the contraction index
 // is permuted consistently on the B side), so W never touches LDS.  Where the expansion cancels
-// (v < BW_TAU (|f_o|^2 + |f_i|^2): a cluster of columns near one query, more than its top-k) the entry's D is
+// (v < TAU (|f_o|^2 + |f_i|^2): a cluster of columns near one query, more than its top-k) the entry's D is
 // redone from the exact difference in a wave-uniform branch that ordinary features never take.
+// The tile, the redo, the skip mask, the apply chain and the output loop are the phase-B pieces of dvm_dist_tile.h.
 #include <algorithm>
 
-#include "dvm_common.h"
+#include "dvm_dist_tile.h"
 
 namespace dvm {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-void launch_rownorm2(const float *x, int rows, int K, float *out, hipStream_t s);
-
 namespace {
 
-constexpr float LOG2E = 1.4426950408889634f;
-constexpr int BW_D = 128;
-constexpr int BW_KT = 64;            // inner rows per LDS tile (two 32-row sub-tiles)
-constexpr int BW_LDK = BW_D + 4;     // padded row
+using namespace dtile;
+
 constexpr int BW_WAVES = 4;
 constexpr int BW_OB = 32 * BW_WAVES;  // outer rows per workgroup
 constexpr int BW_THREADS = 64 * BW_WAVES;
-constexpr int BW_LD_PER_THREAD = BW_KT * BW_D / 4 / BW_THREADS;  // 8 float4 per thread per tile
-constexpr int BW_MASK = 256;                                      // skip-mask words per tile (see issue_loads)
-constexpr int BW_TILE_FLOATS = BW_KT * BW_LDK + 3 * BW_KT + BW_MASK;  // rows + {norm, c2, coef} + mask
-constexpr float BW_TAU = 1.f / 64.f;  // the norm expansion's v is redone exactly below this share of |f_o|^2 + |f_i|^2
+constexpr int BW_LD_PER_THREAD = KT * D / 4 / BW_THREADS;  // 8 float4 per thread per tile
+constexpr int BW_MASK = 64 * BW_WAVES;                     // skip-mask words per tile (skip_mask_load)
+constexpr int BW_TILE_FLOATS = ROWS_FLOATS + 3 * KT + BW_MASK;  // rows + {norm, c2, coef} + mask
 constexpr size_t BW_LDS_BYTES = ((size_t)2 * BW_TILE_FLOATS + BW_OB) * sizeof(float);
 
 
@@ -81,26 +73,21 @@ __global__ __launch_bounds__(BW_THREADS, 2) void softcorr_bwd_mfma_kernel(const 
     const int r32 = lane & 31, h = lane >> 5;
     const float a2 = args.a2;
 
-    const float *ibase = G.fi + (size_t)b * Ni * BW_D;
+    const float *ibase = G.fi + (size_t)b * Ni * D;
     const float *inb = G.ni + (size_t)b * Ni;
     const float *ic2 = G.c2i ? G.c2i + (size_t)b * Ni : nullptr;
     const float *icf = G.coefi ? G.coefi + (size_t)b * Ni : nullptr;
 
     const int orow = ot * BW_OB + wave * 32 + r32;
     const int orc = orow < No ? orow : No - 1;
-    const float *op = G.fo + ((size_t)b * No + orc) * BW_D;
-    float q[BW_D / 2];  // B operand of the distance GEMM: q[s] = -2 * fo[row][channel(s, h)]
-#pragma unroll
-    for (int c = 0; c < BW_D / 4; ++c) {
-        f32x4 v = *(const f32x4 *)(op + 4 * c);
-        q[2 * c] = -2.f * (h ? v.y : v.x);
-        q[2 * c + 1] = -2.f * (h ? v.w : v.z);
-    }
+    const float *op = G.fo + ((size_t)b * No + orc) * D;
+    float q[D / 2];  // B operand of the distance GEMM
+    load_query_frag(op, h, q);
     const float nrm_o = G.no[(size_t)b * No + orc];
     const float c2_o = G.c2o ? G.c2o[(size_t)b * No + orc] : 0.f;
     const float coef_o = orow < No ? (G.coefo ? G.coefo[(size_t)b * No + orc] : 1.f) : 0.f;
 
-    const int ntiles = (Ni + BW_KT - 1) / BW_KT;
+    const int ntiles = (Ni + KT - 1) / KT;
     const int per = (ntiles + args.split - 1) / args.split;
     const int t0 = sp * per, t1 = min(ntiles, t0 + per);
     if (t0 >= t1) return;  // uniform over the workgroup
@@ -111,45 +98,22 @@ __global__ __launch_bounds__(BW_THREADS, 2) void softcorr_bwd_mfma_kernel(const 
     const uint32_t *bits = args.topk_bits;
     const int wpr = args.wpr;
     auto issue_loads = [&](int t) {
-        const int j0 = t * BW_KT;
-#pragma unroll
-        for (int e = 0; e < BW_LD_PER_THREAD; ++e) {
-            int id = tid + e * BW_THREADS;
-            int r = id >> 5, c = id & 31;
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (j0 + r < Ni) v = *(const f32x4 *)(ibase + (size_t)(j0 + r) * BW_D + 4 * c);
-            pre[e] = v;
-        }
-        if (tid < 3 * BW_KT) {  // threads 0..63: norm, 64..127: c2, 128..191: coef
+        const int j0 = t * KT;
+        issue_tile<BW_THREADS>(ibase, j0, Ni, tid, pre);
+        if (tid < 3 * KT) {  // threads 0..63: norm, 64..127: c2, 128..191: coef
             const int which = tid >> 6, j = j0 + (tid & 63);
             const bool ok = j < Ni;
             if (which == 0) pres = ok ? inb[j] : 0.f;
             else if (which == 1) pres = (ok && ic2) ? ic2[j] : 0.f;
             else pres = ok ? (icf ? icf[j] : 1.f) : 0.f;
         }
-        // the top-k skip mask of this tile x the workgroup's outer block, one word per thread.  df1 pass: word
-        // [outer row tid/2][32-column half tid%2]; df2 pass: word [inner row tid/4][32-column group tid%4 of the block]
-        if (grp == 0) {
-            const int mrow = ot * BW_OB + (tid >> 1), wc = (j0 >> 5) + (tid & 1);
-            prem = (mrow < No && wc < wpr) ? bits[((size_t)b * No + mrow) * wpr + wc] : 0u;
-        } else {
-            const int irow = j0 + (tid >> 2), wc = ot * (BW_OB / 32) + (tid & 3);
-            prem = (irow < Ni && wc < wpr) ? bits[((size_t)b * Ni + irow) * wpr + wc] : 0u;
-        }
+        prem = skip_mask_load<BW_WAVES>(grp, bits, wpr, b, ot, j0, No, Ni, tid);
     };
     auto commit_loads = [&](int buf) {
         float *kt = smem + buf * BW_TILE_FLOATS;
-#pragma unroll
-        for (int e = 0; e < BW_LD_PER_THREAD; ++e) {
-            int id = tid + e * BW_THREADS;
-            int r = id >> 5, c = id & 31;
-            // position p < 64 holds channel 2p, position 64 + p holds channel 2p + 1
-            float2 ev = {pre[e].x, pre[e].z}, od = {pre[e].y, pre[e].w};
-            *(float2 *)(kt + r * BW_LDK + 2 * c) = ev;
-            *(float2 *)(kt + r * BW_LDK + 64 + 2 * c) = od;
-        }
-        if (tid < 3 * BW_KT) kt[BW_KT * BW_LDK + tid] = pres;
-        ((uint32_t *)kt)[BW_KT * BW_LDK + 3 * BW_KT + tid] = prem;
+        commit_tile<BW_THREADS>(kt, tid, pre);
+        if (tid < 3 * KT) kt[ROWS_FLOATS + tid] = pres;
+        ((uint32_t *)kt)[ROWS_FLOATS + 3 * KT + tid] = prem;
     };
 
     f32x16 acc2[4];  // [position block cb] : out[outer row (C layout)][position 4*r32 + cb]
@@ -169,109 +133,38 @@ __global__ __launch_bounds__(BW_THREADS, 2) void softcorr_bwd_mfma_kernel(const 
         if (t + 1 < t1) issue_loads(t + 1);
 #pragma unroll 1
         for (int sub = 0; sub < 2; ++sub) {
-            const float *arow = kt + (sub * 32 + r32) * BW_LDK + h * 64;
-            f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int c = 0; c < 16; ++c) {
-                f32x4 a = *(const f32x4 *)(arow + 4 * c);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, q[4 * c], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, q[4 * c + 1], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, q[4 * c + 2], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, q[4 * c + 3], acc, 0, 0, 0);
-            }
-            // this lane's 16 inner rows: local row = (r&3) + 8*(r>>2) + 4*h
-            const float *sc = kt + BW_KT * BW_LDK + sub * 32 + 4 * h;
-            const uint32_t *msk = (const uint32_t *)(kt + BW_KT * BW_LDK + 3 * BW_KT);
-            unsigned exact = 0;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const f32x4 nb = *(const f32x4 *)(sc + 8 * g);
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int r = 4 * g + u;
-                    acc[r] = (acc[r] + nrm_o) + nb[u];
-                    exact |= (acc[r] < BW_TAU * (nrm_o + nb[u]) ? 1u : 0u) << r;
-                }
-            }
-            if (__any(exact != 0)) {  // rare: redo v = |f_o - f_i|^2 from the difference where the expansion cancelled
-#pragma unroll 1
-                for (int r = 0; r < 16; ++r) {
-                    if (!__any((exact >> r) & 1u)) continue;
-                    // this lane's entry r: its outer row (op, from global, cached) against LDS row `er` of the tile
-                    // (position p < 64 holds channel 2p, 64 + p channel 2p + 1), all 128 channels by one lane
-                    const int er = sub * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                    const float *xr = kt + er * BW_LDK;
-                    float v = 0.f;
-#pragma unroll 4
-                    for (int c = 0; c < BW_D / 4; ++c) {
-                        const f32x4 o4 = *(const f32x4 *)(op + 4 * c);
-                        const float2 ev = *(const float2 *)(xr + 2 * c), od = *(const float2 *)(xr + 64 + 2 * c);
-                        const float d0 = ev.x - o4.x, d1 = od.x - o4.y, d2 = ev.y - o4.z, d3 = od.y - o4.w;
-                        v = fmaf(d0, d0, v);
-                        v = fmaf(d1, d1, v);
-                        v = fmaf(d2, d2, v);
-                        v = fmaf(d3, d3, v);
-                    }
-#pragma unroll
-                    for (int rr = 0; rr < 16; ++rr)
-                        if (rr == r && ((exact >> r) & 1u)) acc[rr] = v;
-                }
-            }
+            f32x16 acc;
+            outer_inner_sqdist(kt, kt + ROWS_FLOATS, sub, r32, h, q, op, nrm_o, acc);
+            // this lane's 16 inner rows: lane_key(r, h)
+            const float *sc = kt + ROWS_FLOATS + sub * 32 + 4 * h;
+            const uint32_t *msk = (const uint32_t *)(kt + ROWS_FLOATS + 3 * KT);
+            const unsigned skip = skip_mask_lane<BW_WAVES>(grp, msk, wave, r32, sub, h);
             float w[16];
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                const f32x4 cc = *(const f32x4 *)(sc + BW_KT + 8 * g);
-                const f32x4 cf = *(const f32x4 *)(sc + 2 * BW_KT + 8 * g);
+                const f32x4 cc = *(const f32x4 *)(sc + KT + 8 * g);
+                const f32x4 cf = *(const f32x4 *)(sc + 2 * KT + 8 * g);
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     const int r = 4 * g + u;
-                    const int il = (r & 3) + 8 * (r >> 2) + 4 * h;  // inner row within the sub-tile
-                    const bool topk = grp == 0 ? ((msk[(wave * 32 + r32) * 2 + sub] >> il) & 1u)
-                                               : ((msk[(sub * 32 + il) * 4 + wave] >> r32) & 1u);
                     const float v = fmaxf(acc[r], 0.f);
-                    const float D = sqrt_rn(v);
-                    const float e = __builtin_amdgcn_exp2f(fmaf(D, a2, -(c2_o + cc[u])));
-                    const float wv = (coef_o * cf[u]) * e * __builtin_amdgcn_rcpf(D);
+                    const float dist = sqrt_rn(v);
+                    const float e = __builtin_amdgcn_exp2f(fmaf(dist, a2, -(c2_o + cc[u])));
+                    const float wv = (coef_o * cf[u]) * e * __builtin_amdgcn_rcpf(dist);
                     // padding rows of the last tile carry coef 0 but zero features: their "distance" |f_o| can be far
                     // below the row minimum, e overflows to +inf and 0 * inf would poison the whole output row
-                    w[r] = (v > 0.f && cf[u] != 0.f && !topk) ? wv : 0.f;
+                    w[r] = (v > 0.f && cf[u] != 0.f && !((skip >> r) & 1u)) ? wv : 0.f;
                     rl += w[r];
                 }
             }
-            // apply: out[o][pos] += sum_t W[t][o] * X[t][pos]; step r contracts t = (r&3)+8*(r>>2)+4*h
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int trow = sub * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                const f32x4 x = *(const f32x4 *)(kt + trow * BW_LDK + 4 * r32);
-                acc2[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[r], x.x, acc2[0], 0, 0, 0);
-                acc2[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[r], x.y, acc2[1], 0, 0, 0);
-                acc2[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[r], x.z, acc2[2], 0, 0, 0);
-                acc2[3] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[r], x.w, acc2[3], 0, 0, 0);
-            }
+            apply_chain(kt, sub, r32, h, w, acc2);
         }
         if (t + 1 < t1) commit_loads(buf ^ 1);
         __syncthreads();
     }
 
-    // d_out[o] += (sum_t W[t][o]) * f_o - acc2[o]
-    const float rtot = rl + __shfl_xor(rl, 32, 64);
-    if (h == 0) rsum[wave * 32 + r32] = rtot;
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int o = (r & 3) + 8 * (r >> 2) + 4 * h;
-        const int row = ot * BW_OB + wave * 32 + o;
-        if (row >= No) continue;
-        const float rr = rsum[wave * 32 + o];
-        const float *fo = G.fo + ((size_t)b * No + row) * BW_D;
-        float *dst = G.dout + ((size_t)b * No + row) * BW_D;
-#pragma unroll
-        for (int cb = 0; cb < 4; ++cb) {
-            const int pos = 4 * r32 + cb;
-            const int ch = pos < 64 ? 2 * pos : 2 * (pos - 64) + 1;
-            unsafeAtomicAdd(dst + ch, rr * fo[ch] - acc2[cb][r]);
-        }
-    }
+    // atomics: the split pieces and the prep kernel's top-k entries add to the same rows
+    store_outer_rows<true>(rsum, rl, G.fo, G.dout, b, ot * BW_OB + wave * 32, No, wave, r32, h, acc2);
 }
 
 // Any d (multiple of 4, <= 512): one wave per outer row, lanes own channels lane + 64u.  Reference-quality
@@ -309,34 +202,17 @@ __global__ __launch_bounds__(256) void softcorr_bwd_scalar_kernel(const SBScalar
     float rsum = 0.f;
     for (int j = 0; j < Ni; ++j) {
         const float *fi = G.fi + ((size_t)b * Ni + j) * d;
-        float xv[8], part = 0.f;
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int c = lane + 64 * u;
-            xv[u] = c < d ? fi[c] : 0.f;
-            part = fmaf(ov[u], xv[u], part);
-        }
+        float xv[8];
+        const float part = wave_row_load_dot(fi, d, lane, ov, xv);
         // the row's top-k columns are the prep kernel's (grp 0: outer = f1 row, grp 1: inner j = f1 row)
         const uint32_t *bw = args.topk_bits + (grp == 0 ? ((size_t)b * No + row) * args.wpr + (j >> 5)
                                                          : ((size_t)b * Ni + j) * args.wpr + (row >> 5));
         if ((*bw >> (grp == 0 ? (j & 31) : (row & 31))) & 1u) continue;  // uniform over the wave
-        const float dot = wave_sum(part);
-        const float ni = G.ni[(size_t)b * Ni + j];
-        float v = (-2.f * dot + nrm_o) + ni;
-        if (v < BW_TAU * (nrm_o + ni)) {  // uniform: the expansion cancelled, redo v from the difference
-            float p2 = 0.f;
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const float dd = ov[u] - xv[u];
-                p2 = fmaf(dd, dd, p2);
-            }
-            v = wave_sum(p2);
-        }
-        v = fmaxf(v, 0.f);
-        const float D = sqrt_rn(v);
+        const float v = wave_row_sqdist(part, ov, xv, nrm_o, G.ni[(size_t)b * Ni + j]);
+        const float dist = sqrt_rn(v);
         const float c2 = c2_o + (G.c2i ? G.c2i[(size_t)b * Ni + j] : 0.f);
         const float cf = coef_o * (G.coefi ? G.coefi[(size_t)b * Ni + j] : 1.f);
-        const float w = v > 0.f ? cf * exp2f(fmaf(D, args.a2, -c2)) / D : 0.f;
+        const float w = v > 0.f ? cf * exp2f(fmaf(dist, args.a2, -c2)) / dist : 0.f;
         rsum += w;
 #pragma unroll
         for (int u = 0; u < 8; ++u) av[u] = fmaf(w, xv[u], av[u]);
@@ -436,7 +312,7 @@ DVM_EXPORT int dvm_softcorr_bwd_f32(const float *f1, const float *f2, int B, int
     DVM_REQUIRE(topk >= 1 && topk <= 16, "dvm_softcorr_bwd_f32: topk=%d unsupported (1..16)", topk);
     DVM_REQUIRE(neg_alpha < 0.f, "dvm_softcorr_bwd_f32: neg_alpha must be negative (got %g)", (double)neg_alpha);
     DVM_REQUIRE(variant >= 0 && variant <= 2, "dvm_softcorr_bwd_f32: bad variant %d", variant);
-    DVM_REQUIRE(variant != 2 || d == BW_D, "dvm_softcorr_bwd_f32: MFMA variant needs d == 128");
+    DVM_REQUIRE(variant != 2 || d == D, "dvm_softcorr_bwd_f32: MFMA variant needs d == 128");
     Arena ar(ws, ws_bytes);
     float *n1 = ar.take<float>((size_t)B * N);
     float *coef = ar.take<float>((size_t)B * N);
@@ -457,14 +333,14 @@ DVM_EXPORT int dvm_softcorr_bwd_f32(const float *f1, const float *f2, int B, int
     hipLaunchKernelGGL(softcorr_bwd_prep_kernel, dim3((unsigned)(((size_t)B * N + 3) / 4)), dim3(256), 0, s, f1, f2, pi_val, pi_idx,
                        g_val, row_smax, row_sum, B, N, M, d, topk, neg_alpha, coef, c2, bits, d_f1, d_f2);
     const float a2 = neg_alpha * LOG2E;
-    const bool mfma = (variant == 2) || (variant == 0 && d == BW_D);
+    const bool mfma = (variant == 2) || (variant == 0 && d == D);
     if (mfma) {
         SBArgs a;
         a.g[0] = SBGroup{f1, f2, n1, n2, c2, coef, nullptr, nullptr, d_f1, N, M, (N + BW_OB - 1) / BW_OB};
         a.g[1] = SBGroup{f2, f1, n2, n1, nullptr, nullptr, c2, coef, d_f2, M, N, (M + BW_OB - 1) / BW_OB};
         int split = 1;
         const int base = B * (a.g[0].tiles_o + a.g[1].tiles_o);
-        const int min_tiles = (std::min(N, M) + BW_KT - 1) / BW_KT;
+        const int min_tiles = (std::min(N, M) + KT - 1) / KT;
         while (base * split < 512 && split < 8 && min_tiles / (2 * split) >= 4) split *= 2;
         a.split = split;
         a.topk_bits = bits;

@@ -12,7 +12,7 @@ import glob, os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "dv-matcher_amd", "csrc")
 FLAGS = "--offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math -fhip-fp32-correctly-rounded-divide-sqrt -fno-slp-vectorize -x hip --cuda-device-only -S".split()
-EXTRA = {"dvm_softcorr_sweep2.hip": ["-fno-honor-nans"]}
+EXTRA = {"dvm_softcorr_coarse.hip": ["-fno-honor-nans"]}
 thresh = int(sys.argv[1]) if len(sys.argv) > 1 else 6
 tmp = tempfile.mkdtemp(prefix="isa_")
 procs = []
