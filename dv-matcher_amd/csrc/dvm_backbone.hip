@@ -1189,10 +1189,6 @@ __global__ void gather_rows_kernel(const float *__restrict__ src, const int32_t 
     dst[((size_t)b * nR + r) * C + c] = src[((size_t)b * N + rows[r]) * C + c];
 }
 
-void launch_rownorm2(const float *x, int rows, int K, float *out, hipStream_t s);  // dvm_softcorr.hip
-
-int launch_reduce_partials(const double *partial, int B, int nparts, float scale, float *out, int stride, int off, hipStream_t s);
-
 int launch_knn_neg(const float *a, const float *bq, int B, int N, int M, int C, int k, int32_t *idx, float *na, float *nb,
                    float *S, hipStream_t s) {
     launch_rownorm2(a, B * N, C, na, s);
@@ -1234,13 +1230,26 @@ int launch_knn_neg(const float *a, const float *bq, int B, int N, int M, int C, 
     return DVM_OK;
 }
 
+// launch_knn_neg's scratch: the norms of both sides and the scores [B][N][M]
+struct KnnNegWs {
+    float *na, *nb, *S;
+};
+static size_t carve_knn_neg(Arena &ar, int B, int N, int M, KnnNegWs &w) {
+    w.na = ar.take<float>((size_t)B * N);
+    w.nb = ar.take<float>((size_t)B * M);
+    w.S = ar.take<float>((size_t)B * N * M);
+    return ar.off;
+}
+static size_t carve_pos_encoding(Arena &ar, float *&part) {   // min / max partials of up to 256 workgroups
+    part = ar.take<float>(2 * 256);
+    return ar.off;
+}
+
 }  // namespace dvm
 
 using namespace dvm;
 
-DVM_EXPORT size_t dvm_knn_neg_workspace_bytes(int B, int N, int M, int C, int k) {
-    return align_up((size_t)B * N * sizeof(float)) + align_up((size_t)B * M * sizeof(float)) + align_up((size_t)B * N * M * sizeof(float));
-}
+DVM_EXPORT size_t dvm_knn_neg_workspace_bytes(int B, int N, int M, int C, int k) { return null_carve<KnnNegWs>(carve_knn_neg, B, N, M); }
 
 DVM_EXPORT int dvm_knn_neg_f32(const float *a, const float *b, int B, int N, int M, int C, int k, int32_t *idx, void *ws,
                                size_t ws_bytes, void *stream) {
@@ -1248,29 +1257,19 @@ DVM_EXPORT int dvm_knn_neg_f32(const float *a, const float *b, int B, int N, int
     DVM_REQUIRE(B >= 1 && N >= 1 && M >= 1 && C >= 1, "dvm_knn_neg_f32: empty input (B=%d N=%d M=%d C=%d)", B, N, M, C);
     DVM_REQUIRE(k >= 1 && k <= 512 && k <= M, "dvm_knn_neg_f32: k=%d unsupported (1..min(512,M=%d))", k, M);
     DVM_REQUIRE(M <= 8192, "dvm_knn_neg_f32: M=%d exceeds 8192", M);
-    Arena ar(ws, ws_bytes);
-    float *na = ar.take<float>((size_t)B * N);
-    float *nb = ar.take<float>((size_t)B * M);
-    float *S = ar.take<float>((size_t)B * N * M);
-    if (!ar.ok()) {
-        set_error("dvm_knn_neg_f32: workspace too small (%zu < %zu)", ws_bytes, ar.off);
-        return DVM_ENOSPACE;
-    }
-    launch_knn_neg(a, b, B, N, M, C, k, idx, na, nb, S, (hipStream_t)stream);
+    KnnNegWs w;
+    if (!carve_ws(ws, ws_bytes, "dvm_knn_neg_f32", w, carve_knn_neg, B, N, M)) return DVM_ENOSPACE;
+    launch_knn_neg(a, b, B, N, M, C, k, idx, w.na, w.nb, w.S, (hipStream_t)stream);
     DVM_CHECK_LAUNCH("knn_neg");
     return DVM_OK;
 }
 
-DVM_EXPORT size_t dvm_pos_encoding_workspace_bytes(void) { return align_up(2 * 256 * sizeof(float)); }
+DVM_EXPORT size_t dvm_pos_encoding_workspace_bytes(void) { return null_carve<float *>(carve_pos_encoding); }
 
 DVM_EXPORT int dvm_pos_encoding_f32(const float *x, int B, int N, float *out, void *ws, size_t ws_bytes, void *stream) {
     DVM_REQUIRE(x && out && B >= 1 && N >= 1, "dvm_pos_encoding_f32: bad arguments");
-    Arena ar(ws, ws_bytes);
-    float *part = ar.take<float>(2 * 256);
-    if (!ar.ok()) {
-        set_error("dvm_pos_encoding_f32: workspace too small");
-        return DVM_ENOSPACE;
-    }
+    float *part;
+    if (!carve_ws(ws, ws_bytes, "dvm_pos_encoding_f32", part, carve_pos_encoding)) return DVM_ENOSPACE;
     hipStream_t s = (hipStream_t)stream;
     long n = (long)B * 3 * N;
     int nparts = (int)((n + 255) / 256 < 256 ? (n + 255) / 256 : 256);
@@ -1295,12 +1294,8 @@ __global__ void minmax_final_kernel(const float *__restrict__ part, int nparts, 
 DVM_EXPORT int dvm_pos_encoding_sync_f32(const float *x, int B, int N, float *out, void *ws, size_t ws_bytes, const dvm_collective *coll,
                                          float *minmax2, void *stream) {
     DVM_REQUIRE(x && out && B >= 1 && N >= 1 && coll && coll->allreduce && minmax2, "dvm_pos_encoding_sync_f32: bad arguments");
-    Arena ar(ws, ws_bytes);
-    float *part = ar.take<float>(2 * 256);
-    if (!ar.ok()) {
-        set_error("dvm_pos_encoding_sync_f32: workspace too small");
-        return DVM_ENOSPACE;
-    }
+    float *part;
+    if (!carve_ws(ws, ws_bytes, "dvm_pos_encoding_sync_f32", part, carve_pos_encoding)) return DVM_ENOSPACE;
     hipStream_t s = (hipStream_t)stream;
     long n = (long)B * 3 * N;
     int nparts = (int)((n + 255) / 256 < 256 ? (n + 255) / 256 : 256);
@@ -1335,30 +1330,18 @@ static size_t sa_partial_floats(int B, int N) {
     const int S = sa_splits(B, N);
     return S > 1 ? (size_t)S * B * N * (2 + SA_C + 1) : 0;
 }
-// fp16x2-split kernels (dvm_sa_f16.hip)
-size_t sa_f16_ws_bytes(int B, int N);
-void sa_f16_carve(void *ws, int B, int N, _Float16 *&pp, _Float16 *&vp);
-void launch_sa_split_f16(const float *p, const float *v, int B, int N, _Float16 *pp, _Float16 *vp, hipStream_t s);
-void launch_sa_rowstats_f16(const _Float16 *pp, int B, int N, int kchunk, int Z, float *stats, hipStream_t s);
-void launch_sa_apply_f16(const _Float16 *pp, const _Float16 *vp, const float *stats, int B, int N, int kchunk, int Z, float *xr,
-                         float *cinv, hipStream_t s);
-
 // stats [B][N][2] and xr [B][N][64] (and cinv [B][N] when given) from p, v; `part` holds sa_partial_floats(B, N) floats,
-// `f16ws` sa_f16_ws_bytes(B, N) bytes
+// pp / vp the split planes (sa_f16_carve), or null
 static void launch_sa_forward(const float *p, const float *v, int B, int N, float *xr, float *stats, float *cinv, float *part,
-                              void *f16ws, hipStream_t s) {
+                              _Float16 *pp, _Float16 *vp, hipStream_t s) {
     const int S = sa_splits(B, N);
     const int kchunk = ((N + S - 1) / S + SA_KB - 1) / SA_KB * SA_KB;
     const int Z = (N + kchunk - 1) / kchunk;
     dim3 grid((N + 31) / 32, B, Z);
     const long rows = (long)B * N;
     float *pstats = part, *po = Z > 1 ? pstats + (size_t)Z * rows * 2 : nullptr, *pc = Z > 1 ? po + (size_t)Z * rows * SA_C : nullptr;
-    const bool f16 = f16ws != nullptr;   // (a caller without the split planes' workspace — the training forward — keeps both contractions on the fp32 matrix instruction)
-    _Float16 *pp = nullptr, *vp = nullptr;
-    if (f16) {
-        sa_f16_carve(f16ws, B, N, pp, vp);
-        launch_sa_split_f16(p, v, B, N, pp, vp, s);
-    }
+    const bool f16 = pp != nullptr;   // (a caller without the split planes' workspace — the training forward — keeps both contractions on the fp32 matrix instruction)
+    if (f16) launch_sa_split_f16(p, v, B, N, pp, vp, s);
     // pass 1
     float *st1 = Z == 1 ? stats : pstats;
     if (f16)
@@ -1374,24 +1357,29 @@ static void launch_sa_forward(const float *p, const float *v, int B, int N, floa
         hipLaunchKernelGGL(sa_apply_kernel, grid, dim3(256), 0, s, p, v, stats, N, kchunk, xo, co);
     if (Z > 1) hipLaunchKernelGGL(sa_apply_merge_kernel, dim3((unsigned)((rows * SA_C + 255) / 256)), dim3(256), 0, s, po, pc, rows, Z, xr, cinv);
 }
+struct SaWs {
+    float *stats, *part;
+    _Float16 *pp, *vp;
+};
+static size_t carve_sa(Arena &ar, int B, int N, SaWs &w) {
+    w.stats = ar.take<float>((size_t)B * N * 2);
+    w.part = ar.take<float>(sa_partial_floats(B, N));
+    return sa_f16_carve(ar, B, N, w.pp, w.vp);
+}
+static size_t carve_sa_train(Arena &ar, int B, int N, float *&part) {   // the training forward: the partials alone
+    part = ar.take<float>(sa_partial_floats(B, N));
+    return ar.off;
+}
 }  // namespace dvm
 
-DVM_EXPORT size_t dvm_sa_attention_workspace_bytes(int B, int N) {
-    return align_up((size_t)B * N * 2 * sizeof(float)) + align_up(sa_partial_floats(B, N) * sizeof(float)) + sa_f16_ws_bytes(B, N);
-}
+DVM_EXPORT size_t dvm_sa_attention_workspace_bytes(int B, int N) { return null_carve<SaWs>(carve_sa, B, N); }
 
 DVM_EXPORT int dvm_sa_attention_fwd_f32(const float *p, const float *v, int B, int N, float *xr, void *ws, size_t ws_bytes,
                                         void *stream) {
     DVM_REQUIRE(p && v && xr && B >= 1 && N >= 1, "dvm_sa_attention_fwd_f32: bad arguments");
-    Arena ar(ws, ws_bytes);
-    float *stats = ar.take<float>((size_t)B * N * 2);
-    float *part = ar.take<float>(sa_partial_floats(B, N));
-    char *f16ws = ar.take<char>(sa_f16_ws_bytes(B, N));
-    if (!ar.ok()) {
-        set_error("dvm_sa_attention_fwd_f32: workspace too small (%zu < %zu)", ws_bytes, ar.off);
-        return DVM_ENOSPACE;
-    }
-    launch_sa_forward(p, v, B, N, xr, stats, nullptr, part, f16ws, (hipStream_t)stream);
+    SaWs w;
+    if (!carve_ws(ws, ws_bytes, "dvm_sa_attention_fwd_f32", w, carve_sa, B, N)) return DVM_ENOSPACE;
+    launch_sa_forward(p, v, B, N, xr, w.stats, nullptr, w.part, w.pp, w.vp, (hipStream_t)stream);
     DVM_CHECK_LAUNCH("sa_attention");
     return DVM_OK;
 }
@@ -1399,7 +1387,7 @@ DVM_EXPORT int dvm_sa_attention_fwd_f32(const float *p, const float *v, int B, i
 // The training forward stays on the fp32 matrix instruction: the backward kernels recompute E in fp32 and take the row
 // statistics and column sums from here — with the fp16-split E (2.4e-7 * sum|p_i p_j| off) the two would disagree by
 // up to 1e-4 relative in dp at large logits.  Inference (dvm_sa_attention_fwd_f32) has no such coupling.
-DVM_EXPORT size_t dvm_sa_attention_train_fwd_workspace_bytes(int B, int N) { return align_up(sa_partial_floats(B, N) * sizeof(float)); }
+DVM_EXPORT size_t dvm_sa_attention_train_fwd_workspace_bytes(int B, int N) { return null_carve<float *>(carve_sa_train, B, N); }
 
 DVM_EXPORT int dvm_sa_attention_train_fwd_f32(const float *p, const float *v, int B, int N, float *xr, float *stats, float *cinv,
                                               void *ws, size_t ws_bytes, void *stream) {
@@ -1407,7 +1395,7 @@ DVM_EXPORT int dvm_sa_attention_train_fwd_f32(const float *p, const float *v, in
     const size_t need = sa_partial_floats(B, N) * sizeof(float);
     DVM_REQUIRE(need == 0 || (ws != nullptr && ws_bytes >= need), "dvm_sa_attention_train_fwd_f32: workspace too small (%zu < %zu)",
                 ws_bytes, need);
-    launch_sa_forward(p, v, B, N, xr, stats, cinv, (float *)ws, nullptr, (hipStream_t)stream);
+    launch_sa_forward(p, v, B, N, xr, stats, cinv, (float *)ws, nullptr, nullptr, (hipStream_t)stream);
     DVM_CHECK_LAUNCH("sa_attention_train_fwd");
     return DVM_OK;
 }
@@ -1444,33 +1432,33 @@ DVM_EXPORT int dvm_dist_loss_bwd_weights_f32(const float *feat, const float *dis
     return DVM_OK;
 }
 
-DVM_EXPORT size_t dvm_dist_loss_workspace_bytes(int B, int N, int C, int nA, int k) {
-    return align_up((size_t)B * nA * C * sizeof(float)) + align_up((size_t)B * nA * k * sizeof(int32_t)) +
-           align_up((size_t)B * ((nA + 3) / 4) * sizeof(double)) + dvm_knn_neg_workspace_bytes(B, nA, N, C, k);
-}
-
 namespace dvm {
+// the anchors' rows, their neighbours, one partial per workgroup of 4 anchors, then the kNN's own scratch (anchors against all rows)
+struct DistLossWs {
+    float *fa;
+    int32_t *idx;
+    double *partial;
+    KnnNegWs knn;
+};
+static size_t carve_dist_loss(Arena &ar, int B, int N, int C, int nA, int k, DistLossWs &w) {
+    w.fa = ar.take<float>((size_t)B * nA * C);
+    w.idx = ar.take<int32_t>((size_t)B * nA * k);
+    w.partial = ar.take<double>((size_t)B * ((nA + 3) / 4));
+    return carve_knn_neg(ar, B, nA, N, w.knn);
+}
 // dvm_dist_loss_fwd_f32 with the sum written at out[b * out_stride + out_off], the selected neighbours at idx_out (NULL: scratch) and, for
 // a backward that does not read the feature rows again (C == 128), x_j / y_j at xsave [B][nA][k] x 2; fa_out [B][nA][C] = the anchors' rows
 int launch_dist_loss_fwd(const float *feat, const float *dist, const int32_t *anchors, int B, int N, int C, int nA, int k, float *out, int out_stride,
                          int out_off, int32_t *idx_out, float *xsave, float *fa_out, void *ws, size_t ws_bytes, hipStream_t s) {
-    Arena ar(ws, ws_bytes);
-    float *fa = ar.take<float>((size_t)B * nA * C);
-    int32_t *idx = ar.take<int32_t>((size_t)B * nA * k);
-    int nblk = (nA + 3) / 4;
-    double *partial = ar.take<double>((size_t)B * nblk);
-    float *na = ar.take<float>((size_t)B * nA);
-    float *nb = ar.take<float>((size_t)B * N);
-    float *S = ar.take<float>((size_t)B * nA * N);
-    if (!ar.ok()) {
-        set_error("dvm_dist_loss_fwd_f32: workspace too small (%zu < %zu)", ws_bytes, ar.off);
-        return DVM_ENOSPACE;
-    }
-    if (idx_out) idx = idx_out;
-    if (fa_out) fa = fa_out;
+    DistLossWs w;
+    if (!carve_ws(ws, ws_bytes, "dvm_dist_loss_fwd_f32", w, carve_dist_loss, B, N, C, nA, k)) return DVM_ENOSPACE;
+    const int nblk = (nA + 3) / 4;
+    double *const partial = w.partial;
+    int32_t *const idx = idx_out ? idx_out : w.idx;
+    float *const fa = fa_out ? fa_out : w.fa;
     hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)(((long)nA * C + 255) / 256), B), dim3(256), 0, s, feat, anchors, N, C, nA,
                        fa);
-    launch_knn_neg(fa, feat, B, nA, N, C, k, idx, na, nb, S, s);
+    launch_knn_neg(fa, feat, B, nA, N, C, k, idx, w.knn.na, w.knn.nb, w.knn.S, s);
     if (C == 128 && k <= 512)
         hipLaunchKernelGGL(dist_loss_kernel, dim3(nblk, B), dim3(256), 0, s, feat, dist, anchors, idx, N, nA, k, partial, xsave);
     else
@@ -1485,6 +1473,10 @@ void launch_dist_loss_bwd_weights_saved(const float *xsave, const int32_t *idx, 
     hipLaunchKernelGGL(dist_loss_bwd_weights_saved_kernel, dim3((nA + 3) / 4, B), dim3(256), 0, s, xsave, idx, gterm, gstride, N, nA, k, W, rs);
 }
 }  // namespace dvm
+
+DVM_EXPORT size_t dvm_dist_loss_workspace_bytes(int B, int N, int C, int nA, int k) {
+    return null_carve<DistLossWs>(carve_dist_loss, B, N, C, nA, k);
+}
 
 DVM_EXPORT int dvm_dist_loss_fwd_f32(const float *feat, const float *dist, const int32_t *anchors, int B, int N, int C, int nA,
                                      int k, float *out, int32_t *idx_out, void *ws, size_t ws_bytes, void *stream) {

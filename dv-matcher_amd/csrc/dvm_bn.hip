@@ -414,12 +414,28 @@ int splits_for(int B, int C, int N) {  // enough workgroups to fill the chip, at
     return S;
 }
 
+// channel-major forward and backward: S partial (sum, sum of squares) pairs per channel
+size_t carve_bn(Arena &ar, int C, int S, double *&partial) {
+    partial = ar.take<double>((size_t)C * S * 2);
+    return ar.off;
+}
+// point-major forward and backward: the partials per (group, channel, row chunk) and the finalised per-channel coefficients
+struct BnPmWs {
+    double *partial;
+    float *fin;
+};
+size_t carve_bn_pm(Arena &ar, long R, int C, int groups, BnPmWs &w) {
+    w.partial = ar.take<double>((size_t)groups * C * pm_splits_for(R, C) * 2);
+    w.fin = ar.take<float>((size_t)groups * C * 4);
+    return ar.off;
+}
+
 }  // namespace
 }  // namespace dvm
 
 using namespace dvm;
 
-DVM_EXPORT size_t dvm_bn_workspace_bytes(int B, int C, int N) { return align_up((size_t)C * splits_for(B, C, N) * 2 * sizeof(double)); }
+DVM_EXPORT size_t dvm_bn_workspace_bytes(int B, int C, int N) { return null_carve<double *>(carve_bn, C, splits_for(B, C, N)); }
 
 DVM_EXPORT int dvm_bn_act_train_fwd_f32(const float *x, const float *res, const float *gamma, const float *beta, int B, int C, int N,
                                         float eps, float slope, float momentum, float *y, float *save_mean, float *save_invstd,
@@ -428,12 +444,8 @@ DVM_EXPORT int dvm_bn_act_train_fwd_f32(const float *x, const float *res, const 
     DVM_REQUIRE(B >= 1 && C >= 1 && N >= 1, "dvm_bn_act_train_fwd_f32: empty input (B=%d C=%d N=%d)", B, C, N);
     DVM_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "dvm_bn_act_train_fwd_f32: running_mean/var go together");
     const int S = splits_for(B, C, N);
-    Arena ar(ws, ws_bytes);
-    double *partial = ar.take<double>((size_t)C * S * 2);
-    if (!ar.ok()) {
-        set_error("dvm_bn_act_train_fwd_f32: workspace too small (%zu < %zu)", ws_bytes, ar.off);
-        return DVM_ENOSPACE;
-    }
+    double *partial;
+    if (!carve_ws(ws, ws_bytes, "dvm_bn_act_train_fwd_f32", partial, carve_bn, C, S)) return DVM_ENOSPACE;
     hipStream_t s = (hipStream_t)stream;
     const long total = (long)B * N;
     const int chunk = (int)((total + S - 1) / S);
@@ -450,12 +462,8 @@ DVM_EXPORT int dvm_bn_act_train_bwd_f32(const float *dy, const float *y, const f
     DVM_REQUIRE(dy && y && x && save_mean && save_invstd && dx, "dvm_bn_act_train_bwd_f32: null pointer");
     DVM_REQUIRE(B >= 1 && C >= 1 && N >= 1, "dvm_bn_act_train_bwd_f32: empty input (B=%d C=%d N=%d)", B, C, N);
     const int S = splits_for(B, C, N);
-    Arena ar(ws, ws_bytes);
-    double *partial = ar.take<double>((size_t)C * S * 2);
-    if (!ar.ok()) {
-        set_error("dvm_bn_act_train_bwd_f32: workspace too small (%zu < %zu)", ws_bytes, ar.off);
-        return DVM_ENOSPACE;
-    }
+    double *partial;
+    if (!carve_ws(ws, ws_bytes, "dvm_bn_act_train_bwd_f32", partial, carve_bn, C, S)) return DVM_ENOSPACE;
     hipStream_t s = (hipStream_t)stream;
     const long total = (long)B * N;
     const int chunk = (int)((total + S - 1) / S);
@@ -468,8 +476,7 @@ DVM_EXPORT int dvm_bn_act_train_bwd_f32(const float *dy, const float *y, const f
 }
 
 DVM_EXPORT size_t dvm_bn_pm_workspace_bytes(long R, int C) {
-    if (R < 1 || C < 4 || C % 4 != 0 || C > 1024) return 0;
-    return align_up((size_t)C * pm_splits_for(R, C) * 2 * sizeof(double)) + align_up((size_t)C * 4 * sizeof(float));
+    return dvm_bn_pm_groups_workspace_bytes(R, C, 1);
 }
 
 DVM_EXPORT int dvm_bn_act_train_fwd_pm_f32(const float *x, const float *res, const float *gamma, const float *beta, long R, int C, float eps,
@@ -481,7 +488,7 @@ DVM_EXPORT int dvm_bn_act_train_fwd_pm_f32(const float *x, const float *res, con
 
 DVM_EXPORT size_t dvm_bn_pm_groups_workspace_bytes(long R, int C, int groups) {
     if (R < 1 || C < 4 || C % 4 != 0 || C > 1024 || groups < 1) return 0;
-    return align_up((size_t)groups * C * pm_splits_for(R, C) * 2 * sizeof(double)) + align_up((size_t)groups * C * 4 * sizeof(float));
+    return null_carve<BnPmWs>(carve_bn_pm, R, C, groups);
 }
 
 DVM_EXPORT size_t dvm_bn_pm_sync_bytes(int C, int groups) { return align_up(((size_t)groups * C * 2 + groups) * sizeof(double)); }
@@ -504,13 +511,10 @@ DVM_EXPORT int dvm_bn_act_train_fwd_pm_sync_f32(const float *x, const float *res
     DVM_REQUIRE(R >= 1 && C >= 4 && C % 4 == 0 && C <= 1024, "dvm_bn_act_train_fwd_pm_f32: need R >= 1 and C a multiple of 4, at most 1024 (R=%ld C=%d)", R, C);
     DVM_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "dvm_bn_act_train_fwd_pm_f32: running_mean/var go together");
     const int S = pm_splits_for(R, C);
-    Arena ar(ws, ws_bytes);
-    double *partial = ar.take<double>((size_t)groups * C * S * 2);
-    float *fin = ar.take<float>((size_t)groups * C * 4);
-    if (!ar.ok()) {
-        set_error("dvm_bn_act_train_fwd_pm_f32: workspace too small (%zu < %zu)", ws_bytes, ar.off);
-        return DVM_ENOSPACE;
-    }
+    BnPmWs w;
+    if (!carve_ws(ws, ws_bytes, "dvm_bn_act_train_fwd_pm_f32", w, carve_bn_pm, R, C, groups)) return DVM_ENOSPACE;
+    double *const partial = w.partial;
+    float *const fin = w.fin;
     hipStream_t s = (hipStream_t)stream;
     const int CG = pm_group_for(C);
     const long Rall = R * groups;   // R: rows PER GROUP
@@ -555,13 +559,10 @@ DVM_EXPORT int dvm_bn_act_train_bwd_pm_sync_f32(const float *dy, const float *y,
     DVM_REQUIRE(groups >= 1 && groups <= 64, "dvm_bn_act_train_bwd_pm_groups_f32: bad group count %d", groups);
     DVM_REQUIRE(R >= 1 && C >= 4 && C % 4 == 0 && C <= 1024, "dvm_bn_act_train_bwd_pm_f32: need R >= 1 and C a multiple of 4, at most 1024 (R=%ld C=%d)", R, C);
     const int S = pm_splits_for(R, C);
-    Arena ar(ws, ws_bytes);
-    double *partial = ar.take<double>((size_t)groups * C * S * 2);
-    float *fin = ar.take<float>((size_t)groups * C * 4);
-    if (!ar.ok()) {
-        set_error("dvm_bn_act_train_bwd_pm_f32: workspace too small (%zu < %zu)", ws_bytes, ar.off);
-        return DVM_ENOSPACE;
-    }
+    BnPmWs w;
+    if (!carve_ws(ws, ws_bytes, "dvm_bn_act_train_bwd_pm_f32", w, carve_bn_pm, R, C, groups)) return DVM_ENOSPACE;
+    double *const partial = w.partial;
+    float *const fin = w.fin;
     hipStream_t s = (hipStream_t)stream;
     const int CG = pm_group_for(C);
     const long Rall = R * groups;   // R: rows PER GROUP

@@ -74,6 +74,28 @@ struct Arena {
     }
     bool ok() const { return base != nullptr && off <= cap; }
 };
+// after the carve, before the first launch: false, with the error message set, if the caller's buffer does not hold the layout
+// (the caller returns DVM_ENOSPACE)
+static inline bool arena_fits(const Arena &ar, const char *who, const char *what = "workspace") {
+    if (!ar.ok()) set_error("%s: %s too small (%zu < %zu)", who, what, ar.cap, ar.off);
+    return ar.ok();
+}
+
+// an entry point's first step: the layout carved over the caller's buffer; false, with the error message set, if it does not fit
+// (the caller returns DVM_ENOSPACE before it launches anything)
+template <typename Ws, typename F, typename... A>
+static inline bool carve_ws(void *ws, size_t ws_bytes, const char *who, Ws &w, F carve, A... a) {
+    Arena ar(ws, ws_bytes);
+    carve(ar, a..., w);
+    return arena_fits(ar, who);
+}
+// the size of a workspace layout: its carve_*(Arena &, sizes..., Ws &) over a null arena — what every *_workspace_bytes returns
+template <typename Ws, typename F, typename... A>
+static inline size_t null_carve(F carve, A... a) {
+    Arena ar(nullptr, 0);
+    Ws w;
+    return carve(ar, a..., w);
+}
 
 // p + n that stays null for a null p: workspace layouts are also carved over a null base to compute their size, and
 // offsetting a null pointer is undefined behaviour (found by the UBSan build, csrc/san/)
@@ -92,8 +114,7 @@ struct GridBuf {
     float *params;
     int P, G;
 };
-size_t grid_bytes(int B, int P);
-// view of shapes [b0, ...) of a batched grid
+// view of shapes [b0, ...) of a batched grid (the grid's launchers: dvm_internal.h)
 static inline GridBuf grid_slice(const GridBuf &g, int b0) {
     GridBuf r = g;
     const int G3 = g.G * g.G * g.G;
@@ -103,15 +124,6 @@ static inline GridBuf grid_slice(const GridBuf &g, int b0) {
     r.params = offset_ptr(g.params, (size_t)b0 * 8);
     return r;
 }
-GridBuf grid_carve(Arena &ar, int B, int P);
-void launch_grid_build(const float *xyz, int B, int Nsrc, const int32_t *sel, const GridBuf &gb, hipStream_t s);
-void launch_grid_build_sets(const float *const *xyz, const int *Nsrc, const GridBuf *gb, int nsets, int B, hipStream_t s);   // up to 4 cloud sets, one launch
-void launch_grid_knn_self(const GridBuf &gb, int B, int k, int32_t *idx, hipStream_t s);
-void launch_grid_ring(const GridBuf &gnodes, int B, int32_t *ring, hipStream_t s);
-void launch_grid_infl(const float *xyz, int B, int N, const GridBuf &gnodes, const GridBuf &gverts, int32_t *infl, float *dists,
-                      double *nnd, hipStream_t s);
-void launch_grid_chamfer(const GridBuf *gq, const GridBuf *gb, float *const *dout, int32_t *const *iout, int ngroups, int B,
-                         hipStream_t s);
 
 // ---------------------------------------------------------------- device helpers
 // Sorted "k best" list in registers: keys ascending, ties keep the earlier (lower-index)
@@ -401,3 +413,5 @@ __device__ __forceinline__ double wave_sum(double v) {
 }
 
 }  // namespace dvm
+
+#include "dvm_internal.h"   // the launchers one .hip file defines and another calls

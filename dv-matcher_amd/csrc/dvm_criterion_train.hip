@@ -25,41 +25,6 @@
 #include "dvm_common.h"
 
 namespace dvm {
-
-// ---- the library's own launchers (dvm_gemm.hip, dvm_geom.hip, dvm_deformer.hip, dvm_graph.hip, dvm_loss_bwd.hip)
-void launch_linear(const float *x, const float *w, int B, int N, int K, int Co, int channel_major, const float *bias, const float *res,
-                   const float *alpha, const float *beta, float slope, float *y, hipStream_t s, const float *xg, int Cg, const float *post_res,
-                   float post_scale);
-void launch_pool_all(const float *feat, const int32_t *idx, int B, int P, int k, const float *cw, const float *cb, float *out, hipStream_t s,
-                     const int32_t *order);
-int launch_dg_warp(const float *xyz, int B, int N, const int32_t *nodes_idx, const int32_t *ring, const int32_t *infl_idx, const float *weights,
-                   const float *def9, float *R, float *T, float *warped, float *arap, int arap_stride, float *sr, hipStream_t s);
-int launch_mean_grouped(const float *const *in, const int *n, float *const *out, const int *off, int ngroups, int B, float scale, int stride,
-                        hipStream_t s);
-int launch_reduce_partials(const double *partial, int B, int nparts, float scale, float *out, int stride, int off, hipStream_t s);
-int map_term_blocks(int N, int k);
-int launch_map_term(const float *verts12, const float *verts2, const int32_t *idx11, const int32_t *idx22, const float *pi_val,
-                    const int32_t *pi_idx, int B, int N, int M, int k, int topk, double *partial, hipStream_t s, float *resid);
-void launch_rev_csr(const int32_t *idx, int B, long E, int M, int32_t *offs, int32_t *cursor, int32_t *edges, hipStream_t s);
-void launch_apply_bwd_dval(const float *pi_val, const int32_t *pi_idx, const float *V, const float *g_out, int B, int N, int M, int topk, int C,
-                           float *d_val, hipStream_t s);
-void launch_apply_bwd_gather(const float *pi_val, const float *g_out, const int32_t *offs, const int32_t *edges, int B, int N, int M, int topk,
-                             int C, float *d_V, hipStream_t s);
-void launch_dg_warp_arap_bwd(const float *xyz, int B, int N, const int32_t *nodes_idx, const int32_t *ring, const int32_t *infl_idx,
-                             const float *weights, const float *R, const float *T, const float *g_warped, const float *g_arap, int garap_stride,
-                             float *d_R, float *d_T, hipStream_t s);
-void launch_def9_bwd(const float *def9, const float *dR, const float *dT, int rows, float *ddef9, hipStream_t s);
-void launch_chamfer_bwd_src2(const float *a0, const float *a1, const float *b0, const float *b1, const int32_t *i1a, const int32_t *i2a,
-                             const int32_t *i1b, const int32_t *i2b, const float *gt, int gstride, int off0, int off1, int B, int N, int M,
-                             float *da0, float *da1, hipStream_t s);
-
- int launch_dist_loss_fwd(const float *feat, const float *dist, const int32_t *anchors, int B, int N, int C, int nA, int k, float *out, int out_stride,
-                         int out_off, int32_t *idx_out, float *xsave, float *fa_out, void *ws, size_t ws_bytes, hipStream_t s);
-void launch_dist_loss_bwd_weights_saved(const float *xsave, const int32_t *idx, const float *gterm, int gstride, int B, int N, int nA, int k, float *W,
-                                        float *rs, hipStream_t s);
-void launch_wgrad_batched(const float *gy, const float *x, int nb, long R, int Co, int K, float *dW, hipStream_t s);
-void launch_linear_bmm(const float *x, const float *w, int B, int N, int K, int Co, float *y, hipStream_t s);
-
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -490,10 +455,7 @@ int crit_fwd(const char *who, const Dims &d, Sides io, const DistIn &di, float n
     Arena ar(arena, arena_bytes);
     CritWs w;
     carve(ar, d, w);
-    if (!ar.ok()) {
-        set_error("%s: arena too small (%zu < %zu)", who, arena_bytes, ar.off);
-        return DVM_ENOSPACE;
-    }
+    if (!arena_fits(ar, who, "arena")) return DVM_ENOSPACE;
     // the dist term of the 2B shapes: independent of the deformation part, on the helper stream of the caller's context (dvm_pair_init)
     PairCtx *cx = d.nA > 0 ? pair_ctx_find(s) : nullptr;
     HelperJoin hj(cx, s);
@@ -564,10 +526,7 @@ int crit_bwd(const char *who, const Dims &d, Sides io, const DistIn &di, const f
     Arena ar(arena, arena_bytes);
     CritWs w;
     carve(ar, d, w);
-    if (!ar.ok()) {
-        set_error("%s: arena too small (%zu < %zu)", who, arena_bytes, ar.off);
-        return DVM_ENOSPACE;
-    }
+    if (!arena_fits(ar, who, "arena")) return DVM_ENOSPACE;
     if (d.swapped) io.feat_t = w.featT, io.verts_t = w.vertsT, io.knn_t = w.idxT;
     const dim3 node_grid((unsigned)(((long)Nn * 32 + 255) / 256), P);
     // the dist term's feature gradient (helper stream): W from the kept x, y, then the two products on the library's GEMM kernels

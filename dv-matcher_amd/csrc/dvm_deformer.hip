@@ -432,10 +432,6 @@ struct DeformerWs {
     char *zp;   // the rows in the plane form (input of the persistent MLP kernel)
 };
 
-size_t mlp_pack_floats();
-void launch_mlp_rows(const float *z, int rows, const float *W0, const float *b0, const float *W1, const float *b1, const float *W2,
-                     const float *b2, const float *W3, const float *b3, float *wp, float *out, hipStream_t s, int variant, void *zp);
-
 static size_t carve(Arena &ar, int B, int M, int Nn, DeformerWs &w) {
     w.g2 = ar.take<float>((size_t)B * M * DF_C);
     w.z = ar.take<float>((size_t)B * Nn * DF_ZS);
@@ -455,13 +451,8 @@ int launch_deformer(const float *feat1, const float *feat2, const float *verts1,
                     int M, int Nn, int k, int topk, const float *conv_w, const float *conv_b, const float *W0,
                     const float *b0, const float *W1, const float *b1, const float *W2, const float *b2, const float *W3,
                     const float *b3, float *out, int variant, void *ws, size_t ws_bytes, hipStream_t s) {
-    Arena ar(ws, ws_bytes);
     DeformerWs w;
-    carve(ar, B, M, Nn, w);
-    if (!ar.ok()) {
-        set_error("dvm_deformer_fwd_f32: workspace too small (%zu < %zu)", ws_bytes, ar.off);
-        return DVM_ENOSPACE;
-    }
+    if (!carve_ws(ws, ws_bytes, "dvm_deformer_fwd_f32", w, carve, B, M, Nn)) return DVM_ENOSPACE;
     const int rows = B * Nn;
     // g2 for every target point; g1 only at the graph nodes (written straight into z[:,3:131])
     hipLaunchKernelGGL(pool_kernel, dim3((unsigned)(((long)M * 32 + 255) / 256), B), dim3(256), 0, s, feat2, idx22,
@@ -540,14 +531,6 @@ void launch_assemble_pooled_pair(const float *verts1, const float *verts2, const
     else hipLaunchKernelGGL(assemble_pooled_kernel<10>, grid, dim3(256), 0, s, a);
     if (!gate) prof_end(s, DVM_PROF_ASSEMBLE);
 }
-size_t mlp_bf16_pack_bytes();
-void launch_mlp_rows_bf16(const float *z, int rows, const float *W0, const float *b0, const float *W1, const float *b1,
-                          const float *W2, const float *b2, const float *W3, const float *b3, void *scratch, float *out,
-                          hipStream_t s, const int *gate);
-size_t mlp_f16_pack_bytes();
-void launch_split_rows(const float *z, int rows, int stride, void *zp, hipStream_t s);
-int *launch_mlp_planes_f16(const void *zp, int rows, const float *W0, const float *b0, const float *W1, const float *b1, const float *W2,
-                           const float *b2, const float *W3, const float *b3, void *scratch, float *out, hipStream_t s);
 // variant 0 on rows that are in the plane form already; returns the range flag for launch_mlp_fallback
 const int *launch_mlp_planes(const void *zp, int rows, const float *W0, const float *b0, const float *W1, const float *b1, const float *W2,
                              const float *b2, const float *W3, const float *b3, float *wp, float *out, hipStream_t s) {
@@ -593,11 +576,7 @@ void launch_mlp_rows(const float *z, int rows, const float *W0, const float *b0,
                        Wp1, b1, Wp2, b2, Wp3, b3, out);
 }
 
-size_t deformer_ws_bytes(int B, int M, int Nn) {
-    Arena ar(nullptr, 0);
-    DeformerWs w;
-    return carve(ar, B, M, Nn, w);
-}
+size_t deformer_ws_bytes(int B, int M, int Nn) { return null_carve<DeformerWs>(carve, B, M, Nn); }
 
 }  // namespace dvm
 
@@ -636,13 +615,8 @@ DVM_EXPORT int dvm_deformer_mlp_fwd_f32(const float *z, int rows, const float *W
                                         float *out, void *ws, size_t ws_bytes, void *stream) {
     DVM_REQUIRE(z && out && rows >= 1, "dvm_deformer_mlp_fwd_f32: bad arguments");
     DVM_REQUIRE(W0 && b0 && W1 && b1 && W2 && b2 && W3 && b3, "dvm_deformer_mlp_fwd_f32: null weight pointer");
-    Arena ar(ws, ws_bytes);
     DeformerWs w;
-    carve(ar, 1, 1, rows, w);
-    if (!ar.ok()) {
-        set_error("dvm_deformer_mlp_fwd_f32: workspace too small (%zu < %zu)", ws_bytes, ar.off);
-        return DVM_ENOSPACE;
-    }
+    if (!carve_ws(ws, ws_bytes, "dvm_deformer_mlp_fwd_f32", w, carve, 1, 1, rows)) return DVM_ENOSPACE;
     hipStream_t s = (hipStream_t)stream;
     long th = (long)rows * DF_ZS;
     hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)((th + 255) / 256)), dim3(256), 0, s, z, rows, DF_IN, DF_ZS, w.z);

@@ -42,8 +42,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr float LOG2E = 1.4426950408889634f;
 
-void launch_rownorm2(const float *x, int rows, int K, float *out, hipStream_t s);   // dvm_softcorr.hip
-
 namespace dtile {
 
 constexpr int D = 128;

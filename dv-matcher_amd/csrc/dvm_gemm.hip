@@ -740,10 +740,15 @@ void launch_wgrad_batched(const float *gy, const float *x, int nb, long R, int C
 }
 }  // namespace dvm
 
+static size_t carve_wgrad(Arena &ar, long chunks, int Co, int K, float *&partial) {   // one [Co][K] tile set per row chunk
+    partial = ar.take<float>((size_t)chunks * Co * K);
+    return ar.off;
+}
+
 DVM_EXPORT size_t dvm_linear_wgrad_workspace_bytes(long R, int Co, int K) {
     if (R < 1 || Co < 1 || K < 1) return 0;
     long rchunk;
-    return align_up((size_t)wgrad_chunks(R, Co, K, rchunk) * Co * K * sizeof(float));
+    return null_carve<float *>(carve_wgrad, wgrad_chunks(R, Co, K, rchunk), Co, K);
 }
 
 // ws == NULL or the deterministic mode off: row chunks combined with fp32 atomics; with a workspace AND dvm_set_deterministic(1):
@@ -757,14 +762,11 @@ DVM_EXPORT int dvm_linear_wgrad_ws_f32(const float *gy, const float *x, long R, 
     DVM_REQUIRE(chunks <= 65535, "dvm_linear_wgrad_f32: too many row chunks");
     hipStream_t s = (hipStream_t)stream;
     if (ws && deterministic()) {
-        const size_t need = (size_t)chunks * Co * K * sizeof(float);
-        if (ws_bytes < need) {
-            set_error("dvm_linear_wgrad_ws_f32: workspace too small (%zu < %zu)", ws_bytes, need);
-            return DVM_ENOSPACE;
-        }
-        hipLaunchKernelGGL(linear_wgrad_kernel<true>, dim3((unsigned)tiles, (unsigned)chunks), dim3(256), 0, s, gy, x, R, Co, K, rchunk, (float *)ws);
+        float *partial;
+        if (!carve_ws(ws, ws_bytes, "dvm_linear_wgrad_ws_f32", partial, carve_wgrad, chunks, Co, K)) return DVM_ENOSPACE;
+        hipLaunchKernelGGL(linear_wgrad_kernel<true>, dim3((unsigned)tiles, (unsigned)chunks), dim3(256), 0, s, gy, x, R, Co, K, rchunk, partial);
         const long n = (long)Co * K;
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float *)ws, (int)chunks, n, dW);
+        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float *)partial, (int)chunks, n, dW);
     } else {
         hipLaunchKernelGGL(linear_wgrad_kernel<false>, dim3((unsigned)tiles, (unsigned)chunks), dim3(256), 0, s, gy, x, R, Co, K, rchunk, dW);
     }

@@ -879,12 +879,6 @@ __global__ void mean_grouped_kernel(const MeanGroups g, float scale, int out_str
 
 using namespace dvm;
 
-namespace dvm {
-size_t argmin_f16_ws_bytes(int B, int N, int M, bool both);
-int launch_argmin_f16(const float *f1, const float *f2, int B, int N, int M, int32_t *T12, float *dmin12, int32_t *T21,
-                      float *dmin21, void *ws, size_t ws_bytes, hipStream_t s);
-}  // namespace dvm
-
 static int argmin_all_columns(const float *f1, const float *f2, int B, int N, int M, int d, int32_t *T, float *dmin, hipStream_t s) {
     size_t lds = (size_t)AM_KT * d * sizeof(float);
     ensure_dyn_lds((const void *)argmin_exact_kernel, 65536);
@@ -929,7 +923,7 @@ DVM_EXPORT int dvm_argmin_pair_f32(const float *f1, const float *f2, int B, int 
 
 DVM_EXPORT size_t dvm_knn_cdist_workspace_bytes(int B, int N, int M, int C) {
     (void)M;
-    return C == 3 ? grid_bytes(B, N) : 256;
+    return C == 3 ? grid_bytes(B, N) : 256;   // (the grid of the self-search; any other case needs none)
 }
 
 DVM_EXPORT int dvm_knn_cdist_f32(const float *x, const float *y, int B, int N, int M, int C, int k, int32_t *idx, void *ws,
@@ -944,10 +938,7 @@ DVM_EXPORT int dvm_knn_cdist_f32(const float *x, const float *y, int B, int N, i
         // a cloud against itself (the hot-path case): exact search on a uniform grid
         Arena ar(ws, ws_bytes);
         GridBuf gb = grid_carve(ar, B, N);
-        if (!ar.ok()) {
-            set_error("dvm_knn_cdist_f32: workspace too small (%zu < %zu)", ws_bytes, ar.off);
-            return DVM_ENOSPACE;
-        }
+        if (!arena_fits(ar, "dvm_knn_cdist_f32")) return DVM_ENOSPACE;
         launch_grid_build(x, B, N, nullptr, gb, s);
         launch_grid_knn_self(gb, B, k, idx, s);
         DVM_CHECK_LAUNCH("knn_cdist(grid)");
@@ -1008,10 +999,18 @@ void launch_apply_bwd_gather(const float *pi_val, const float *g_out, const int3
 }
 }  // namespace dvm
 
-DVM_EXPORT size_t dvm_softcorr_apply_bwd_workspace_bytes(int B, int N, int M, int topk) {
-    return align_up((size_t)B * (M + 1) * sizeof(int32_t)) + align_up((size_t)B * M * sizeof(int32_t)) +
-           align_up((size_t)B * N * topk * sizeof(int32_t));
+// the reversed lists of launch_rev_csr
+struct RevCsrWs {
+    int32_t *offs, *cursor, *edges;
+};
+static size_t carve_rev_csr(Arena &ar, int B, int N, int M, int topk, RevCsrWs &w) {
+    w.offs = ar.take<int32_t>((size_t)B * (M + 1));
+    w.cursor = ar.take<int32_t>((size_t)B * M);
+    w.edges = ar.take<int32_t>((size_t)B * N * topk);
+    return ar.off;
 }
+
+DVM_EXPORT size_t dvm_softcorr_apply_bwd_workspace_bytes(int B, int N, int M, int topk) { return null_carve<RevCsrWs>(carve_rev_csr, B, N, M, topk); }
 
 DVM_EXPORT int dvm_softcorr_apply_bwd_f32(const float *pi_val, const int32_t *pi_idx, const float *V, const float *g_out, int B,
                                           int N, int M, int topk, int C, float *d_val, float *d_V, void *ws, size_t ws_bytes,
@@ -1026,17 +1025,11 @@ DVM_EXPORT int dvm_softcorr_apply_bwd_f32(const float *pi_val, const int32_t *pi
     long threads = (long)N * gp2;
     dim3 grid((unsigned)((threads + 255) / 256), B), block(256);
     if (ws != nullptr) {  // reversed lists + gather: no float atomics
-        Arena ar(ws, ws_bytes);
-        int32_t *offs = ar.take<int32_t>((size_t)B * (M + 1));
-        int32_t *cursor = ar.take<int32_t>((size_t)B * M);
-        int32_t *edges = ar.take<int32_t>((size_t)B * N * topk);
-        if (!ar.ok()) {
-            set_error("dvm_softcorr_apply_bwd_f32: workspace too small (%zu < %zu)", ws_bytes, ar.off);
-            return DVM_ENOSPACE;
-        }
-        launch_rev_csr(pi_idx, B, (long)N * topk, M, offs, cursor, edges, s);
+        RevCsrWs w;
+        if (!carve_ws(ws, ws_bytes, "dvm_softcorr_apply_bwd_f32", w, carve_rev_csr, B, N, M, topk)) return DVM_ENOSPACE;
+        launch_rev_csr(pi_idx, B, (long)N * topk, M, w.offs, w.cursor, w.edges, s);
         launch_apply_bwd_dval(pi_val, pi_idx, V, g_out, B, N, M, topk, C, d_val, s);
-        launch_apply_bwd_gather(pi_val, g_out, offs, edges, B, N, M, topk, C, d_V, s);
+        launch_apply_bwd_gather(pi_val, g_out, w.offs, w.edges, B, N, M, topk, C, d_V, s);
         DVM_CHECK_LAUNCH("softcorr_apply_bwd(gather)");
         return DVM_OK;
     }
@@ -1046,7 +1039,15 @@ DVM_EXPORT int dvm_softcorr_apply_bwd_f32(const float *pi_val, const int32_t *pi
     return DVM_OK;
 }
 
-DVM_EXPORT size_t dvm_chamfer_workspace_bytes(int B, int N, int M) { return grid_bytes(B, N) + grid_bytes(B, M); }
+struct ChamferWs {
+    GridBuf ga, gb;   // the grids of both clouds
+};
+static size_t carve_chamfer(Arena &ar, int B, int N, int M, ChamferWs &w) {
+    w.ga = grid_carve(ar, B, N), w.gb = grid_carve(ar, B, M);
+    return ar.off;
+}
+
+DVM_EXPORT size_t dvm_chamfer_workspace_bytes(int B, int N, int M) { return null_carve<ChamferWs>(carve_chamfer, B, N, M); }
 
 DVM_EXPORT int dvm_chamfer_fwd_f32(const float *a, const float *b, int B, int N, int M, float *d1, float *d2, int32_t *i1,
                                    int32_t *i2, void *ws, size_t ws_bytes, void *stream) {
@@ -1059,12 +1060,9 @@ DVM_EXPORT int dvm_chamfer_fwd_f32(const float *a, const float *b, int B, int N,
     // fraction of that.  Same minima, same tie rule (lowest index).  The grid pays from ~100 k queries on (the pair bench).
     const bool few = (long)B * ((d1 ? N : 0) + (d2 ? M : 0)) <= 65536 && (long)N * M <= (1L << 25);
     if (ws != nullptr && N >= 64 && M >= 64 && !few) {
-        Arena ar(ws, ws_bytes);
-        GridBuf ga = grid_carve(ar, B, N), gb = grid_carve(ar, B, M);
-        if (!ar.ok()) {
-            set_error("dvm_chamfer_fwd_f32: workspace too small (%zu < %zu)", ws_bytes, ar.off);
-            return DVM_ENOSPACE;
-        }
+        ChamferWs w;
+        if (!carve_ws(ws, ws_bytes, "dvm_chamfer_fwd_f32", w, carve_chamfer, B, N, M)) return DVM_ENOSPACE;
+        const GridBuf &ga = w.ga, &gb = w.gb;
         GridBuf qg[2] = {ga, gb}, tg[2] = {gb, ga};
         float *dout[2] = {d1, d2};
         int32_t *iout[2] = {i1, i2};
@@ -1095,8 +1093,13 @@ DVM_EXPORT int dvm_chamfer_fwd_f32(const float *a, const float *b, int B, int N,
     return DVM_OK;
 }
 
+static size_t carve_map_term(Arena &ar, int B, int N, int k, double *&partial) {   // one partial per workgroup
+    partial = ar.take<double>((size_t)B * map_term_blocks(N, k));
+    return ar.off;
+}
+
 DVM_EXPORT size_t dvm_map_term_workspace_bytes(int B, int N) {
-    return align_up((size_t)B * (((size_t)N * 16 + 255) / 256) * sizeof(double));
+    return null_carve<double *>(carve_map_term, B, N, 16);   // (the query does not know k: sized for the largest, 16)
 }
 
 DVM_EXPORT int dvm_map_term_f32(const float *verts12, const float *verts2, const int32_t *idx11, const int32_t *idx22,
@@ -1105,13 +1108,9 @@ DVM_EXPORT int dvm_map_term_f32(const float *verts12, const float *verts2, const
     DVM_REQUIRE(verts12 && verts2 && idx11 && idx22 && pi_val && pi_idx && out, "dvm_map_term_f32: null pointer");
     DVM_REQUIRE(B >= 1 && N >= 1 && M >= 1, "dvm_map_term_f32: empty input");
     DVM_REQUIRE(k >= 1 && k <= 16 && topk >= 1 && topk <= 16, "dvm_map_term_f32: k/topk out of range");
-    int nblk = (int)(((long)N * k + 255) / 256);
-    Arena ar(ws, ws_bytes);
-    double *partial = ar.take<double>((size_t)B * nblk);
-    if (!ar.ok()) {
-        set_error("dvm_map_term_f32: workspace too small (%zu < %zu)", ws_bytes, ar.off);
-        return DVM_ENOSPACE;
-    }
+    const int nblk = map_term_blocks(N, k);
+    double *partial;
+    if (!carve_ws(ws, ws_bytes, "dvm_map_term_f32", partial, carve_map_term, B, N, k)) return DVM_ENOSPACE;
     hipStream_t s = (hipStream_t)stream;
     if (topk <= 10)
         hipLaunchKernelGGL(map_term_kernel<10>, dim3(nblk, B), dim3(256), 0, s, verts12, verts2, idx11, idx22, pi_val, pi_idx,

@@ -544,9 +544,17 @@ DVM_EXPORT int dvm_fps_f32(const float *xyz, int B, int N, int npoint, const int
     return DVM_OK;
 }
 
-DVM_EXPORT size_t dvm_dg_build_workspace_bytes(int B, int N) {
-    return align_up((size_t)B * N * sizeof(double)) + grid_bytes(B, N) + grid_bytes(B, N / 2);
+struct DgBuildWs {
+    double *nnd;
+    GridBuf gv, gn;   // grids of the vertices and of the N / 2 nodes
+};
+static size_t carve_dg_build(Arena &ar, int B, int N, DgBuildWs &w) {
+    w.nnd = ar.take<double>((size_t)B * N);
+    w.gv = grid_carve(ar, B, N), w.gn = grid_carve(ar, B, N / 2);
+    return ar.off;
 }
+
+DVM_EXPORT size_t dvm_dg_build_workspace_bytes(int B, int N) { return null_carve<DgBuildWs>(carve_dg_build, B, N); }
 
 DVM_EXPORT int dvm_dg_build_f32(const float *xyz, int B, int N, const int32_t *start, int32_t *nodes_idx, int32_t *ring,
                                 int32_t *infl_idx, float *dists, float *weights, double *sigma, void *ws, size_t ws_bytes,
@@ -554,14 +562,9 @@ DVM_EXPORT int dvm_dg_build_f32(const float *xyz, int B, int N, const int32_t *s
     DVM_REQUIRE(xyz && start && nodes_idx && ring && infl_idx && dists && weights, "dvm_dg_build_f32: null pointer");
     DVM_REQUIRE(B >= 1 && N >= 2, "dvm_dg_build_f32: bad sizes (B=%d N=%d)", B, N);
     DVM_REQUIRE(N <= DVM_MAX_POINTS, "dvm_dg_build_f32: N=%d exceeds %d", N, DVM_MAX_POINTS);
-    Arena ar(ws, ws_bytes);
-    double *nnd = ar.take<double>((size_t)B * N);
-    GridBuf gv = grid_carve(ar, B, N), gn = grid_carve(ar, B, N / 2);
-    if (!ar.ok()) {
-        set_error("dvm_dg_build_f32: workspace too small (%zu < %zu)", ws_bytes, ar.off);
-        return DVM_ENOSPACE;
-    }
-    launch_dg_build(xyz, B, N, start, nodes_idx, ring, infl_idx, dists, weights, sigma, nnd, gv, gn, true, (hipStream_t)stream, nullptr);
+    DgBuildWs w;
+    if (!carve_ws(ws, ws_bytes, "dvm_dg_build_f32", w, carve_dg_build, B, N)) return DVM_ENOSPACE;
+    launch_dg_build(xyz, B, N, start, nodes_idx, ring, infl_idx, dists, weights, sigma, w.nnd, w.gv, w.gn, true, (hipStream_t)stream);
     DVM_CHECK_LAUNCH("dg_build");
     return DVM_OK;
 }

@@ -844,12 +844,6 @@ __global__ __launch_bounds__(THREADS) void grid_chamfer_kernel(const ChGridArgs 
 }
 
 // ---------------------------------------------------------------- host side
-size_t grid_bytes(int B, int P) {
-    const int G = grid_dim_for(P), G3 = G * G * G;
-    return align_up((size_t)B * P * sizeof(float4)) + align_up((size_t)B * P * sizeof(int32_t)) +
-           align_up((size_t)B * (G3 + 1) * sizeof(int32_t)) + align_up((size_t)B * 8 * sizeof(float));
-}
-
 GridBuf grid_carve(Arena &ar, int B, int P) {
     GridBuf gb;
     gb.P = P;
@@ -860,6 +854,11 @@ GridBuf grid_carve(Arena &ar, int B, int P) {
     gb.start = ar.take<int32_t>((size_t)B * (G3 + 1));
     gb.params = ar.take<float>((size_t)B * 8);
     return gb;
+}
+size_t grid_bytes(int B, int P) {
+    Arena ar(nullptr, 0);
+    grid_carve(ar, B, P);
+    return ar.off;
 }
 
 void launch_grid_build_sets(const float *const *xyz, const int *Nsrc, const GridBuf *gb, int nsets, int B, hipStream_t s) {

@@ -1,0 +1,155 @@
+// dvm_internal.h — every dvm:: function that one translation unit of libdvm_hip.so defines and another one calls, declared
+// ONCE, grouped by the file that defines it; default arguments appear here and nowhere else.  Included at the end of
+// dvm_common.h: no .hip file declares a function it does not define.  (The K1 sweep's launchers, whose signatures need its
+// argument structs, are in dvm_softcorr_f16.h; set_error / prof_* / options and their kin, defined in dvm_api.cpp, in dvm_common.h.)
+#pragma once
+
+namespace dvm {
+
+// ---- dvm_backbone.hip
+// W [B][nA][N] (zeroed here) and its row sums from the forward's xsave; gterm read at gterm[b * gstride]
+int launch_dist_loss_fwd(const float *feat, const float *dist, const int32_t *anchors, int B, int N, int C, int nA, int k, float *out, int out_stride,
+                         int out_off, int32_t *idx_out, float *xsave, float *fa_out, void *ws, size_t ws_bytes, hipStream_t s);
+void launch_dist_loss_bwd_weights_saved(const float *xsave, const int32_t *idx, const float *gterm, int gstride, int B, int N, int nA, int k, float
+                                        *W, float *rs, hipStream_t s);
+
+// ---- dvm_bn.hip
+int launch_bn_running_update(float *const *rm, float *const *rv, const float *const *mean, const float *const *var, const int *C, int count, float
+                             momentum, hipStream_t s);
+
+// ---- dvm_deformer.hip
+void launch_pool_all(const float *feat, const int32_t *idx, int B, int P, int k, const float *cw, const float *cb, float *out, hipStream_t s, const
+                     int32_t *order = nullptr);
+size_t mlp_pack_floats();
+// z [rows][264] -> out [rows][9]; wp = scratch of mlp_pack_floats() floats; variant as dvm_deformer_fwd_f32
+void launch_mlp_rows(const float *z, int rows, const float *W0, const float *b0, const float *W1, const float *b1, const float *W2, const float *b2,
+                     const float *W3, const float *b3, float *wp, float *out, hipStream_t s, int variant, void *zp);
+int launch_deformer(const float *feat1, const float *feat2, const float *verts1, const float *verts12, const int32_t *idx11, const int32_t *idx22,
+                    const float *pi_val, const int32_t *pi_idx, const int32_t *fps1, int B, int N, int M, int Nn, int k, int topk, const float
+                    *conv_w, const float *conv_b, const float *W0, const float *b0, const float *W1, const float *b1, const float *W2, const float
+                    *b2, const float *W3, const float *b3, float *out, int variant, void *ws, size_t ws_bytes, hipStream_t s);
+size_t deformer_ws_bytes(int B, int M, int Nn);
+void launch_assemble_pooled(const float *vsrc, const float *vcorr, const float *gsrc, const float *gtgt, const float *pi_val, const int32_t *pi_idx,
+                            const int32_t *fps, int B, int N, int M, int Nn, float *z, hipStream_t s, const int *gate = nullptr);
+void launch_assemble_pooled_planes(const float *vsrc, const float *vcorr, const float *gsrc, const float *gtgt, const float *pi_val, const int32_t
+                                   *pi_idx, const int32_t *fps, int B, int N, int M, int Nn, void *zp, hipStream_t s);
+// both directions of the pair path in one launch; planes: the plane form (z*), else the fp32 rows behind `gate`
+void launch_assemble_pooled_pair(const float *verts1, const float *verts2, const float *verts12, const float *verts21, const float *g1, const float
+                                 *g2, const float *val12, const int32_t *idx12, const float *val21, const int32_t *idx21, const int32_t *nodes1, const
+                                 int32_t *nodes2, int B, int N, int M, void *z12, void *z21, bool planes, const int *gate, hipStream_t s);
+// variant 0 on rows that are in the plane form already; returns the range flag for launch_mlp_fallback
+const int *launch_mlp_planes(const void *zp, int rows, const float *W0, const float *b0, const float *W1, const float *b1, const float *W2, const
+                             float *b2, const float *W3, const float *b3, float *wp, float *out, hipStream_t s);
+// the bf16x3 kernel on the fp32 rows, gated on the flag
+void launch_mlp_fallback(const float *z, int rows, const float *W0, const float *b0, const float *W1, const float *b1, const float *W2, const float
+                         *b2, const float *W3, const float *b3, float *wp, float *out, hipStream_t s, const int *flag);
+
+// ---- dvm_gemm.hip
+void launch_linear(const float *x, const float *w, int B, int N, int K, int Co, int channel_major, const float *bias, const float *res, const float
+                   *alpha, const float *beta, float slope, float *y, hipStream_t s, const float *xg, int Cg, const float *post_res, float post_scale);
+// dW[b] [Co][K] += gy[b]^T x[b] for nb products of one shape, operands and results back to back (dW zeroed by the caller)
+void launch_wgrad_batched(const float *gy, const float *x, int nb, long R, int Co, int K, float *dW, hipStream_t s);
+void launch_linear_bmm(const float *x, const float *w, int B, int N, int K, int Co, float *y, hipStream_t s);
+
+// ---- dvm_geom.hip
+int launch_reduce_partials(const double *partial, int B, int nparts, float scale, float *out, int stride, int off, hipStream_t s);
+int launch_mean_grouped(const float *const *in, const int *n, float *const *out, const int *off, int ngroups, int B, float scale, int stride,
+                        hipStream_t s);
+int map_term_blocks(int N, int k);
+int launch_map_term(const float *verts12, const float *verts2, const int32_t *idx11, const int32_t *idx22, const float *pi_val, const int32_t *pi_idx,
+                    int B, int N, int M, int k, int topk, double *partial, hipStream_t s, float *resid = nullptr);
+// idx [B][E] (entries with a target in [0, M)) -> offs [B][M+1], edges [B][E] (entry numbers grouped by target); cursor [B][M] scratch
+void launch_rev_csr(const int32_t *idx, int B, long E, int M, int32_t *offs, int32_t *cursor, int32_t *edges, hipStream_t s);
+void launch_apply_bwd_dval(const float *pi_val, const int32_t *pi_idx, const float *V, const float *g_out, int B, int N, int M, int topk, int C, float
+                           *d_val, hipStream_t s);
+void launch_apply_bwd_gather(const float *pi_val, const float *g_out, const int32_t *offs, const int32_t *edges, int B, int N, int M, int topk, int C,
+                             float *d_V, hipStream_t s);
+int launch_mean(const float *in, int B, int n, float scale, float *out, int stride, int off, int accumulate, hipStream_t s);
+void launch_gather_nbr_xyz(const float *verts, const int32_t *idx, int B, int M, int k, float *nbr, hipStream_t s);
+int launch_map_term_nbr(const float *verts12, const float *nbr2, const int32_t *idx11, const float *pi_val, const int32_t *pi_idx, int B, int N, int
+                        M, int k, int topk, double *partial, hipStream_t s);
+// -> true if the LDS form ran (topk == 10, the target side fits 150 KB of LDS); else the caller uses one of the older forms
+bool launch_map_term_lds(const float *verts12, const float *verts2, const int32_t *idx11, const int32_t *idx22, const float *pi_val, const int32_t
+                         *pi_idx, int B, int N, int M, int k, int topk, double *partial, hipStream_t s);
+bool map_term_lds_applies(int N, int M, int k);
+bool launch_map_term_lds_pair(const float *verts12, const float *verts21, const float *verts1, const float *verts2, const int32_t *idx11, const
+                              int32_t *idx22, const float *val12, const int32_t *pidx12, const float *val21, const int32_t *pidx21, int B, int N, int
+                              M, int k, int topk, double *partial12, double *partial21, hipStream_t s);
+// -> false if a target cloud does not fit LDS (the caller then uses apply_kernel + take_col0)
+bool launch_apply3_pair(const float *val12, const int32_t *idx12, const float *verts2, float *verts12, int32_t *T12, const float *val21, const int32_t
+                        *idx21, const float *verts1, float *verts21, int32_t *T21, int B, int N, int M, hipStream_t s);
+int launch_chamfer_grouped(const float *const *a, const float *const *b, const int *Na, const int *Nb, float *const *dout, int ngroups, int B,
+                           hipStream_t s);
+
+// ---- dvm_graph.hip
+int launch_dg_warp(const float *xyz, int B, int N, const int32_t *nodes_idx, const int32_t *ring, const int32_t *infl_idx, const float *weights, const
+                   float *def9, float *R, float *T, float *warped, float *arap, int arap_stride, float *sr, hipStream_t s);
+int launch_dg_build(const float *xyz, int B, int N, const int32_t *start, int32_t *nodes_idx, int32_t *ring, int32_t *infl_idx, float *dists, float
+                    *weights, double *sigma, double *nnd, const GridBuf &gverts, const GridBuf &gnodes, bool build_gverts, hipStream_t s, hipEvent_t
+                    gverts_ready = nullptr);
+bool launch_dg_warp_pair(const float *xyz1, const float *xyz2, int B, int N, int M, const int32_t *const nodes[2], const int32_t *const ring[2], const
+                         int32_t *const infl[2], const float *const weights[2], const float *def9_12, const float *def9_21, float *R12, float *R21,
+                         float *T12, float *T21, float *warped12, float *warped21, float *arap12, float *arap21, int arap_stride, hipStream_t s);
+
+// ---- dvm_grid.hip: uniform-grid neighbour search over GridBuf (dvm_common.h)
+size_t grid_bytes(int B, int P);
+GridBuf grid_carve(Arena &ar, int B, int P);
+void launch_grid_build(const float *xyz, int B, int Nsrc, const int32_t *sel, const GridBuf &gb, hipStream_t s);
+void launch_grid_build_sets(const float *const *xyz, const int *Nsrc, const GridBuf *gb, int nsets, int B, hipStream_t s);   // up to 4 cloud sets, one launch
+void launch_grid_knn_self(const GridBuf &gb, int B, int k, int32_t *idx, hipStream_t s);
+void launch_grid_ring(const GridBuf &gnodes, int B, int32_t *ring, hipStream_t s);
+void launch_grid_infl(const float *xyz, int B, int N, const GridBuf &gnodes, const GridBuf &gverts, int32_t *infl, float *dists, double *nnd,
+                      hipStream_t s);
+void launch_grid_chamfer(const GridBuf *gq, const GridBuf *gb, float *const *dout, int32_t *const *iout, int ngroups, int B, hipStream_t s);
+
+// ---- dvm_loss_bwd.hip
+void launch_dg_warp_arap_bwd(const float *xyz, int B, int N, const int32_t *nodes_idx, const int32_t *ring, const int32_t *infl_idx, const float
+                             *weights, const float *R, const float *T, const float *g_warped, const float *g_arap, int garap_stride, float *d_R, float
+                             *d_T, hipStream_t s);
+void launch_def9_bwd(const float *def9, const float *dR, const float *dT, int rows, float *ddef9, hipStream_t s);
+void launch_chamfer_bwd_src2(const float *a0, const float *a1, const float *b0, const float *b1, const int32_t *i1a, const int32_t *i2a, const int32_t
+                             *i1b, const int32_t *i2b, const float *gt, int gstride, int off0, int off1, int B, int N, int M, float *da0, float *da1,
+                             hipStream_t s);
+
+// ---- dvm_mlp_bf16.hip
+size_t mlp_bf16_pack_bytes();
+void launch_mlp_rows_bf16(const float *z, int rows, const float *W0, const float *b0, const float *W1, const float *b1, const float *W2, const float
+                          *b2, const float *W3, const float *b3, void *scratch, float *out, hipStream_t s, const int *gate);
+
+// ---- dvm_mlp_f16.hip
+size_t mlp_f16_pack_bytes();
+void launch_split_rows(const float *z, int rows, int stride, void *zp, hipStream_t s);
+int *launch_mlp_planes_f16(const void *zp, int rows, const float *W0, const float *b0, const float *W1, const float *b1, const float *W2, const float
+                           *b2, const float *W3, const float *b3, void *scratch, float *out, hipStream_t s);
+size_t mlp_zplane_bytes(int rows);   // bytes of the plane form of `rows` z rows (padded to whole 64-row blocks)
+size_t mlp_zplane_row_bytes();   // MH_SZ
+
+// ---- dvm_sa_f16.hip: fp16x2-split kernels of the SA attention core
+size_t sa_f16_carve(Arena &ar, int B, int N, _Float16 *&pp, _Float16 *&vp);   // the split planes of p and v, carved from the caller's arena
+void launch_sa_split_f16(const float *p, const float *v, int B, int N, _Float16 *pp, _Float16 *vp, hipStream_t s);
+void launch_sa_rowstats_f16(const _Float16 *pp, int B, int N, int kchunk, int Z, float *stats, hipStream_t s);
+void launch_sa_apply_f16(const _Float16 *pp, const _Float16 *vp, const float *stats, int B, int N, int kchunk, int Z, float *xr, float *cinv,
+                         hipStream_t s);
+
+// ---- dvm_softcorr.hip
+void launch_rownorm2(const float *x, int rows, int K, float *out, hipStream_t s);
+int launch_softcorr_both(const float *f1, const float *f2, const float *n1, const float *n2, int B, int N, int M, float neg_alpha, float *val12,
+                         int32_t *idx12, float *val21, int32_t *idx21, hipStream_t s);
+size_t softcorr_pair_ws_bytes(int B, int N, int M);
+int launch_softcorr_pair(const float *f1, const float *f2, float *n1, float *n2, int B, int N, int M, float neg_alpha, float *val12, int32_t *idx12,
+                         float *val21, int32_t *idx21, void *ws, size_t ws_bytes, hipStream_t s);
+// K == 128 only: also maxes the bit pattern of max |x| into the 256 slots of `absmax_slots` (zero them first);
+// launch_absmax_finalize folds nt x 256 slots into nt values
+void launch_rownorm2_absmax(const float *x, int rows, float *out, int *absmax_slots, hipStream_t s);
+void launch_absmax_finalize(const int *slots, int nt, int *out, hipStream_t s);
+
+// ---- dvm_softcorr_f16.hip
+size_t argmin_f16_ws_bytes(int B, int N, int M, bool both);
+int launch_argmin_f16(const float *f1, const float *f2, int B, int N, int M, int32_t *T12, float *dmin12, int32_t *T21, float *dmin21, void *ws,
+                      size_t ws_bytes, hipStream_t s);
+size_t softcorr_f16_ws_bytes(int B, int N, int M, bool both);
+int launch_softcorr_f16(const float *f1, const float *f2, const float *n1, const float *n2, int B, int N, int M, float neg_alpha, int topk, float
+                        *val12, int32_t *idx12, float *smax12, float *sum12, float *val21, int32_t *idx21, float *smax21, float *sum21, const int
+                        *amax, void *ws, size_t ws_bytes, hipStream_t s, int *fuse_slots = nullptr);
+
+}  // namespace dvm

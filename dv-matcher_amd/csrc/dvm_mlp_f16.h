@@ -28,7 +28,4 @@ __device__ __forceinline__ void split2x2(float a0, float a1, unsigned &h, unsign
     asm("v_fma_mixhi_f16 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(m) : "v"(a1), "v"(h));
 }
 
-size_t mlp_zplane_bytes(int rows);   // bytes of the plane form of `rows` z rows (padded to whole 64-row blocks)
-size_t mlp_zplane_row_bytes();       // MH_SZ
-
 }  // namespace dvm

@@ -393,11 +393,21 @@ DVM_EXPORT int dvm_n2p_core_fwd_f32(const float *qkv, const int32_t *idx, int B,
     return DVM_OK;
 }
 
-DVM_EXPORT size_t dvm_n2p_core_bwd_workspace_bytes(int B, int N, int K) {
-    return align_up((size_t)B * N * K * NP_H * sizeof(float)) + align_up((size_t)B * (N + 1) * sizeof(int32_t)) +
-           align_up((size_t)B * N * sizeof(int32_t)) + align_up((size_t)B * N * K * sizeof(int2)) +
-           align_up((size_t)B * DET_CHUNKS * N * sizeof(int32_t));   // (last: per-chunk histograms of the deterministic list build)
+struct N2pBwdWs {
+    float *de;
+    int32_t *offs, *cursor, *hist;   // hist: per-chunk histograms of the deterministic list build
+    int2 *edges;
+};
+static size_t carve_n2p_bwd(Arena &ar, int B, int N, int K, N2pBwdWs &w) {
+    w.de = ar.take<float>((size_t)B * N * K * NP_H);
+    w.offs = ar.take<int32_t>((size_t)B * (N + 1));
+    w.cursor = ar.take<int32_t>((size_t)B * N);
+    w.edges = ar.take<int2>((size_t)B * N * K);
+    w.hist = ar.take<int32_t>((size_t)B * DET_CHUNKS * N);
+    return ar.off;
 }
+
+DVM_EXPORT size_t dvm_n2p_core_bwd_workspace_bytes(int B, int N, int K) { return null_carve<N2pBwdWs>(carve_n2p_bwd, B, N, K); }
 
 DVM_EXPORT int dvm_n2p_core_bwd_f32(const float *qkv, const int32_t *idx, const float *attn, const float *g_out, int B, int N, int C,
                                     int K, int heads, float *d_qkv, void *ws, size_t ws_bytes, void *stream) {
@@ -406,16 +416,11 @@ DVM_EXPORT int dvm_n2p_core_bwd_f32(const float *qkv, const int32_t *idx, const 
     DVM_REQUIRE((C == 64 || C == 128) && heads == NP_H, "dvm_n2p_core_bwd_f32: need C in {64,128}, heads == 4 (C=%d heads=%d)", C,
                 heads);
     DVM_REQUIRE(K >= 1 && K <= NP_KMAX, "dvm_n2p_core_bwd_f32: K=%d unsupported (1..64)", K);
-    Arena ar(ws, ws_bytes);
-    float *de = ar.take<float>((size_t)B * N * K * NP_H);
-    int32_t *offs = ar.take<int32_t>((size_t)B * (N + 1));
-    int32_t *cursor = ar.take<int32_t>((size_t)B * N);
-    int2 *edges = ar.take<int2>((size_t)B * N * K);
-    int32_t *hist = ar.take<int32_t>((size_t)B * DET_CHUNKS * N);
-    if (!ar.ok()) {
-        set_error("dvm_n2p_core_bwd_f32: workspace too small (%zu < %zu)", ws_bytes, ar.off);
-        return DVM_ENOSPACE;
-    }
+    N2pBwdWs w;
+    if (!carve_ws(ws, ws_bytes, "dvm_n2p_core_bwd_f32", w, carve_n2p_bwd, B, N, K)) return DVM_ENOSPACE;
+    float *const de = w.de;
+    int32_t *const offs = w.offs, *const cursor = w.cursor, *const hist = w.hist;
+    int2 *const edges = w.edges;
     hipStream_t s = (hipStream_t)stream;
     dim3 grid((N + 3) / 4, B), egrid((unsigned)(((long)N * K + 255) / 256), B);
     const size_t csr_lds = (size_t)(2 * N + 1) * sizeof(int);

@@ -6,42 +6,6 @@
 #include "dvm_common.h"
 
 namespace dvm {
-// dvm_softcorr.hip / dvm_geom.hip / dvm_graph.hip / dvm_deformer.hip
-int launch_mean(const float *in, int B, int n, float scale, float *out, int stride, int off, int accumulate, hipStream_t s);
-int launch_mean_grouped(const float *const *in, const int *n, float *const *out, const int *off, int ngroups, int B, float scale,
-                        int stride, hipStream_t s);
-int launch_reduce_partials(const double *partial, int B, int nparts, float scale, float *out, int stride, int off, hipStream_t s);
-int map_term_blocks(int N, int k);
-void launch_gather_nbr_xyz(const float *verts, const int32_t *idx, int B, int M, int k, float *nbr, hipStream_t s);
-int launch_map_term_nbr(const float *verts12, const float *nbr2, const int32_t *idx11, const float *pi_val, const int32_t *pi_idx,
-                        int B, int N, int M, int k, int topk, double *partial, hipStream_t s);
-int launch_map_term(const float *verts12, const float *verts2, const int32_t *idx11, const int32_t *idx22, const float *pi_val,
-                    const int32_t *pi_idx, int B, int N, int M, int k, int topk, double *partial, hipStream_t s, float *resid = nullptr);
-bool launch_map_term_lds(const float *verts12, const float *verts2, const int32_t *idx11, const int32_t *idx22, const float *pi_val,
-                         const int32_t *pi_idx, int B, int N, int M, int k, int topk, double *partial, hipStream_t s);
-bool map_term_lds_applies(int N, int M, int k);
-bool launch_map_term_lds_pair(const float *verts12, const float *verts21, const float *verts1, const float *verts2, const int32_t *idx11,
-                              const int32_t *idx22, const float *val12, const int32_t *pidx12, const float *val21, const int32_t *pidx21, int B,
-                              int N, int M, int k, int topk, double *partial12, double *partial21, hipStream_t s);
-bool launch_apply3_pair(const float *val12, const int32_t *idx12, const float *verts2, float *verts12, int32_t *T12, const float *val21,
-                        const int32_t *idx21, const float *verts1, float *verts21, int32_t *T21, int B, int N, int M, hipStream_t s);
-int launch_dg_build(const float *xyz, int B, int N, const int32_t *start, int32_t *nodes_idx, int32_t *ring, int32_t *infl_idx,
-                    float *dists, float *weights, double *sigma, double *nnd, const GridBuf &gverts, const GridBuf &gnodes,
-                    bool build_gverts, hipStream_t s, hipEvent_t gverts_ready = nullptr);
-int launch_dg_warp(const float *xyz, int B, int N, const int32_t *nodes_idx, const int32_t *ring, const int32_t *infl_idx,
-                   const float *weights, const float *def9, float *R, float *T, float *warped, float *arap, int arap_stride,
-                   float *sr, hipStream_t s);
-bool launch_dg_warp_pair(const float *xyz1, const float *xyz2, int B, int N, int M, const int32_t *const nodes[2], const int32_t *const ring[2],
-                         const int32_t *const infl[2], const float *const weights[2], const float *def9_12, const float *def9_21, float *R12,
-                         float *R21, float *T12, float *T21, float *warped12, float *warped21, float *arap12, float *arap21, int arap_stride,
-                         hipStream_t s);
-int launch_deformer(const float *feat1, const float *feat2, const float *verts1, const float *verts12, const int32_t *idx11,
-                    const int32_t *idx22, const float *pi_val, const int32_t *pi_idx, const int32_t *fps1, int B, int N, int M,
-                    int Nn, int k, int topk, const float *conv_w, const float *conv_b, const float *W0, const float *b0,
-                    const float *W1, const float *b1, const float *W2, const float *b2, const float *W3, const float *b3,
-                    float *out, int variant, void *ws, size_t ws_bytes, hipStream_t s);
-size_t deformer_ws_bytes(int B, int M, int Nn);
-
 __global__ void take_col0_kernel(const int32_t *__restrict__ in, int rows, int stride, int32_t *__restrict__ out) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < rows) out[i] = in[(size_t)i * stride];
@@ -101,11 +65,7 @@ static size_t carve_pair(Arena &ar, int B, int N, int M, PairWs &w) {
 
 using namespace dvm;
 
-DVM_EXPORT size_t dvm_pair_direction_workspace_bytes(int B, int N, int M) {
-    Arena ar(nullptr, 0);
-    PairWs w;
-    return carve_pair(ar, B, N, M, w);
-}
+DVM_EXPORT size_t dvm_pair_direction_workspace_bytes(int B, int N, int M) { return null_carve<PairWs>(carve_pair, B, N, M); }
 
 DVM_EXPORT int dvm_pair_direction_fwd_f32(const float *feat1, const float *feat2, const float *verts1, const float *verts2,
                                           int B, int N, int M, float neg_alpha, const int32_t *fps_start, const float *conv_w,
@@ -119,13 +79,8 @@ DVM_EXPORT int dvm_pair_direction_fwd_f32(const float *feat1, const float *feat2
                 "dvm_pair_direction_fwd_f32: null weight pointer");
     DVM_REQUIRE(B >= 1 && N >= 20 && M >= 10, "dvm_pair_direction_fwd_f32: bad sizes (B=%d N=%d M=%d)", B, N, M);
     DVM_REQUIRE(neg_alpha < 0.f, "dvm_pair_direction_fwd_f32: neg_alpha must be negative");
-    Arena ar(ws, ws_bytes);
     PairWs w;
-    carve_pair(ar, B, N, M, w);
-    if (!ar.ok()) {
-        set_error("dvm_pair_direction_fwd_f32: workspace too small (%zu < %zu)", ws_bytes, ar.off);
-        return DVM_ENOSPACE;
-    }
+    if (!carve_ws(ws, ws_bytes, "dvm_pair_direction_fwd_f32", w, carve_pair, B, N, M)) return DVM_ENOSPACE;
     hipStream_t s = (hipStream_t)stream;
     const int Nn = N / 2, k = 10, topk = 10;
     int rc;
@@ -181,34 +136,6 @@ DVM_EXPORT int dvm_pair_direction_fwd_f32(const float *feat1, const float *feat2
 // one Deformer-MLP launch over all nodes of both directions, warps, 4 Chamfer terms in one grouped
 // launch, map terms.  When N == M the per-cloud stages run as single launches over 2B shapes.
 namespace dvm {
-int launch_softcorr_both(const float *f1, const float *f2, const float *n1, const float *n2, int B, int N, int M,
-                         float neg_alpha, float *val12, int32_t *idx12, float *val21, int32_t *idx21, hipStream_t s);
-void launch_rownorm2(const float *x, int rows, int K, float *out, hipStream_t s);
-size_t softcorr_pair_ws_bytes(int B, int N, int M);
-int launch_softcorr_pair(const float *f1, const float *f2, float *n1, float *n2, int B, int N, int M, float neg_alpha, float *val12,
-                         int32_t *idx12, float *val21, int32_t *idx21, void *ws, size_t ws_bytes, hipStream_t s);
-void launch_pool_all(const float *feat, const int32_t *idx, int B, int P, int k, const float *cw, const float *cb, float *out,
-                     hipStream_t s, const int32_t *order = nullptr);
-void launch_assemble_pooled(const float *vsrc, const float *vcorr, const float *gsrc, const float *gtgt, const float *pi_val,
-                            const int32_t *pi_idx, const int32_t *fps, int B, int N, int M, int Nn, float *z, hipStream_t s, const int *gate = nullptr);
-void launch_assemble_pooled_planes(const float *vsrc, const float *vcorr, const float *gsrc, const float *gtgt, const float *pi_val,
-                                   const int32_t *pi_idx, const int32_t *fps, int B, int N, int M, int Nn, void *zp, hipStream_t s);
-void launch_assemble_pooled_pair(const float *verts1, const float *verts2, const float *verts12, const float *verts21, const float *g1,
-                                 const float *g2, const float *val12, const int32_t *idx12, const float *val21, const int32_t *idx21,
-                                 const int32_t *nodes1, const int32_t *nodes2, int B, int N, int M, void *z12, void *z21, bool planes,
-                                 const int *gate, hipStream_t s);
-size_t mlp_pack_floats();
-size_t mlp_zplane_bytes(int rows);
-size_t mlp_zplane_row_bytes();
-void launch_mlp_rows(const float *z, int rows, const float *W0, const float *b0, const float *W1, const float *b1, const float *W2,
-                     const float *b2, const float *W3, const float *b3, float *wp, float *out, hipStream_t s, int variant, void *zp);
-const int *launch_mlp_planes(const void *zp, int rows, const float *W0, const float *b0, const float *W1, const float *b1, const float *W2,
-                             const float *b2, const float *W3, const float *b3, float *wp, float *out, hipStream_t s);
-void launch_mlp_fallback(const float *z, int rows, const float *W0, const float *b0, const float *W1, const float *b1, const float *W2,
-                         const float *b2, const float *W3, const float *b3, float *wp, float *out, hipStream_t s, const int *flag);
-int launch_chamfer_grouped(const float *const *a, const float *const *b, const int *Na, const int *Nb, float *const *dout,
-                           int ngroups, int B, hipStream_t s);
-
 struct Pair2Ws {
     float *vcat;                                  // [2B][N][3] when N == M
     int32_t *startcat;                            // [2B]
@@ -281,11 +208,7 @@ static bool contiguous_sides(int B, int N) {
 }
 }  // namespace dvm
 
-DVM_EXPORT size_t dvm_pair_workspace_bytes(int B, int N, int M) {
-    Arena ar(nullptr, 0);
-    Pair2Ws w;
-    return carve_pair2(ar, B, N, M, w);
-}
+DVM_EXPORT size_t dvm_pair_workspace_bytes(int B, int N, int M) { return null_carve<Pair2Ws>(carve_pair2, B, N, M); }
 
 // 1 (default): the geometry chain runs on a helper stream next to the soft-correspondence chain; 0: one stream
 static int g_pair_overlap = options().pair_overlap;
@@ -379,13 +302,8 @@ static int pair_fwd_impl(const float *feat1, const float *feat2, const float *ve
     DVM_REQUIRE(conv_w && conv_b && W0 && b0 && W1 && b1 && W2 && b2 && W3 && b3, "dvm_pair_fwd_f32: null weight pointer");
     DVM_REQUIRE(B >= 1 && N >= 20 && M >= 20, "dvm_pair_fwd_f32: bad sizes (B=%d N=%d M=%d)", B, N, M);
     DVM_REQUIRE(neg_alpha < 0.f, "dvm_pair_fwd_f32: neg_alpha must be negative");
-    Arena ar(ws, ws_bytes);
     Pair2Ws w;
-    carve_pair2(ar, B, N, M, w);
-    if (!ar.ok()) {
-        set_error("dvm_pair_fwd_f32: workspace too small (%zu < %zu)", ws_bytes, ar.off);
-        return DVM_ENOSPACE;
-    }
+    if (!carve_ws(ws, ws_bytes, "dvm_pair_fwd_f32", w, carve_pair2, B, N, M)) return DVM_ENOSPACE;
     hipStream_t s = (hipStream_t)stream;
     int rc;
     const bool both = (N == M) && contiguous_sides(B, N);
@@ -550,13 +468,8 @@ DVM_EXPORT int dvm_pair_geometry_f32(const float *verts1, const float *verts2, i
                                      const int32_t *start2, int with_map, void *ws, size_t ws_bytes, void *stream) {
     DVM_REQUIRE(verts1 && verts2 && start1 && start2, "dvm_pair_geometry_f32: null input pointer");
     DVM_REQUIRE(B >= 1 && N >= 20 && M >= 20, "dvm_pair_geometry_f32: bad sizes (B=%d N=%d M=%d)", B, N, M);
-    Arena ar(ws, ws_bytes);
     Pair2Ws w;
-    carve_pair2(ar, B, N, M, w);
-    if (!ar.ok()) {
-        set_error("dvm_pair_geometry_f32: workspace too small (%zu < %zu)", ws_bytes, ar.off);
-        return DVM_ENOSPACE;
-    }
+    if (!carve_ws(ws, ws_bytes, "dvm_pair_geometry_f32", w, carve_pair2, B, N, M)) return DVM_ENOSPACE;
     hipStream_t s = (hipStream_t)stream;
     PairCtx *cx = g_pair_overlap != 0 ? pair_ctx_find(s) : nullptr;
     const bool both = (N == M) && contiguous_sides(B, N);

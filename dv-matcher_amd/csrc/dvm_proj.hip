@@ -249,23 +249,27 @@ __global__ __launch_bounds__(256) void i2p_kernel(const float *__restrict__ pts,
 
 using namespace dvm;
 
-DVM_EXPORT size_t dvm_proj2img_workspace_bytes(int B) {
-    return align_up((size_t)B * IMG * IMG * sizeof(unsigned long long)) + align_up((size_t)B * 8 * sizeof(float)) +
-           align_up((size_t)B * 2 * sizeof(float));
+struct ProjWs {
+    unsigned long long *acc;
+    float *params, *mm;
+};
+static size_t carve_proj(Arena &ar, int B, ProjWs &w) {
+    w.acc = ar.take<unsigned long long>((size_t)B * IMG * IMG);
+    w.params = ar.take<float>((size_t)B * 8);
+    w.mm = ar.take<float>((size_t)B * 2);
+    return ar.off;
 }
+
+DVM_EXPORT size_t dvm_proj2img_workspace_bytes(int B) { return null_carve<ProjWs>(carve_proj, B); }
 
 DVM_EXPORT int dvm_proj2img_f32(const float *pts, int B, int N, float *img, float *pc_min, float *grid_size, float *offsets,
                                 void *ws, size_t ws_bytes, void *stream) {
     DVM_REQUIRE(pts && img && pc_min && grid_size && offsets, "dvm_proj2img_f32: null pointer");
     DVM_REQUIRE(B >= 1 && N >= 1, "dvm_proj2img_f32: empty input (B=%d N=%d)", B, N);
-    Arena ar(ws, ws_bytes);
-    unsigned long long *acc = ar.take<unsigned long long>((size_t)B * IMG * IMG);
-    float *params = ar.take<float>((size_t)B * 8);
-    float *mm = ar.take<float>((size_t)B * 2);
-    if (!ar.ok()) {
-        set_error("dvm_proj2img_f32: workspace too small (%zu < %zu)", ws_bytes, ar.off);
-        return DVM_ENOSPACE;
-    }
+    ProjWs w;
+    if (!carve_ws(ws, ws_bytes, "dvm_proj2img_f32", w, carve_proj, B)) return DVM_ENOSPACE;
+    unsigned long long *const acc = w.acc;
+    float *const params = w.params, *const mm = w.mm;
     hipStream_t s = (hipStream_t)stream;
     (void)hipMemsetAsync(acc, 0, (size_t)B * IMG * IMG * sizeof(unsigned long long), s);
     hipLaunchKernelGGL(proj_range_kernel, dim3(B), dim3(256), 0, s, pts, N, pc_min, grid_size, offsets, params);

@@ -257,20 +257,25 @@ __global__ __launch_bounds__(256) void sa_bwd_dp_kernel(const SaBwdArgs a) {
 
 using namespace dvm;
 
-DVM_EXPORT size_t dvm_sa_attention_bwd_workspace_bytes(int B, int N) { return 2 * align_up((size_t)B * N * sizeof(float)); }
+struct SaBwdWs {
+    float *t, *u;
+};
+static size_t carve_sa_bwd(Arena &ar, int B, int N, SaBwdWs &w) {
+    w.t = ar.take<float>((size_t)B * N);
+    w.u = ar.take<float>((size_t)B * N);
+    return ar.off;
+}
+
+DVM_EXPORT size_t dvm_sa_attention_bwd_workspace_bytes(int B, int N) { return null_carve<SaBwdWs>(carve_sa_bwd, B, N); }
 
 DVM_EXPORT int dvm_sa_attention_bwd_f32(const float *p, const float *v, const float *xr, const float *stats, const float *cinv,
                                         const float *g_xr, int B, int N, float *d_p, float *d_v, void *ws, size_t ws_bytes,
                                         void *stream) {
     DVM_REQUIRE(p && v && xr && stats && cinv && g_xr && d_p && d_v, "dvm_sa_attention_bwd_f32: null pointer");
     DVM_REQUIRE(B >= 1 && N >= 1, "dvm_sa_attention_bwd_f32: empty input");
-    Arena ar(ws, ws_bytes);
-    float *t = ar.take<float>((size_t)B * N);
-    float *u = ar.take<float>((size_t)B * N);
-    if (!ar.ok()) {
-        set_error("dvm_sa_attention_bwd_f32: workspace too small (%zu < %zu)", ws_bytes, ar.off);
-        return DVM_ENOSPACE;
-    }
+    SaBwdWs w;
+    if (!carve_ws(ws, ws_bytes, "dvm_sa_attention_bwd_f32", w, carve_sa_bwd, B, N)) return DVM_ENOSPACE;
+    float *const t = w.t, *const u = w.u;
     hipStream_t s = (hipStream_t)stream;
     (void)hipMemsetAsync(u, 0, (size_t)B * N * sizeof(float), s);
     (void)hipMemsetAsync(d_p, 0, (size_t)B * N * SB_P * sizeof(float), s);

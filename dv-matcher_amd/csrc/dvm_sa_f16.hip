@@ -247,14 +247,11 @@ __global__ __launch_bounds__(256) void sa_apply_f16_kernel(const _Float16 *__res
 
 }  // namespace
 
-size_t sa_f16_ws_bytes(int B, int N) {
+size_t sa_f16_carve(Arena &ar, int B, int N, _Float16 *&pp, _Float16 *&vp) {
     const size_t T = (N + 31) / 32;
-    return align_up((size_t)B * N * 2 * SF_P * sizeof(_Float16)) + align_up((size_t)B * T * 2 * SF_C * 32 * sizeof(_Float16));
-}
-
-void sa_f16_carve(void *ws, int B, int N, _Float16 *&pp, _Float16 *&vp) {
-    pp = (_Float16 *)ws;
-    vp = (_Float16 *)((char *)ws + align_up((size_t)B * N * 2 * SF_P * sizeof(_Float16)));
+    pp = ar.take<_Float16>((size_t)B * N * 2 * SF_P);
+    vp = ar.take<_Float16>((size_t)B * T * 2 * SF_C * 32);
+    return ar.off;
 }
 
 void launch_sa_split_f16(const float *p, const float *v, int B, int N, _Float16 *pp, _Float16 *vp, hipStream_t s) {

@@ -389,11 +389,23 @@ int sinkhorn_run(const float *f1, const float *f2, int B, int N, int M, int d, f
 
 using namespace dvm;
 
+// |f1|^2, |f2|^2 (both entry points) and, with `potentials`, u and v (used when the caller does not ask for them; the hist form
+// writes the caller's histories instead)
+struct SinkhornWs {
+    float *n1, *n2, *wu, *wv;
+};
+static size_t carve_sinkhorn(Arena &ar, int B, int N, int M, bool potentials, SinkhornWs &w) {
+    w.n1 = ar.take<float>((size_t)B * N);
+    w.n2 = ar.take<float>((size_t)B * M);
+    w.wu = potentials ? ar.take<float>((size_t)B * N) : nullptr;
+    w.wv = potentials ? ar.take<float>((size_t)B * M) : nullptr;
+    return ar.off;
+}
+
 DVM_EXPORT size_t dvm_sinkhorn_workspace_bytes(int B, int N, int M, int d) {
     (void)d;
     if (B < 1 || N < 1 || M < 1) return 0;
-    // |f1|^2, |f2|^2 and the two potentials (used when the caller does not ask for u / v)
-    return 2 * (align_up((size_t)B * N * sizeof(float)) + align_up((size_t)B * M * sizeof(float)));
+    return null_carve<SinkhornWs>(carve_sinkhorn, B, N, M, true);
 }
 
 DVM_EXPORT int dvm_sinkhorn_fwd_f32(const float *f1, const float *f2, int B, int N, int M, int d, float neg_alpha, int n_iter,
@@ -406,27 +418,20 @@ DVM_EXPORT int dvm_sinkhorn_fwd_f32(const float *f1, const float *f2, int B, int
     DVM_REQUIRE(n_iter >= 0, "dvm_sinkhorn_fwd_f32: n_iter=%d must not be negative", n_iter);
     DVM_REQUIRE(neg_alpha < 0.f, "dvm_sinkhorn_fwd_f32: neg_alpha must be negative (got %g)", (double)neg_alpha);
     DVM_REQUIRE(variant == 0 || variant == 1, "dvm_sinkhorn_fwd_f32: bad variant %d (0 = auto, 1 = scalar)", variant);
-    Arena ar(ws, ws_bytes);
-    float *n1 = ar.take<float>((size_t)B * N);
-    float *n2 = ar.take<float>((size_t)B * M);
-    float *wu = ar.take<float>((size_t)B * N);
-    float *wv = ar.take<float>((size_t)B * M);
-    if (!ar.ok()) {
-        set_error("dvm_sinkhorn_fwd_f32: workspace too small (%zu < %zu)", ws_bytes, ar.off);
-        return DVM_ENOSPACE;
-    }
+    SinkhornWs w;
+    if (!carve_ws(ws, ws_bytes, "dvm_sinkhorn_fwd_f32", w, carve_sinkhorn, B, N, M, true)) return DVM_ENOSPACE;
     hipStream_t s = (hipStream_t)stream;
-    float *ub = u ? u : wu, *vb = v ? v : wv;
+    float *ub = u ? u : w.wu, *vb = v ? v : w.wv;
     const bool mfma = variant == 0 && d == D;
     if (n_iter == 0 && v) (void)hipMemsetAsync(v, 0, (size_t)B * M * sizeof(float), s);
-    return sinkhorn_run(f1, f2, B, N, M, d, neg_alpha, n_iter, topk, pi_val, pi_idx, row_lmax, row_sum, n1, n2, ub, 0, N, vb, 0, M, u,
+    return sinkhorn_run(f1, f2, B, N, M, d, neg_alpha, n_iter, topk, pi_val, pi_idx, row_lmax, row_sum, w.n1, w.n2, ub, 0, N, vb, 0, M, u,
                         mfma, s);
 }
 
 DVM_EXPORT size_t dvm_sinkhorn_hist_workspace_bytes(int B, int N, int M, int d) {
     (void)d;
     if (B < 1 || N < 1 || M < 1) return 0;
-    return align_up((size_t)B * N * sizeof(float)) + align_up((size_t)B * M * sizeof(float));   // |f1|^2, |f2|^2
+    return null_carve<SinkhornWs>(carve_sinkhorn, B, N, M, false);
 }
 
 DVM_EXPORT int dvm_sinkhorn_fwd_hist_f32(const float *f1, const float *f2, int B, int N, int M, int d, float neg_alpha, int n_iter,
@@ -439,16 +444,11 @@ DVM_EXPORT int dvm_sinkhorn_fwd_hist_f32(const float *f1, const float *f2, int B
     DVM_REQUIRE(n_iter >= 0, "dvm_sinkhorn_fwd_hist_f32: n_iter=%d must not be negative", n_iter);
     DVM_REQUIRE(neg_alpha < 0.f, "dvm_sinkhorn_fwd_hist_f32: neg_alpha must be negative (got %g)", (double)neg_alpha);
     DVM_REQUIRE(variant == 0 || variant == 1, "dvm_sinkhorn_fwd_hist_f32: bad variant %d (0 = auto, 1 = scalar)", variant);
-    Arena ar(ws, ws_bytes);
-    float *n1 = ar.take<float>((size_t)B * N);
-    float *n2 = ar.take<float>((size_t)B * M);
-    if (!ar.ok()) {
-        set_error("dvm_sinkhorn_fwd_hist_f32: workspace too small (%zu < %zu)", ws_bytes, ar.off);
-        return DVM_ENOSPACE;
-    }
+    SinkhornWs w;
+    if (!carve_ws(ws, ws_bytes, "dvm_sinkhorn_fwd_hist_f32", w, carve_sinkhorn, B, N, M, false)) return DVM_ENOSPACE;
     hipStream_t s = (hipStream_t)stream;
     const long u_bs = (long)(n_iter + 1) * N, v_bs = (long)(n_iter + 1) * M;
     hipLaunchKernelGGL(sinkhorn_zero_slice_kernel, dim3((M + 255) / 256, B), dim3(256), 0, s, v_hist, M, v_bs);   // v^0
-    return sinkhorn_run(f1, f2, B, N, M, d, neg_alpha, n_iter, topk, pi_val, pi_idx, row_lmax, row_sum, n1, n2, u_hist, N, u_bs, v_hist,
+    return sinkhorn_run(f1, f2, B, N, M, d, neg_alpha, n_iter, topk, pi_val, pi_idx, row_lmax, row_sum, w.n1, w.n2, u_hist, N, u_bs, v_hist,
                         M, v_bs, u_hist + (size_t)n_iter * N, variant == 0 && d == D, s);
 }

@@ -609,10 +609,7 @@ DVM_EXPORT int dvm_sinkhorn_bwd_f32(const float *f1, const float *f2, int B, int
     DVM_REQUIRE(variant == 0 || variant == 1, "dvm_sinkhorn_bwd_f32: bad variant %d (0 = auto, 1 = scalar)", variant);
     Arena ar(ws, ws_bytes);
     const SkbWs w = skb_carve(ar, B, N, M, n_iter, topk);
-    if (!ar.ok()) {
-        set_error("dvm_sinkhorn_bwd_f32: workspace too small (%zu < %zu)", ws_bytes, ar.off);
-        return DVM_ENOSPACE;
-    }
+    if (!arena_fits(ar, "dvm_sinkhorn_bwd_f32")) return DVM_ENOSPACE;
     hipStream_t s = (hipStream_t)stream;
     const int T = n_iter, wpr = (M + 31) / 32;
     const bool mfma = variant == 0 && d == D;

@@ -480,12 +480,6 @@ int launch_softcorr_both(const float *f1, const float *f2, const float *n1, cons
     return DVM_OK;
 }
 
-// dvm_softcorr_f16.hip
-size_t softcorr_f16_ws_bytes(int B, int N, int M, bool both);
-int launch_softcorr_f16(const float *f1, const float *f2, const float *n1, const float *n2, int B, int N, int M, float neg_alpha,
-                         int topk, float *val12, int32_t *idx12, float *smax12, float *sum12, float *val21, int32_t *idx21,
-                         float *smax21, float *sum21, const int *amax, void *ws, size_t ws_bytes, hipStream_t s, int *fuse_slots = nullptr);
-
 // K == 128 only: also maxes the bit pattern of max |x| into the 256 slots of `absmax_slots` (zero them first);
 // launch_absmax_finalize folds nt x 256 slots into nt values
 void launch_rownorm2_absmax(const float *x, int rows, float *out, int *absmax_slots, hipStream_t s) {
@@ -504,20 +498,40 @@ void launch_absmax_finalize(const int *slots, int nt, int *out, hipStream_t s) {
 }
 
 // norms of both sides + soft correspondence in both directions for the fused pair path (d = 128, top-10)
-size_t softcorr_pair_ws_bytes(int B, int N, int M) { return align_up(514 * sizeof(int)) + softcorr_f16_ws_bytes(B, N, M, true); }
+// the 2 x 256 absmax slots + the two absmax values, with the K1 workspace (dvm_softcorr_f16.hip) RIGHT behind them: there
+// launch_softcorr_f16 clears the slots and its own zero-initialised head with one fill
+struct K1CallWs {
+    int *slots;
+    char *k1ws;
+    size_t k1_bytes;
+};
+static size_t carve_k1_call(Arena &ar, int B, int N, int M, bool both, K1CallWs &w) {
+    w.slots = ar.take<int>(2 * 256 + 2);
+    w.k1_bytes = softcorr_f16_ws_bytes(B, N, M, both);
+    w.k1ws = ar.take<char>(w.k1_bytes);
+    return ar.off;
+}
+size_t softcorr_pair_ws_bytes(int B, int N, int M) { return null_carve<K1CallWs>(carve_k1_call, B, N, M, true); }
 int launch_softcorr_pair(const float *f1, const float *f2, float *n1, float *n2, int B, int N, int M, float neg_alpha, float *val12,
                          int32_t *idx12, float *val21, int32_t *idx21, void *ws, size_t ws_bytes, hipStream_t s) {
-    Arena ar(ws, ws_bytes);
-    int *slots = ar.take<int>(2 * 256 + 2);
-    int *amax = slots + 512;
-    char *bws = ar.take<char>(0);
-    if (!ar.ok()) {
-        set_error("softcorr (pair): workspace too small (%zu < %zu)", ws_bytes, ar.off);
-        return DVM_ENOSPACE;
-    }
+    K1CallWs w;
+    if (!carve_ws(ws, ws_bytes, "softcorr (pair)", w, carve_k1_call, B, N, M, true)) return DVM_ENOSPACE;
     // (row norms, absmax and the fp16 planes come out of ONE pass over the features inside launch_softcorr_f16: `slots`)
     return launch_softcorr_f16(f1, f2, n1, n2, B, N, M, neg_alpha, 10, val12, idx12, nullptr, nullptr, val21, idx21, nullptr, nullptr,
-                                amax, bws, ws_bytes - ar.off, s, slots);
+                                w.slots + 512, w.k1ws, w.k1_bytes, s, w.slots);
+}
+
+// dvm_softcorr_fwd_f32's workspace: the norms of both sides and, for the fp16-split sweep (k1), what carve_k1_call lays out
+struct SoftcorrWs {
+    float *n1, *n2;
+    K1CallWs k;
+};
+static size_t carve_softcorr(Arena &ar, int B, int N, int M, bool k1, SoftcorrWs &w) {
+    w.n1 = ar.take<float>((size_t)B * N);
+    w.n2 = ar.take<float>((size_t)B * M);
+    w.k = K1CallWs{nullptr, nullptr, 0};
+    if (k1) carve_k1_call(ar, B, N, M, false, w.k);
+    return ar.off;
 }
 
 void launch_rownorm2(const float *x, int rows, int K, float *out, hipStream_t s) {
@@ -541,8 +555,7 @@ DVM_EXPORT int dvm_rownorm2_f32(const float *x, int rows, int K, float *out, voi
 }
 
 DVM_EXPORT size_t dvm_softcorr_workspace_bytes(int B, int N, int M, int d) {
-    return align_up((size_t)B * N * sizeof(float)) + align_up((size_t)B * M * sizeof(float)) +
-           (d == D ? align_up(514 * sizeof(int)) + softcorr_f16_ws_bytes(B, N, M, false) : 0);
+    return null_carve<SoftcorrWs>(carve_softcorr, B, N, M, d == D);   // (d == 128: sized for the fp16-split sweep, whichever variant is asked for)
 }
 
 DVM_EXPORT int dvm_softcorr_fwd_f32(const float *f1, const float *f2, int B, int N, int M, int d, float neg_alpha,
@@ -556,29 +569,19 @@ DVM_EXPORT int dvm_softcorr_fwd_f32(const float *f1, const float *f2, int B, int
     DVM_REQUIRE(variant >= 0 && variant <= 3, "dvm_softcorr_fwd_f32: bad variant %d", variant);
     DVM_REQUIRE(variant < 2 || d == D, "dvm_softcorr_fwd_f32: the matrix-core variants need d == 128");
     DVM_REQUIRE(variant != 3 || topk <= 10, "dvm_softcorr_fwd_f32: the bf16 variant keeps 12 candidates (topk <= 10)");
-    Arena ar(ws, ws_bytes);
-    float *n1 = ar.take<float>((size_t)B * N);
-    float *n2 = ar.take<float>((size_t)B * M);
-    if (!ar.ok()) {
-        set_error("dvm_softcorr_fwd_f32: workspace too small (%zu < %zu)", ws_bytes, ar.off);
-        return DVM_ENOSPACE;
-    }
-    hipStream_t s = (hipStream_t)stream;
     if (variant == 0 && d == D && topk <= 10) variant = 3;   // auto: the fp16-split sweep (variants 1 / 2: the `variant` argument)
+    SoftcorrWs w;
+    if (!carve_ws(ws, ws_bytes, "dvm_softcorr_fwd_f32", w, carve_softcorr, B, N, M, variant == 3)) return DVM_ENOSPACE;
+    float *const n1 = w.n1, *const n2 = w.n2;
+    hipStream_t s = (hipStream_t)stream;
     if (variant == 3) {
-        int *slots = ar.take<int>(2 * 256 + 2);
-        int *amax = slots + 512;
-        char *bws = ar.take<char>(0);
-        if (!ar.ok()) {
-            set_error("dvm_softcorr_fwd_f32: workspace too small (%zu < %zu)", ws_bytes, ar.off);
-            return DVM_ENOSPACE;
-        }
+        int *const slots = w.k.slots, *const amax = slots + 512;
         (void)hipMemsetAsync(slots, 0, 512 * sizeof(int), s);
         launch_rownorm2_absmax(f1, B * N, n1, slots, s);
         launch_rownorm2_absmax(f2, B * M, n2, slots + 256, s);
         launch_absmax_finalize(slots, 2, amax, s);
         int rc = launch_softcorr_f16(f1, f2, n1, n2, B, N, M, neg_alpha, topk, pi_val, pi_idx, row_smax, row_sum, nullptr, nullptr,
-                                      nullptr, nullptr, amax, bws, ws_bytes - ar.off, s);
+                                      nullptr, nullptr, amax, w.k.k1ws, w.k.k1_bytes, s);
         if (rc != DVM_OK) return rc;
         DVM_CHECK_LAUNCH("softcorr (fp16)");
         return DVM_OK;
@@ -616,9 +619,22 @@ DVM_EXPORT int dvm_softcorr_fwd_f32(const float *f1, const float *f2, int B, int
     return DVM_OK;
 }
 
+// dvm_softcorr_fwd_f32's workspace in front (its norms are read again here), then the row statistics and the top-1 outputs
+struct SoftcorrDenseWs {
+    SoftcorrWs sc;
+    size_t sc_bytes;
+    float *smax, *ssum, *v1;
+    int32_t *i1;
+};
+static size_t carve_softcorr_dense(Arena &ar, int B, int N, int M, int d, SoftcorrDenseWs &w) {
+    w.sc_bytes = carve_softcorr(ar, B, N, M, d == D, w.sc);   // (first in the arena: its end offset is its size)
+    w.smax = ar.take<float>((size_t)B * N), w.ssum = ar.take<float>((size_t)B * N);
+    w.v1 = ar.take<float>((size_t)B * N);
+    w.i1 = ar.take<int32_t>((size_t)B * N);
+    return ar.off;
+}
 DVM_EXPORT size_t dvm_softcorr_dense_workspace_bytes(int B, int N, int M, int d) {
-    return dvm_softcorr_workspace_bytes(B, N, M, d) + 2 * align_up((size_t)B * N * sizeof(float)) +
-           align_up((size_t)B * N * sizeof(float)) + align_up((size_t)B * N * sizeof(int32_t));
+    return null_carve<SoftcorrDenseWs>(carve_softcorr_dense, B, N, M, d);
 }
 
 DVM_EXPORT int dvm_softcorr_dense_f32(const float *f1, const float *f2, int B, int N, int M, int d, float neg_alpha, float *P,
@@ -627,22 +643,13 @@ DVM_EXPORT int dvm_softcorr_dense_f32(const float *f1, const float *f2, int B, i
     DVM_REQUIRE(B >= 1 && N >= 1 && M >= 1, "dvm_softcorr_dense_f32: empty input");
     DVM_REQUIRE(d >= 4 && d % 4 == 0 && d <= 512, "dvm_softcorr_dense_f32: d=%d unsupported", d);
     DVM_REQUIRE(neg_alpha < 0.f, "dvm_softcorr_dense_f32: neg_alpha must be negative");
-    Arena ar(ws, ws_bytes);
-    size_t scb = dvm_softcorr_workspace_bytes(B, N, M, d);
-    char *scws = ar.take<char>(scb);
-    float *smax = ar.take<float>((size_t)B * N), *ssum = ar.take<float>((size_t)B * N);
-    float *v1 = ar.take<float>((size_t)B * N);
-    int32_t *i1 = ar.take<int32_t>((size_t)B * N);
-    if (!ar.ok()) {
-        set_error("dvm_softcorr_dense_f32: workspace too small (%zu < %zu)", ws_bytes, ar.off);
-        return DVM_ENOSPACE;
-    }
-    int rc = dvm_softcorr_fwd_f32(f1, f2, B, N, M, d, neg_alpha, 1, v1, i1, smax, ssum, 0, scws, scb, stream);
+    SoftcorrDenseWs w;
+    if (!carve_ws(ws, ws_bytes, "dvm_softcorr_dense_f32", w, carve_softcorr_dense, B, N, M, d)) return DVM_ENOSPACE;
+    float *const smax = w.smax, *const ssum = w.ssum;
+    // (the soft-correspondence call carves the head of `ws` as carve_softcorr did here: its norms are w.sc.n1 / n2)
+    int rc = dvm_softcorr_fwd_f32(f1, f2, B, N, M, d, neg_alpha, 1, w.v1, w.i1, smax, ssum, 0, ws, w.sc_bytes, stream);
     if (rc != DVM_OK) return rc;
-    // the norms are the first two carve-outs of the soft-correspondence workspace
-    Arena a2(scws, scb);
-    float *n1 = a2.take<float>((size_t)B * N);
-    float *n2 = a2.take<float>((size_t)B * M);
+    const float *n1 = w.sc.n1, *n2 = w.sc.n2;
     size_t lds = (size_t)(SC_KT * d + SC_KT) * sizeof(float);
     (void)hipFuncSetAttribute((const void *)softcorr_dense_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 66 * 1024);
     hipLaunchKernelGGL(softcorr_dense_kernel<0>, dim3((N + 127) / 128, B), dim3(128), lds, (hipStream_t)stream, f1, f2, n1, n2, smax,

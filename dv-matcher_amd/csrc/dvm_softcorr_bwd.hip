@@ -296,10 +296,24 @@ __global__ __launch_bounds__(256) void softcorr_bwd_prep_kernel(const float *__r
 
 using namespace dvm;
 
+struct SoftcorrBwdWs {
+    float *n1, *coef, *c2, *n2;
+    uint32_t *bits;   // [B][N][wpr]: one bit per column
+    int wpr;
+};
+static size_t carve_softcorr_bwd(Arena &ar, int B, int N, int M, SoftcorrBwdWs &w) {
+    w.n1 = ar.take<float>((size_t)B * N);
+    w.coef = ar.take<float>((size_t)B * N);
+    w.c2 = ar.take<float>((size_t)B * N);
+    w.n2 = ar.take<float>((size_t)B * M);
+    w.wpr = (M + 31) / 32;
+    w.bits = ar.take<uint32_t>((size_t)B * N * w.wpr);
+    return ar.off;
+}
+
 DVM_EXPORT size_t dvm_softcorr_bwd_workspace_bytes(int B, int N, int M, int d) {
     (void)d;
-    return 3 * align_up((size_t)B * N * sizeof(float)) + align_up((size_t)B * M * sizeof(float)) +
-           align_up((size_t)B * N * ((M + 31) / 32) * sizeof(uint32_t));
+    return null_carve<SoftcorrBwdWs>(carve_softcorr_bwd, B, N, M);
 }
 
 DVM_EXPORT int dvm_softcorr_bwd_f32(const float *f1, const float *f2, int B, int N, int M, int d, float neg_alpha, int topk,
@@ -313,17 +327,11 @@ DVM_EXPORT int dvm_softcorr_bwd_f32(const float *f1, const float *f2, int B, int
     DVM_REQUIRE(neg_alpha < 0.f, "dvm_softcorr_bwd_f32: neg_alpha must be negative (got %g)", (double)neg_alpha);
     DVM_REQUIRE(variant >= 0 && variant <= 2, "dvm_softcorr_bwd_f32: bad variant %d", variant);
     DVM_REQUIRE(variant != 2 || d == D, "dvm_softcorr_bwd_f32: MFMA variant needs d == 128");
-    Arena ar(ws, ws_bytes);
-    float *n1 = ar.take<float>((size_t)B * N);
-    float *coef = ar.take<float>((size_t)B * N);
-    float *c2 = ar.take<float>((size_t)B * N);
-    float *n2 = ar.take<float>((size_t)B * M);
-    const int wpr = (M + 31) / 32;
-    uint32_t *bits = ar.take<uint32_t>((size_t)B * N * wpr);
-    if (!ar.ok()) {
-        set_error("dvm_softcorr_bwd_f32: workspace too small (%zu < %zu)", ws_bytes, ar.off);
-        return DVM_ENOSPACE;
-    }
+    SoftcorrBwdWs w;
+    if (!carve_ws(ws, ws_bytes, "dvm_softcorr_bwd_f32", w, carve_softcorr_bwd, B, N, M)) return DVM_ENOSPACE;
+    float *const n1 = w.n1, *const coef = w.coef, *const c2 = w.c2, *const n2 = w.n2;
+    uint32_t *const bits = w.bits;
+    const int wpr = w.wpr;
     hipStream_t s = (hipStream_t)stream;
     (void)hipMemsetAsync(d_f1, 0, (size_t)B * N * d * sizeof(float), s);
     (void)hipMemsetAsync(d_f2, 0, (size_t)B * M * d * sizeof(float), s);

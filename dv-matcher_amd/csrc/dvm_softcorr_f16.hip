@@ -20,11 +20,6 @@
 #include "dvm_softcorr_f16.h"
 
 namespace dvm {
-
-void launch_rownorm2(const float *x, int rows, int K, float *out, hipStream_t s);
-void launch_rownorm2_absmax(const float *x, int rows, float *out, int *absmax_slots, hipStream_t s);
-void launch_absmax_finalize(const int *slots, int nt, int *out, hipStream_t s);
-
 namespace {
 
 using namespace k1;
@@ -1193,20 +1188,59 @@ struct K1LastLaunch {
 };
 static thread_local K1LastLaunch g_k1_last;
 
-// workspace of the fp16 path for (B, N, M): planes of both sides, candidates of both directions, flags
-size_t softcorr_f16_ws_bytes(int B, int N, int M, bool both) {
-    const size_t Np = (size_t)(N + HB_KT - 1) / HB_KT * HB_KT, Mp = (size_t)(M + HB_KT - 1) / HB_KT * HB_KT;
-    size_t n = align_up((size_t)B * N * HB_ROWB) + align_up((size_t)B * M * HB_ROWB) + 2 * align_up((size_t)B * sizeof(float)) +
-               2 * align_up(2 * sizeof(int)) + align_up(B * Np * sizeof(float)) + align_up(B * Mp * sizeof(float)) +
-               align_up(B * Np * 32) + align_up(B * Mp * 32) +   // (norm fragments of the second sweep form)
-               2 * align_up(2 * (size_t)B * sizeof(int)) + align_up(2 * (size_t)B * sizeof(float));   // routes (both passes) + probe fractions
-    const int dirs = both ? 2 : 1;
-    for (int d = 0; d < dirs; ++d) {
+// The K1 workspace for (B, N, M): planes of both sides, candidates of both directions (one without `both`), flags.  ONE layout for
+// launch_softcorr_f16 and launch_argmin_f16 (which uses neither spec, route2 nor pfrac) and for the two size queries.
+struct K1Ws {
+    float *nmax[2];   // [B] maxima of the norms, zero-initialised
+    int *amax;        // [2] bit patterns of max|f1|, max|f2| when the caller did not fuse them into the norms
+    int *spec;        // fused preparation: [0] absmax of the sampled rows (provisional scale), [1] planes must be re-made
+    char *p[2];       // fp16 planes [B][rows][HB_ROWB]
+    float *npad[2];   // norms padded to whole key tiles
+    char *nfrag[2];   // norm fragments of the coarse screen
+    int *route, *route2;   // [2B] routes of the first pass and of the gate's second pass
+    float *pfrac;          // [2B] the probe's fractions
+    int32_t *cidx[2], *flag[2];   // per direction: candidate columns; flag [0] = counter, [1..] = rows
+    float *cd2[2], *lsum[2];
+    int pad[2];       // rows of either side padded to whole key tiles
+};
+static size_t carve_k1(Arena &ar, int B, int N, int M, bool both, K1Ws &w) {
+    // The small zero-initialised slots first, back to back (a 256-byte slot each): nmax[0], nmax[1], amax, spec are cleared by ONE
+    // fill from nmax[0] to the end of spec (launch_softcorr_f16) or of amax (launch_argmin_f16); in the pair path the caller's 514
+    // absmax slots lie right in front of nmax[0] and the same fill starts there (launch_softcorr_f16 tests that adjacency).
+    w.nmax[0] = ar.take<float>(B), w.nmax[1] = ar.take<float>(B);
+    w.amax = ar.take<int>(2);
+    w.spec = ar.take<int>(2);
+    w.p[0] = ar.take<char>((size_t)B * N * HB_ROWB), w.p[1] = ar.take<char>((size_t)B * M * HB_ROWB);
+    w.pad[0] = (N + HB_KT - 1) / HB_KT * HB_KT, w.pad[1] = (M + HB_KT - 1) / HB_KT * HB_KT;
+    w.npad[0] = ar.take<float>((size_t)B * w.pad[0]), w.npad[1] = ar.take<float>((size_t)B * w.pad[1]);
+    w.nfrag[0] = ar.take<char>((size_t)B * w.pad[0] * 32), w.nfrag[1] = ar.take<char>((size_t)B * w.pad[1] * 32);
+    w.route = ar.take<int>(2 * (size_t)B), w.route2 = ar.take<int>(2 * (size_t)B);
+    w.pfrac = ar.take<float>(2 * (size_t)B);
+    for (int d = 0; d < 2; ++d) w.cidx[d] = w.flag[d] = nullptr, w.cd2[d] = w.lsum[d] = nullptr;
+    for (int d = 0; d < (both ? 2 : 1); ++d) {
         const size_t R = (size_t)B * (d == 0 ? N : M);
-        n += align_up(R * K1_KC_COARSE * sizeof(int32_t)) + align_up(R * K1_KC_COARSE * sizeof(float)) + align_up(R * 2 * sizeof(float)) +
-             align_up((R + 1) * sizeof(int32_t));   // (candidate lists sized for the longest form's)
+        w.cidx[d] = ar.take<int32_t>(R * K1_KC_COARSE);   // (candidate lists sized for the longest form's)
+        w.cd2[d] = ar.take<float>(R * K1_KC_COARSE);
+        w.lsum[d] = ar.take<float>(R * 2);
+        w.flag[d] = ar.take<int32_t>(R + 1);
     }
-    return n;
+    return ar.off;
+}
+size_t softcorr_f16_ws_bytes(int B, int N, int M, bool both) { return null_carve<K1Ws>(carve_k1, B, N, M, both); }
+// bytes of nmax[0] .. the two ints at `last` (w.spec or w.amax): the one fill of the zero-initialised slots
+static size_t k1_zero_bytes(const K1Ws &w, const int *last) { return (size_t)((const char *)last - (const char *)w.nmax[0]) + 2 * sizeof(int); }
+// What both launchers hand to the norm preparation and to pass A, from the one layout: norms n1 / n2, scales at amax[0], amax[1];
+// frags: the coarse screen's norm fragments are made.  Returns the number of pass-A workgroups.
+static int k1_pass_a_args(const K1Ws &w, const float *n1, const float *n2, int B, int N, int M, bool both, bool frags, const int *amax, NormPrep &np,
+                          HBArgs &a) {
+    np = NormPrep{{n1, n2}, {N, M}, {w.pad[0], w.pad[1]}, {w.nmax[0], w.nmax[1]}, {both ? w.npad[0] : nullptr, w.npad[1]},
+                  {frags && both ? w.nfrag[0] : nullptr, frags ? w.nfrag[1] : nullptr}, amax, {w.flag[0], both ? w.flag[1] : nullptr}};
+    a.g[0] = HBGroup{w.p[0], w.p[1], amax, amax + 1, n1, w.npad[1], N, M, w.pad[1], (N + HB_QB - 1) / HB_QB, w.cidx[0], w.cd2[0], w.lsum[0]};
+    a.g[1] = both ? HBGroup{w.p[1], w.p[0], amax + 1, amax, n2, w.npad[0], M, N, w.pad[0], (M + HB_QB - 1) / HB_QB, w.cidx[1], w.cd2[1], w.lsum[1]}
+                  : a.g[0];
+    a.blocks0 = B * a.g[0].tiles;
+    a.nb = B;
+    return a.blocks0 + (both ? B * a.g[1].tiles : 0);
 }
 
 // f1 [B][N][128], f2 [B][M][128] with norms n1, n2; direction 0 = rows of f1 against f2; direction 1 (optional) the
@@ -1217,38 +1251,23 @@ int launch_softcorr_f16(const float *f1, const float *f2, const float *n1, const
     // fuse_slots != nullptr (the pair path): n1 / n2 and the absmax values at amax_in are NOT computed yet - this call makes them
     // in the same pass that writes the fp16 planes (rownorm_split_kernel); fuse_slots = 512 ints of scratch
     const bool both = val21 != nullptr;
-    Arena ar(ws, ws_bytes);
-    // (the small zero-initialised slots first: in the pair path they follow the caller's absmax slots directly — one fill for all)
-    float *nmax1 = ar.take<float>(B), *nmax2 = ar.take<float>(B);
-    int *amax_own = ar.take<int>(2);  // bit patterns of max|f1|, max|f2| when the caller did not fuse them into the norms
-    int *spec = ar.take<int>(2);      // fused preparation: [0] absmax of the sampled rows (provisional scale), [1] planes must be re-made
-    char *p1 = ar.take<char>((size_t)B * N * HB_ROWB), *p2 = ar.take<char>((size_t)B * M * HB_ROWB);
+    K1Ws w;
+    if (!carve_ws(ws, ws_bytes, "softcorr (fp16 path)", w, carve_k1, B, N, M, both)) return DVM_ENOSPACE;
+    float *const nmax1 = w.nmax[0], *const nmax2 = w.nmax[1];
+    int *const amax_own = w.amax, *const spec = w.spec;
+    char *const p1 = w.p[0], *const p2 = w.p[1], *const nf1 = w.nfrag[0], *const nf2 = w.nfrag[1];
     const int *amax = amax_own;   // ONE scale for both sides (the larger absmax), see common_absmax_kernel
-    const int Np = (N + HB_KT - 1) / HB_KT * HB_KT, Mp = (M + HB_KT - 1) / HB_KT * HB_KT;
-    float *n1p = ar.take<float>((size_t)B * Np), *n2p = ar.take<float>((size_t)B * Mp);
-    char *nf1 = ar.take<char>((size_t)B * Np * 32), *nf2 = ar.take<char>((size_t)B * Mp * 32);
-    int *route = ar.take<int>(2 * (size_t)B), *route2 = ar.take<int>(2 * (size_t)B);
-    float *pfrac = ar.take<float>(2 * (size_t)B);
-    int32_t *cidx[2] = {nullptr, nullptr}, *flag[2] = {nullptr, nullptr};
-    float *cd2[2] = {nullptr, nullptr}, *lsum[2] = {nullptr, nullptr};
-    for (int d = 0; d < (both ? 2 : 1); ++d) {
-        const size_t R = (size_t)B * (d == 0 ? N : M);
-        cidx[d] = ar.take<int32_t>(R * K1_KC_COARSE);
-        cd2[d] = ar.take<float>(R * K1_KC_COARSE);
-        lsum[d] = ar.take<float>(R * 2);
-        flag[d] = ar.take<int32_t>(R + 1);  // [0] = counter, [1..] = rows
-    }
-    if (!ar.ok()) {
-        set_error("softcorr (fp16 path): workspace too small (%zu < %zu)", ws_bytes, ar.off);
-        return DVM_ENOSPACE;
-    }
+    int *const route = w.route, *const route2 = w.route2;
+    float *const pfrac = w.pfrac;
+    int32_t *const *cidx = w.cidx, *const *flag = w.flag;
+    float *const *cd2 = w.cd2, *const *lsum = w.lsum;
     const long r1 = (long)B * N, r2 = (long)B * M;
-    // nmax1, nmax2, amax_own and spec lie back to back in the arena (256-byte slots), and in the pair path right behind the caller's
+    // nmax1, nmax2, amax_own and spec lie back to back in the arena (carve_k1), and in the pair path right behind the caller's
     // 514 absmax slots: one fill
     if (fuse_slots && (char *)fuse_slots + align_up(514 * sizeof(int)) == (char *)nmax1) {
-        (void)hipMemsetAsync(fuse_slots, 0, (size_t)((char *)spec - (char *)fuse_slots) + 2 * sizeof(int), s);
+        (void)hipMemsetAsync(fuse_slots, 0, align_up(514 * sizeof(int)) + k1_zero_bytes(w, spec), s);
     } else {
-        (void)hipMemsetAsync(nmax1, 0, (size_t)((char *)spec - (char *)nmax1) + 2 * sizeof(int), s);
+        (void)hipMemsetAsync(nmax1, 0, k1_zero_bytes(w, spec), s);
         if (fuse_slots) (void)hipMemsetAsync(fuse_slots, 0, 512 * sizeof(int), s);
     }
     if (fuse_slots) {
@@ -1290,23 +1309,15 @@ int launch_softcorr_f16(const float *f1, const float *f2, const float *n1, const
         hipLaunchKernelGGL(k1_route_kernel, dim3(both ? 2 : 1), dim3(256), 0, s, pa, B);
         if (pol.debug & DVM_DEBUG_K1_ROUTES) report_routes(route, pfrac, B * (both ? 2 : 1), s);
     }
-    {   // the norms' maxima, the first form's padded norms (also behind the coarse screen, for the gate's second pass), the coarse
-        // screen's norm fragments and the flagged-row counters: one launch
-        const bool frags = routed ? havec : fixed == K1_ROUTE_COARSE;
-        NormPrep np{{n1, n2}, {N, M}, {Np, Mp}, {nmax1, nmax2}, {both ? n1p : nullptr, n2p}, {frags && both ? nf1 : nullptr, frags ? nf2 : nullptr},
-                    amax, {flag[0], both ? flag[1] : nullptr}};
-        launch_norm_prep(np, B, s);
-    }
-
+    NormPrep np;
     HBArgs a;
-    a.g[0] = HBGroup{p1, p2, amax, amax + 1, n1, n2p, N, M, Mp, (N + HB_QB - 1) / HB_QB, cidx[0], cd2[0], lsum[0]};
-    a.g[1] = both ? HBGroup{p2, p1, amax + 1, amax, n2, n1p, M, N, Np, (M + HB_QB - 1) / HB_QB, cidx[1], cd2[1], lsum[1]} : a.g[0];
-    a.blocks0 = B * a.g[0].tiles;
+    const int blocks = k1_pass_a_args(w, n1, n2, B, N, M, both, routed ? havec : fixed == K1_ROUTE_COARSE, amax, np, a);
+    // the norms' maxima, the first form's padded norms (also behind the coarse screen, for the gate's second pass), the coarse
+    // screen's norm fragments and the flagged-row counters: one launch
+    launch_norm_prep(np, B, s);
     a.neg_alpha = neg_alpha;
     a.cutw = 20.f / -neg_alpha;
-    const int blocks = a.blocks0 + (both ? B * a.g[1].tiles : 0);
     a.route = routed ? route : nullptr;
-    a.nb = B;
     prof_note(DVM_PROF_K1_SWEEP, routed ? (havec ? "routed: softcorr_coarse_kernel | softcorr_sweep_f16_kernel<lean> | softcorr_sweep_f16_kernel<full>"
                                                  : "routed: softcorr_sweep_f16_kernel<lean> | softcorr_sweep_f16_kernel<full>")
                                         : fixed == K1_ROUTE_COARSE ? "softcorr_coarse_kernel"
@@ -1380,39 +1391,31 @@ int launch_softcorr_f16(const float *f1, const float *f2, const float *n1, const
     return DVM_OK;
 }
 
-size_t argmin_f16_ws_bytes(int B, int N, int M, bool both) {
-    return align_up((size_t)B * N * sizeof(float)) + align_up((size_t)B * M * sizeof(float)) + softcorr_f16_ws_bytes(B, N, M, both);
+// the arg-min sweep's workspace: the norms of both sides in front of the K1 layout
+struct ArgminWs {
+    float *n1, *n2;
+    K1Ws k1;
+};
+static size_t carve_argmin(Arena &ar, int B, int N, int M, bool both, ArgminWs &w) {
+    w.n1 = ar.take<float>((size_t)B * N), w.n2 = ar.take<float>((size_t)B * M);
+    return carve_k1(ar, B, N, M, both, w.k1);
 }
+size_t argmin_f16_ws_bytes(int B, int N, int M, bool both) { return null_carve<ArgminWs>(carve_argmin, B, N, M, both); }
 
 // hard maps of f1 -> f2 (T12 [B][N]) and, when T21 != nullptr, f2 -> f1 (T21 [B][M]); d = 128
 int launch_argmin_f16(const float *f1, const float *f2, int B, int N, int M, int32_t *T12, float *dmin12, int32_t *T21,
                       float *dmin21, void *ws, size_t ws_bytes, hipStream_t s) {
     const bool both = T21 != nullptr;
-    Arena ar(ws, ws_bytes);
-    float *n1 = ar.take<float>((size_t)B * N), *n2 = ar.take<float>((size_t)B * M);
-    char *p1 = ar.take<char>((size_t)B * N * HB_ROWB), *p2 = ar.take<char>((size_t)B * M * HB_ROWB);
-    float *nmax1 = ar.take<float>(B), *nmax2 = ar.take<float>(B);
-    int *amax = ar.take<int>(2);
-    const int Np = (N + HB_KT - 1) / HB_KT * HB_KT, Mp = (M + HB_KT - 1) / HB_KT * HB_KT;
-    float *n1p = ar.take<float>((size_t)B * Np), *n2p = ar.take<float>((size_t)B * Mp);
-    char *nf1 = ar.take<char>((size_t)B * Np * 32), *nf2 = ar.take<char>((size_t)B * Mp * 32);
-    int32_t *cidx[2] = {nullptr, nullptr}, *flag[2] = {nullptr, nullptr};
-    float *cd2[2] = {nullptr, nullptr}, *lsum[2] = {nullptr, nullptr};
-    for (int d = 0; d < (both ? 2 : 1); ++d) {
-        const size_t R = (size_t)B * (d == 0 ? N : M);
-        cidx[d] = ar.take<int32_t>(R * K1_KC_COARSE);
-        cd2[d] = ar.take<float>(R * K1_KC_COARSE);
-        lsum[d] = ar.take<float>(R * 2);
-        flag[d] = ar.take<int32_t>(R + 1);
-    }
-    if (!ar.ok()) {
-        set_error("argmin (fp16 sweep): workspace too small (%zu < %zu)", ws_bytes, ar.off);
-        return DVM_ENOSPACE;
-    }
+    ArgminWs aw;
+    if (!carve_ws(ws, ws_bytes, "argmin (fp16 sweep)", aw, carve_argmin, B, N, M, both)) return DVM_ENOSPACE;
+    const K1Ws &w = aw.k1;
+    float *const n1 = aw.n1, *const n2 = aw.n2;
+    int *const amax = w.amax, *const route = w.route;
+    char *const p1 = w.p[0], *const p2 = w.p[1];
     const long r1 = (long)B * N, r2 = (long)B * M;
     launch_rownorm2(f1, (int)r1, HB_D, n1, s);
     launch_rownorm2(f2, (int)r2, HB_D, n2, s);
-    (void)hipMemsetAsync(nmax1, 0, 2 * align_up((size_t)B * sizeof(float)) + 2 * sizeof(int), s);
+    (void)hipMemsetAsync(w.nmax[0], 0, k1_zero_bytes(w, amax), s);   // nmax[0], nmax[1], amax: back to back (carve_k1)
     hipLaunchKernelGGL(absmax_kernel, dim3(2048), dim3(256), 0, s, f1, r1 * 32, amax);
     hipLaunchKernelGGL(absmax_kernel, dim3(2048), dim3(256), 0, s, f2, r2 * 32, amax + 1);
     hipLaunchKernelGGL(common_absmax_kernel, dim3(1), dim3(1), 0, s, amax, amax);
@@ -1420,28 +1423,16 @@ int launch_argmin_f16(const float *f1, const float *f2, int B, int N, int M, int
     hipLaunchKernelGGL(split_planes_kernel, dim3((unsigned)((r2 * 16 + 255) / 256)), dim3(256), 0, s, f2, r2, amax + 1, p2);
     // coarse screen first (lists of 16), the first form behind the device-side gate for directions it serves badly
     const bool havec = coarse_supports(N, M);
-    int *route = ar.take<int>(2 * (size_t)B);
-    if (!ar.ok()) {
-        set_error("argmin (fp16 sweep): workspace too small (%zu < %zu)", ws_bytes, ar.off);
-        return DVM_ENOSPACE;
-    }
-    {
-        NormPrep np{{n1, n2}, {N, M}, {Np, Mp}, {nmax1, nmax2}, {both ? n1p : nullptr, n2p}, {havec && both ? nf1 : nullptr, havec ? nf2 : nullptr},
-                    amax, {flag[0], both ? flag[1] : nullptr}};
-        launch_norm_prep(np, B, s);
-    }
+    NormPrep np;
     HBArgs a;
-    a.g[0] = HBGroup{p1, p2, amax, amax + 1, n1, n2p, N, M, Mp, (N + HB_QB - 1) / HB_QB, cidx[0], cd2[0], lsum[0]};
-    a.g[1] = both ? HBGroup{p2, p1, amax + 1, amax, n2, n1p, M, N, Np, (M + HB_QB - 1) / HB_QB, cidx[1], cd2[1], lsum[1]} : a.g[0];
-    a.blocks0 = B * a.g[0].tiles;
+    const int blocks = k1_pass_a_args(w, n1, n2, B, N, M, both, havec, amax, np, a);
+    launch_norm_prep(np, B, s);
     a.neg_alpha = -100.f;  // only the candidate lists are used; the lean sweep keeps them exactly as the full one does
     a.cutw = 0.f;
     a.route = nullptr;
-    a.nb = B;
-    const int blocks = a.blocks0 + (both ? B * a.g[1].tiles : 0);
     AMArgs r;
-    r.g[0] = AMGroup{f1, f2, n1, nmax2, N, M, cidx[0], cd2[0], T12, dmin12, flag[0] + 1, flag[0]};
-    r.g[1] = both ? AMGroup{f2, f1, n2, nmax1, M, N, cidx[1], cd2[1], T21, dmin21, flag[1] + 1, flag[1]}
+    r.g[0] = AMGroup{f1, f2, n1, w.nmax[1], N, M, w.cidx[0], w.cd2[0], T12, dmin12, w.flag[0] + 1, w.flag[0]};
+    r.g[1] = both ? AMGroup{f2, f1, n2, w.nmax[0], M, N, w.cidx[1], w.cd2[1], T21, dmin21, w.flag[1] + 1, w.flag[1]}
                   : AMGroup{nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     r.rows0 = r1;
     r.rows_total = r1 + (both ? r2 : 0);
@@ -1449,7 +1440,7 @@ int launch_argmin_f16(const float *f1, const float *f2, int B, int N, int M, int
     r.nb = B;
     const dim3 rgrid((unsigned)((r.rows_total + 255) / 256));
     if (havec) {
-        launch_coarse(a, nf2, nf1, amax, blocks, s);
+        launch_coarse(a, w.nfrag[1], w.nfrag[0], amax, blocks, s);
         hipLaunchKernelGGL((argmin_refine_kernel<K1_KC_COARSE, true, false>), rgrid, dim3(256), 0, s, r);
         hipLaunchKernelGGL(argmin_gate_kernel, dim3(1), dim3(64), 0, s, r, both ? 2 : 1, route);
         a.route = route, r.route = route;

@@ -15,11 +15,6 @@
 #include "dvm_uni3fc_kernels.h"
 
 namespace dvm {
-
-void launch_linear(const float *x, const float *w, int B, int N, int K, int Co, int channel_major, const float *bias,
-                   const float *res, const float *alpha, const float *beta, float slope, float *y, hipStream_t s, const float *xg,
-                   int Cg, const float *post_res, float post_scale);   // dvm_gemm.hip
-
 namespace {
 
 // indices into the weight table (include/dvm.h)
@@ -155,13 +150,8 @@ DVM_EXPORT int dvm_uni3fc_fwd_f32(const float *xyz, const float *dino, int B, in
     DVM_REQUIRE(nweights == DVM_U3_NWEIGHTS, "dvm_uni3fc_fwd_f32: the weight table has %d entries, expected %d", nweights, DVM_U3_NWEIGHTS);
     for (int i = 0; i < nweights; ++i) DVM_REQUIRE(weights[i] != nullptr, "dvm_uni3fc_fwd_f32: weight table entry %d is null", i);
     DVM_REQUIRE(B >= 1 && N >= 1 && k >= 1 && k <= 64 && k <= N, "dvm_uni3fc_fwd_f32: bad sizes (B=%d N=%d k=%d)", B, N, k);
-    Arena ar(ws, ws_bytes);
     U3Ws w;
-    carve(ar, B, N, k, w);
-    if (!ar.ok()) {
-        set_error("dvm_uni3fc_fwd_f32: workspace too small (%zu < %zu)", ws_bytes, ar.off);
-        return DVM_ENOSPACE;
-    }
+    if (!carve_ws(ws, ws_bytes, "dvm_uni3fc_fwd_f32", w, carve, B, N, k)) return DVM_ENOSPACE;
     hipStream_t s = (hipStream_t)stream;
     const long R = (long)B * N;
     const float *const *W = weights;

@@ -18,15 +18,6 @@
 #include "dvm_uni3fc_kernels.h"
 
 namespace dvm {
-
-void launch_linear(const float *x, const float *w, int B, int N, int K, int Co, int channel_major, const float *bias,
-                   const float *res, const float *alpha, const float *beta, float slope, float *y, hipStream_t s, const float *xg,
-                   int Cg, const float *post_res, float post_scale);   // dvm_gemm.hip
-
-// dvm_bn.hip
-int launch_bn_running_update(float *const *rm, float *const *rv, const float *const *mean, const float *const *var, const int *C, int count,
-                             float momentum, hipStream_t s);
-
 namespace {
 
 // ---- parameter table (include/dvm.h, dvm_uni3fc_train_fwd_f32): raw trainable tensors + BatchNorm running statistics
@@ -429,10 +420,7 @@ DVM_EXPORT int dvm_uni3fc_train_fwd_sync_f32(const float *xyz, const float *dino
     n.defer_stats = defer_running_stats != 0;
     Arena ar(arena, arena_bytes);
     carve(ar, B, N, k, n.w);
-    if (!ar.ok()) {
-        set_error("dvm_uni3fc_train_fwd_f32: arena too small (%zu < %zu)", arena_bytes, ar.off);
-        return DVM_ENOSPACE;
-    }
+    if (!arena_fits(ar, "dvm_uni3fc_train_fwd_f32", "arena")) return DVM_ENOSPACE;
     TrainWs &w = n.w;
     w.cv[1].y = tmp, w.cv[7].y = feat;
     hipStream_t s = (hipStream_t)stream;
@@ -532,10 +520,7 @@ DVM_EXPORT int dvm_uni3fc_train_bwd_sync_f32(const float *g_feat, const float *g
     n.coll = coll;
     Arena ar(arena, arena_bytes);
     carve(ar, B, N, k, n.w);
-    if (!ar.ok()) {
-        set_error("dvm_uni3fc_train_bwd_f32: arena too small (%zu < %zu)", arena_bytes, ar.off);
-        return DVM_ENOSPACE;
-    }
+    if (!arena_fits(ar, "dvm_uni3fc_train_bwd_f32", "arena")) return DVM_ENOSPACE;
     TrainWs &w = n.w;
     w.cv[1].y = (float *)tmp, w.cv[7].y = (float *)feat;
     hipStream_t s = (hipStream_t)stream;
@@ -633,10 +618,7 @@ DVM_EXPORT int dvm_uni3fc_train_running_stats_f32(const float *const *params, in
     TrainWs w;
     Arena ar(arena, arena_bytes);
     carve(ar, B, N, k, w);
-    if (!ar.ok()) {
-        set_error("dvm_uni3fc_train_running_stats_f32: arena too small (%zu < %zu)", arena_bytes, ar.off);
-        return DVM_ENOSPACE;
-    }
+    if (!arena_fits(ar, "dvm_uni3fc_train_running_stats_f32", "arena")) return DVM_ENOSPACE;
     float *rm[26], *rv[26];
     const float *mean[26], *var[26];
     int C[26], n = 0;

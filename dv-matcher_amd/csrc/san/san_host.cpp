@@ -104,6 +104,99 @@ int main() {
     EXPECT(dvm_rot6d_f32(nullptr, 4, nullptr, nullptr) == DVM_EINVAL);
     EXPECT(dvm_pair_geometry_f32(nullptr, nullptr, 1, 64, 64, nullptr, nullptr, 1, nullptr, 0, nullptr) == DVM_EINVAL);
     EXPECT(dvm_pair_geometry_f32(dummy, dummy, 1, 64, 64, idummy, idummy, 1, nullptr, 0, nullptr) == DVM_ENOSPACE);
+    // every entry point with a workspace: valid small sizes, a non-null workspace, one byte less than its query asks for ->
+    // DVM_ENOSPACE and a message that says what was too small, before anything is launched (the buffers are never touched)
+    {
+        const int B = 1, N = 64, M = 64, d = 128, k = 10;
+        float *const F = dummy;
+        int32_t *const I = idummy;
+        double dd[8] = {0};
+        void *const ws = dummy;
+        const float *ptab[DVM_U3_TRAIN_NPARAMS];
+        float *gtab[DVM_U3_TRAIN_NPARAMS];
+        for (int q = 0; q < DVM_U3_TRAIN_NPARAMS; ++q) ptab[q] = F, gtab[q] = F;
+        static_assert(DVM_U3_TRAIN_NPARAMS >= DVM_U3_NWEIGHTS && DVM_U3_TRAIN_NPARAMS >= DVM_CRIT_TRAIN_NPARAMS, "one table serves all three");
+        const dvm_collective coll = {[](void *, void *, size_t, int, int, void *) { return 0; }, nullptr};
+        size_t q = 0;
+#define SHORT(query, call)                                                                    \
+    do {                                                                                      \
+        q = (query);                                                                          \
+        EXPECT(q > 0);                                                                        \
+        EXPECT((call) == DVM_ENOSPACE);                                                       \
+        EXPECT(strstr(dvm_last_error(), "workspace too small") || strstr(dvm_last_error(), "arena too small")); \
+    } while (0)
+        const int det = dvm_set_deterministic(1);   // (the weight gradient uses its workspace in the deterministic mode only)
+        SHORT(dvm_linear_wgrad_workspace_bytes(4096, 128, 128), dvm_linear_wgrad_ws_f32(F, F, 4096, 128, 128, F, ws, q - 1, nullptr));
+        dvm_set_deterministic(det);
+        SHORT(dvm_softcorr_workspace_bytes(B, N, M, d), dvm_softcorr_fwd_f32(F, F, B, N, M, d, -1.f, 10, F, I, F, F, 0, ws, q - 1, nullptr));
+        SHORT(dvm_softcorr_workspace_bytes(B, N, M, 64), dvm_softcorr_fwd_f32(F, F, B, N, M, 64, -1.f, 10, F, I, F, F, 0, ws, q - 1, nullptr));
+        SHORT(dvm_softcorr_bwd_workspace_bytes(B, N, M, d), dvm_softcorr_bwd_f32(F, F, B, N, M, d, -1.f, 10, F, I, F, F, F, F, F, 0, ws, q - 1, nullptr));
+        SHORT(dvm_argmin_workspace_bytes(B, N, M, d, 0), dvm_argmin_exact_f32(F, F, B, N, M, d, I, F, ws, q - 1, nullptr));
+        SHORT(dvm_argmin_workspace_bytes(B, N, M, d, 1), dvm_argmin_pair_f32(F, F, B, N, M, d, I, I, F, F, ws, q - 1, nullptr));
+        SHORT(dvm_knn_cdist_workspace_bytes(B, N, N, 3), dvm_knn_cdist_f32(F, F, B, N, N, 3, k, I, ws, q - 1, nullptr));
+        SHORT(dvm_knn_neg_workspace_bytes(B, N, M, d, k), dvm_knn_neg_f32(F, F, B, N, M, d, k, I, ws, q - 1, nullptr));
+        SHORT(dvm_softcorr_dense_workspace_bytes(B, N, M, d), dvm_softcorr_dense_f32(F, F, B, N, M, d, -1.f, F, ws, q - 1, nullptr));
+        SHORT(dvm_softcorr_apply_bwd_workspace_bytes(B, N, M, 10), dvm_softcorr_apply_bwd_f32(F, I, F, F, B, N, M, 10, 3, F, F, ws, q - 1, nullptr));
+        SHORT(dvm_dg_build_workspace_bytes(B, N), dvm_dg_build_f32(F, B, N, I, I, I, I, F, F, dd, ws, q - 1, nullptr));
+        SHORT(dvm_chamfer_workspace_bytes(B, 8192, 8192), dvm_chamfer_fwd_f32(F, F, B, 8192, 8192, F, F, I, I, ws, q - 1, nullptr));   // (large enough for the grid form)
+        SHORT(dvm_deformer_workspace_bytes(B, N, M, N / 2),
+              dvm_deformer_fwd_f32(F, F, F, F, I, I, F, I, I, B, N, M, N / 2, k, 10, F, F, F, F, F, F, F, F, F, F, F, 0, ws, q - 1, nullptr));
+        SHORT(dvm_deformer_mlp_workspace_bytes(N), dvm_deformer_mlp_fwd_f32(F, N, F, F, F, F, F, F, F, F, F, ws, q - 1, nullptr));
+        SHORT(dvm_pos_encoding_workspace_bytes(), dvm_pos_encoding_f32(F, B, N, F, ws, q - 1, nullptr));
+        SHORT(dvm_pos_encoding_workspace_bytes(), dvm_pos_encoding_sync_f32(F, B, N, F, ws, q - 1, &coll, F, nullptr));
+        SHORT(dvm_bn_workspace_bytes(B, d, N), dvm_bn_act_train_fwd_f32(F, nullptr, F, F, B, d, N, 1e-5f, 0.2f, 0.1f, F, F, F, nullptr, nullptr, ws, q - 1, nullptr));
+        SHORT(dvm_bn_workspace_bytes(B, d, N), dvm_bn_act_train_bwd_f32(F, F, F, nullptr, F, F, F, B, d, N, 0.2f, F, F, F, ws, q - 1, nullptr));
+        SHORT(dvm_bn_pm_workspace_bytes(N, d),
+              dvm_bn_act_train_fwd_pm_f32(F, nullptr, F, F, N, d, 1e-5f, 0.2f, 0.1f, F, F, F, nullptr, nullptr, ws, q - 1, nullptr));
+        SHORT(dvm_bn_pm_workspace_bytes(N, d), dvm_bn_act_train_bwd_pm_f32(F, F, F, nullptr, F, F, F, N, d, 0.2f, F, F, F, 0, ws, q - 1, nullptr));
+        SHORT(dvm_bn_pm_groups_workspace_bytes(N, d, 2),
+              dvm_bn_act_train_fwd_pm_var_f32(F, nullptr, F, F, N, d, 2, 1e-5f, 0.2f, 0.1f, F, F, F, F, nullptr, nullptr, ws, q - 1, nullptr));
+        SHORT(dvm_bn_pm_groups_workspace_bytes(N, d, 2),
+              dvm_bn_act_train_fwd_pm_sync_f32(F, nullptr, F, F, N, d, 2, 1e-5f, 0.2f, 0.1f, F, F, F, F, nullptr, nullptr, ws, q - 1, &coll, dd, nullptr));
+        SHORT(dvm_bn_pm_groups_workspace_bytes(N, d, 2),
+              dvm_bn_act_train_bwd_pm_groups_f32(F, F, F, nullptr, F, F, F, N, d, 2, 0.2f, F, F, F, 0, ws, q - 1, nullptr));
+        SHORT(dvm_bn_pm_groups_workspace_bytes(N, d, 2),
+              dvm_bn_act_train_bwd_pm_sync_f32(F, F, F, nullptr, F, F, F, N, d, 2, 0.2f, F, F, F, 0, ws, q - 1, &coll, dd, nullptr));
+        SHORT(dvm_proj2img_workspace_bytes(B), dvm_proj2img_f32(F, B, N, F, F, F, F, ws, q - 1, nullptr));
+        SHORT(dvm_sa_attention_workspace_bytes(B, N), dvm_sa_attention_fwd_f32(F, F, B, N, F, ws, q - 1, nullptr));
+        SHORT(dvm_sa_attention_bwd_workspace_bytes(B, N), dvm_sa_attention_bwd_f32(F, F, F, F, F, F, B, N, F, F, ws, q - 1, nullptr));
+        SHORT(dvm_n2p_core_bwd_workspace_bytes(B, N, 16), dvm_n2p_core_bwd_f32(F, I, F, F, B, N, d, 16, 4, F, ws, q - 1, nullptr));
+        SHORT(dvm_dist_loss_workspace_bytes(B, N, d, 16, k), dvm_dist_loss_fwd_f32(F, F, I, B, N, d, 16, k, F, I, ws, q - 1, nullptr));
+        SHORT(dvm_map_term_workspace_bytes(B, N), dvm_map_term_f32(F, F, I, I, F, I, B, N, M, 16, 10, F, ws, q - 1, nullptr));
+        SHORT(dvm_pair_direction_workspace_bytes(B, N, M),
+              dvm_pair_direction_fwd_f32(F, F, F, F, B, N, M, -1.f, I, F, F, F, F, F, F, F, F, F, F, 1, F, F, I, F, ws, q - 1, nullptr));
+        SHORT(dvm_pair_workspace_bytes(B, N, M),
+              dvm_pair_fwd_f32(F, F, F, F, B, N, M, -1.f, I, I, F, F, F, F, F, F, F, F, F, F, 1, F, F, I, F, F, F, I, F, ws, q - 1, nullptr));
+        SHORT(dvm_pair_workspace_bytes(B, N, M),
+              dvm_pair_fwd_cached_f32(F, F, F, F, B, N, M, -1.f, I, I, F, F, F, F, F, F, F, F, F, F, 1, F, F, I, F, F, F, I, F, ws, q - 1, 1, nullptr));
+        SHORT(dvm_pair_workspace_bytes(B, N, M), dvm_pair_geometry_f32(F, F, B, N, M, I, I, 1, ws, q - 1, nullptr));
+        SHORT(dvm_uni3fc_fwd_workspace_bytes(B, N, k), dvm_uni3fc_fwd_f32(F, F, B, N, ptab, DVM_U3_NWEIGHTS, k, F, F, ws, q - 1, nullptr));
+        SHORT(dvm_uni3fc_train_workspace_bytes(B, N, k),
+              dvm_uni3fc_train_fwd_f32(F, F, B, N, ptab, DVM_U3_TRAIN_NPARAMS, k, 1e-5f, 0.1f, 1, 0, nullptr, nullptr, F, F, ws, q - 1, nullptr));
+        SHORT(dvm_uni3fc_train_workspace_bytes(B, N, k),
+              dvm_uni3fc_train_fwd_sync_f32(F, F, B, N, ptab, DVM_U3_TRAIN_NPARAMS, k, 1e-5f, 0.1f, 1, 0, nullptr, nullptr, F, F, ws, q - 1, &coll, nullptr));
+        SHORT(dvm_uni3fc_train_workspace_bytes(B, N, k),
+              dvm_uni3fc_train_bwd_f32(F, F, F, F, F, B, N, ptab, gtab, DVM_U3_TRAIN_NPARAMS, k, 1, ws, q - 1, nullptr));
+        SHORT(dvm_uni3fc_train_workspace_bytes(B, N, k),
+              dvm_uni3fc_train_bwd_sync_f32(F, F, F, F, F, B, N, ptab, gtab, DVM_U3_TRAIN_NPARAMS, k, 1, ws, q - 1, &coll, nullptr));
+        SHORT(dvm_uni3fc_train_workspace_bytes(B, N, k),
+              dvm_uni3fc_train_running_stats_f32(ptab, DVM_U3_TRAIN_NPARAMS, B, N, k, 1, 0.1f, ws, q - 1, nullptr));
+        SHORT(dvm_criterion_train_workspace_bytes(B, N, k, 10, 16, k),
+              dvm_criterion_train_fwd_f32(F, F, I, I, I, F, I, B, N, d, k, 10, -1.f, ptab, DVM_CRIT_TRAIN_NPARAMS, 1, F, F, I, I, 16, k, F, ws, q - 1, nullptr));
+        SHORT(dvm_criterion_train_workspace_bytes(B, N, k, 10, 16, k),
+              dvm_criterion_train_bwd_f32(F, F, F, I, I, I, F, I, B, N, d, k, 10, -1.f, ptab, gtab, DVM_CRIT_TRAIN_NPARAMS, 1, I, I, 16, k, F, ws, q - 1, nullptr));
+        SHORT(dvm_criterion_dir_train_workspace_bytes(B, N, M, k, 10),
+              dvm_criterion_dir_train_fwd_f32(F, F, F, F, I, I, I, F, I, I, B, N, M, d, k, 10, -1.f, ptab, DVM_CRIT_TRAIN_NPARAMS, 1, F, ws, q - 1, nullptr));
+        SHORT(dvm_criterion_dir_train_workspace_bytes(B, N, M, k, 10),
+              dvm_criterion_dir_train_bwd_f32(F, F, F, F, F, I, I, I, F, I, I, B, N, M, d, k, 10, -1.f, ptab, gtab, DVM_CRIT_TRAIN_NPARAMS, 1, F, F, ws, q - 1,
+                                              nullptr));
+#undef SHORT
+        // dvm_sa_attention_train_fwd_f32 needs no workspace at this size; where it needs one, a short one is an argument error
+        EXPECT(dvm_sa_attention_train_fwd_workspace_bytes(B, N) == 0);
+        q = dvm_sa_attention_train_fwd_workspace_bytes(1, 4995);
+        EXPECT(q > 0 && dvm_sa_attention_train_fwd_f32(F, F, 1, 4995, F, F, F, ws, q / 2, nullptr) == DVM_EINVAL);
+        EXPECT(strstr(dvm_last_error(), "workspace too small") != nullptr);
+    }
     EXPECT(dvm_graph_geodesics_f64(nullptr, nullptr, 10, 4, nullptr, nullptr) == DVM_EINVAL);
     EXPECT(dvm_profile_read(nullptr, nullptr) == DVM_EINVAL);
     EXPECT(dvm_profile_enable(0) == DVM_EINVAL);
