@@ -916,77 +916,22 @@ __global__ __launch_bounds__(256) void n2p_attention_kernel(const float *__restr
 
 // ============================================================== K10: dist loss term
 // per (b, anchor n): x_j = |feat[idx_j] - feat[a_n]|_2, y_j = dist[b, idx_j, a_n], j < k;
-// term = 1 - |cos(x, y)|;  out[b] = sum_n term.   One wave per (b, n).
-__global__ __launch_bounds__(256) void dist_loss_generic_kernel(const float *__restrict__ feat, const float *__restrict__ dist,
-                                                        const int32_t *__restrict__ anchors, const int32_t *__restrict__ idx,
-                                                        int N, int C, int nA, int k, double *__restrict__ partial) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int n = blockIdx.x * (blockDim.x >> 6) + wave;
-    const int b = blockIdx.y;
-    __shared__ double red[4];
-    double term = 0.0;
-    if (n < nA) {
-        const int a = anchors[n];
-        const float *fa = feat + ((size_t)b * N + a) * C;
-        const int32_t *ix = idx + ((size_t)b * nA + n) * k;
-        float sxy = 0.f, sxx = 0.f, syy = 0.f;
-        for (int j = lane; j < k; j += 64) {
-            const int v = ix[j];
-            const float *fv = feat + ((size_t)b * N + v) * C;
-            float s2 = 0.f;
-            for (int c = 0; c < C; c += 4) {
-                f32x4 p = *(const f32x4 *)(fv + c), q = *(const f32x4 *)(fa + c);
-                float d0 = p.x - q.x, d1 = p.y - q.y, d2 = p.z - q.z, d3 = p.w - q.w;
-                s2 = fmaf(d0, d0, s2);
-                s2 = fmaf(d1, d1, s2);
-                s2 = fmaf(d2, d2, s2);
-                s2 = fmaf(d3, d3, s2);
-            }
-            float x = sqrt_rn(s2);
-            float y = dist[((size_t)b * N + v) * N + a];
-            sxy = fmaf(x, y, sxy);
-            sxx = fmaf(x, x, sxx);
-            syy = fmaf(y, y, syy);
-        }
-        sxy = wave_sum(sxy);
-        sxx = wave_sum(sxx);
-        syy = wave_sum(syy);
-        float nx = fmaxf(sqrt_rn(sxx), 1e-8f), ny = fmaxf(sqrt_rn(syy), 1e-8f);
-        float cosv = sxy / (nx * ny);
-        term = 1.0 - (double)fabsf(cosv);
-    }
-    if (lane == 0) red[wave] = term;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[(size_t)b * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
-}
+// term = 1 - |cos(x, y)|;  out[b] = sum_n term.   One wave per (b, n), k <= 512: lane l keeps x_j, y_j of j = l + 64 u, u < 8, in
+// xs[u] / ys[u] (0 past k).  Where they come from is the only difference between the forms of the forward and of the backward
+// weights; the cosine and the weight are written once, below, so that the forms agree bit for bit.
+enum DistRows { DIST_ROWS_128, DIST_ROWS_GENERIC, DIST_ROWS_SAVED };   // C == 128 half-wave form | any C % 4 == 0 | the forward's xsave
 
-// Backward of the dist-loss term, first half: the (anchor, point) weights
-//     W[b, n, idx_j] = g[b] * d term_n / d x_j / x_j          (0 where x_j = 0; idx rows are distinct points)
-// with d term / d x_j = -sgn(cos) (y_j / (|x||y|) - cos x_j / |x|^2).  The caller finishes with plain GEMMs:
-//     d feat      = diag(colsum W) feat - W^T feat[anchors]
-//     d feat[a_n] += rowsum(W)_n feat[a_n] - (W feat)_n
-// (k = 500 neighbours x 128 channels per anchor as atomics would be 0.5 G atomics per shape batch).
-// W [B][nA][N] must be zero-filled by the caller.  One wave per (b, n), k <= 512.
-__global__ __launch_bounds__(256) void dist_loss_bwd_weights_generic_kernel(const float *__restrict__ feat, const float *__restrict__ dist,
-                                                                    const int32_t *__restrict__ anchors,
-                                                                    const int32_t *__restrict__ idx, const float *__restrict__ gterm,
-                                                                    int N, int C, int nA, int k, float *__restrict__ W) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int n = blockIdx.x * (blockDim.x >> 6) + wave;
-    const int b = blockIdx.y;
-    if (n >= nA) return;
-    const int a = anchors[n];
-    const float *fa = feat + ((size_t)b * N + a) * C;
-    const int32_t *ix = idx + ((size_t)b * nA + n) * k;
-    float xs[8], ys[8];
-    float sxy = 0.f, sxx = 0.f, syy = 0.f;
+// any C % 4 == 0: a lane streams its own rows, 16 bytes per instruction
+__device__ __forceinline__ void dist_rows_generic(const float *__restrict__ featb, const float *__restrict__ distb, int N, int C, int a,
+                                                  const int32_t *__restrict__ ix, int k, int lane, float (&xs)[8], float (&ys)[8]) {
+    const float *fa = featb + (size_t)a * C;
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
         const int j = lane + 64 * u;
         xs[u] = ys[u] = 0.f;
         if (j < k) {
             const int v = ix[j];
-            const float *fv = feat + ((size_t)b * N + v) * C;
+            const float *fv = featb + (size_t)v * C;
             float s2 = 0.f;
             for (int c = 0; c < C; c += 4) {
                 f32x4 p = *(const f32x4 *)(fv + c), q = *(const f32x4 *)(fa + c);
@@ -997,32 +942,15 @@ __global__ __launch_bounds__(256) void dist_loss_bwd_weights_generic_kernel(cons
                 s2 = fmaf(d3, d3, s2);
             }
             xs[u] = sqrt_rn(s2);
-            ys[u] = dist[((size_t)b * N + v) * N + a];
-            sxy = fmaf(xs[u], ys[u], sxy);
-            sxx = fmaf(xs[u], xs[u], sxx);
-            syy = fmaf(ys[u], ys[u], syy);
+            ys[u] = distb[(size_t)v * N + a];
         }
-    }
-    sxy = wave_sum(sxy);
-    sxx = wave_sum(sxx);
-    syy = wave_sum(syy);
-    const float nx = fmaxf(sqrt_rn(sxx), 1e-8f), ny = fmaxf(sqrt_rn(syy), 1e-8f);
-    const float cosv = sxy / (nx * ny);
-    const float sg = cosv > 0.f ? -1.f : (cosv < 0.f ? 1.f : 0.f);  // d(1 - |cos|)/d cos
-    const float g = gterm[b] * sg;
-    const float inv = 1.f / (nx * ny), cx = cosv / (nx * nx);
-    float *Wr = W + ((size_t)b * nA + n) * N;
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-        const int j = lane + 64 * u;
-        if (j < k && xs[u] > 0.f) Wr[ix[j]] = g * (ys[u] * inv - cx * xs[u]) / xs[u];
     }
 }
 
-// C = 128 (LG-Net's feature width), k <= 512: the rows above are read by 64 lanes streaming 64 DIFFERENT rows, 16 bytes
+// C = 128 (LG-Net's feature width), k <= 512: dist_rows_generic's 64 lanes stream 64 DIFFERENT rows, 16 bytes
 // each per instruction — 64 cache lines per load, every line fetched 8 times (0.55 ms per call at 8 x 1000 anchors x 500
 // neighbours).  Here a 32-lane half reads ONE whole row per instruction (512 contiguous bytes), the half's partial sums
-// are combined on the DPP network, and lane j % 64 keeps x_j, so that what follows is the arithmetic of the kernels above.
+// are combined on the DPP network, and lane j % 64 keeps x_j, so that what follows is the same arithmetic.
 __device__ __forceinline__ void dist_rows128(const float *__restrict__ featb, const float *__restrict__ distb, int N, int a,
                                              const int32_t *__restrict__ ix, int k, int lane, float (&xs)[8], float (&ys)[8]) {
     const int half = lane >> 5, l = lane & 31;
@@ -1066,9 +994,39 @@ __device__ __forceinline__ void dist_rows128(const float *__restrict__ featb, co
     }
 }
 
+// cos(x, y) of a wave's k pairs: per lane the three fmaf chains over u = 0..7 (the slots past k add +0 to sums that are never -0),
+// wave_sum, norms floored at 1e-8
+__device__ __forceinline__ float dist_cos(const float (&xs)[8], const float (&ys)[8], float &nx, float &ny) {
+    float sxy = 0.f, sxx = 0.f, syy = 0.f;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+        sxy = fmaf(xs[u], ys[u], sxy);
+        sxx = fmaf(xs[u], xs[u], sxx);
+        syy = fmaf(ys[u], ys[u], syy);
+    }
+    sxy = wave_sum(sxy);
+    sxx = wave_sum(sxx);
+    syy = wave_sum(syy);
+    nx = fmaxf(sqrt_rn(sxx), 1e-8f), ny = fmaxf(sqrt_rn(syy), 1e-8f);
+    return sxy / (nx * ny);
+}
+// W[b, n, idx_j] = g * d term / d x_j / x_j for x_j > 0, with d term / d x_j = -sgn(cos) (y_j / (|x||y|) - cos x_j / |x|^2): an anchor's
+// coefficients once, then a weight per (x_j, y_j)
+struct DistWeight {
+    float g, inv, cx;
+    __device__ __forceinline__ DistWeight(float gterm, float cosv, float nx, float ny) {
+        const float sg = cosv > 0.f ? -1.f : (cosv < 0.f ? 1.f : 0.f);  // d(1 - |cos|)/d cos
+        g = gterm * sg;
+        inv = 1.f / (nx * ny), cx = cosv / (nx * nx);
+    }
+    __device__ __forceinline__ float operator()(float x, float y) const { return g * (y * inv - cx * x) / x; }
+};
+
+// the forward: one partial per workgroup of 4 anchors, the four terms added pairwise (r0 + r1) + (r2 + r3) — NOT the map term's order
+template <DistRows ROWS>
 __global__ __launch_bounds__(256) void dist_loss_kernel(const float *__restrict__ feat, const float *__restrict__ dist,
                                                         const int32_t *__restrict__ anchors, const int32_t *__restrict__ idx,
-                                                        int N, int nA, int k, double *__restrict__ partial,
+                                                        int N, int C, int nA, int k, double *__restrict__ partial,
                                                         float *__restrict__ xsave /* nullptr, or [B][nA][k] x 2: x_j, y_j kept for the backward */) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int n = blockIdx.x * (blockDim.x >> 6) + wave;
@@ -1076,108 +1034,73 @@ __global__ __launch_bounds__(256) void dist_loss_kernel(const float *__restrict_
     __shared__ double red[4];
     double term = 0.0;
     if (n < nA) {
-        float xs[8], ys[8];
-        dist_rows128(feat + (size_t)b * N * 128, dist + (size_t)b * N * N, N, anchors[n], idx + ((size_t)b * nA + n) * k, k, lane, xs, ys);
+        float xs[8], ys[8], nx, ny;
+        const int32_t *ix = idx + ((size_t)b * nA + n) * k;
+        if (ROWS == DIST_ROWS_128) dist_rows128(feat + (size_t)b * N * 128, dist + (size_t)b * N * N, N, anchors[n], ix, k, lane, xs, ys);
+        else dist_rows_generic(feat + (size_t)b * N * C, dist + (size_t)b * N * N, N, C, anchors[n], ix, k, lane, xs, ys);
         if (xsave) {
             float *xr = xsave + ((size_t)b * nA + n) * k * 2;
 #pragma unroll
             for (int u = 0; u < 8; ++u)
                 if (lane + 64 * u < k) xr[lane + 64 * u] = xs[u], xr[k + lane + 64 * u] = ys[u];
         }
-        float sxy = 0.f, sxx = 0.f, syy = 0.f;
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            sxy = fmaf(xs[u], ys[u], sxy);
-            sxx = fmaf(xs[u], xs[u], sxx);
-            syy = fmaf(ys[u], ys[u], syy);
-        }
-        sxy = wave_sum(sxy);
-        sxx = wave_sum(sxx);
-        syy = wave_sum(syy);
-        const float nx = fmaxf(sqrt_rn(sxx), 1e-8f), ny = fmaxf(sqrt_rn(syy), 1e-8f);
-        term = 1.0 - (double)fabsf(sxy / (nx * ny));
+        term = 1.0 - (double)fabsf(dist_cos(xs, ys, nx, ny));
     }
     if (lane == 0) red[wave] = term;
     __syncthreads();
     if (threadIdx.x == 0) partial[(size_t)b * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-__global__ __launch_bounds__(256) void dist_loss_bwd_weights_kernel(const float *__restrict__ feat, const float *__restrict__ dist,
+// Backward of the dist-loss term, first half: the (anchor, point) weights
+//     W[b, n, idx_j] = g[b] * d term_n / d x_j / x_j          (0 where x_j = 0; idx rows are distinct points)
+// The caller finishes with plain GEMMs:
+//     d feat      = diag(colsum W) feat - W^T feat[anchors]
+//     d feat[a_n] += rowsum(W)_n feat[a_n] - (W feat)_n
+// (k = 500 neighbours x 128 channels per anchor as atomics would be 0.5 G atomics per shape batch).
+// W [B][nA][N] must be zero-filled by the caller.  One wave per (b, n), k <= 512.  x_j, y_j are recomputed from the feature rows, or,
+// DIST_ROWS_SAVED, read from what the forward kept (`rows` = its xsave: no second pass over the feature rows), and then also the row
+// sums rs [B][nA] = sum_v W[b, n, v] (in lane order + a wave reduction).  gterm read at gterm[b * gstride].
+template <DistRows ROWS>
+__global__ __launch_bounds__(256) void dist_loss_bwd_weights_kernel(const float *__restrict__ rows /* feat, or xsave */, const float *__restrict__ dist,
                                                                     const int32_t *__restrict__ anchors,
                                                                     const int32_t *__restrict__ idx, const float *__restrict__ gterm,
-                                                                    int N, int nA, int k, float *__restrict__ W) {
+                                                                    int gstride, int N, int C, int nA, int k, float *__restrict__ W,
+                                                                    float *__restrict__ rs) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int n = blockIdx.x * (blockDim.x >> 6) + wave;
     const int b = blockIdx.y;
     if (n >= nA) return;
     const int32_t *ix = idx + ((size_t)b * nA + n) * k;
-    float xs[8], ys[8];
-    dist_rows128(feat + (size_t)b * N * 128, dist + (size_t)b * N * N, N, anchors[n], ix, k, lane, xs, ys);
-    float sxy = 0.f, sxx = 0.f, syy = 0.f;
+    float xs[8], ys[8], nx, ny;
+    if (ROWS == DIST_ROWS_128) {
+        dist_rows128(rows + (size_t)b * N * 128, dist + (size_t)b * N * N, N, anchors[n], ix, k, lane, xs, ys);
+    } else if (ROWS == DIST_ROWS_GENERIC) {
+        dist_rows_generic(rows + (size_t)b * N * C, dist + (size_t)b * N * N, N, C, anchors[n], ix, k, lane, xs, ys);
+    } else {
+        const float *xr = rows + ((size_t)b * nA + n) * k * 2;
 #pragma unroll
-    for (int u = 0; u < 8; ++u) {
-        sxy = fmaf(xs[u], ys[u], sxy);
-        sxx = fmaf(xs[u], xs[u], sxx);
-        syy = fmaf(ys[u], ys[u], syy);
+        for (int u = 0; u < 8; ++u) {
+            const int j = lane + 64 * u;
+            xs[u] = j < k ? xr[j] : 0.f, ys[u] = j < k ? xr[k + j] : 0.f;
+        }
     }
-    sxy = wave_sum(sxy);
-    sxx = wave_sum(sxx);
-    syy = wave_sum(syy);
-    const float nx = fmaxf(sqrt_rn(sxx), 1e-8f), ny = fmaxf(sqrt_rn(syy), 1e-8f);
-    const float cosv = sxy / (nx * ny);
-    const float sg = cosv > 0.f ? -1.f : (cosv < 0.f ? 1.f : 0.f);  // d(1 - |cos|)/d cos
-    const float g = gterm[b] * sg;
-    const float inv = 1.f / (nx * ny), cx = cosv / (nx * nx);
-    float *Wr = W + ((size_t)b * nA + n) * N;
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-        const int j = lane + 64 * u;
-        if (j < k && xs[u] > 0.f) Wr[ix[j]] = g * (ys[u] * inv - cx * xs[u]) / xs[u];
-    }
-}
-
-// the same weights from the x_j, y_j the forward kept (dist_loss_kernel's xsave): no second pass over the feature rows; also the row
-// sums rs [B][nA] = sum_v W[b, n, v] (in lane order + a wave reduction).  gterm read at gterm[b * gstride].
-__global__ __launch_bounds__(256) void dist_loss_bwd_weights_saved_kernel(const float *__restrict__ xsave, const int32_t *__restrict__ idx,
-                                                                          const float *__restrict__ gterm, int gstride, int N, int nA, int k,
-                                                                          float *__restrict__ W, float *__restrict__ rs) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int n = blockIdx.x * (blockDim.x >> 6) + wave;
-    const int b = blockIdx.y;
-    if (n >= nA) return;
-    const int32_t *ix = idx + ((size_t)b * nA + n) * k;
-    const float *xr = xsave + ((size_t)b * nA + n) * k * 2;
-    float xs[8], ys[8];
-    float sxy = 0.f, sxx = 0.f, syy = 0.f;
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-        const int j = lane + 64 * u;
-        xs[u] = j < k ? xr[j] : 0.f, ys[u] = j < k ? xr[k + j] : 0.f;
-        sxy = fmaf(xs[u], ys[u], sxy);
-        sxx = fmaf(xs[u], xs[u], sxx);
-        syy = fmaf(ys[u], ys[u], syy);
-    }
-    sxy = wave_sum(sxy);
-    sxx = wave_sum(sxx);
-    syy = wave_sum(syy);
-    const float nx = fmaxf(sqrt_rn(sxx), 1e-8f), ny = fmaxf(sqrt_rn(syy), 1e-8f);
-    const float cosv = sxy / (nx * ny);
-    const float sg = cosv > 0.f ? -1.f : (cosv < 0.f ? 1.f : 0.f);
-    const float g = gterm[(size_t)b * gstride] * sg;
-    const float inv = 1.f / (nx * ny), cx = cosv / (nx * nx);
+    const float cosv = dist_cos(xs, ys, nx, ny);
+    const DistWeight weight(gterm[(size_t)b * gstride], cosv, nx, ny);
     float *Wr = W + ((size_t)b * nA + n) * N;
     float acc = 0.f;
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
         const int j = lane + 64 * u;
         if (j < k && xs[u] > 0.f) {
-            const float wv = g * (ys[u] * inv - cx * xs[u]) / xs[u];
+            const float wv = weight(xs[u], ys[u]);
             Wr[ix[j]] = wv;
             acc += wv;
         }
     }
-    acc = wave_sum(acc);
-    if (lane == 0) rs[(size_t)b * nA + n] = acc;
+    if (ROWS == DIST_ROWS_SAVED) {
+        acc = wave_sum(acc);
+        if (lane == 0) rs[(size_t)b * nA + n] = acc;
+    }
 }
 
 __global__ void gather_rows_kernel(const float *__restrict__ src, const int32_t *__restrict__ rows, int N, int C, int nR,
@@ -1423,11 +1346,13 @@ DVM_EXPORT int dvm_dist_loss_bwd_weights_f32(const float *feat, const float *dis
     DVM_REQUIRE(k >= 1 && k <= 512 && k <= N, "dvm_dist_loss_bwd_weights_f32: k=%d unsupported", k);
     hipStream_t s = (hipStream_t)stream;
     (void)hipMemsetAsync(W, 0, (size_t)B * nA * N * sizeof(float), s);
+    const dim3 grid((nA + 3) / 4, B);
     if (C == 128)
-        hipLaunchKernelGGL(dist_loss_bwd_weights_kernel, dim3((nA + 3) / 4, B), dim3(256), 0, s, feat, dist, anchors, idx, g_out, N, nA, k, W);
+        hipLaunchKernelGGL(dist_loss_bwd_weights_kernel<DIST_ROWS_128>, grid, dim3(256), 0, s, feat, dist, anchors, idx, g_out, 1, N, C, nA, k, W,
+                           (float *)nullptr);
     else
-        hipLaunchKernelGGL(dist_loss_bwd_weights_generic_kernel, dim3((nA + 3) / 4, B), dim3(256), 0, s, feat, dist, anchors, idx, g_out, N, C, nA,
-                           k, W);
+        hipLaunchKernelGGL(dist_loss_bwd_weights_kernel<DIST_ROWS_GENERIC>, grid, dim3(256), 0, s, feat, dist, anchors, idx, g_out, 1, N, C, nA, k, W,
+                           (float *)nullptr);
     DVM_CHECK_LAUNCH("dist_loss_bwd_weights");
     return DVM_OK;
 }
@@ -1447,7 +1372,7 @@ static size_t carve_dist_loss(Arena &ar, int B, int N, int C, int nA, int k, Dis
     return carve_knn_neg(ar, B, nA, N, w.knn);
 }
 // dvm_dist_loss_fwd_f32 with the sum written at out[b * out_stride + out_off], the selected neighbours at idx_out (NULL: scratch) and, for
-// a backward that does not read the feature rows again (C == 128), x_j / y_j at xsave [B][nA][k] x 2; fa_out [B][nA][C] = the anchors' rows
+// a backward that does not read the feature rows again, x_j / y_j at xsave [B][nA][k] x 2; fa_out [B][nA][C] = the anchors' rows
 int launch_dist_loss_fwd(const float *feat, const float *dist, const int32_t *anchors, int B, int N, int C, int nA, int k, float *out, int out_stride,
                          int out_off, int32_t *idx_out, float *xsave, float *fa_out, void *ws, size_t ws_bytes, hipStream_t s) {
     DistLossWs w;
@@ -1459,10 +1384,10 @@ int launch_dist_loss_fwd(const float *feat, const float *dist, const int32_t *an
     hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)(((long)nA * C + 255) / 256), B), dim3(256), 0, s, feat, anchors, N, C, nA,
                        fa);
     launch_knn_neg(fa, feat, B, nA, N, C, k, idx, w.knn.na, w.knn.nb, w.knn.S, s);
-    if (C == 128 && k <= 512)
-        hipLaunchKernelGGL(dist_loss_kernel, dim3(nblk, B), dim3(256), 0, s, feat, dist, anchors, idx, N, nA, k, partial, xsave);
+    if (C == 128)
+        hipLaunchKernelGGL(dist_loss_kernel<DIST_ROWS_128>, dim3(nblk, B), dim3(256), 0, s, feat, dist, anchors, idx, N, C, nA, k, partial, xsave);
     else
-        hipLaunchKernelGGL(dist_loss_generic_kernel, dim3(nblk, B), dim3(256), 0, s, feat, dist, anchors, idx, N, C, nA, k, partial);
+        hipLaunchKernelGGL(dist_loss_kernel<DIST_ROWS_GENERIC>, dim3(nblk, B), dim3(256), 0, s, feat, dist, anchors, idx, N, C, nA, k, partial, xsave);
     launch_reduce_partials(partial, B, nblk, 1.f, out, out_stride, out_off, s);
     return DVM_OK;
 }
@@ -1470,7 +1395,8 @@ int launch_dist_loss_fwd(const float *feat, const float *dist, const int32_t *an
 void launch_dist_loss_bwd_weights_saved(const float *xsave, const int32_t *idx, const float *gterm, int gstride, int B, int N, int nA, int k, float *W,
                                         float *rs, hipStream_t s) {
     (void)hipMemsetAsync(W, 0, (size_t)B * nA * N * sizeof(float), s);
-    hipLaunchKernelGGL(dist_loss_bwd_weights_saved_kernel, dim3((nA + 3) / 4, B), dim3(256), 0, s, xsave, idx, gterm, gstride, N, nA, k, W, rs);
+    hipLaunchKernelGGL(dist_loss_bwd_weights_kernel<DIST_ROWS_SAVED>, dim3((nA + 3) / 4, B), dim3(256), 0, s, xsave, (const float *)nullptr,
+                       (const int32_t *)nullptr, idx, gterm, gstride, N, 0, nA, k, W, rs);
 }
 }  // namespace dvm
 

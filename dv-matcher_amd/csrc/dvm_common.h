@@ -411,6 +411,19 @@ __device__ __forceinline__ double wave_sum(double v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+// Sum of one double per thread of a 256-THREAD workgroup, returned in every thread: the fixed tree red[t] += red[t + o],
+// o = 128, 64, .. 1, a barrier per level.  Every fixed-order fp64 reduction of the loss scalars ends in this one tree (the
+// map term's and the dist term's four-wave block sums are other orders and stay with their kernels).
+__device__ __forceinline__ double block_tree_sum(double s) {
+    __shared__ double red[256];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    return red[0];
+}
 
 }  // namespace dvm
 

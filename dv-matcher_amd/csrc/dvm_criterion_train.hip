@@ -146,31 +146,19 @@ __global__ __launch_bounds__(64) void colsum_any_final_kernel(const float *__res
 }
 // out[0] += sum of n floats, fixed order (double partials)
 __global__ __launch_bounds__(256) void sum_all_partial_kernel(const f32x4 *__restrict__ x, long n4, double *__restrict__ partial) {
-    __shared__ double red[256];
     double s = 0.0;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
         const f32x4 v = x[i];
         s += (double)((v.x + v.y) + (v.z + v.w));
     }
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+    s = block_tree_sum(s);
+    if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 __global__ __launch_bounds__(256) void sum_all_final_kernel(const double *__restrict__ partial, int n, float *__restrict__ out) {
-    __shared__ double red[256];
     double s = 0.0;
     for (int i = threadIdx.x; i < n; i += 256) s += partial[i];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) atomicAdd(out, (float)red[0]);
+    s = block_tree_sum(s);
+    if (threadIdx.x == 0) atomicAdd(out, (float)s);
 }
 
 // d z [P][Nn][262] back to its sources, first half: d verts12[v] += dz[131:134], and the Pi~ gp^T part as compact rows g2t_c [P][Nn][128]

@@ -495,25 +495,6 @@ void launch_pool_all(const float *feat, const int32_t *idx, int B, int P, int k,
                        (const int32_t *)nullptr, P, P, k, cw, cb, out, DF_C, 0, order);
     prof_end(s, DVM_PROF_POOL);
 }
-void launch_assemble_pooled(const float *vsrc, const float *vcorr, const float *gsrc, const float *gtgt, const float *pi_val,
-                            const int32_t *pi_idx, const int32_t *fps, int B, int N, int M, int Nn, float *z, hipStream_t s, const int *gate) {
-    AssembleArgs a;
-    a.d[0] = a.d[1] = AssembleSide{vsrc, vcorr, gsrc, gtgt, pi_val, pi_idx, fps, N, M, Nn, z};
-    a.topk = 10, a.gate = gate;
-    if (!gate) prof_begin(s, DVM_PROF_ASSEMBLE);
-    hipLaunchKernelGGL(assemble_pooled_kernel<10>, dim3((unsigned)(((long)Nn * 32 + 255) / 256), B, 1), dim3(256), 0, s, a);
-    if (!gate) prof_end(s, DVM_PROF_ASSEMBLE);
-}
-// the rows in the plane form (zp: row (b, n) at ((b Nn + n) MH_SZ) bytes)
-void launch_assemble_pooled_planes(const float *vsrc, const float *vcorr, const float *gsrc, const float *gtgt, const float *pi_val,
-                                   const int32_t *pi_idx, const int32_t *fps, int B, int N, int M, int Nn, void *zp, hipStream_t s) {
-    AssembleArgs a;
-    a.d[0] = a.d[1] = AssembleSide{vsrc, vcorr, gsrc, gtgt, pi_val, pi_idx, fps, N, M, Nn, (float *)zp};
-    a.topk = 10, a.gate = nullptr;
-    prof_begin(s, DVM_PROF_ASSEMBLE);
-    hipLaunchKernelGGL((assemble_pooled_kernel<10, true>), dim3((unsigned)(((long)Nn * 32 + 255) / 256), B, 1), dim3(256), 0, s, a);
-    prof_end(s, DVM_PROF_ASSEMBLE);
-}
 // both directions of the pair path in one launch: side 0 = (clouds 1 -> 2), side 1 = (2 -> 1); planes: the plane form (zp*), else the
 // fp32 rows behind `gate`
 void launch_assemble_pooled_pair(const float *verts1, const float *verts2, const float *verts12, const float *verts21, const float *g1,

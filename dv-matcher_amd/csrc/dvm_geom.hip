@@ -126,11 +126,29 @@ __global__ __launch_bounds__(128) void knn_cdist_kernel(const float *__restrict_
             if (t < k) idx[((size_t)b * N + i) * k + t] = t < M ? kb.idx[t] : 0;
 }
 
+__shared__ float4 tile3[KN_PT];   // (per kernel that names it)
+// One tile of the brute-force scans below (between two barriers): the next KN_PT points of a cloud, `left` of them real, from
+// tp [left][3] into LDS as (x, y, z, w).  w is the caller's — |p|^2 in ATen order (the matmul form's operand) where NORM, else
+// 0 — and the rows past the cloud's end are (0, 0, 0, pad_w).
+template <bool NORM>
+__device__ __forceinline__ void stage_tile3(const float *tp, int left, float pad_w) {
+    __syncthreads();
+    for (int e = threadIdx.x; e < KN_PT; e += blockDim.x) {
+        float4 p = {0.f, 0.f, 0.f, pad_w};
+        if (e < left) {
+            const float *pp = tp + 3 * e;
+            p.x = pp[0], p.y = pp[1], p.z = pp[2];
+            p.w = NORM ? sumsq3(p.x, p.y, p.z) : 0.f;
+        }
+        tile3[e] = p;
+    }
+    __syncthreads();
+}
+
 // specialisation for C == 3 (the only shape on the hot path): coordinates in registers
 template <int K>
 __global__ __launch_bounds__(128) void knn_cdist3_kernel(const float *__restrict__ x, const float *__restrict__ y, int N,
                                                          int M, int k, int32_t *__restrict__ idx) {
-    __shared__ float4 pts[KN_PT];  // x,y,z,|p|^2
     const int b = blockIdx.y;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const int ic = i < N ? i : N - 1;
@@ -141,21 +159,11 @@ __global__ __launch_bounds__(128) void knn_cdist3_kernel(const float *__restrict
     kb.init(INFINITY);
     const float *yb = y + (size_t)b * M * 3;
     for (int j0 = 0; j0 < M; j0 += KN_PT) {
-        __syncthreads();
-        for (int e = threadIdx.x; e < KN_PT; e += blockDim.x) {
-            float4 p = {0.f, 0.f, 0.f, INFINITY};
-            if (j0 + e < M) {
-                const float *pp = yb + (size_t)(j0 + e) * 3;
-                p.x = pp[0], p.y = pp[1], p.z = pp[2];
-                p.w = sumsq3(p.x, p.y, p.z);
-            }
-            pts[e] = p;
-        }
-        __syncthreads();
+        stage_tile3<true>(yb + (size_t)j0 * 3, M - j0, INFINITY);
         int lim = M - j0 < KN_PT ? M - j0 : KN_PT;
 #pragma unroll 4
         for (int j = 0; j < lim; ++j) {
-            float4 p = pts[j];
+            float4 p = tile3[j];
             float d2 = d2_mm3(qx, qy, qz, nq, p.x, p.y, p.z, p.w);
             kb.insert(sqrt_rn(d2), j0 + j);
         }
@@ -430,7 +438,6 @@ __global__ __launch_bounds__(256) void apply_bwd_gather_kernel(const float *__re
 // d1[i] = min_j |a_i - b_j|^2 ((dx^2+dy^2)+dz^2, no contraction), first minimum wins.
 __global__ __launch_bounds__(128) void chamfer_kernel(const float *__restrict__ a, const float *__restrict__ bpts, int N,
                                                       int M, float *__restrict__ dout, int32_t *__restrict__ iout) {
-    __shared__ float4 pts[KN_PT];
     const int b = blockIdx.y;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const int ic = i < N ? i : N - 1;
@@ -440,20 +447,11 @@ __global__ __launch_bounds__(128) void chamfer_kernel(const float *__restrict__ 
     int bj = 0;
     const float *yb = bpts + (size_t)b * M * 3;
     for (int j0 = 0; j0 < M; j0 += KN_PT) {
-        __syncthreads();
-        for (int e = threadIdx.x; e < KN_PT; e += blockDim.x) {
-            float4 p = {0.f, 0.f, 0.f, 0.f};
-            if (j0 + e < M) {
-                const float *pp = yb + (size_t)(j0 + e) * 3;
-                p.x = pp[0], p.y = pp[1], p.z = pp[2];
-            }
-            pts[e] = p;
-        }
-        __syncthreads();
+        stage_tile3<false>(yb + (size_t)j0 * 3, M - j0, 0.f);
         int lim = M - j0 < KN_PT ? M - j0 : KN_PT;
 #pragma unroll 4
         for (int j = 0; j < lim; ++j) {
-            float4 p = pts[j];
+            float4 p = tile3[j];
             float dv = d2_diff3(qx, qy, qz, p.x, p.y, p.z);
             if (dv < best) {
                 best = dv;
@@ -506,50 +504,41 @@ __global__ __launch_bounds__(256) void chamfer_split_kernel(const float *__restr
     }
 }
 
-// grouped form: up to 8 independent (a -> b) nearest-neighbour problems in one launch
-struct ChGroup {
-    const float *a, *b;
-    int Na, Nb;
-    float *dout;
-};
-struct ChArgs {
-    ChGroup g[8];
-};
-__global__ __launch_bounds__(128) void chamfer_grouped_kernel(const ChArgs args) {
-    __shared__ float4 pts[KN_PT];
-    const ChGroup &G = args.g[blockIdx.z];
-    const int N = G.Na, M = G.Nb;
-    if ((int)(blockIdx.x * blockDim.x) >= N) return;  // uniform per block
-    const int b = blockIdx.y;
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const int ic = i < N ? i : N - 1;
-    const float *qp = G.a + ((size_t)b * N + ic) * 3;
-    const float qx = qp[0], qy = qp[1], qz = qp[2];
-    float best = INFINITY;
-    const float *yb = G.b + (size_t)b * M * 3;
-    for (int j0 = 0; j0 < M; j0 += KN_PT) {
-        __syncthreads();
-        for (int e = threadIdx.x; e < KN_PT; e += blockDim.x) {
-            float4 p = {0.f, 0.f, 0.f, 0.f};
-            if (j0 + e < M) {
-                const float *pp = yb + (size_t)(j0 + e) * 3;
-                p.x = pp[0], p.y = pp[1], p.z = pp[2];
-            }
-            pts[e] = p;
-        }
-        __syncthreads();
-        int lim = M - j0 < KN_PT ? M - j0 : KN_PT;
-#pragma unroll 4
-        for (int j = 0; j < lim; ++j) {
-            float4 p = pts[j];
-            float dv = d2_diff3(qx, qy, qz, p.x, p.y, p.z);
-            best = dv < best ? dv : best;
+// ---------------------------------------------------------------- map-loss numerator
+// The pieces every form of the map term shares, so that the forms agree bit for bit.
+// One slot's residual from the TOPK weights and the TOPK coordinates already gathered: e = p12 - sum_t w[t] p[t], the products
+// summed by fmaf in t order over t < topk (the row's own order, not the dense matmul's column order: a loss term, compared at
+// 1e-4); returns (e0^2 + e1^2) + e2^2.
+template <int TOPK>
+__device__ __forceinline__ float map_term_resid(const float (&w)[TOPK], const float (&px)[TOPK], const float (&py)[TOPK],
+                                                const float (&pz)[TOPK], int topk, float p12x, float p12y, float p12z, float &e0,
+                                                float &e1, float &e2c) {
+    float acc[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (int t = 0; t < TOPK; ++t) {
+        if (t < topk) {
+            acc[0] = fmaf(w[t], px[t], acc[0]);
+            acc[1] = fmaf(w[t], py[t], acc[1]);
+            acc[2] = fmaf(w[t], pz[t], acc[2]);
         }
     }
-    if (i < N) G.dout[(size_t)b * N + i] = best;
+    e0 = p12x - acc[0], e1 = p12y - acc[1], e2c = p12z - acc[2];
+    return (e0 * e0 + e1 * e1) + e2c * e2c;
+}
+// Epilogue of the 256-thread (point, slot) forms: a wave's sum in double, the block's four wave sums added in order
+// (((0 + r0) + r1) + r2) + r3 — NOT the pairwise order of the dist term — one partial per block.
+__device__ __forceinline__ void map_term_block_partial(float e2, int b, double *__restrict__ partial) {
+    __shared__ double red[256 / 64];
+    const double w = wave_sum((double)e2);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = w;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+        for (int q = 0; q < 256 / 64; ++q) s += red[q];
+        partial[(size_t)b * gridDim.x + blockIdx.x] = s;
+    }
 }
 
-// ---------------------------------------------------------------- map-loss numerator
 // thread per (i, s): e_c = verts12[idx11[i,s],c] - sum_t P[i,t] verts2[idx22[pidx[i,t],s],c]
 template <int TOPK>
 __global__ __launch_bounds__(256) void map_term_kernel(const float *__restrict__ verts12, const float *__restrict__ verts2,
@@ -563,8 +552,6 @@ __global__ __launch_bounds__(256) void map_term_kernel(const float *__restrict__
     if (g < (long)N * k) {
         const int i = (int)(g / k), s = (int)(g % k);
         const size_t row = (size_t)b * N + i;
-        // (a loss term, compared at 1e-4: the ten products are summed in the row's own order — sorting them by column
-        // to mimic the dense matmul's order, once per (i, s) thread, was most of this kernel's instructions)
         const float *v2 = verts2 + (size_t)b * M * 3;
         const int32_t *i22 = idx22 + (size_t)b * M * k;
         int nb[TOPK];
@@ -586,33 +573,15 @@ __global__ __launch_bounds__(256) void map_term_kernel(const float *__restrict__
             const float *p = v2 + 3 * (size_t)nb[t];
             px[t] = p[0], py[t] = p[1], pz[t] = p[2];
         }
-        float acc[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-        for (int t = 0; t < TOPK; ++t) {
-            if (t < topk) {
-                acc[0] = fmaf(v[t], px[t], acc[0]);
-                acc[1] = fmaf(v[t], py[t], acc[1]);
-                acc[2] = fmaf(v[t], pz[t], acc[2]);
-            }
-        }
         const float *p12 = verts12 + ((size_t)b * N + idx11[row * k + s]) * 3;
-        float e0 = p12[0] - acc[0], e1 = p12[1] - acc[1], e2c = p12[2] - acc[2];
-        e2 = (e0 * e0 + e1 * e1) + e2c * e2c;
+        float e0, e1, e2c;
+        e2 = map_term_resid<TOPK>(v, px, py, pz, topk, p12[0], p12[1], p12[2], e0, e1, e2c);
         if (resid) {
             float *r = resid + ((size_t)b * N * k + g) * 3;
             r[0] = e0, r[1] = e1, r[2] = e2c;
         }
     }
-    // block reduction in double, fixed order
-    __shared__ double red[256 / 64];
-    double w = wave_sum((double)e2);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = w;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double s = 0.0;
-        for (int q = 0; q < (int)(blockDim.x >> 6); ++q) s += red[q];
-        partial[(size_t)b * gridDim.x + blockIdx.x] = s;
-    }
+    map_term_block_partial(e2, b, partial);
 }
 
 // Round 4: the map term with the TARGET side resident in LDS — one workgroup of 1024 threads per cloud stages verts2 (12 M bytes)
@@ -714,7 +683,9 @@ __global__ __launch_bounds__(1024) void map_term_lds_kernel(const MapTermArgs ar
             }
             // Pi-weighted sums of the targets' neighbour coordinates: slot s of correspondence t is neighbour s of column col[t]; a
             // correspondence's K neighbour indices are one 40-byte LDS row (five 8-byte reads), a coordinate one 16-byte read; the
-            // sum over t runs in t order for every slot (the order of the (point, slot) form)
+            // sum over t runs in t order for every slot (the order of the (point, slot) form).  map_term_resid's arithmetic, written out:
+            // with all K slots of a point in one thread the chains advance together, one correspondence's index row at a time, and
+            // gathering a slot's TOPK coordinates first (the helper's shape) costs 32 registers or spills (profiles/notes_loss_kernels.md)
             float acc[K][3];
 #pragma unroll
             for (int s = 0; s < K; ++s) acc[s][0] = acc[s][1] = acc[s][2] = 0.f;
@@ -773,87 +744,38 @@ __global__ __launch_bounds__(256) void map_term_nbr_kernel(const float *__restri
         const int i = (int)(g / k), s = (int)(g % k);
         const size_t row = (size_t)b * N + i;
         const float *nb2 = nbr2 + (size_t)b * M * k * 3 + 3 * s;
-        float acc[3] = {0.f, 0.f, 0.f};
-        if (topk == TOPK) {   // (uniform) the usual case without predicates: columns and weights, then all gathers, then the chain
-            int col[TOPK];
-            float w[TOPK], px[TOPK], py[TOPK], pz[TOPK];
+        // columns and weights, then all gathers, then the chain: addresses clamped, values selected by the chain's t < topk
+        int col[TOPK];
+        float w[TOPK], px[TOPK], py[TOPK], pz[TOPK];
 #pragma unroll
-            for (int t = 0; t < TOPK; ++t) col[t] = pi_idx[row * TOPK + t], w[t] = pi_val[row * TOPK + t];
+        for (int t = 0; t < TOPK; ++t) {
+            const size_t o = row * topk + (t < topk ? t : 0);
+            col[t] = pi_idx[o], w[t] = pi_val[o];
+        }
 #pragma unroll
-            for (int t = 0; t < TOPK; ++t) {
-                const float *p = nb2 + (size_t)col[t] * k * 3;
-                px[t] = p[0], py[t] = p[1], pz[t] = p[2];
-            }
-#pragma unroll
-            for (int t = 0; t < TOPK; ++t) {
-                acc[0] = fmaf(w[t], px[t], acc[0]);
-                acc[1] = fmaf(w[t], py[t], acc[1]);
-                acc[2] = fmaf(w[t], pz[t], acc[2]);
-            }
-        } else {
-#pragma unroll
-            for (int t = 0; t < TOPK; ++t) {
-                if (t < topk) {
-                    const float *p = nb2 + (size_t)pi_idx[row * topk + t] * k * 3;
-                    const float w = pi_val[row * topk + t];
-                    acc[0] = fmaf(w, p[0], acc[0]);
-                    acc[1] = fmaf(w, p[1], acc[1]);
-                    acc[2] = fmaf(w, p[2], acc[2]);
-                }
-            }
+        for (int t = 0; t < TOPK; ++t) {
+            const float *p = nb2 + (size_t)col[t] * k * 3;
+            px[t] = p[0], py[t] = p[1], pz[t] = p[2];
         }
         const float *p12 = verts12 + ((size_t)b * N + idx11[row * k + s]) * 3;
-        float e0 = p12[0] - acc[0], e1 = p12[1] - acc[1], e2c = p12[2] - acc[2];
-        e2 = (e0 * e0 + e1 * e1) + e2c * e2c;
+        float e0, e1, e2c;
+        e2 = map_term_resid<TOPK>(w, px, py, pz, topk, p12[0], p12[1], p12[2], e0, e1, e2c);
     }
-    __shared__ double red[256 / 64];
-    double w = wave_sum((double)e2);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = w;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double sum = 0.0;
-        for (int q = 0; q < (int)(blockDim.x >> 6); ++q) sum += red[q];
-        partial[(size_t)b * gridDim.x + blockIdx.x] = sum;
-    }
+    map_term_block_partial(e2, b, partial);
 }
 
 // out[b] = scale * sum_q partial[b,q]   (one block per b, fixed order)
 __global__ void reduce_partials_kernel(const double *__restrict__ partial, int nparts, float scale, float *__restrict__ out,
                                        int out_stride, int out_off) {
     const int b = blockIdx.x;
-    __shared__ double red[256];
     double s = 0.0;
     for (int q = threadIdx.x; q < nparts; q += blockDim.x) s += partial[(size_t)b * nparts + q];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = blockDim.x / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[(size_t)b * out_stride + out_off] = (float)(red[0] * (double)scale);
+    s = block_tree_sum(s);
+    if (threadIdx.x == 0) out[(size_t)b * out_stride + out_off] = (float)(s * (double)scale);
 }
 
-// out[b*stride+off] (+)= scale * mean(in[b, 0..n))  — fixed-order double accumulation
-__global__ void mean_kernel(const float *__restrict__ in, int n, float scale, float *__restrict__ out, int out_stride,
-                            int out_off, int accumulate) {
-    const int b = blockIdx.x;
-    __shared__ double red[256];
-    double s = 0.0;
-    for (int q = threadIdx.x; q < n; q += blockDim.x) s += (double)in[(size_t)b * n + q];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = blockDim.x / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        float v = (float)(red[0] / (double)n * (double)scale);
-        float *o = out + (size_t)b * out_stride + out_off;
-        *o = accumulate ? *o + v : v;
-    }
-}
-
-// the same for up to eight inputs in one launch (blockIdx.y = input): the pair path reduces its eight Chamfer terms at once
+// out[q][b*stride+off[q]] = scale * mean(in[q][b, 0..n[q])) for up to eight inputs in one launch (blockIdx.y = input), fixed-order double
+// accumulation: the pair path reduces its eight Chamfer terms at once, launch_mean is the one-input case
 struct MeanGroups {
     const float *in[8];
     float *out[8];
@@ -863,16 +785,10 @@ __global__ void mean_grouped_kernel(const MeanGroups g, float scale, int out_str
     const int b = blockIdx.x, q8 = blockIdx.y;
     const float *in = g.in[q8];
     const int n = g.n[q8];
-    __shared__ double red[256];
     double s = 0.0;
     for (int q = threadIdx.x; q < n; q += blockDim.x) s += (double)in[(size_t)b * n + q];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = blockDim.x / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) g.out[q8][(size_t)b * out_stride + g.off[q8]] = (float)(red[0] / (double)n * (double)scale);
+    s = block_tree_sum(s);
+    if (threadIdx.x == 0) g.out[q8][(size_t)b * out_stride + g.off[q8]] = (float)(s / (double)n * (double)scale);
 }
 
 }  // namespace dvm
@@ -1125,10 +1041,6 @@ DVM_EXPORT int dvm_map_term_f32(const float *verts12, const float *verts2, const
 
 // internal helpers used by dvm_pair.hip
 namespace dvm {
-int launch_mean(const float *in, int B, int n, float scale, float *out, int stride, int off, int accumulate, hipStream_t s) {
-    hipLaunchKernelGGL(mean_kernel, dim3(B), dim3(256), 0, s, in, n, scale, out, stride, off, accumulate);
-    return DVM_OK;
-}
 int launch_mean_grouped(const float *const *in, const int *n, float *const *out, const int *off, int ngroups, int B, float scale,
                         int stride, hipStream_t s) {
     MeanGroups g;
@@ -1139,21 +1051,12 @@ int launch_mean_grouped(const float *const *in, const int *n, float *const *out,
     hipLaunchKernelGGL(mean_grouped_kernel, dim3(B, ngroups), dim3(256), 0, s, g, scale, stride);
     return DVM_OK;
 }
+int launch_mean(const float *in, int B, int n, float scale, float *out, int stride, int off, hipStream_t s) {
+    return launch_mean_grouped(&in, &n, &out, &off, 1, B, scale, stride, s);
+}
 int launch_reduce_partials(const double *partial, int B, int nparts, float scale, float *out, int stride, int off,
                            hipStream_t s) {
     hipLaunchKernelGGL(reduce_partials_kernel, dim3(B), dim3(256), 0, s, partial, nparts, scale, out, stride, off);
-    return DVM_OK;
-}
-int launch_chamfer_grouped(const float *const *a, const float *const *b, const int *Na, const int *Nb, float *const *dout,
-                           int ngroups, int B, hipStream_t s) {
-    ChArgs args;
-    int maxN = 1;
-    for (int g = 0; g < 8; ++g) {
-        int q = g < ngroups ? g : 0;
-        args.g[g] = ChGroup{a[q], b[q], Na[q], Nb[q], dout[q]};
-        if (g < ngroups && Na[q] > maxN) maxN = Na[q];
-    }
-    hipLaunchKernelGGL(chamfer_grouped_kernel, dim3((maxN + 127) / 128, B, ngroups), dim3(128), 0, s, args);
     return DVM_OK;
 }
 int map_term_blocks(int N, int k) { return (int)(((long)N * k + 255) / 256); }
@@ -1167,7 +1070,6 @@ int launch_map_term_nbr(const float *verts12, const float *nbr2, const int32_t *
                        partial);
     return DVM_OK;
 }
-// -> true if the LDS form ran (topk == 10, the target side fits 150 KB of LDS); else the caller uses one of the older forms
 // -> false if a target cloud does not fit LDS (the caller then uses apply_kernel + take_col0)
 bool launch_apply3_pair(const float *val12, const int32_t *idx12, const float *verts2, float *verts12, int32_t *T12, const float *val21,
                         const int32_t *idx21, const float *verts1, float *verts21, int32_t *T21, int B, int N, int M, hipStream_t s) {
@@ -1183,30 +1085,29 @@ bool launch_apply3_pair(const float *val12, const int32_t *idx12, const float *v
 // LDS of a workgroup: the target's coordinates and xyz-kNN table + the mapped cloud's coordinates (up to 2 x M points of it)
 static size_t map_term_lds_bytes(int N, int M, int k) { return (size_t)(M + N) * sizeof(float4) + (size_t)M * k * sizeof(int32_t); }
 bool map_term_lds_applies(int N, int M, int k) { return k == 10 && map_term_lds_bytes(N, M, k) <= 150 * 1024; }
-bool launch_map_term_lds(const float *verts12, const float *verts2, const int32_t *idx11, const int32_t *idx22, const float *pi_val,
-                         const int32_t *pi_idx, int B, int N, int M, int k, int topk, double *partial, hipStream_t s) {
-    const size_t lds = map_term_lds_bytes(N, M, k);
+// the LDS form on nd = 1 or 2 directions of B pairs in one launch (blockIdx.y = direction) -> true if it ran (topk == 10, k == 10, the
+// larger side's tables fit 150 KB of LDS); else nothing is launched and the caller uses one of the older forms
+static bool map_term_lds_run(const MapTermSide &d0, const MapTermSide &d1, int nd, int B, int k, int topk, hipStream_t s) {
+    const size_t l0 = map_term_lds_bytes(d0.N, d0.M, k), l1 = map_term_lds_bytes(d1.N, d1.M, k), lds = l0 > l1 ? l0 : l1;
     if (topk != 10 || k != 10 || lds > 150 * 1024) return false;
     ensure_dyn_lds((const void *)map_term_lds_kernel<10>, (int)lds);
     MapTermArgs a;
-    a.d[0] = a.d[1] = MapTermSide{verts12, verts2, idx11, idx22, pi_val, pi_idx, N, M, map_term_blocks(N, k), partial};
+    a.d[0] = d0, a.d[1] = d1;
     a.k = k;
-    hipLaunchKernelGGL(map_term_lds_kernel<10>, dim3(B, 1), dim3(1024), lds, s, a);
+    hipLaunchKernelGGL(map_term_lds_kernel<10>, dim3(B, nd), dim3(1024), lds, s, a);
     return true;
+}
+bool launch_map_term_lds(const float *verts12, const float *verts2, const int32_t *idx11, const int32_t *idx22, const float *pi_val,
+                         const int32_t *pi_idx, int B, int N, int M, int k, int topk, double *partial, hipStream_t s) {
+    const MapTermSide d{verts12, verts2, idx11, idx22, pi_val, pi_idx, N, M, map_term_blocks(N, k), partial};
+    return map_term_lds_run(d, d, 1, B, k, topk, s);
 }
 // both directions of B pairs in one launch (direction 0: N sources against M targets; direction 1: the reverse); same partial sums
 bool launch_map_term_lds_pair(const float *verts12, const float *verts21, const float *verts1, const float *verts2, const int32_t *idx11,
                               const int32_t *idx22, const float *val12, const int32_t *pidx12, const float *val21, const int32_t *pidx21, int B,
                               int N, int M, int k, int topk, double *partial12, double *partial21, hipStream_t s) {
-    const size_t l0 = map_term_lds_bytes(N, M, k), l1 = map_term_lds_bytes(M, N, k), lds = l0 > l1 ? l0 : l1;
-    if (topk != 10 || k != 10 || lds > 150 * 1024) return false;
-    ensure_dyn_lds((const void *)map_term_lds_kernel<10>, (int)lds);
-    MapTermArgs a;
-    a.d[0] = MapTermSide{verts12, verts2, idx11, idx22, val12, pidx12, N, M, map_term_blocks(N, k), partial12};
-    a.d[1] = MapTermSide{verts21, verts1, idx22, idx11, val21, pidx21, M, N, map_term_blocks(M, k), partial21};
-    a.k = k;
-    hipLaunchKernelGGL(map_term_lds_kernel<10>, dim3(B, 2), dim3(1024), lds, s, a);
-    return true;
+    return map_term_lds_run(MapTermSide{verts12, verts2, idx11, idx22, val12, pidx12, N, M, map_term_blocks(N, k), partial12},
+                            MapTermSide{verts21, verts1, idx22, idx11, val21, pidx21, M, N, map_term_blocks(M, k), partial21}, 2, B, k, topk, s);
 }
 int launch_map_term(const float *verts12, const float *verts2, const int32_t *idx11, const int32_t *idx22,
                     const float *pi_val, const int32_t *pi_idx, int B, int N, int M, int k, int topk, double *partial,

@@ -85,121 +85,13 @@ __global__ __launch_bounds__(FPS_T) void fps_kernel(const float *__restrict__ xy
     }
 }
 
-// ---------------------------------------------------------------- node ring: 9-NN among nodes
-// scipy.spatial.KDTree(nodes).query(nodes, 9): fp64 squared distances of the fp32 coordinates,
-// ascending, self first.  Thread per node, nodes staged through LDS.
-constexpr int DG_TILE = 256;
-
-__device__ __forceinline__ double d2_f64(float ax, float ay, float az, float bx, float by, float bz) {
-    double dx = (double)ax - (double)bx, dy = (double)ay - (double)by, dz = (double)az - (double)bz;
-    double s = 0.0;
-    s = s + dx * dx;
-    s = s + dy * dy;
-    s = s + dz * dz;
-    return s;
-}
-
-__global__ __launch_bounds__(128) void dg_ring_kernel(const float *__restrict__ xyz, const int32_t *__restrict__ nodes_idx,
-                                                      int N, int Nn, int32_t *__restrict__ ring) {
-    __shared__ float tx[DG_TILE], ty[DG_TILE], tz[DG_TILE];
-    const int b = blockIdx.y;
-    const int a = blockIdx.x * blockDim.x + threadIdx.x;
-    const float *p = xyz + (size_t)b * N * 3;
-    const int32_t *nid = nodes_idx + (size_t)b * Nn;
-    const int ac = a < Nn ? a : Nn - 1;
-    const int va = nid[ac];
-    const float ax = p[3 * va], ay = p[3 * va + 1], az = p[3 * va + 2];
-    KBest<9, double> kb;
-    kb.init((double)INFINITY);
-    for (int j0 = 0; j0 < Nn; j0 += DG_TILE) {
-        __syncthreads();
-        for (int e = threadIdx.x; e < DG_TILE; e += blockDim.x) {
-            int v = (j0 + e < Nn) ? nid[j0 + e] : 0;
-            tx[e] = p[3 * v], ty[e] = p[3 * v + 1], tz[e] = p[3 * v + 2];
-        }
-        __syncthreads();
-        int lim = Nn - j0 < DG_TILE ? Nn - j0 : DG_TILE;
-        for (int j = 0; j < lim; ++j) kb.insert(d2_f64(ax, ay, az, tx[j], ty[j], tz[j]), j0 + j);
-    }
-    if (a < Nn)
-        for (int t = 0; t < 9; ++t) ring[((size_t)b * Nn + a) * 9 + t] = t < Nn ? kb.idx[t] : a;
-}
-
-// ---------------------------------------------------------------- influence nodes + 1-NN distance
-// (dists, infl) = 3 smallest of cdist(verts,verts)[nodes_idx] (matmul form, node = row operand);
-// nnd[i] = distance to the nearest other vertex in fp64 (KDTree(vertices).query(vertices,2)[:,1]).
-__global__ __launch_bounds__(128) void dg_infl_kernel(const float *__restrict__ xyz, const int32_t *__restrict__ nodes_idx,
-                                                      int N, int Nn, int32_t *__restrict__ infl, float *__restrict__ dists,
-                                                      double *__restrict__ nnd) {
-    __shared__ float4 tp[DG_TILE];
-    const int b = blockIdx.y;
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const float *p = xyz + (size_t)b * N * 3;
-    const int32_t *nid = nodes_idx + (size_t)b * Nn;
-    const int ic = i < N ? i : N - 1;
-    const float vx = p[3 * ic], vy = p[3 * ic + 1], vz = p[3 * ic + 2];
-    const float nv = sumsq3(vx, vy, vz);
-    KBest<3, float> kb;
-    kb.init(INFINITY);
-    for (int j0 = 0; j0 < Nn; j0 += DG_TILE) {
-        __syncthreads();
-        for (int e = threadIdx.x; e < DG_TILE; e += blockDim.x) {
-            int v = (j0 + e < Nn) ? nid[j0 + e] : 0;
-            float4 q = {p[3 * v], p[3 * v + 1], p[3 * v + 2], 0.f};
-            q.w = sumsq3(q.x, q.y, q.z);
-            tp[e] = q;
-        }
-        __syncthreads();
-        int lim = Nn - j0 < DG_TILE ? Nn - j0 : DG_TILE;
-#pragma unroll 4
-        for (int j = 0; j < lim; ++j) {
-            float4 q = tp[j];
-            kb.insert(sqrt_rn(d2_mm3(q.x, q.y, q.z, q.w, vx, vy, vz, nv)), j0 + j);
-        }
-    }
-    double m1 = (double)INFINITY, m2 = (double)INFINITY;
-    for (int j0 = 0; j0 < N; j0 += DG_TILE) {
-        __syncthreads();
-        for (int e = threadIdx.x; e < DG_TILE; e += blockDim.x) {
-            int v = (j0 + e < N) ? j0 + e : 0;
-            float4 q = {p[3 * v], p[3 * v + 1], p[3 * v + 2], 0.f};
-            tp[e] = q;
-        }
-        __syncthreads();
-        int lim = N - j0 < DG_TILE ? N - j0 : DG_TILE;
-#pragma unroll 4
-        for (int j = 0; j < lim; ++j) {
-            float4 q = tp[j];
-            double v = d2_f64(vx, vy, vz, q.x, q.y, q.z);
-            bool lt1 = v < m1, lt2 = v < m2;
-            m2 = lt1 ? m1 : (lt2 ? v : m2);
-            m1 = lt1 ? v : m1;
-        }
-    }
-    if (i < N) {
-        size_t row = (size_t)b * N + i;
-        for (int t = 0; t < 3; ++t) {
-            infl[row * 3 + t] = t < Nn ? kb.idx[t] : 0;
-            dists[row * 3 + t] = kb.key[t];
-        }
-        nnd[row] = sqrt(m2);
-    }
-}
-
 // sigma = 20 * mean(nnd) (fp64, fixed order); weights = exp(-d^2 / float(2 sigma^2)) row-normalised
 __global__ __launch_bounds__(256) void dg_weights_kernel(const double *__restrict__ nnd, const float *__restrict__ dists,
                                                          int N, float *__restrict__ weights, double *__restrict__ sigma) {
-    __shared__ double red[256];
     const int b = blockIdx.x;
     double s = 0.0;
     for (int q = threadIdx.x; q < N; q += blockDim.x) s += nnd[(size_t)b * N + q];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = blockDim.x / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    const double sg = 20.0 * (red[0] / (double)N);
+    const double sg = 20.0 * (block_tree_sum(s) / (double)N);
     if (threadIdx.x == 0 && sigma) sigma[b] = sg;
     const float den = (float)(2.0 * sg * sg);
     for (int i = threadIdx.x; i < N; i += blockDim.x) {
@@ -416,7 +308,6 @@ struct WarpArgs {
 };
 __global__ __launch_bounds__(256) void dg_warp_arap_fused_kernel(const WarpArgs args) {
     extern __shared__ __attribute__((aligned(16))) float wa_lds[];   // gpos [Nn][3] | R [Nn][9] | T [Nn][3]
-    __shared__ double red[256];
     const WarpSide &A = args.d[blockIdx.y];
     const float *__restrict__ xyz = A.xyz, *__restrict__ weights = A.weights, *__restrict__ def9 = A.def9;
     const int32_t *__restrict__ nodes_idx = A.nodes_idx, *__restrict__ ring = A.ring, *__restrict__ infl = A.infl;
@@ -473,13 +364,8 @@ __global__ __launch_bounds__(256) void dg_warp_arap_fused_kernel(const WarpArgs 
             }
         }
     }
-    red[threadIdx.x] = sa;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) arap[(size_t)b * arap_stride] = (float)(red[0] / (double)Nn);
+    sa = block_tree_sum(sa);
+    if (threadIdx.x == 0) arap[(size_t)b * arap_stride] = (float)(sa / (double)Nn);
 }
 
 int launch_dg_warp_rt(const float *xyz, int B, int N, const int32_t *nodes_idx, const int32_t *ring,

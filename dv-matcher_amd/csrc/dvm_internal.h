@@ -7,9 +7,10 @@
 namespace dvm {
 
 // ---- dvm_backbone.hip
-// W [B][nA][N] (zeroed here) and its row sums from the forward's xsave; gterm read at gterm[b * gstride]
+// dvm_dist_loss_fwd_f32 with the sum at out[b * out_stride + out_off]; idx_out, xsave ([B][nA][k] x 2: x_j, y_j), fa_out: NULL or kept for the backward
 int launch_dist_loss_fwd(const float *feat, const float *dist, const int32_t *anchors, int B, int N, int C, int nA, int k, float *out, int out_stride,
                          int out_off, int32_t *idx_out, float *xsave, float *fa_out, void *ws, size_t ws_bytes, hipStream_t s);
+// W [B][nA][N] (zeroed here) and its row sums from the forward's xsave; gterm read at gterm[b * gstride]
 void launch_dist_loss_bwd_weights_saved(const float *xsave, const int32_t *idx, const float *gterm, int gstride, int B, int N, int nA, int k, float
                                         *W, float *rs, hipStream_t s);
 
@@ -29,10 +30,6 @@ int launch_deformer(const float *feat1, const float *feat2, const float *verts1,
                     *conv_w, const float *conv_b, const float *W0, const float *b0, const float *W1, const float *b1, const float *W2, const float
                     *b2, const float *W3, const float *b3, float *out, int variant, void *ws, size_t ws_bytes, hipStream_t s);
 size_t deformer_ws_bytes(int B, int M, int Nn);
-void launch_assemble_pooled(const float *vsrc, const float *vcorr, const float *gsrc, const float *gtgt, const float *pi_val, const int32_t *pi_idx,
-                            const int32_t *fps, int B, int N, int M, int Nn, float *z, hipStream_t s, const int *gate = nullptr);
-void launch_assemble_pooled_planes(const float *vsrc, const float *vcorr, const float *gsrc, const float *gtgt, const float *pi_val, const int32_t
-                                   *pi_idx, const int32_t *fps, int B, int N, int M, int Nn, void *zp, hipStream_t s);
 // both directions of the pair path in one launch; planes: the plane form (z*), else the fp32 rows behind `gate`
 void launch_assemble_pooled_pair(const float *verts1, const float *verts2, const float *verts12, const float *verts21, const float *g1, const float
                                  *g2, const float *val12, const int32_t *idx12, const float *val21, const int32_t *idx21, const int32_t *nodes1, const
@@ -64,7 +61,7 @@ void launch_apply_bwd_dval(const float *pi_val, const int32_t *pi_idx, const flo
                            *d_val, hipStream_t s);
 void launch_apply_bwd_gather(const float *pi_val, const float *g_out, const int32_t *offs, const int32_t *edges, int B, int N, int M, int topk, int C,
                              float *d_V, hipStream_t s);
-int launch_mean(const float *in, int B, int n, float scale, float *out, int stride, int off, int accumulate, hipStream_t s);
+int launch_mean(const float *in, int B, int n, float scale, float *out, int stride, int off, hipStream_t s);   // launch_mean_grouped with one input
 void launch_gather_nbr_xyz(const float *verts, const int32_t *idx, int B, int M, int k, float *nbr, hipStream_t s);
 int launch_map_term_nbr(const float *verts12, const float *nbr2, const int32_t *idx11, const float *pi_val, const int32_t *pi_idx, int B, int N, int
                         M, int k, int topk, double *partial, hipStream_t s);
@@ -78,8 +75,6 @@ bool launch_map_term_lds_pair(const float *verts12, const float *verts21, const 
 // -> false if a target cloud does not fit LDS (the caller then uses apply_kernel + take_col0)
 bool launch_apply3_pair(const float *val12, const int32_t *idx12, const float *verts2, float *verts12, int32_t *T12, const float *val21, const int32_t
                         *idx21, const float *verts1, float *verts21, int32_t *T21, int B, int N, int M, hipStream_t s);
-int launch_chamfer_grouped(const float *const *a, const float *const *b, const int *Na, const int *Nb, float *const *dout, int ngroups, int B,
-                           hipStream_t s);
 
 // ---- dvm_graph.hip
 int launch_dg_warp(const float *xyz, int B, int N, const int32_t *nodes_idx, const int32_t *ring, const int32_t *infl_idx, const float *weights, const
@@ -133,8 +128,6 @@ void launch_sa_apply_f16(const _Float16 *pp, const _Float16 *vp, const float *st
 
 // ---- dvm_softcorr.hip
 void launch_rownorm2(const float *x, int rows, int K, float *out, hipStream_t s);
-int launch_softcorr_both(const float *f1, const float *f2, const float *n1, const float *n2, int B, int N, int M, float neg_alpha, float *val12,
-                         int32_t *idx12, float *val21, int32_t *idx21, hipStream_t s);
 size_t softcorr_pair_ws_bytes(int B, int N, int M);
 int launch_softcorr_pair(const float *f1, const float *f2, float *n1, float *n2, int B, int N, int M, float neg_alpha, float *val12, int32_t *idx12,
                          float *val21, int32_t *idx21, void *ws, size_t ws_bytes, hipStream_t s);

@@ -111,12 +111,12 @@ DVM_EXPORT int dvm_pair_direction_fwd_f32(const float *feat1, const float *feat2
         GridBuf qg[2] = {w.gw, w.gv2}, tg[2] = {w.gv2, w.gw};
         float *dout[2] = {w.d1, w.d2};
         launch_grid_chamfer(qg, tg, dout, nullptr, 2, B, s);
-        launch_mean(w.d1, B, N, 1.f, losses, 6, 0, 0, s);
-        launch_mean(w.d2, B, M, 1.f, losses, 6, 1, 0, s);
+        launch_mean(w.d1, B, N, 1.f, losses, 6, 0, s);
+        launch_mean(w.d2, B, M, 1.f, losses, 6, 1, s);
         GridBuf qg2[2] = {w.g12, w.gv2}, tg2[2] = {w.gv2, w.g12};
         launch_grid_chamfer(qg2, tg2, dout, nullptr, 2, B, s);
-        launch_mean(w.d1, B, N, 1.f, losses, 6, 3, 0, s);
-        launch_mean(w.d2, B, M, 1.f, losses, 6, 4, 0, s);
+        launch_mean(w.d1, B, N, 1.f, losses, 6, 3, s);
+        launch_mean(w.d2, B, M, 1.f, losses, 6, 4, s);
     }
     if (with_map) {
         if (!launch_map_term_lds(verts12, verts2, w.idx11, w.idx22, w.pval, w.pidx, B, N, M, k, topk, w.partial, s))

@@ -464,22 +464,6 @@ static void launch_softcorr_mfma(SCArgs &a, int blocks, hipStream_t s) {
         hipLaunchKernelGGL((softcorr_mfma_kernel<TOPK, false>), dim3(blocks), dim3(MF_THREADS), MF_LDS_BYTES, s, a);
 }
 
-// both directions of B pairs in one launch; n1/n2 are the row norms of f1/f2 (computed once)
-int launch_softcorr_both(const float *f1, const float *f2, const float *n1, const float *n2, int B, int N, int M,
-                         float neg_alpha, float *val12, int32_t *idx12, float *val21, int32_t *idx21, hipStream_t s) {
-    SCArgs a;
-    a.g[0] = SCGroup{f1, f2, n1, n2, N, M, (N + MF_QB - 1) / MF_QB, val12, idx12, nullptr, nullptr};
-    a.g[1] = SCGroup{f2, f1, n2, n1, M, N, (M + MF_QB - 1) / MF_QB, val21, idx21, nullptr, nullptr};
-    a.blocks0 = B * a.g[0].tiles;
-    a.neg_alpha = neg_alpha;
-    a.topk = 10;
-    prof_note(DVM_PROF_K1_SWEEP, "softcorr_mfma_kernel");
-    prof_begin(s);
-    launch_softcorr_mfma<10>(a, a.blocks0 + B * a.g[1].tiles, s);
-    prof_end(s);
-    return DVM_OK;
-}
-
 // K == 128 only: also maxes the bit pattern of max |x| into the 256 slots of `absmax_slots` (zero them first);
 // launch_absmax_finalize folds nt x 256 slots into nt values
 void launch_rownorm2_absmax(const float *x, int rows, float *out, int *absmax_slots, hipStream_t s) {

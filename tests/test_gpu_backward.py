@@ -127,9 +127,10 @@ def test_sparse_apply_bwd_vs_fp64_autograd(ops, C, atomics):
     assert rel(dval, v64.grad) < 1e-5 and rel(dV, V64.grad) < 1e-5
 
 
-def test_dist_loss_bwd_vs_fp64_autograd(ops):
+@pytest.mark.parametrize("C", [128, 64])   # the half-wave row form | the generic one, forward and backward weights
+def test_dist_loss_bwd_vs_fp64_autograd(ops, C):
     from dvm import nn_ops
-    B, N, C, nA, k = 2, 300, 128, 40, 25
+    B, N, nA, k = 2, 300, 40, 25
     g = torch.Generator().manual_seed(31)
     feat = torch.randn(B, N, C, generator=g)
     v = torch.rand(B, N, 3, generator=g)

@@ -24,7 +24,8 @@ launch_dg_warp / launch_dg_warp_pair (Nn * 60 B <= 150 KiB) in csrc/dvm_graph.hi
   (5200, 64)                Nn * 60 B = 156 000 B > 150 KiB: rot6d_kernel, dg_warp_kernel, dg_arap_kernel instead of
                             dg_warp_arap_fused_kernel (every other shape: fused; in ops.pair_forward blockIdx.y = direction);
                             map_term_lds_kernel with six passes
-ops.pair_forward reduces its eight Chamfer vectors by mean_grouped_kernel, ops.pair_direction by mean_kernel; both sum the map
+ops.pair_forward reduces its eight Chamfer vectors by one launch of mean_grouped_kernel, ops.pair_direction its four by one-input
+launches of the same kernel (launch_mean); both sum the map
 term's partials by reduce_partials_kernel.  A mirrored planting (exact in both directions) exists when max(N, M) <= 8 groups
 <= 8 min(N, M): ops.pair_forward runs those, and the one-way plantings of (300, 2700) / (2700, 300) both straight (direction 12
 is the planted one) and with the clouds swapped (direction 21 is); the unplanted direction's ARAP is still exact.
