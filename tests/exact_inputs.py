@@ -99,10 +99,11 @@ def _features(grp, chans):
     return f
 
 
-def plant_pair(N, M, seed, both=False):
-    """One planted pair: dict(verts1 (N,3), verts2 (M,3), feat1 (N,128), feat2 (M,128), grp1 (N,), grp2 (M,), start1, start2)."""
+def plant_pair(N, M, seed, both=False, hi=255):
+    """One planted pair: dict(verts1 (N,3), verts2 (M,3), feat1 (N,128), feat2 (M,128), grp1 (N,), grp2 (M,), start1, start2).
+    hi: the clouds' coordinate range [0, hi] (the backward plantings need small residuals: criterion_bwd_reference)."""
     rng = np.random.default_rng([seed, N, M, int(both)])
-    verts1, verts2 = lattice_cloud(rng, N), lattice_cloud(rng, M)
+    verts1, verts2 = lattice_cloud(rng, N, hi), lattice_cloud(rng, M, hi)
     if both:
         G = min(min(N, M), max(-(-max(N, M) // 3), min(N, M) // 2))
         n1, n2 = partition_sizes(rng, N, G), partition_sizes(rng, M, G)
@@ -197,9 +198,9 @@ def reference_direction(verts_s, verts_t, grp_s, grp_t, start):
 
 
 @functools.lru_cache(maxsize=None)
-def planted_case(N, M, seed, both=False):
+def planted_case(N, M, seed, both=False, hi=255):
     """-> (pair, ref12, ref21): ref21 (cloud 2 -> cloud 1) only for the mirrored planting, else None.  Shared, never modified."""
-    p = plant_pair(N, M, seed, both)
+    p = plant_pair(N, M, seed, both, hi)
     r12 = reference_direction(p["verts1"], p["verts2"], p["grp1"], p["grp2"], p["start1"])
     r21 = reference_direction(p["verts2"], p["verts1"], p["grp2"], p["grp1"], p["start2"]) if both else None
     return p, r12, r21
@@ -214,9 +215,9 @@ def reference_arap(verts, start):
     return f32(arap_rows(g, np.broadcast_to(R_PLANTED, (Nn, 3, 3)), g, graph["one_ring"]).sum() / Nn)
 
 
-def planted_batch(N, M, seed, B=3, both=False):
+def planted_batch(N, M, seed, B=3, both=False, hi=255):
     """B different planted pairs (seeds seed .. seed + B - 1) -> (stacked arrays, [(pair, ref12, ref21)])"""
-    cases = [planted_case(N, M, seed + b, both) for b in range(B)]
+    cases = [planted_case(N, M, seed + b, both, hi) for b in range(B)]
     arrays = {k: np.stack([c[0][k] for c in cases]) for k in ("verts1", "verts2", "feat1", "feat2")}
     arrays["start1"] = np.array([c[0]["start1"] for c in cases], np.int32)
     arrays["start2"] = np.array([c[0]["start2"] for c in cases], np.int32)
@@ -283,3 +284,175 @@ def warp_direct(N, Nn, K, seed):
     d["arap_rows"], d["sr_rows"] = arap_rows(xyz[nodes], R, T, ring), sr_rows(R, ring)
     d["arap"], d["sr"] = f32(d["arap_rows"].sum() / Nn), f32(d["sr_rows"].sum() / (float(Nn) * K * 9.0))
     return d
+
+
+# --------------------------------------------------------------------- backward plantings: exact gradients, no tolerance either
+# The geometric backward kernels (csrc/dvm_loss_bwd.hip) scatter-add products of their inputs.  On the plantings below every
+# addend is a multiple of 2^-4 and, per output element, the MAGNITUDES of its addends sum to less than 2^20: every partial sum, in
+# any order and any grouping (atomics, per-thread accumulators), is then a multiple of 2^-4 below 2^20, i.e. at most 24 significant
+# bits — exact in fp32.  exact_sums() is that condition; the CPU half (tests/test_geom_backward_rows_cpu.py) asserts it for every case.
+SUM_GRID = 16.0
+SUM_LIMIT = float(1 << 24)
+
+
+def exact_sums(addends, mags):
+    """every addend * 2^4 is an integer and every element's summed magnitudes * 2^4 stay below 2^24"""
+    return all(np.array_equal(np.asarray(a) * SUM_GRID, np.rint(np.asarray(a) * SUM_GRID)) for a in addends) and \
+        all((np.asarray(m) * SUM_GRID < SUM_LIMIT).all() for m in mags)
+
+
+def scatter_sum(shape, idx, val):
+    """(sum, sum of magnitudes) of the addends val[l] landing on rows idx[l] of a zero array (float64)"""
+    out, mag = np.zeros(shape), np.zeros(shape)
+    np.add.at(out, idx, val)
+    np.add.at(mag, idx, np.abs(val))
+    return out, mag
+
+
+def warp_arap_bwd_rows(xyz, nodes_idx, ring, infl, weights, R, T, gw, g_arap):
+    """The definition's gradient in float64: L = sum(warped * gw) + g_arap * arap (warp_rows, arap_rows / Nn) w.r.t. R and T:
+      d_T[s] += w gw_i, d_R[s] += w gw_i (v_i - g_s)^T for the three slots s of vertex i;
+      with e = (g_a + t_a) - (g_b + t_b) - R_a (g_a - g_b), k = 2 g_arap / Nn:  d_T[a] += k e, d_T[b] -= k e, d_R[a] -= k e (g_a - g_b)^T.
+    -> dict(d_R (Nn,3,3), d_T (Nn,3), mag_R, mag_T (summed magnitudes of the addends), addends)"""
+    xyz, R, T, w, gw = (np.asarray(x, np.float64) for x in (xyz, R, T, weights, gw))
+    nodes_idx, ring, infl = np.asarray(nodes_idx), np.asarray(ring), np.asarray(infl)
+    Nn = nodes_idx.size
+    g = xyz[nodes_idx]
+    wg = w[:, :, None] * gw[:, None, :]                                              # (N, 3, c)
+    wgd = wg[..., None] * (xyz[:, None] - g[infl])[:, :, None, :]                     # (N, 3, c, e)
+    k = 2.0 * float(g_arap) / Nn
+    df = g[:, None] - g[ring]
+    ge = k * ((g + T)[:, None] - (g + T)[ring] - np.einsum("aij,aqj->aqi", R, df))   # (Nn, K, c)
+    ged = ge[..., None] * df[:, :, None, :]                                           # (Nn, K, c, e)
+    own = np.broadcast_to(np.arange(Nn)[:, None], ring.shape).ravel()
+    dT, mT = scatter_sum((Nn, 3), np.concatenate([infl.ravel(), own, ring.ravel()]),
+                         np.concatenate([wg.reshape(-1, 3), ge.reshape(-1, 3), -ge.reshape(-1, 3)]))
+    dR, mR = scatter_sum((Nn, 3, 3), np.concatenate([infl.ravel(), own]), np.concatenate([wgd.reshape(-1, 3, 3), -ged.reshape(-1, 3, 3)]))
+    return dict(d_R=dR, d_T=dT, mag_R=mR, mag_T=mT, addends=(wg, wgd, ge, ged))
+
+
+def warp_bwd_direct(N, seed, hub=False, sign=1):
+    """ops.dg_warp_arap_bwd: warp_direct's graph at Nn = N // 2, K = 9, plus integer gw in [-8, 8] and g_arap = sign * Nn / 8
+    (sign in {1, -1, 0}): 2 g_arap / Nn is exactly +-1/4 or 0 whatever Nn.  hub: slots 0 and 2 of EVERY row point at node 0 (in-degree
+    2 N, two addends per vertex on one address), ring column 0 at node Nn // 2 (Nn contended -ge scatters), ring column 8 at the node
+    itself (an exactly-zero residual)."""
+    Nn = N // 2
+    d = {k: v for k, v in warp_direct(N, Nn, 9, seed).items() if k in ("xyz", "nodes_idx", "one_ring", "infl_idx", "weights", "R", "T")}
+    rng = np.random.default_rng([seed, N, 9, 77, int(hub)])
+    if hub:
+        d["one_ring"], d["infl_idx"] = d["one_ring"].copy(), d["infl_idx"].copy()
+        d["infl_idx"][:, 0] = d["infl_idx"][:, 2] = 0
+        d["one_ring"][:, 0] = Nn // 2
+        d["one_ring"][:, 8] = np.arange(Nn)
+    d["gw"] = rng.integers(-8, 9, (N, 3)).astype(np.float32)
+    d["ga"] = np.float32(sign * Nn / 8.0)
+    d.update(warp_arap_bwd_rows(d["xyz"], d["nodes_idx"], d["one_ring"], d["infl_idx"], d["weights"], d["R"], d["T"], d["gw"], d["ga"]))
+    return d
+
+
+def rot6d_grad64(d6, gR):
+    """float64 autograd of the definition (oracle/torch_ref.py::rot6d): d sum(R * gR) / d d6"""
+    import torch
+    from oracle import torch_ref as TR
+    x = torch.from_numpy(np.asarray(d6, np.float64)).requires_grad_(True)
+    (TR.rot6d(x) * torch.from_numpy(np.asarray(gR, np.float64)).reshape(-1, 3, 3)).sum().backward()
+    return x.grad.numpy()
+
+
+ROT6D_C = (0.0, 0.5, -0.5, 0.25, -0.25, 1.0, -1.0, 1.5, -2.0, 0.0, 0.75)   # the a1 component of a2: small dyadics, 0 included
+
+
+def rot6d_bwd_direct(seed):
+    """ops.rot6d_bwd: frames a1 = 2^p s e_i, a2 = 2^q t e_j + c a1 (j != i; signs s, t; p, q in [-3, 3]; c from ROT6D_C): n1 = 2^p,
+    dot = c 2^p, u = 2^q t e_j, n2 = 2^q are exact, every later value a short dyadic.  All 24 (i, j, s, t) orientations, each with every
+    c (264 rows: two workgroups); gR small integers.  -> dict(d6 (264,6), gR (264,3,3), grad (264,6) float64)"""
+    rng = np.random.default_rng([seed, 6])
+    rows = []
+    for i, j in itertools.permutations(range(3), 2):
+        for s, t in itertools.product((1.0, -1.0), repeat=2):
+            for c in ROT6D_C:
+                p, q = rng.integers(-3, 4, 2)
+                a1, a2 = np.zeros(3), np.zeros(3)
+                a1[i] = s * 2.0 ** p
+                a2[j] = t * 2.0 ** q
+                rows.append(np.concatenate([a1, a2 + c * a1]))
+    d6 = np.array(rows, np.float32)
+    assert np.array_equal(d6, np.array(rows)) and d6.shape == (24 * len(ROT6D_C), 6)
+    gR = rng.integers(-4, 5, (d6.shape[0], 3, 3)).astype(np.float32)
+    return dict(d6=d6, gR=gR, grad=rot6d_grad64(d6, gR))
+
+
+def chamfer_bwd_rows(a, b, i1, i2, g1, g2):
+    """float64: L = sum(g1 * |a_i - b_i1(i)|^2) + sum(g2 * |b_j - a_i2(j)|^2) with the indices held fixed
+    -> dict(d_a, d_b, mag_a, mag_b, addends)"""
+    a, b, g1, g2 = (np.asarray(x, np.float64) for x in (a, b, g1, g2))
+    i1, i2 = np.asarray(i1), np.asarray(i2)
+    va, vb = 2.0 * g1[:, None] * (a - b[i1]), 2.0 * g2[:, None] * (b - a[i2])
+    da, ma = scatter_sum(a.shape, np.concatenate([np.arange(a.shape[0]), i2]), np.concatenate([va, -vb]))
+    db, mb = scatter_sum(b.shape, np.concatenate([np.arange(b.shape[0]), i1]), np.concatenate([vb, -va]))
+    return dict(d_a=da, d_b=db, mag_a=ma, mag_b=mb, addends=(va, vb))
+
+
+CHAMFER_VARIANTS = ("nn", "hub", "arbitrary")
+
+
+def chamfer_bwd_direct(N, M, seed, variant):
+    """ops.chamfer_bwd: integer clouds in [0, 63], g1 / g2 multiples of 1/4 in [-2, 2]; the index lists are
+    nn: the true nearest neighbours (oracle; the clouds hold ties and coincident points); hub: every a_i -> one b, every b_j -> one a;
+    arbitrary: any valid index.  The kernel must use the lists it is handed."""
+    rng = np.random.default_rng([seed, N, M, CHAMFER_VARIANTS.index(variant)])
+    a, b = rng.integers(0, 64, (N, 3)).astype(np.float32), rng.integers(0, 64, (M, 3)).astype(np.float32)
+    g1, g2 = (rng.integers(-8, 9, N) / 4.0).astype(np.float32), (rng.integers(-8, 9, M) / 4.0).astype(np.float32)
+    if variant == "nn":
+        from oracle import oracle as O
+        _, _, i1, i2 = O.chamfer(a, b)
+    elif variant == "hub":
+        i1, i2 = np.full(N, rng.integers(0, M), np.int32), np.full(M, rng.integers(0, N), np.int32)
+    else:
+        i1, i2 = rng.integers(0, M, N).astype(np.int32), rng.integers(0, N, M).astype(np.int32)
+    d = dict(a=a, b=b, g1=g1, g2=g2, i1=i1, i2=i2)
+    d.update(chamfer_bwd_rows(a, b, i1, i2, g1, g2))
+    return d
+
+
+BWD_SIZES = [2, 3, 64, 257, 513, 2048]
+CHAMFER_BWD_SHAPES = [(1, 1), (255, 1), (256, 257), (300, 170), (2048, 2048)]
+BWD_SEED = 5200
+
+
+def warp_bwd_batch(N, hub, B=3):
+    """B different entries, g_arap = +Nn/8, -Nn/8, 0"""
+    return [warp_bwd_direct(N, BWD_SEED + b, hub, (1, -1, 0)[b % 3]) for b in range(B)]
+
+
+def chamfer_bwd_batch(N, M, variant, B=3):
+    return [chamfer_bwd_direct(N, M, BWD_SEED + b, variant) for b in range(B)]
+
+
+# criterion level: (N, M, hi) — the coordinate range [0, hi] is small enough that the column sums of ddef9 over all P * Nn rows, and
+# those of ddef9^T h2 (the first three input columns of W3), stay exact: criterion_bwd_reference, checked by the CPU half (at hi = 255
+# the residuals are ~100 times larger and the sums leave 24 bits).  (64, 65) and (300, 170) take the fused warp forward, (5200, 64)
+# the three-kernel one; CRIT_BWD_SWAPPED is the swapped-halves form (N == M, mirrored planting).
+CRIT_BWD_CASES = [(64, 65, 7), (300, 170, 7), (5200, 64, 19)]
+CRIT_BWD_SWAPPED = (300, 7)
+DEF9_IDENTITY = np.array([1, 0, 0, 0, 1, 0], np.float64)
+
+
+def criterion_bwd_reference(refs, g_arap):
+    """g_terms zero except the ARAP column = g_arap[p] (+-Nn/8) for the directional pairs `refs` (reference_direction): dwarped and
+    dv12 are exactly 0, so ddef9[p] = [d_T | rot6d gradient of (def9[3:] + identity) against d_R] from ARAP alone.  The last decoder
+    layer's bias gradient is the column sum of ddef9 over all pairs' nodes, its weight gradient ddef9^T h2 with h2[:, :3] = the node
+    positions (the pass-through Deformer) and 0 elsewhere.  -> dict(ddef9 [P x (Nn,9)], db3 (9,), dW3 (9,3), mag_b3, mag_W3, addends)"""
+    dd, hs, adds = [], [], []
+    for r, ga in zip(refs, g_arap):
+        Nn = r["Nn"]
+        zero = np.zeros((Nn, 3))      # no warp gradient: the nodes as a cloud of their own, weights and gw zero
+        w = warp_arap_bwd_rows(r["g"], np.arange(Nn), r["graph"]["one_ring"], zero.astype(np.int64), zero, r["R"], r["T"], zero, ga)
+        d6 = r["def9"][:, 3:] + DEF9_IDENTITY
+        dd.append(np.concatenate([w["d_T"], rot6d_grad64(d6, w["d_R"])], 1))
+        hs.append(r["g"])
+        adds += [w["addends"][2], w["addends"][3]]
+        assert exact_sums(w["addends"], (w["mag_R"], w["mag_T"]))
+    D, H = np.concatenate(dd), np.concatenate(hs)
+    prod = D[:, :, None] * H[:, None, :]
+    return dict(ddef9=dd, db3=D.sum(0), mag_b3=np.abs(D).sum(0), dW3=prod.sum(0), mag_W3=np.abs(prod).sum(0), addends=adds + [D, prod])
