@@ -23,6 +23,12 @@
 //
 // dvm_sinkhorn_fwd_hist_f32 is the same run with every iterate's potentials left in memory (u_hist, v_hist) for the
 // backward, dvm_sinkhorn_bwd.hip: only the destination of each sweep's output changes.
+//
+// dvm_sinkhorn_ub_fwd_f32 / dvm_sinkhorn_ub_fwd_hist_f32 are the unbalanced (KL-relaxed) operator of include/dvm.h on the same
+// sweeps: a potential sweep leaves tau * (log weight + normaliser) where the balanced one leaves add - LSE, the final sweep
+// scales the values by the row's mass exp(u^f - m^f) and writes its logarithm.  The history of that form keeps the
+// normalisers m^t, n^t; a potential is re-made from one wherever it is needed as tau * (log weight + normaliser), a sum, then a
+// product (this file is compiled without contraction), so that the forward and the backward hold the same bits.
 #include <float.h>
 #include <math.h>
 
@@ -65,10 +71,15 @@ struct LseState {
 // operator returns.
 template <int TOPK>
 __device__ __forceinline__ void store_final(const KBest<TOPK, float> &kb, bool hasv, const LseState &st, int topk, int M, float neg_alpha,
-                                            float *val, int32_t *idx, float *row_lmax, float *row_sum, float *u) {
+                                            float *val, int32_t *idx, float *row_lmax, float *row_sum, float *u, bool relaxed,
+                                            float tau, float logw, float *nrm, float *row_lmass) {
     const float lmax = hasv ? -kb.key[0] : kb.key[0] * neg_alpha;   // = st.m: every candidate went through the same L
     const float lsum = (float)st.l;
-    const float inv = 1.0f / lsum;
+    const float mf = -(lmax + logf(lsum));
+    // relaxed: u^f = tau (log_a + m^f), the row's mass exp(u^f - m^f) on every value (0, never NaN, where it underflows)
+    const float uf = relaxed ? tau * (logw + mf) : mf;
+    const float lmass = relaxed ? uf - mf : 0.f;
+    const float inv = relaxed ? (1.0f / lsum) * exp2f(lmass * LOG2E) : 1.0f / lsum;
 #pragma unroll
     for (int t = 0; t < TOPK; ++t) {
         if (t < topk) {
@@ -80,7 +91,9 @@ __device__ __forceinline__ void store_final(const KBest<TOPK, float> &kb, bool h
     }
     if (row_lmax) *row_lmax = lmax;
     if (row_sum) *row_sum = lsum;
-    if (u) *u = -(lmax + logf(lsum));
+    if (u) *u = uf;
+    if (nrm) *nrm = mf;
+    if (row_lmass) *row_lmass = lmass;
 }
 
 struct SKArgs {
@@ -90,13 +103,28 @@ struct SKArgs {
     long pot_bs, out_bs;    // batch strides (floats) of pot and of out / u: M and N, or a slice of a potential history
     int N, M, d, tiles;     // tiles = query blocks per entry
     float neg_alpha;
-    float add;              // potential sweep: out = add - LSE (0 for the row step, log(N / M) for the column step)
+    float add;              // potential sweep: out = tau * (add - LSE) (0 for the row step, log(N / M) for the column step)
+    float tau;              // 1 in the balanced operator
+    const float *logw;      // the queries' log weight [B][N] in place of add; NULL = add
     float *out;             // potential sweep: the queries' new potential [B][N]
+    float *nrm;             // the queries' normaliser -LSE, entry b at nrm + b * nrm_bs; NULL = not kept
+    long nrm_bs;
+    bool relaxed;           // final row sweep: tau / logw apply (u^f = tau (logw + m^f), values scaled by the row's mass)
+    float *lmass;           // final row sweep: log of the row's mass [B][N]; may be NULL
     int topk;               // final row sweep
     float *val;
     int32_t *idx;
     float *lmax, *sum, *u;
 };
+
+// a potential sweep's result for query i of entry b (row = b * N + i): the normaliser -LSE, kept if asked for, and the
+// potential tau * (log weight + normaliser) — with tau = 1 and no weights the balanced add - LSE, bit for bit
+__device__ __forceinline__ void store_potential(const SKArgs &a, int b, int i, size_t row, const LseState &st) {
+    const float nrm = -(st.m + logf((float)st.l));
+    const float w = a.logw ? a.logw[row] : a.add;
+    if (a.nrm) a.nrm[(size_t)b * a.nrm_bs + i] = nrm;
+    a.out[(size_t)b * a.out_bs + i] = a.tau * (w + nrm);
+}
 
 // ------------------------------------------------------------ scalar variant
 // One thread per query row (the scalar sweep of dvm_dist_tile.h).  Any d % 4 == 0.  The cross-check form of the
@@ -154,9 +182,10 @@ __global__ __launch_bounds__(128) void sinkhorn_scalar_kernel(const SKArgs a) {
         if (FINAL)
             store_final<TOPK>(kb, hasv, st, a.topk, M, neg_alpha, a.val + row * a.topk, a.idx + row * a.topk,
                               a.lmax ? a.lmax + row : nullptr, a.sum ? a.sum + row : nullptr,
-                              a.u ? a.u + (size_t)b * a.out_bs + i : nullptr);
+                              a.u ? a.u + (size_t)b * a.out_bs + i : nullptr, a.relaxed, a.tau, a.logw ? a.logw[row] : 0.f,
+                              a.nrm ? a.nrm + (size_t)b * a.nrm_bs + i : nullptr, a.lmass ? a.lmass + row : nullptr);
         else
-            a.out[(size_t)b * a.out_bs + i] = a.add - (st.m + logf((float)st.l));
+            store_potential(a, b, i, row, st);
     }
 }
 
@@ -297,9 +326,10 @@ __global__ __launch_bounds__(SK_THREADS, 2) void sinkhorn_mfma_kernel(const SKAr
         if (FINAL)
             store_final<TOPK>(kb, HASV, st, a.topk, M, neg_alpha, a.val + row * a.topk, a.idx + row * a.topk,
                               a.lmax ? a.lmax + row : nullptr, a.sum ? a.sum + row : nullptr,
-                              a.u ? a.u + (size_t)b * a.out_bs + qrow : nullptr);
+                              a.u ? a.u + (size_t)b * a.out_bs + qrow : nullptr, a.relaxed, a.tau, a.logw ? a.logw[row] : 0.f,
+                              a.nrm ? a.nrm + (size_t)b * a.nrm_bs + qrow : nullptr, a.lmass ? a.lmass + row : nullptr);
         else
-            a.out[(size_t)b * a.out_bs + qrow] = a.add - (st.m + logf((float)st.l));
+            store_potential(a, b, qrow, row, st);
     }
 }
 
@@ -355,9 +385,16 @@ __global__ void sinkhorn_zero_slice_kernel(float *p, int n, long bs) {
 // v^t to V + t * v_step (batch strides u_bs / v_bs); the final row step reads v^T and writes its u to uf (batch stride
 // u_bs, may be NULL).  dvm_sinkhorn_fwd_f32 runs it with steps 0 (one buffer per side), dvm_sinkhorn_fwd_hist_f32 with a
 // history slice per iterate: the same kernels on the same operands, so the same bits.
+// The unbalanced entries pass a Relax: the factors and log weights of the two sides, row_lmass, and (history form) where the
+// normalisers go — m^t to RN + (t-1) * N, m^f to RN + T * N, n^t to CN + t * M, batch strides (T + 1) N and (T + 1) M.
+struct Relax {
+    float tau_row, tau_col;
+    const float *log_a, *log_b;
+    float *row_lmass, *RN, *CN;
+};
 int sinkhorn_run(const float *f1, const float *f2, int B, int N, int M, int d, float neg_alpha, int n_iter, int topk, float *pi_val,
                  int32_t *pi_idx, float *row_lmax, float *row_sum, float *n1, float *n2, float *U, long u_step, long u_bs, float *V,
-                 long v_step, long v_bs, float *uf, bool mfma, hipStream_t s) {
+                 long v_step, long v_bs, float *uf, bool mfma, hipStream_t s, const Relax *rx = nullptr) {
     launch_rownorm2(f1, B * N, d, n1, s);
     launch_rownorm2(f2, B * M, d, n2, s);
     const float log_ratio = (float)log((double)N / (double)M);
@@ -365,16 +402,27 @@ int sinkhorn_run(const float *f1, const float *f2, int B, int N, int M, int d, f
     row.q = f1, row.k = f2, row.nq = n1, row.nk = n2, row.N = N, row.M = M, row.d = d, row.neg_alpha = neg_alpha;
     col.q = f2, col.k = f1, col.nq = n2, col.nk = n1, col.N = M, col.M = N, col.d = d, col.neg_alpha = neg_alpha;
     row.pot_bs = v_bs, row.out_bs = u_bs, col.pot_bs = u_bs, col.out_bs = v_bs;
+    row.tau = col.tau = 1.f;
+    row.add = 0.f, col.add = log_ratio;
+    if (rx) {
+        row.tau = rx->tau_row, col.tau = rx->tau_col, row.logw = rx->log_a, col.logw = rx->log_b;
+        row.nrm_bs = (long)(n_iter + 1) * N, col.nrm_bs = (long)(n_iter + 1) * M;
+    }
     for (int it = 0; it < n_iter; ++it) {
         row.pot = it ? V + it * v_step : nullptr;   // v = 0 before the first row step: nothing is read from the buffer
-        row.add = 0.f, row.out = U + it * u_step;
+        row.out = U + it * u_step;
+        row.nrm = rx && rx->RN ? rx->RN + (size_t)it * N : nullptr;
         launch_sweep(mfma, false, row, B, s);
         col.pot = row.out;
-        col.add = log_ratio, col.out = V + (it + 1) * v_step;
+        col.out = V + (it + 1) * v_step;
+        col.nrm = rx && rx->CN ? rx->CN + (size_t)(it + 1) * M : nullptr;
         launch_sweep(mfma, true, col, B, s);
     }
     row.pot = n_iter ? V + n_iter * v_step : nullptr;
     row.out = nullptr;
+    row.nrm = rx && rx->RN ? rx->RN + (size_t)n_iter * N : nullptr;
+    // (tau_row = 1 without row weights is the balanced row step: u^f = m^f, mass 1, row_lmass 0)
+    row.relaxed = rx && (rx->tau_row != 1.f || rx->log_a), row.lmass = rx ? rx->row_lmass : nullptr;
     row.topk = topk, row.val = pi_val, row.idx = pi_idx, row.lmax = row_lmax, row.sum = row_sum, row.u = uf;
     if (topk <= 10)
         launch_final<10>(mfma, row, B, s);
@@ -451,4 +499,68 @@ DVM_EXPORT int dvm_sinkhorn_fwd_hist_f32(const float *f1, const float *f2, int B
     hipLaunchKernelGGL(sinkhorn_zero_slice_kernel, dim3((M + 255) / 256, B), dim3(256), 0, s, v_hist, M, v_bs);   // v^0
     return sinkhorn_run(f1, f2, B, N, M, d, neg_alpha, n_iter, topk, pi_val, pi_idx, row_lmax, row_sum, w.n1, w.n2, u_hist, N, u_bs, v_hist,
                         M, v_bs, u_hist + (size_t)n_iter * N, variant == 0 && d == D, s);
+}
+
+// ---------------------------------------------------------------------------------------- unbalanced (KL-relaxed) entries
+// the argument checks the two entries share; the message names the entry
+static int sinkhorn_ub_check(const char *who, const void *f1, const void *f2, const void *pi_val, const void *pi_idx, int B, int N, int M, int d,
+                             float neg_alpha, int n_iter, int topk, float tau_row, float tau_col, int variant) {
+    DVM_REQUIRE(f1 && f2 && pi_val && pi_idx, "%s: null pointer", who);
+    DVM_REQUIRE(B >= 1 && N >= 1 && M >= 1, "%s: empty input (B=%d N=%d M=%d)", who, B, N, M);
+    DVM_REQUIRE(d >= 4 && d % 4 == 0 && d <= 512, "%s: d=%d unsupported (need d%%4==0, 4<=d<=512)", who, d);
+    DVM_REQUIRE(topk >= 1 && topk <= 16, "%s: topk=%d unsupported (1..16)", who, topk);
+    DVM_REQUIRE(n_iter >= 0, "%s: n_iter=%d must not be negative", who, n_iter);
+    DVM_REQUIRE(neg_alpha < 0.f, "%s: neg_alpha must be negative (got %g)", who, (double)neg_alpha);
+    DVM_REQUIRE(tau_row > 0.f && tau_row <= 1.f && tau_col > 0.f && tau_col <= 1.f, "%s: tau=(%g, %g) outside (0, 1]", who, (double)tau_row,
+                (double)tau_col);
+    DVM_REQUIRE(variant == 0 || variant == 1, "%s: bad variant %d (0 = auto, 1 = scalar)", who, variant);
+    return DVM_OK;
+}
+
+// both entries: |f1|^2, |f2|^2 and the current potentials of the two sides (the caller's u / v where given)
+static size_t carve_sinkhorn_ub(Arena &ar, int B, int N, int M, SinkhornWs &w) { return carve_sinkhorn(ar, B, N, M, true, w); }
+
+DVM_EXPORT size_t dvm_sinkhorn_ub_workspace_bytes(int B, int N, int M, int d) {
+    (void)d;
+    if (B < 1 || N < 1 || M < 1) return 0;
+    return null_carve<SinkhornWs>(carve_sinkhorn_ub, B, N, M);
+}
+
+DVM_EXPORT int dvm_sinkhorn_ub_fwd_f32(const float *f1, const float *f2, int B, int N, int M, int d, float neg_alpha, int n_iter, int topk,
+                                       float tau_row, float tau_col, const float *log_a, const float *log_b, float *pi_val,
+                                       int32_t *pi_idx, float *row_lmax, float *row_sum, float *row_lmass, float *u, float *v, int variant,
+                                       void *ws, size_t ws_bytes, void *stream) {
+    const int rc = sinkhorn_ub_check("dvm_sinkhorn_ub_fwd_f32", f1, f2, pi_val, pi_idx, B, N, M, d, neg_alpha, n_iter, topk, tau_row, tau_col, variant);
+    if (rc != DVM_OK) return rc;
+    SinkhornWs w;
+    if (!carve_ws(ws, ws_bytes, "dvm_sinkhorn_ub_fwd_f32", w, carve_sinkhorn_ub, B, N, M)) return DVM_ENOSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    float *ub = u ? u : w.wu, *vb = v ? v : w.wv;
+    if (n_iter == 0 && v) (void)hipMemsetAsync(v, 0, (size_t)B * M * sizeof(float), s);
+    const Relax rx{tau_row, tau_col, log_a, log_b, row_lmass, nullptr, nullptr};
+    return sinkhorn_run(f1, f2, B, N, M, d, neg_alpha, n_iter, topk, pi_val, pi_idx, row_lmax, row_sum, w.n1, w.n2, ub, 0, N, vb, 0, M, u,
+                        variant == 0 && d == D, s, &rx);
+}
+
+DVM_EXPORT size_t dvm_sinkhorn_ub_hist_workspace_bytes(int B, int N, int M, int d) {
+    (void)d;
+    if (B < 1 || N < 1 || M < 1) return 0;
+    return null_carve<SinkhornWs>(carve_sinkhorn_ub, B, N, M);
+}
+
+DVM_EXPORT int dvm_sinkhorn_ub_fwd_hist_f32(const float *f1, const float *f2, int B, int N, int M, int d, float neg_alpha, int n_iter,
+                                            int topk, float tau_row, float tau_col, const float *log_a, const float *log_b, float *pi_val,
+                                            int32_t *pi_idx, float *row_lmax, float *row_sum, float *row_lmass, float *rn_hist,
+                                            float *cn_hist, int variant, void *ws, size_t ws_bytes, void *stream) {
+    const char *who = "dvm_sinkhorn_ub_fwd_hist_f32";
+    const int rc = sinkhorn_ub_check(who, f1, f2, pi_val, pi_idx, B, N, M, d, neg_alpha, n_iter, topk, tau_row, tau_col, variant);
+    if (rc != DVM_OK) return rc;
+    DVM_REQUIRE(rn_hist && cn_hist, "%s: null pointer", who);
+    SinkhornWs w;
+    if (!carve_ws(ws, ws_bytes, who, w, carve_sinkhorn_ub, B, N, M)) return DVM_ENOSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(sinkhorn_zero_slice_kernel, dim3((M + 255) / 256, B), dim3(256), 0, s, cn_hist, M, (long)(n_iter + 1) * M);   // slot 0
+    const Relax rx{tau_row, tau_col, log_a, log_b, row_lmass, rn_hist, cn_hist};
+    return sinkhorn_run(f1, f2, B, N, M, d, neg_alpha, n_iter, topk, pi_val, pi_idx, row_lmax, row_sum, w.n1, w.n2, w.wu, 0, N, w.wv, 0, M,
+                        nullptr, variant == 0 && d == D, s, &rx);
 }

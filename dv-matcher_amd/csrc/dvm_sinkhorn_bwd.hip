@@ -33,6 +33,13 @@
 // with one term; dvm_softcorr_bwd_f32's atomics are not used).  variant 1 runs scalar forms of phase A and B (any
 // d % 4 == 0, d <= 512; untuned): the cross-check of the matrix-core kernels and the path for d != 128.
 // Every kernel here forms its distances with dvm_dist_tile.h.
+//
+// dvm_sinkhorn_ub_bwd_f32 is the same structure for the unbalanced operator (the formulas are in include/dvm.h).  Its history
+// holds the normalisers m^t, n^t; skb_ub_pots_kernel re-makes the potentials u^t, v^t from them by the forward's expression.
+// prep takes H_i = tau_row G_i - (1 - tau_row) g_lmass_i for G_i and R^f = val exp(-row_lmass) for P; a phase A sweep scales
+// what it stores (nbar^t = tau_col vbar^t, mbar^t = tau_row ubar^t are what the next sweep and phase B read); Q^t pairs
+// (u^t, n^t) and R^t pairs (m^t, v^(t-1)), so phase B reads R^t's potentials from a third group of planes; and
+// skb_ub_logw_kernel adds the adjoints over t, in ascending t, into d_log_a / d_log_b.
 #include <float.h>
 #include <math.h>
 
@@ -53,7 +60,8 @@ __global__ __launch_bounds__(256) void skb_prep_kernel(const float *__restrict__
                                                        const float *__restrict__ gval, int B, int N, int M, int d, int topk,
                                                        float neg_alpha, float *__restrict__ Gout, float *__restrict__ esp,
                                                        float *__restrict__ wsp, uint32_t *__restrict__ topk_bits,
-                                                       float *__restrict__ df1) {
+                                                       float *__restrict__ df1, const float *__restrict__ row_lmass,
+                                                       const float *__restrict__ g_lmass, float tau_row, float *__restrict__ Graw) {
     const int lane = threadIdx.x & 63;
     const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= (long)B * N) return;
@@ -68,6 +76,14 @@ __global__ __launch_bounds__(256) void skb_prep_kernel(const float *__restrict__
     }
     float G = 0.f;
     for (int t = 0; t < topk; ++t) G += gval[(size_t)row * topk + t] * pi_val[(size_t)row * topk + t];
+    // unbalanced (row_lmass given): the final step's coefficient is H, its probability R^f = val / mass.  exp(-row_lmass) is
+    // applied as two equal factors: it alone leaves fp32's range where the mass is below 2^-126 and val is still nonzero.
+    const float Graw_i = G;
+    float unmass = 1.f;
+    if (row_lmass) {
+        G = tau_row * G - (1.f - tau_row) * (g_lmass ? g_lmass[row] : 0.f);
+        unmass = expf(-0.5f * fmaxf(row_lmass[row], -170.f));   // (below e^-170 every val is 0)
+    }
     const int wpr = (M + 31) >> 5;
     for (int t = 0; t < topk; ++t) {
         const int j = pi_idx[(size_t)row * topk + t];
@@ -75,7 +91,7 @@ __global__ __launch_bounds__(256) void skb_prep_kernel(const float *__restrict__
         if (j >= 0 && j < M) {   // uniform over the wave
             if (lane == 0) atomicOr(topk_bits + (size_t)row * wpr + (j >> 5), 1u << (j & 31));
             const float val = pi_val[(size_t)row * topk + t];
-            E = fmaf(-val, G, gval[(size_t)row * topk + t] * val);
+            E = fmaf(row_lmass ? -((val * unmass) * unmass) : -val, G, gval[(size_t)row * topk + t] * val);
             if (E != 0.f) {
                 const float *x = f2 + ((size_t)b * M + j) * d;
                 float dx[8], part = 0.f;
@@ -99,6 +115,7 @@ __global__ __launch_bounds__(256) void skb_prep_kernel(const float *__restrict__
         }
     }
     if (lane == 0) Gout[row] = G;
+    if (lane == 0 && Graw) Graw[row] = Graw_i;
     float *dst = df1 + (size_t)row * d;
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
@@ -183,6 +200,63 @@ __global__ void skb_pack_kernel(const float *__restrict__ u_hist, const float *_
     }
 }
 
+// unbalanced: the potentials of every iterate from the normalisers, by the forward's expression tau * (log weight + normaliser)
+//   upot [B][T][N]: u^1..u^T      vpot [B][T+1][M]: v^0 = 0, v^1..v^T      (log_a NULL = 0, log_b NULL = log_ratio)
+__global__ void skb_ub_pots_kernel(const float *__restrict__ rn_hist, const float *__restrict__ cn_hist, const float *__restrict__ log_a,
+                                   const float *__restrict__ log_b, float tau_row, float tau_col, float log_ratio, int N, int M, int T,
+                                   float *__restrict__ upot, float *__restrict__ vpot) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int t = blockIdx.y, b = blockIdx.z;
+    if (i < N && t < T) {
+        const float w = log_a ? log_a[(size_t)b * N + i] : 0.f;
+        upot[((size_t)b * T + t) * N + i] = tau_row * (w + rn_hist[((size_t)b * (T + 1) + t) * N + i]);
+    }
+    if (i < M) {
+        const float w = log_b ? log_b[(size_t)b * M + i] : log_ratio;
+        vpot[((size_t)b * (T + 1) + t) * M + i] = t == 0 ? 0.f : tau_col * (w + cn_hist[((size_t)b * (T + 1) + t) * M + i]);
+    }
+}
+
+// unbalanced planes of phase B, K2 = 3 (T + 1) per side: [0..T] Q^t's potentials, [T+1..2T+1] coefficients, [2T+2..3T+2] R^t's
+//   rows:    potQ[0] = m^f, potQ[t] = u^t;   coef[0] = H, coef[t] = mbar^t;   potR[0] = m^f, potR[t] = m^t
+//   columns: potQ[t] = n^t;                  coef[0] unused, coef[t] = nbar^t;   potR[t] = v^t (t = 0..T: R^t reads v^(t-1), the final step v^T)
+__global__ void skb_ub_pack_kernel(const float *__restrict__ rn_hist, const float *__restrict__ cn_hist, const float *__restrict__ upot,
+                                   const float *__restrict__ vpot, const float *__restrict__ H, const float *__restrict__ mbar,
+                                   const float *__restrict__ nbar, int N, int M, int T, float *__restrict__ tabR, float *__restrict__ tabC) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int t = blockIdx.y, b = blockIdx.z;
+    const int K2 = 3 * (T + 1);
+    if (i < N) {
+        const float m = rn_hist[((size_t)b * (T + 1) + (t == 0 ? T : t - 1)) * N + i] * LOG2E;
+        tabR[((size_t)b * K2 + t) * N + i] = t == 0 ? m : upot[((size_t)b * T + t - 1) * N + i] * LOG2E;
+        tabR[((size_t)b * K2 + T + 1 + t) * N + i] = t == 0 ? H[(size_t)b * N + i] : mbar[((size_t)b * T + t - 1) * N + i];
+        tabR[((size_t)b * K2 + 2 * T + 2 + t) * N + i] = m;
+    }
+    if (i < M) {
+        tabC[((size_t)b * K2 + t) * M + i] = cn_hist[((size_t)b * (T + 1) + t) * M + i] * LOG2E;
+        tabC[((size_t)b * K2 + T + 1 + t) * M + i] = t == 0 ? 0.f : nbar[((size_t)b * T + t - 1) * M + i];
+        tabC[((size_t)b * K2 + 2 * T + 2 + t) * M + i] = vpot[((size_t)b * (T + 1) + t) * M + i] * LOG2E;
+    }
+}
+
+// d_log_a_i = tau_row (G_i + g_lmass_i) + sum_t mbar^t_i      d_log_b_j = sum_t nbar^t_j      (t ascending; either may be NULL)
+__global__ void skb_ub_logw_kernel(const float *__restrict__ G, const float *__restrict__ g_lmass, const float *__restrict__ mbar,
+                                   const float *__restrict__ nbar, float tau_row, int N, int M, int T, float *__restrict__ d_log_a,
+                                   float *__restrict__ d_log_b) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int b = blockIdx.y;
+    if (d_log_a && i < N) {
+        float acc = tau_row * (G[(size_t)b * N + i] + (g_lmass ? g_lmass[(size_t)b * N + i] : 0.f));
+        for (int t = 0; t < T; ++t) acc += mbar[((size_t)b * T + t) * N + i];
+        d_log_a[(size_t)b * N + i] = acc;
+    }
+    if (d_log_b && i < M) {
+        float acc = 0.f;
+        for (int t = 0; t < T; ++t) acc += nbar[((size_t)b * T + t) * M + i];
+        d_log_b[(size_t)b * M + i] = acc;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ phase A
 struct SAArgs {
     const float *q, *k;       // queries [B][N][d], keys [B][M][d]
@@ -190,6 +264,7 @@ struct SAArgs {
     const float *potq, *potk, *coefk;   // the queries' potential, the keys' potential and coefficient (entry b at p + b * bs)
     long potq_bs, potk_bs, coefk_bs, out_bs;
     float add;                // added to the queries' potential (-c in the sweeps over Q^t)
+    float scale;              // on what is stored: 1, or the tau that turns vbar into nbar / ubar into mbar (unbalanced)
     int N, M, d, tiles;
     float neg_alpha;
     float *out;               // out_q = [MASKED: out_q] - sum_k coef_k exp(S_qk + potk_k + (potq_q + add))
@@ -243,7 +318,7 @@ __global__ __launch_bounds__(128) void skb_sweep_scalar_kernel(const SAArgs a) {
     }
     if (i < N) {
         float *o = a.out + (size_t)b * a.out_bs + i;
-        *o = (float)((MASKED ? (double)*o : 0.0) - sum);
+        *o = (float)((MASKED ? (double)*o : 0.0) - sum) * a.scale;
     }
 }
 
@@ -333,7 +408,7 @@ __global__ __launch_bounds__(SK_THREADS, 2) void skb_sweep_mfma_kernel(const SAA
     sum += __shfl_xor(sum, 32, 64);
     if (h == 0 && qrow < N) {
         float *o = a.out + (size_t)b * a.out_bs + qrow;
-        *o = (float)((MASKED ? (double)*o : 0.0) - sum);
+        *o = (float)((MASKED ? (double)*o : 0.0) - sum) * a.scale;
     }
 }
 
@@ -372,7 +447,8 @@ struct PBArgs {
     float a2, nalpha;   // neg_alpha * log2(e), -neg_alpha
 };
 
-template <int grp>
+// UB: the unbalanced operator's planes (skb_ub_pack_kernel): R^t takes its two potentials from the third group
+template <int grp, bool UB>
 __global__ __launch_bounds__(BW_THREADS, 2) void skb_apply_mfma_kernel(const PBArgs args) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int TF = args.tile_floats;
@@ -380,7 +456,8 @@ __global__ __launch_bounds__(BW_THREADS, 2) void skb_apply_mfma_kernel(const PBA
 
     const int lid = xcd_remap(blockIdx.x, gridDim.x);
     const PBGroup &G = args.g[grp];
-    const int No = G.No, Ni = G.Ni, T = args.T, K2 = 2 * (T + 1);
+    const int No = G.No, Ni = G.Ni, T = args.T, K2 = (UB ? 3 : 2) * (T + 1);
+    const int PR = 2 * T + 2;   // UB: the first of R^t's planes
     const int ot = lid % G.tiles_o, b = lid / G.tiles_o;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r32 = lane & 31, h = lane >> 5;
@@ -420,7 +497,7 @@ __global__ __launch_bounds__(BW_THREADS, 2) void skb_apply_mfma_kernel(const PBA
         ((uint32_t *)kt)[ROWS_FLOATS + KT + tid] = prem;
         for (int e = tid; e < K2 * KT; e += BW_THREADS) {
             const int kk = e >> 6, j = j0 + (e & 63);
-            kt[BW_FIXED_FLOATS + e] = j < Ni ? itab[(size_t)kk * Ni + j] : (kk <= T ? -INFINITY : 0.f);
+            kt[BW_FIXED_FLOATS + e] = j < Ni ? itab[(size_t)kk * Ni + j] : ((kk <= T || kk >= PR) ? -INFINITY : 0.f);
         }
     };
 
@@ -449,9 +526,10 @@ __global__ __launch_bounds__(BW_THREADS, 2) void skb_apply_mfma_kernel(const PBA
             float w[16];
             {   // the final row step's term, skipped on the row's top-k columns (prep / colgather own it there)
                 const unsigned skip = skip_mask_lane<BW_WAVES>(grp, msk, wave, r32, sub, h);
-                const float po = to[(size_t)(grp == 0 ? 0 : T) * No];
+                const int vT = UB ? PR + T : T;   // the columns' plane of v^T
+                const float po = to[(size_t)(grp == 0 ? 0 : vT) * No];
                 const float co = grp == 0 ? to[(size_t)(T + 1) * No] : 1.f;
-                const float *pin = tb + (grp == 0 ? T : 0) * KT;
+                const float *pin = tb + (grp == 0 ? vT : 0) * KT;
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     const f32x4 pi = *(const f32x4 *)(pin + 8 * g);
@@ -469,13 +547,17 @@ __global__ __launch_bounds__(BW_THREADS, 2) void skb_apply_mfma_kernel(const PBA
 #pragma unroll 1
             for (int tt = 1; tt <= T; ++tt) {
                 const float po = to[(size_t)tt * No];
-                const float pox = grp == 0 ? po : to[(size_t)(tt - 1) * No];
+                // R^t: balanced, the row's u^t again and the column's v^(t-1); UB, the row's m^t and the column's v^(t-1)
+                const float pox = UB ? to[(size_t)(PR + tt - grp) * No] : (grp == 0 ? po : to[(size_t)(tt - 1) * No]);
                 const float co = to[(size_t)(T + 1 + tt) * No];
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     const f32x4 pi = *(const f32x4 *)(tb + tt * KT + 8 * g);
                     f32x4 pix = pi;
-                    if (grp == 0) pix = *(const f32x4 *)(tb + (tt - 1) * KT + 8 * g);
+                    if (UB)
+                        pix = *(const f32x4 *)(tb + (PR + tt - 1 + grp) * KT + 8 * g);
+                    else if (grp == 0)
+                        pix = *(const f32x4 *)(tb + (tt - 1) * KT + 8 * g);
                     const f32x4 ci = *(const f32x4 *)(tb + (T + 1 + tt) * KT + 8 * g);
 #pragma unroll
                     for (int u = 0; u < 4; ++u) {
@@ -510,6 +592,7 @@ struct PBScalarArgs {
     float *df1, *df2;
     const uint32_t *topk_bits;
     int N, M, d, T, wpr;
+    int ub;   // the unbalanced operator's planes (skb_ub_pack_kernel)
     long rows0, rows_total;
     float a2, nalpha;
 };
@@ -520,7 +603,8 @@ __global__ __launch_bounds__(256) void skb_apply_scalar_kernel(const PBScalarArg
     if (gw >= args.rows_total) return;
     const int grp = gw >= args.rows0 ? 1 : 0;
     gw -= grp ? args.rows0 : 0;
-    const int N = args.N, M = args.M, d = args.d, T = args.T, K2 = 2 * (T + 1);
+    const int N = args.N, M = args.M, d = args.d, T = args.T, K2 = (args.ub ? 3 : 2) * (T + 1);
+    const int PR = args.ub ? 2 * T + 2 : 0;   // the first of R^t's planes (balanced: R^t reads Q^t's)
     const int No = grp ? M : N, Ni = grp ? N : M;
     const int b = (int)(gw / No), row = (int)(gw % No);
     const float *fob = grp ? args.f2 : args.f1, *fib = grp ? args.f1 : args.f2;
@@ -545,11 +629,12 @@ __global__ __launch_bounds__(256) void skb_apply_scalar_kernel(const PBScalarArg
         const float v = wave_row_sqdist(part, ov, xv, nrm_o, nib[(size_t)b * Ni + j]);
         if (!(v > 0.f)) continue;
         const float D = sqrt_rn(v);
-        float sum = topk ? 0.f : tr[(size_t)(T + 1) * N + ri] * exp2f(fmaf(D, args.a2, tr[ri] + tc[(size_t)T * M + ci]));
+        float sum = topk ? 0.f : tr[(size_t)(T + 1) * N + ri] * exp2f(fmaf(D, args.a2, tr[ri] + tc[(size_t)(PR + T) * M + ci]));
         for (int t = 1; t <= T; ++t) {
             const float pr = tr[(size_t)t * N + ri];
             sum = fmaf(tc[(size_t)(T + 1 + t) * M + ci], exp2f(fmaf(D, args.a2, pr + tc[(size_t)t * M + ci])), sum);
-            sum = fmaf(tr[(size_t)(T + 1 + t) * N + ri], exp2f(fmaf(D, args.a2, pr + tc[(size_t)(t - 1) * M + ci])), sum);
+            sum = fmaf(tr[(size_t)(T + 1 + t) * N + ri],
+                       exp2f(fmaf(D, args.a2, tr[(size_t)(PR + t) * N + ri] + tc[(size_t)(PR + t - 1) * M + ci])), sum);
         }
         const float w = args.nalpha * sum / D;
         rsum += w;
@@ -564,13 +649,15 @@ __global__ __launch_bounds__(256) void skb_apply_scalar_kernel(const PBScalarArg
     }
 }
 
+// ub (dvm_sinkhorn_ub_bwd_f32): ubar / vbar hold mbar / nbar, the planes are 3 (T + 1) per side, plus the unscaled G and the
+// re-made potentials upot [B][T][N], vpot [B][T+1][M]
 struct SkbWs {
-    float *n1, *n2, *G, *esp, *wsp, *ubar, *vbar, *tabR, *tabC;
+    float *n1, *n2, *G, *esp, *wsp, *ubar, *vbar, *tabR, *tabC, *Graw, *upot, *vpot;
     uint32_t *bits;
 };
-SkbWs skb_carve(Arena &ar, int B, int N, int M, int n_iter, int topk) {
+SkbWs skb_carve(Arena &ar, int B, int N, int M, int n_iter, int topk, bool ub = false) {
     SkbWs w;
-    const size_t T = (size_t)n_iter;
+    const size_t T = (size_t)n_iter, P = ub ? 3 : 2;
     w.n1 = ar.take<float>((size_t)B * N);
     w.n2 = ar.take<float>((size_t)B * M);
     w.G = ar.take<float>((size_t)B * N);
@@ -578,9 +665,12 @@ SkbWs skb_carve(Arena &ar, int B, int N, int M, int n_iter, int topk) {
     w.wsp = ar.take<float>((size_t)B * N * topk);
     w.ubar = ar.take<float>((size_t)B * N * (T ? T : 1));
     w.vbar = ar.take<float>((size_t)B * M * (T ? T : 1));
-    w.tabR = ar.take<float>((size_t)B * N * 2 * (T + 1));
-    w.tabC = ar.take<float>((size_t)B * M * 2 * (T + 1));
+    w.tabR = ar.take<float>((size_t)B * N * P * (T + 1));
+    w.tabC = ar.take<float>((size_t)B * M * P * (T + 1));
     w.bits = ar.take<uint32_t>((size_t)B * N * ((M + 31) / 32));
+    w.Graw = ub ? ar.take<float>((size_t)B * N) : nullptr;
+    w.upot = ub ? ar.take<float>((size_t)B * N * (T ? T : 1)) : nullptr;
+    w.vpot = ub ? ar.take<float>((size_t)B * M * (T + 1)) : nullptr;
     return w;
 }
 
@@ -597,6 +687,105 @@ DVM_EXPORT size_t dvm_sinkhorn_bwd_workspace_bytes(int B, int N, int M, int d, i
     return ar.off;
 }
 
+// what the unbalanced entry adds to the run below
+struct SkbUb {
+    float tau_row, tau_col;
+    const float *log_a, *log_b, *row_lmass, *g_lmass;
+    float *d_log_a, *d_log_b;
+};
+
+// Both backward entries.  balanced (ub NULL): rhist / chist are u_hist / v_hist.  unbalanced: they are rn_hist / cn_hist, the
+// potentials come from skb_ub_pots_kernel, and every sweep stores its result times the tau of the side it belongs to.
+static int skb_run(const SkbWs &w, const float *f1, const float *f2, int B, int N, int M, int d, float neg_alpha, int T, int topk,
+                   const float *pi_val, const int32_t *pi_idx, const float *rhist, const float *chist, const float *g_val, float *d_f1,
+                   float *d_f2, bool mfma, const SkbUb *ub, hipStream_t s) {
+    const int wpr = (M + 31) / 32;
+    const long u_bs = (long)(T + 1) * N, v_bs = (long)(T + 1) * M;
+    const float c = (float)log((double)N / (double)M);
+    (void)hipMemsetAsync(w.bits, 0, (size_t)B * N * wpr * sizeof(uint32_t), s);
+    launch_rownorm2(f1, B * N, d, w.n1, s);
+    launch_rownorm2(f2, B * M, d, w.n2, s);
+    if (ub)
+        hipLaunchKernelGGL(skb_ub_pots_kernel, dim3((std::max(N, M) + 255) / 256, T + 1, B), dim3(256), 0, s, rhist, chist, ub->log_a, ub->log_b,
+                           ub->tau_row, ub->tau_col, c, N, M, T, w.upot, w.vpot);
+    hipLaunchKernelGGL(skb_prep_kernel, dim3((unsigned)(((size_t)B * N + 3) / 4)), dim3(256), 0, s, f1, f2, pi_val, pi_idx, g_val, B, N, M, d,
+                       topk, neg_alpha, w.G, w.esp, w.wsp, w.bits, d_f1, ub ? ub->row_lmass : nullptr, ub ? ub->g_lmass : nullptr,
+                       ub ? ub->tau_row : 1.f, w.Graw);
+    {
+        const size_t lds = (size_t)(32 * d + 32) * sizeof(float);
+        ensure_dyn_lds((const void *)skb_colgather_kernel, 66 * 1024);
+        hipLaunchKernelGGL(skb_colgather_kernel, dim3(wpr, B), dim3(256), lds, s, f1, f2, pi_idx, w.esp, w.wsp, w.bits, N, M, d, topk, d_f2,
+                           T ? w.vbar + (size_t)(T - 1) * M : nullptr, (long)T * M);
+    }
+    if (T) {
+        // the potentials of the queries / keys of each sweep: balanced, slices of the two histories (Q^t's -c on the row side);
+        // unbalanced, Q^t = exp(S + u^t + n^t) and R^t = exp(S + m^t + v^(t-1)) pair a re-made potential with a normaliser
+        const float *uQ = ub ? w.upot : rhist, *vR = ub ? w.vpot : chist;
+        const long uQ_bs = ub ? (long)T * N : u_bs;
+        SAArgs row{}, col{};
+        row.q = f1, row.k = f2, row.nq = w.n1, row.nk = w.n2, row.N = N, row.M = M, row.d = d, row.neg_alpha = neg_alpha;
+        col.q = f2, col.k = f1, col.nq = w.n2, col.nk = w.n1, col.N = M, col.M = N, col.d = d, col.neg_alpha = neg_alpha;
+        row.potq_bs = uQ_bs, row.potk_bs = v_bs, row.coefk_bs = (long)T * M, row.out_bs = (long)T * N, row.add = ub ? 0.f : -c;
+        col.potq_bs = v_bs, col.potk_bs = u_bs, col.out_bs = (long)T * M, col.add = 0.f;
+        row.scale = ub ? ub->tau_row : 1.f, col.scale = ub ? ub->tau_col : 1.f;
+        // vbar^T_j = [colgather: the top-k slots] - sum_i G_i P_ij over the other entries (unbalanced: H_i R^f_ij)
+        col.potq = vR + (size_t)T * M, col.potk = rhist + (size_t)T * N, col.coefk = w.G, col.coefk_bs = N;
+        col.out = w.vbar + (size_t)(T - 1) * M, col.bits = w.bits, col.wpr = wpr;
+        launch_sweep_t<true, true>(mfma, col, B, s);
+        col.bits = nullptr, col.coefk_bs = (long)T * N;
+        for (int t = T; t >= 1; --t) {
+            row.potq = uQ + (size_t)(t - 1) * N, row.potk = chist + (size_t)t * M, row.coefk = w.vbar + (size_t)(t - 1) * M;
+            row.out = w.ubar + (size_t)(t - 1) * N;
+            launch_sweep_t<false, false>(mfma, row, B, s);   // ubar^t = -sum_j vbar^t_j Q^t_ij
+            if (t > 1) {
+                col.potq = vR + (size_t)(t - 1) * M, col.potk = rhist + (size_t)(t - 1) * N, col.coefk = w.ubar + (size_t)(t - 1) * N;
+                col.out = w.vbar + (size_t)(t - 2) * M;
+                launch_sweep_t<true, false>(mfma, col, B, s);   // vbar^(t-1) = -sum_i ubar^t_i R^t_ij
+            }
+        }
+    }
+    const dim3 pgrid((std::max(N, M) + 255) / 256, T + 1, B);
+    if (ub) {
+        hipLaunchKernelGGL(skb_ub_pack_kernel, pgrid, dim3(256), 0, s, rhist, chist, w.upot, w.vpot, w.G, w.ubar, w.vbar, N, M, T, w.tabR, w.tabC);
+        if (ub->d_log_a || ub->d_log_b)
+            hipLaunchKernelGGL(skb_ub_logw_kernel, dim3((std::max(N, M) + 255) / 256, B), dim3(256), 0, s, w.Graw, ub->g_lmass, w.ubar, w.vbar,
+                               ub->tau_row, N, M, T, ub->d_log_a, ub->d_log_b);
+    } else {
+        hipLaunchKernelGGL(skb_pack_kernel, pgrid, dim3(256), 0, s, rhist, chist, w.G, w.ubar, w.vbar, N, M, T, (float)((double)M / (double)N),
+                           w.tabR, w.tabC);
+    }
+    const float a2 = neg_alpha * LOG2E;
+    const int planes = (ub ? 3 : 2) * (T + 1);
+    if (mfma) {
+        PBArgs a;
+        a.g[0] = PBGroup{f1, f2, w.n1, w.n2, w.tabR, w.tabC, d_f1, N, M, (N + BW_OB - 1) / BW_OB};
+        a.g[1] = PBGroup{f2, f1, w.n2, w.n1, w.tabC, w.tabR, d_f2, M, N, (M + BW_OB - 1) / BW_OB};
+        a.topk_bits = w.bits, a.wpr = wpr, a.T = T, a.a2 = a2, a.nalpha = -neg_alpha;
+        a.tile_floats = BW_FIXED_FLOATS + planes * KT;
+        const size_t lds = ((size_t)2 * a.tile_floats + BW_OB) * sizeof(float);
+        const int lds_max = (int)(((size_t)2 * (BW_FIXED_FLOATS + (ub ? 3 : 2) * (SKB_MAX_ITER + 1) * KT) + BW_OB) * sizeof(float));
+        if (ub) {
+            ensure_dyn_lds((const void *)skb_apply_mfma_kernel<0, true>, lds_max);
+            ensure_dyn_lds((const void *)skb_apply_mfma_kernel<1, true>, lds_max);
+            hipLaunchKernelGGL((skb_apply_mfma_kernel<0, true>), dim3(B * a.g[0].tiles_o), dim3(BW_THREADS), lds, s, a);
+            hipLaunchKernelGGL((skb_apply_mfma_kernel<1, true>), dim3(B * a.g[1].tiles_o), dim3(BW_THREADS), lds, s, a);
+        } else {
+            ensure_dyn_lds((const void *)skb_apply_mfma_kernel<0, false>, lds_max);
+            ensure_dyn_lds((const void *)skb_apply_mfma_kernel<1, false>, lds_max);
+            hipLaunchKernelGGL((skb_apply_mfma_kernel<0, false>), dim3(B * a.g[0].tiles_o), dim3(BW_THREADS), lds, s, a);
+            hipLaunchKernelGGL((skb_apply_mfma_kernel<1, false>), dim3(B * a.g[1].tiles_o), dim3(BW_THREADS), lds, s, a);
+        }
+    } else {
+        PBScalarArgs a;
+        a.f1 = f1, a.f2 = f2, a.n1 = w.n1, a.n2 = w.n2, a.tabR = w.tabR, a.tabC = w.tabC, a.df1 = d_f1, a.df2 = d_f2;
+        a.topk_bits = w.bits, a.N = N, a.M = M, a.d = d, a.T = T, a.wpr = wpr, a.ub = ub ? 1 : 0, a.a2 = a2, a.nalpha = -neg_alpha;
+        a.rows0 = (long)B * N, a.rows_total = (long)B * N + (long)B * M;
+        hipLaunchKernelGGL(skb_apply_scalar_kernel, dim3((unsigned)((a.rows_total + 3) / 4)), dim3(256), 0, s, a);
+    }
+    DVM_CHECK_LAUNCH("sinkhorn_bwd");
+    return DVM_OK;
+}
+
 DVM_EXPORT int dvm_sinkhorn_bwd_f32(const float *f1, const float *f2, int B, int N, int M, int d, float neg_alpha, int n_iter, int topk,
                                     const float *pi_val, const int32_t *pi_idx, const float *u_hist, const float *v_hist,
                                     const float *g_val, float *d_f1, float *d_f2, int variant, void *ws, size_t ws_bytes, void *stream) {
@@ -610,66 +799,36 @@ DVM_EXPORT int dvm_sinkhorn_bwd_f32(const float *f1, const float *f2, int B, int
     Arena ar(ws, ws_bytes);
     const SkbWs w = skb_carve(ar, B, N, M, n_iter, topk);
     if (!arena_fits(ar, "dvm_sinkhorn_bwd_f32")) return DVM_ENOSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    const int T = n_iter, wpr = (M + 31) / 32;
-    const bool mfma = variant == 0 && d == D;
-    const long u_bs = (long)(T + 1) * N, v_bs = (long)(T + 1) * M;
-    (void)hipMemsetAsync(w.bits, 0, (size_t)B * N * wpr * sizeof(uint32_t), s);
-    launch_rownorm2(f1, B * N, d, w.n1, s);
-    launch_rownorm2(f2, B * M, d, w.n2, s);
-    hipLaunchKernelGGL(skb_prep_kernel, dim3((unsigned)(((size_t)B * N + 3) / 4)), dim3(256), 0, s, f1, f2, pi_val, pi_idx, g_val, B, N, M, d,
-                       topk, neg_alpha, w.G, w.esp, w.wsp, w.bits, d_f1);
-    {
-        const size_t lds = (size_t)(32 * d + 32) * sizeof(float);
-        ensure_dyn_lds((const void *)skb_colgather_kernel, 66 * 1024);
-        hipLaunchKernelGGL(skb_colgather_kernel, dim3(wpr, B), dim3(256), lds, s, f1, f2, pi_idx, w.esp, w.wsp, w.bits, N, M, d, topk, d_f2,
-                           T ? w.vbar + (size_t)(T - 1) * M : nullptr, (long)T * M);
-    }
-    if (T) {
-        const float c = (float)log((double)N / (double)M);
-        SAArgs row{}, col{};
-        row.q = f1, row.k = f2, row.nq = w.n1, row.nk = w.n2, row.N = N, row.M = M, row.d = d, row.neg_alpha = neg_alpha;
-        col.q = f2, col.k = f1, col.nq = w.n2, col.nk = w.n1, col.N = M, col.M = N, col.d = d, col.neg_alpha = neg_alpha;
-        row.potq_bs = u_bs, row.potk_bs = v_bs, row.coefk_bs = (long)T * M, row.out_bs = (long)T * N, row.add = -c;
-        col.potq_bs = v_bs, col.potk_bs = u_bs, col.out_bs = (long)T * M, col.add = 0.f;
-        // vbar^T_j = [colgather: the top-k slots] - sum_i G_i P_ij over the other entries
-        col.potq = v_hist + (size_t)T * M, col.potk = u_hist + (size_t)T * N, col.coefk = w.G, col.coefk_bs = N;
-        col.out = w.vbar + (size_t)(T - 1) * M, col.bits = w.bits, col.wpr = wpr;
-        launch_sweep_t<true, true>(mfma, col, B, s);
-        col.bits = nullptr, col.coefk_bs = (long)T * N;
-        for (int t = T; t >= 1; --t) {
-            row.potq = u_hist + (size_t)(t - 1) * N, row.potk = v_hist + (size_t)t * M, row.coefk = w.vbar + (size_t)(t - 1) * M;
-            row.out = w.ubar + (size_t)(t - 1) * N;
-            launch_sweep_t<false, false>(mfma, row, B, s);   // ubar^t = -sum_j vbar^t_j Q^t_ij
-            if (t > 1) {
-                col.potq = v_hist + (size_t)(t - 1) * M, col.potk = u_hist + (size_t)(t - 1) * N, col.coefk = w.ubar + (size_t)(t - 1) * N;
-                col.out = w.vbar + (size_t)(t - 2) * M;
-                launch_sweep_t<true, false>(mfma, col, B, s);   // vbar^(t-1) = -sum_i ubar^t_i R^t_ij
-            }
-        }
-    }
-    hipLaunchKernelGGL(skb_pack_kernel, dim3((std::max(N, M) + 255) / 256, T + 1, B), dim3(256), 0, s, u_hist, v_hist, w.G, w.ubar, w.vbar, N,
-                       M, T, (float)((double)M / (double)N), w.tabR, w.tabC);
-    const float a2 = neg_alpha * LOG2E;
-    if (mfma) {
-        PBArgs a;
-        a.g[0] = PBGroup{f1, f2, w.n1, w.n2, w.tabR, w.tabC, d_f1, N, M, (N + BW_OB - 1) / BW_OB};
-        a.g[1] = PBGroup{f2, f1, w.n2, w.n1, w.tabC, w.tabR, d_f2, M, N, (M + BW_OB - 1) / BW_OB};
-        a.topk_bits = w.bits, a.wpr = wpr, a.T = T, a.a2 = a2, a.nalpha = -neg_alpha;
-        a.tile_floats = BW_FIXED_FLOATS + 2 * (T + 1) * KT;
-        const size_t lds = ((size_t)2 * a.tile_floats + BW_OB) * sizeof(float);
-        const int lds_max = (int)(((size_t)2 * (BW_FIXED_FLOATS + 2 * (SKB_MAX_ITER + 1) * KT) + BW_OB) * sizeof(float));
-        ensure_dyn_lds((const void *)skb_apply_mfma_kernel<0>, lds_max);
-        ensure_dyn_lds((const void *)skb_apply_mfma_kernel<1>, lds_max);
-        hipLaunchKernelGGL(skb_apply_mfma_kernel<0>, dim3(B * a.g[0].tiles_o), dim3(BW_THREADS), lds, s, a);
-        hipLaunchKernelGGL(skb_apply_mfma_kernel<1>, dim3(B * a.g[1].tiles_o), dim3(BW_THREADS), lds, s, a);
-    } else {
-        PBScalarArgs a;
-        a.f1 = f1, a.f2 = f2, a.n1 = w.n1, a.n2 = w.n2, a.tabR = w.tabR, a.tabC = w.tabC, a.df1 = d_f1, a.df2 = d_f2;
-        a.topk_bits = w.bits, a.N = N, a.M = M, a.d = d, a.T = T, a.wpr = wpr, a.a2 = a2, a.nalpha = -neg_alpha;
-        a.rows0 = (long)B * N, a.rows_total = (long)B * N + (long)B * M;
-        hipLaunchKernelGGL(skb_apply_scalar_kernel, dim3((unsigned)((a.rows_total + 3) / 4)), dim3(256), 0, s, a);
-    }
-    DVM_CHECK_LAUNCH("sinkhorn_bwd");
-    return DVM_OK;
+    return skb_run(w, f1, f2, B, N, M, d, neg_alpha, n_iter, topk, pi_val, pi_idx, u_hist, v_hist, g_val, d_f1, d_f2, variant == 0 && d == D,
+                   nullptr, (hipStream_t)stream);
+}
+
+DVM_EXPORT size_t dvm_sinkhorn_ub_bwd_workspace_bytes(int B, int N, int M, int d, int n_iter) {
+    (void)d;
+    if (B < 1 || N < 1 || M < 1 || n_iter < 0 || n_iter > SKB_MAX_ITER) return 0;
+    Arena ar(nullptr, 0);
+    (void)skb_carve(ar, B, N, M, n_iter, 16, true);
+    return ar.off;
+}
+
+DVM_EXPORT int dvm_sinkhorn_ub_bwd_f32(const float *f1, const float *f2, int B, int N, int M, int d, float neg_alpha, int n_iter, int topk,
+                                       float tau_row, float tau_col, const float *log_a, const float *log_b, const float *pi_val,
+                                       const int32_t *pi_idx, const float *row_lmass, const float *rn_hist, const float *cn_hist,
+                                       const float *g_val, const float *g_lmass, float *d_f1, float *d_f2, float *d_log_a, float *d_log_b,
+                                       int variant, void *ws, size_t ws_bytes, void *stream) {
+    DVM_REQUIRE(f1 && f2 && pi_val && pi_idx && row_lmass && rn_hist && cn_hist && g_val && d_f1 && d_f2, "dvm_sinkhorn_ub_bwd_f32: null pointer");
+    DVM_REQUIRE(B >= 1 && N >= 1 && M >= 1, "dvm_sinkhorn_ub_bwd_f32: empty input (B=%d N=%d M=%d)", B, N, M);
+    DVM_REQUIRE(d >= 4 && d % 4 == 0 && d <= 512, "dvm_sinkhorn_ub_bwd_f32: d=%d unsupported (need d%%4==0, 4<=d<=512)", d);
+    DVM_REQUIRE(topk >= 1 && topk <= 16, "dvm_sinkhorn_ub_bwd_f32: topk=%d unsupported (1..16)", topk);
+    DVM_REQUIRE(n_iter >= 0 && n_iter <= SKB_MAX_ITER, "dvm_sinkhorn_ub_bwd_f32: n_iter=%d unsupported (0..%d)", n_iter, SKB_MAX_ITER);
+    DVM_REQUIRE(neg_alpha < 0.f, "dvm_sinkhorn_ub_bwd_f32: neg_alpha must be negative (got %g)", (double)neg_alpha);
+    DVM_REQUIRE(tau_row > 0.f && tau_row <= 1.f && tau_col > 0.f && tau_col <= 1.f, "dvm_sinkhorn_ub_bwd_f32: tau=(%g, %g) outside (0, 1]",
+                (double)tau_row, (double)tau_col);
+    DVM_REQUIRE(variant == 0 || variant == 1, "dvm_sinkhorn_ub_bwd_f32: bad variant %d (0 = auto, 1 = scalar)", variant);
+    Arena ar(ws, ws_bytes);
+    const SkbWs w = skb_carve(ar, B, N, M, n_iter, topk, true);
+    if (!arena_fits(ar, "dvm_sinkhorn_ub_bwd_f32")) return DVM_ENOSPACE;
+    const SkbUb ub{tau_row, tau_col, log_a, log_b, row_lmass, g_lmass, d_log_a, d_log_b};
+    return skb_run(w, f1, f2, B, N, M, d, neg_alpha, n_iter, topk, pi_val, pi_idx, rn_hist, cn_hist, g_val, d_f1, d_f2, variant == 0 && d == D,
+                   &ub, (hipStream_t)stream);
 }

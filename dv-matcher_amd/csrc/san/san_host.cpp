@@ -91,6 +91,56 @@ int main() {
     EXPECT(dvm_sinkhorn_bwd_f32(dummy, dummy, 1, 8, 8, 128, -1.f, 5, 10, dummy, idummy, dummy, dummy, dummy, dummy, dummy, 0, sbws.data(), dvm_sinkhorn_bwd_workspace_bytes(1, 8, 8, 128, 0), nullptr) == DVM_ENOSPACE);
     EXPECT(strstr(dvm_last_error(), "workspace") != nullptr);
     EXPECT(dvm_sinkhorn_bwd_f32(dummy, dummy, 1, 8, 8, 128, -1.f, 5, 10, dummy, idummy, dummy, dummy, dummy, dummy, dummy, 0, nullptr, 0, nullptr) == DVM_ENOSPACE);
+    // the unbalanced entries (dvm_sinkhorn_ub_*): the workspace queries, then the same rejection paths plus tau outside (0, 1]
+    {
+        const size_t ufb = dvm_sinkhorn_ub_workspace_bytes(1, 8, 8, 128), uhb = dvm_sinkhorn_ub_hist_workspace_bytes(1, 8, 8, 128),
+                     ubb = dvm_sinkhorn_ub_bwd_workspace_bytes(1, 8, 8, 128, 5);
+        std::vector<char> ufws(ufb), uhws(uhb), ubws(ubb);
+        float *const F = dummy;
+        int32_t *const I = idummy;
+        EXPECT(ufb >= (size_t)8 * (8 + 8) && uhb >= (size_t)8 * (8 + 8) && ubb > sbb);   // bwd: a third group of planes and the re-made potentials
+        EXPECT(dvm_sinkhorn_ub_workspace_bytes(0, 8, 8, 128) == 0 && dvm_sinkhorn_ub_hist_workspace_bytes(0, 8, 8, 128) == 0);
+        EXPECT(dvm_sinkhorn_ub_bwd_workspace_bytes(0, 8, 8, 128, 5) == 0 && dvm_sinkhorn_ub_bwd_workspace_bytes(1, 8, 8, 128, 33) == 0);
+        EXPECT(dvm_sinkhorn_ub_bwd_workspace_bytes(1, 8, 8, 128, 20) > ubb);   // grows with the history
+        for (auto &sh : shapes) EXPECT(dvm_sinkhorn_ub_bwd_workspace_bytes(sh[0], sh[1], sh[2], 128, 32) > dvm_sinkhorn_bwd_workspace_bytes(sh[0], sh[1], sh[2], 128, 32));
+#define UBF(B, d, na, T, k, tr, tc, var, ws, nb) dvm_sinkhorn_ub_fwd_f32(F, F, B, 8, 8, d, na, T, k, tr, tc, F, F, F, I, F, F, F, F, F, var, ws, nb, nullptr)
+#define UBH(B, d, na, T, k, tr, tc, var, ws, nb) dvm_sinkhorn_ub_fwd_hist_f32(F, F, B, 8, 8, d, na, T, k, tr, tc, F, F, F, I, F, F, F, F, F, var, ws, nb, nullptr)
+#define UBB(B, d, na, T, k, tr, tc, var, ws, nb) \
+    dvm_sinkhorn_ub_bwd_f32(F, F, B, 8, 8, d, na, T, k, tr, tc, F, F, F, I, F, F, F, F, F, F, F, F, F, var, ws, nb, nullptr)
+        EXPECT(dvm_sinkhorn_ub_fwd_f32(nullptr, nullptr, 1, 8, 8, 128, -1.f, 5, 10, .9f, .9f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                       nullptr, nullptr, 0, nullptr, 0, nullptr) == DVM_EINVAL);
+        EXPECT(strstr(dvm_last_error(), "null pointer") != nullptr);
+        EXPECT(dvm_sinkhorn_ub_fwd_hist_f32(F, F, 1, 8, 8, 128, -1.f, 5, 10, .9f, .9f, F, F, F, I, F, F, F, nullptr, F, 0, uhws.data(), uhb, nullptr) == DVM_EINVAL);
+        EXPECT(strstr(dvm_last_error(), "null pointer") != nullptr);
+        EXPECT(dvm_sinkhorn_ub_bwd_f32(F, F, 1, 8, 8, 128, -1.f, 5, 10, .9f, .9f, F, F, F, I, nullptr, F, F, F, F, F, F, F, F, 0, ubws.data(), ubb, nullptr) == DVM_EINVAL);
+        EXPECT(strstr(dvm_last_error(), "null pointer") != nullptr);
+        EXPECT(UBF(0, 128, -1.f, 5, 10, .9f, .9f, 0, ufws.data(), ufb) == DVM_EINVAL && UBH(0, 128, -1.f, 5, 10, .9f, .9f, 0, uhws.data(), uhb) == DVM_EINVAL &&
+               UBB(0, 128, -1.f, 5, 10, .9f, .9f, 0, ubws.data(), ubb) == DVM_EINVAL);   // empty
+        EXPECT(UBF(1, 130, -1.f, 5, 10, .9f, .9f, 0, ufws.data(), ufb) == DVM_EINVAL && UBH(1, 516, -1.f, 5, 10, .9f, .9f, 0, uhws.data(), uhb) == DVM_EINVAL &&
+               UBB(1, 130, -1.f, 5, 10, .9f, .9f, 0, ubws.data(), ubb) == DVM_EINVAL);   // d
+        EXPECT(UBF(1, 128, -1.f, 5, 17, .9f, .9f, 0, ufws.data(), ufb) == DVM_EINVAL && UBH(1, 128, -1.f, 5, 0, .9f, .9f, 0, uhws.data(), uhb) == DVM_EINVAL &&
+               UBB(1, 128, -1.f, 5, 17, .9f, .9f, 0, ubws.data(), ubb) == DVM_EINVAL);   // topk
+        EXPECT(UBF(1, 128, -1.f, -1, 10, .9f, .9f, 0, ufws.data(), ufb) == DVM_EINVAL && UBH(1, 128, -1.f, -1, 10, .9f, .9f, 0, uhws.data(), uhb) == DVM_EINVAL &&
+               UBB(1, 128, -1.f, 33, 10, .9f, .9f, 0, ubws.data(), ubb) == DVM_EINVAL);   // n_iter (the backward's limit is 32)
+        EXPECT(strstr(dvm_last_error(), "n_iter") != nullptr);
+        EXPECT(UBF(1, 128, 0.f, 5, 10, .9f, .9f, 0, ufws.data(), ufb) == DVM_EINVAL && UBH(1, 128, 1.f, 5, 10, .9f, .9f, 0, uhws.data(), uhb) == DVM_EINVAL &&
+               UBB(1, 128, 0.f, 5, 10, .9f, .9f, 0, ubws.data(), ubb) == DVM_EINVAL);   // alpha sign
+        EXPECT(UBF(1, 128, -1.f, 5, 10, 0.f, .9f, 0, ufws.data(), ufb) == DVM_EINVAL && UBF(1, 128, -1.f, 5, 10, .9f, 1.5f, 0, ufws.data(), ufb) == DVM_EINVAL);
+        EXPECT(strstr(dvm_last_error(), "tau") != nullptr);
+        EXPECT(UBH(1, 128, -1.f, 5, 10, -.5f, .9f, 0, uhws.data(), uhb) == DVM_EINVAL && UBB(1, 128, -1.f, 5, 10, .9f, 0.f, 0, ubws.data(), ubb) == DVM_EINVAL);
+        EXPECT(strstr(dvm_last_error(), "tau") != nullptr);
+        EXPECT(UBF(1, 128, -1.f, 5, 10, .9f, .9f, 7, ufws.data(), ufb) == DVM_EINVAL && UBH(1, 128, -1.f, 5, 10, .9f, .9f, 2, uhws.data(), uhb) == DVM_EINVAL &&
+               UBB(1, 128, -1.f, 5, 10, .9f, .9f, 2, ubws.data(), ubb) == DVM_EINVAL);   // variant
+        EXPECT(UBF(1, 128, -1.f, 5, 10, 1.f, 1.f, 0, ufws.data(), ufb - 1) == DVM_ENOSPACE && strstr(dvm_last_error(), "workspace") != nullptr);
+        EXPECT(UBH(1, 128, -1.f, 5, 10, 1.f, 1.f, 0, uhws.data(), uhb - 1) == DVM_ENOSPACE && strstr(dvm_last_error(), "workspace") != nullptr);
+        EXPECT(UBB(1, 128, -1.f, 5, 10, 1.f, 1.f, 0, ubws.data(), dvm_sinkhorn_ub_bwd_workspace_bytes(1, 8, 8, 128, 0)) == DVM_ENOSPACE);
+        EXPECT(strstr(dvm_last_error(), "workspace") != nullptr);
+        EXPECT(UBF(1, 128, -1.f, 5, 10, .9f, .9f, 0, nullptr, 0) == DVM_ENOSPACE && UBH(1, 128, -1.f, 5, 10, .9f, .9f, 0, nullptr, 0) == DVM_ENOSPACE &&
+               UBB(1, 128, -1.f, 5, 10, .9f, .9f, 0, nullptr, 0) == DVM_ENOSPACE);
+#undef UBF
+#undef UBH
+#undef UBB
+    }
     EXPECT(dvm_linear_f32(nullptr, dummy, 1, 4, 4, 4, 0, nullptr, nullptr, nullptr, nullptr, 1.f, dummy, nullptr) == DVM_EINVAL);
     EXPECT(dvm_linear_f32(dummy, dummy, 1, 4, 4, 4, 0, nullptr, nullptr, dummy, nullptr, 1.f, dummy, nullptr) == DVM_EINVAL);               // alpha without beta
     EXPECT(dvm_linear_f32(dummy, dummy, 1, 4, 100000, 4, 0, nullptr, nullptr, nullptr, nullptr, 1.f, dummy, nullptr) == DVM_EINVAL);        // K too large

@@ -9,7 +9,7 @@ Default: the fused C-ABI path (dvm_pair_direction_fwd_f32, nothing N x M in HBM)
 same steps one by one through the reference-named module API (models.loss / models.model / lib.*), dense Pi
 included; both must give the same points (tests/test_gpu_backbone.py::test_deform_driver).
 --sinkhorn T replaces Pi_12 by the Sinkhorn-normalised correspondence (models.loss.sinkhorn_pi, T iterations; not in the
-reference) and runs the same steps through the per-op calls.
+reference) and runs the same steps through the per-op calls; --sinkhorn-tau R[,C] makes it the unbalanced operator.
 Features come from --pairs (.npz with verts1, verts2, feat1, feat2, name1, name2) or are synthetic.
 """
 import argparse
@@ -50,10 +50,13 @@ def deform_reference_sequence(deformer, feat1, feat2, verts1, verts2, alpha, sta
     return torch.cat(pts, dim=0)
 
 
-def deform_sinkhorn(deformer, feat1, feat2, verts1, verts2, alpha, start, n_iter, k_deform=10):
+def deform_sinkhorn(deformer, feat1, feat2, verts1, verts2, alpha, start, n_iter, k_deform=10, tau=None):
     """The same deformation with Pi_12 = sinkhorn_pi(feat1, feat2): the per-op chain of GraphDeformLoss_Neural._direction."""
     g1 = ops.dg_build(verts1, start)
-    pi = ml.sinkhorn_pi(feat1, feat2, alpha=alpha, n_iter=n_iter, topk=10)
+    if tau is None:
+        pi = ml.sinkhorn_pi(feat1, feat2, alpha=alpha, n_iter=n_iter, topk=10)
+    else:
+        pi = ml.sinkhorn_pi_unbalanced(feat1, feat2, alpha=alpha, n_iter=n_iter, topk=10, tau=tau)
     idx11, idx22 = ops.knn_cdist(verts1, verts1, k_deform), ops.knn_cdist(verts2, verts2, k_deform)
     verts12 = ops.apply(pi.val, pi.idx, verts2)
     def9 = ops.deformer(deformer.weight_list(feat1.device), feat1, feat2, verts1, verts12, idx11, idx22, pi.val, pi.idx, g1["nodes_idx"])
@@ -75,8 +78,13 @@ def main(argv=None):
     ap.add_argument("--reference-sequence", action="store_true")
     ap.add_argument("--sinkhorn", type=int, default=None, metavar="T",
                     help="Pi_12 from T Sinkhorn iterations (models.loss.sinkhorn_pi) through the per-op calls; default: the row softmax")
+    ap.add_argument("--sinkhorn-tau", type=ops.tau_pair, default=None, metavar="R[,C]",
+                    help="with --sinkhorn: the unbalanced operator's damping factors (tau_row, tau_col) in (0, 1] — source points "
+                         "without a partner keep little mass; default: the balanced operator")
     ap.add_argument("--out", default="result/deform_amd")
     args = ap.parse_args(argv)
+    if args.sinkhorn_tau is not None and args.sinkhorn is None:
+        ap.error("--sinkhorn-tau needs --sinkhorn")
     assert torch.cuda.is_available(), "the deformation path needs a HIP device"
     dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
     torch.cuda.set_device(dev)
@@ -104,7 +112,7 @@ def main(argv=None):
             v1, v2, f1, f2 = (t.to(dev)[None] for t in (v1, v2, f1, f2))
             start = torch.randint(0, v1.shape[1], (1,), generator=g)   # deform.py draws it inside FPS
             if args.sinkhorn is not None:
-                warped = deform_sinkhorn(deformer, f1, f2, v1, v2, args.alpha, start.to(dev), args.sinkhorn)
+                warped = deform_sinkhorn(deformer, f1, f2, v1, v2, args.alpha, start.to(dev), args.sinkhorn, tau=args.sinkhorn_tau)
             else:
                 fn = deform_reference_sequence if args.reference_sequence else deform_fused
                 warped = fn(deformer, f1, f2, v1, v2, args.alpha, start.to(dev))

@@ -47,6 +47,15 @@ SIGNATURES = {
     "dvm_sinkhorn_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "dvm_sinkhorn_bwd_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_float, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, c_int,
                                      _P, c_size_t, _P]),
+    "dvm_sinkhorn_ub_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "dvm_sinkhorn_ub_fwd_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_float, c_float, _P, _P, _P, _P, _P, _P, _P,
+                                        _P, _P, c_int, _P, c_size_t, _P]),
+    "dvm_sinkhorn_ub_hist_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "dvm_sinkhorn_ub_fwd_hist_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_float, c_float, _P, _P, _P, _P, _P, _P,
+                                             _P, _P, _P, c_int, _P, c_size_t, _P]),
+    "dvm_sinkhorn_ub_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "dvm_sinkhorn_ub_bwd_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_float, c_float, _P, _P, _P, _P, _P, _P, _P,
+                                        _P, _P, _P, _P, _P, _P, c_int, _P, c_size_t, _P]),
     "dvm_softcorr_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "dvm_softcorr_bwd_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_float, c_int, _P, _P, _P, _P, _P, _P, _P, c_int,
                                      _P, c_size_t, _P]),

@@ -523,6 +523,45 @@ def sinkhorn_topk(f1, f2, alpha, n_iter, topk=10):
     return _SinkhornTopK.apply(f1, f2, alpha, int(n_iter), topk)
 
 
+class _SinkhornUnbalancedTopK(torch.autograd.Function):
+    """Top-k unbalanced Sinkhorn correspondence and the log mass of its rows with their HIP backward: the forward keeps the
+    normalisers of every iterate (dvm_sinkhorn_ub_fwd_hist_f32), the backward is the reverse sweep over them
+    (dvm_sinkhorn_ub_bwd_f32), differentiable in f1, f2, log_a and log_b through val and lmass."""
+
+    @staticmethod
+    def forward(ctx, f1, f2, log_a, log_b, alpha, n_iter, tau, topk):
+        val, idx, _, _, lmass, rn_hist, cn_hist = ops.sinkhorn_unbalanced_hist(f1, f2, alpha, n_iter, tau, log_a, log_b, topk=topk)
+        keep = [f1.detach(), f2.detach(), val, idx, lmass, rn_hist, cn_hist]
+        ctx.has_a, ctx.has_b = log_a is not None, log_b is not None
+        keep += [t.detach() for t in (log_a, log_b) if t is not None]
+        ctx.save_for_backward(*keep)
+        ctx.alpha, ctx.n_iter, ctx.tau = alpha, n_iter, tau
+        ctx.mark_non_differentiable(idx)
+        return val, idx, lmass
+
+    @staticmethod
+    def backward(ctx, gval, _gidx, glmass):
+        f1, f2, val, idx, lmass, rn_hist, cn_hist = ctx.saved_tensors[:7]
+        rest = list(ctx.saved_tensors[7:])
+        log_a = rest.pop(0) if ctx.has_a else None
+        log_b = rest.pop(0) if ctx.has_b else None
+        df1, df2, dla, dlb = ops.sinkhorn_unbalanced_bwd(f1, f2, ctx.alpha, ctx.n_iter, ctx.tau, log_a, log_b, val, idx, lmass, rn_hist, cn_hist,
+                                                         gval.contiguous(), None if glmass is None else glmass.contiguous())
+        return df1, df2, (dla if ctx.has_a else None), (dlb if ctx.has_b else None), None, None, None, None
+
+
+def sinkhorn_unbalanced_topk(f1, f2, alpha, n_iter, tau=(1.0, 1.0), log_a=None, log_b=None, topk=10):
+    """Differentiable (w.r.t. f1, f2, log_a, log_b, through val and lmass) top-k unbalanced Sinkhorn correspondence:
+    (val (B,N,k), idx (B,N,k) int32, lmass (B,N) = the log of every row's mass).  Without grad it is ops.sinkhorn_unbalanced (no
+    history is kept); under grad it is one autograd node, at n_iter = 0 too (the row softmax scaled by a mass is not
+    softcorr_topk)."""
+    tau = ops.tau_pair(tau)
+    if not (torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (f1, f2, log_a, log_b))):
+        val, idx, _, _, lmass, _, _ = ops.sinkhorn_unbalanced(f1, f2, alpha, n_iter, tau, log_a, log_b, topk=topk)
+        return val, idx, lmass
+    return _SinkhornUnbalancedTopK.apply(f1, f2, log_a, log_b, alpha, int(n_iter), tau, topk)
+
+
 class _SparseApply(torch.autograd.Function):
     """out[i] = sum_t val[i,t] V[idx[i,t]] on the HIP kernels, both ways (no (B,N,k,C) gather in HBM)."""
 

@@ -332,6 +332,121 @@ def sinkhorn_bwd(f1, f2, alpha, n_iter, val, idx, u_hist, v_hist, gval, variant=
     return df1, df2
 
 
+def unbalanced_tau(alpha, rho):
+    """The damping factor of unbalanced Sinkhorn with marginal penalty rho * KL at regularisation 1 / alpha:
+    rho / (rho + 1 / alpha), in (0, 1); rho = inf gives 1, the balanced operator."""
+    alpha, rho = float(alpha), float(rho)
+    if not (alpha > 0 and rho > 0):
+        raise ValueError("unbalanced_tau: alpha and rho must be positive (got %g, %g)" % (alpha, rho))
+    return 1.0 if rho == float("inf") else rho / (rho + 1.0 / alpha)
+
+
+def tau_pair(tau):
+    """(tau_row, tau_col) from a pair, one number for both, or the drivers' text form "R[,C]"; each must lie in (0, 1]."""
+    if isinstance(tau, str):
+        tau = [float(x) for x in tau.split(",")]
+        tau = tau[0] if len(tau) == 1 else tau
+    tr, tc = (tau, tau) if isinstance(tau, (int, float)) else tau
+    tr, tc = float(tr), float(tc)
+    if not (0.0 < tr <= 1.0 and 0.0 < tc <= 1.0):
+        raise ValueError("tau = (%g, %g): each factor must lie in (0, 1]" % (tr, tc))
+    return tr, tc
+
+
+def _log_weight(t, B, n, name):
+    if t is None:
+        return None
+    t = _f(t)
+    if tuple(t.shape) != (B, n):
+        raise ValueError("%s must be (B, %d) = (%d, %d), got %s" % (name, n, B, n, tuple(t.shape)))
+    return t
+
+
+def sinkhorn_unbalanced(f1, f2, alpha, n_iter, tau=(1.0, 1.0), log_a=None, log_b=None, topk=10, variant=0):
+    """Unbalanced (KL-relaxed) Sinkhorn correspondence (dvm_sinkhorn_ub_fwd_f32; the definition is in include/dvm.h): every
+    potential update is damped by tau = (tau_row, tau_col) in (0, 1], log_a (B,N) / log_b (B,M) are the log weights of the two
+    sides (None = 0 / log(N/M)), and a row whose matches are all expensive ends with a small mass.
+    -> pi_val (B,N,topk), pi_idx int32, row_lmax, row_sum, row_lmass (B,N) = log sum_j P_ij, u (B,N), v (B,M).
+    tau = (1, 1) without weights is ops.sinkhorn, bit for bit (row_lmass = 0).  Forward only, like ops.sinkhorn: the
+    differentiable entry is nn_ops.sinkhorn_unbalanced_topk."""
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (f1, f2, log_a, log_b)):
+        raise DvmError("sinkhorn_unbalanced is forward only (it keeps no history for a backward): use "
+                       "nn_ops.sinkhorn_unbalanced_topk to differentiate, or detach the inputs / call it under torch.no_grad()")
+    _need_gpu(f1, f2, log_a, log_b)
+    f1, f2 = _f(f1), _f(f2)
+    B, N, d = f1.shape
+    M = f2.shape[1]
+    tr, tc = tau_pair(tau)
+    log_a, log_b = _log_weight(log_a, B, N, "log_a"), _log_weight(log_b, B, M, "log_b")
+    lib = _lib.load()
+    dev = f1.device
+    val = torch.empty(B, N, topk, dtype=torch.float32, device=dev)
+    idx = torch.empty(B, N, topk, dtype=torch.int32, device=dev)
+    lmax, lsum, lmass, u = (torch.empty(B, N, dtype=torch.float32, device=dev) for _ in range(4))
+    v = torch.empty(B, M, dtype=torch.float32, device=dev)
+    nb = lib.dvm_sinkhorn_ub_workspace_bytes(B, N, M, d)
+    ws = workspace(nb, dev, "sinkhorn_ub")
+    check(lib.dvm_sinkhorn_ub_fwd_f32(_p(f1), _p(f2), B, N, M, d, neg_alpha_f32(alpha), int(n_iter), topk, tr, tc, _p(log_a), _p(log_b),
+                                      _p(val), _p(idx), _p(lmax), _p(lsum), _p(lmass), _p(u), _p(v), variant, _p(ws), nb, _stream()),
+          "dvm_sinkhorn_ub_fwd_f32")
+    return val, idx, lmax, lsum, lmass, u, v
+
+
+def sinkhorn_unbalanced_hist(f1, f2, alpha, n_iter, tau=(1.0, 1.0), log_a=None, log_b=None, topk=10, variant=0):
+    """ops.sinkhorn_unbalanced with the normalisers of every iterate kept for sinkhorn_unbalanced_bwd
+    (dvm_sinkhorn_ub_fwd_hist_f32): the same sweeps on the same operands, so the same bits.
+    -> pi_val, pi_idx, row_lmax, row_sum, row_lmass, rn_hist (B,n_iter+1,N) = m^1..m^T, m^final, cn_hist (B,n_iter+1,M) = 0, n^1..n^T.
+    Takes no part in autograd itself (nn_ops.sinkhorn_unbalanced_topk is the node)."""
+    _need_gpu(f1, f2, log_a, log_b)
+    f1, f2 = _f(f1), _f(f2)
+    B, N, d = f1.shape
+    M = f2.shape[1]
+    n_iter = int(n_iter)
+    tr, tc = tau_pair(tau)
+    log_a, log_b = _log_weight(log_a, B, N, "log_a"), _log_weight(log_b, B, M, "log_b")
+    lib = _lib.load()
+    dev = f1.device
+    val = torch.empty(B, N, topk, dtype=torch.float32, device=dev)
+    idx = torch.empty(B, N, topk, dtype=torch.int32, device=dev)
+    lmax, lsum, lmass = (torch.empty(B, N, dtype=torch.float32, device=dev) for _ in range(3))
+    rn_hist = torch.empty(B, max(n_iter, 0) + 1, N, dtype=torch.float32, device=dev)
+    cn_hist = torch.empty(B, max(n_iter, 0) + 1, M, dtype=torch.float32, device=dev)
+    nb = lib.dvm_sinkhorn_ub_hist_workspace_bytes(B, N, M, d)
+    ws = workspace(nb, dev, "sinkhorn_ub_hist")
+    check(lib.dvm_sinkhorn_ub_fwd_hist_f32(_p(f1), _p(f2), B, N, M, d, neg_alpha_f32(alpha), n_iter, topk, tr, tc, _p(log_a), _p(log_b),
+                                           _p(val), _p(idx), _p(lmax), _p(lsum), _p(lmass), _p(rn_hist), _p(cn_hist), variant, _p(ws), nb,
+                                           _stream()), "dvm_sinkhorn_ub_fwd_hist_f32")
+    return val, idx, lmax, lsum, lmass, rn_hist, cn_hist
+
+
+def sinkhorn_unbalanced_bwd(f1, f2, alpha, n_iter, tau, log_a, log_b, val, idx, lmass, rn_hist, cn_hist, gval, glmass=None, variant=0):
+    """Backward of the unrolled unbalanced operator (dvm_sinkhorn_ub_bwd_f32): gval (B,N,topk) = dL/d pi_val and glmass (B,N) =
+    dL/d row_lmass (None = 0) -> (d_f1 (B,N,d), d_f2 (B,M,d), d_log_a (B,N), d_log_b (B,M)).  val / idx / lmass / rn_hist /
+    cn_hist are sinkhorn_unbalanced_hist's outputs for the same inputs.  No float atomics: two calls give the same bits."""
+    _need_gpu(f1, f2, gval, glmass, log_a, log_b)
+    f1, f2, gval, val, lmass, rn_hist, cn_hist = _f(f1), _f(f2), _f(gval), _f(val), _f(lmass), _f(rn_hist), _f(cn_hist)
+    B, N, d = f1.shape
+    M = f2.shape[1]
+    n_iter = int(n_iter)
+    topk = val.shape[-1]
+    tr, tc = tau_pair(tau)
+    log_a, log_b = _log_weight(log_a, B, N, "log_a"), _log_weight(log_b, B, M, "log_b")
+    glmass = _log_weight(glmass, B, N, "glmass")
+    if n_iter >= 0 and (tuple(rn_hist.shape) != (B, n_iter + 1, N) or tuple(cn_hist.shape) != (B, n_iter + 1, M)):
+        raise ValueError("sinkhorn_unbalanced_bwd: rn_hist / cn_hist must be (B, n_iter + 1, N) / (B, n_iter + 1, M), got %s / %s"
+                         % (tuple(rn_hist.shape), tuple(cn_hist.shape)))
+    lib = _lib.load()
+    df1, df2 = torch.empty_like(f1), torch.empty_like(f2)
+    dla = torch.empty(B, N, dtype=torch.float32, device=f1.device)
+    dlb = torch.empty(B, M, dtype=torch.float32, device=f1.device)
+    nb = lib.dvm_sinkhorn_ub_bwd_workspace_bytes(B, N, M, d, n_iter)
+    ws = workspace(nb, f1.device, "sinkhorn_ub_bwd")
+    check(lib.dvm_sinkhorn_ub_bwd_f32(_p(f1), _p(f2), B, N, M, d, neg_alpha_f32(alpha), n_iter, topk, tr, tc, _p(log_a), _p(log_b), _p(val),
+                                      _p(idx.contiguous()), _p(lmass), _p(rn_hist), _p(cn_hist), _p(gval), _p(glmass), _p(df1), _p(df2),
+                                      _p(dla), _p(dlb), variant, _p(ws), nb, _stream()), "dvm_sinkhorn_ub_bwd_f32")
+    return df1, df2, dla, dlb
+
+
 def softcorr_bwd(f1, f2, alpha, val, idx, smax, ssum, gval, variant=0):
     """Backward of softcorr: gval (B,N,topk) -> (d_f1 (B,N,d), d_f2 (B,M,d)).  val / idx / smax / ssum are softcorr's outputs for
     the same f1, f2, alpha: a row's in-range columns must be distinct (repeated slots carry val 0, as softcorr writes them at

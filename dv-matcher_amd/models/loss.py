@@ -97,8 +97,9 @@ def _joint(u, v):
 class SparsePi:
     """Top-k rows of the soft correspondence: val/idx (B,N,k); stands in for the dense (B,N,M) Pi."""
 
-    def __init__(self, val, idx, M):
+    def __init__(self, val, idx, M, log_mass=None):
         self.val, self.idx, self.M = val, idx, M
+        self.log_mass = log_mass   # (B,N) log of every row's mass: the unbalanced Sinkhorn operator only (sinkhorn_pi_unbalanced)
 
     def to_dense(self):
         B, N, _ = self.val.shape
@@ -111,13 +112,27 @@ class SparsePi:
         return ops.apply(self.val, self.idx, V)
 
 
+def _relaxed(tau):
+    """Whether a sinkhorn_tau setting leaves the balanced operator: None and (1, 1) do not."""
+    return tau is not None and tuple(ops.tau_pair(tau)) != (1.0, 1.0)
+
+
 def sinkhorn_pi(x, y, alpha=100, n_iter=5, topk=10):
     """Sinkhorn-normalised counterpart of topk_pi(knnsearch_t_grad(x, y, alpha)) as a SparsePi (not in the reference): n_iter
     row / column normalisations keep many source points from sharing one target point.  When x or y requires grad the
     SparsePi's val carries the graph (nn_ops.sinkhorn_topk: the exact gradient of the unrolled iterations); otherwise it is
-    ops.sinkhorn."""
+    ops.sinkhorn.  Every row of it carries mass 1; sinkhorn_pi_unbalanced relaxes that."""
     val, idx = nn_ops.sinkhorn_topk(x, y, alpha, n_iter, topk=topk)
     return SparsePi(val, idx, y.shape[1])
+
+
+def sinkhorn_pi_unbalanced(x, y, alpha=100, n_iter=5, topk=10, tau=(1.0, 1.0), log_a=None, log_b=None):
+    """sinkhorn_pi with relaxed marginals and per-point weights (nn_ops.sinkhorn_unbalanced_topk; not in the reference):
+    tau = (tau_row, tau_col) in (0, 1] damps every potential update, log_a (B,N) / log_b (B,M) are the log weights of the two
+    sides.  The SparsePi carries .log_mass (B,N), the log of every row's mass: small where a source point has no partner.
+    Differentiable in x, y, log_a and log_b through val and log_mass; tau = (1, 1) without weights gives sinkhorn_pi's values."""
+    val, idx, lmass = nn_ops.sinkhorn_unbalanced_topk(x, y, alpha, n_iter, tau, log_a, log_b, topk=topk)
+    return SparsePi(val, idx, y.shape[1], log_mass=lmass)
 
 
 def rank_term(pval, pidx, M):
@@ -164,6 +179,9 @@ class GraphDeformLoss_Neural(nn.Module):
         # row softmax.  0 = the reference's operator, on exactly the paths above; > 0 leaves the native nodes (they have the row
         # softmax built in) for the per-op paths
         self.sinkhorn_iters = 0
+        # with sinkhorn_iters > 0: (tau_row, tau_col) of the unbalanced operator (ops.sinkhorn_unbalanced: rows without a partner
+        # keep little mass); None or (1, 1) = the balanced operator, on exactly the paths of sinkhorn_iters alone
+        self.sinkhorn_tau = None
 
     def _identity6(self, device):
         """[1,0,0,0,1,0]: the identity rotation in the 6D parametrisation (models/loss.py:1258-1262), made once per device."""
@@ -200,7 +218,9 @@ class GraphDeformLoss_Neural(nn.Module):
 
     def _direction(self, feat1, feat2, verts1, verts2, alpha, g1, deformer, idx11, idx22):
         """deform() of the reference for one direction -> (map_sum (B,), cd_warp, arap_sum, cd_self, extras)."""
-        if self.sinkhorn_iters > 0:
+        if self.sinkhorn_iters > 0 and _relaxed(self.sinkhorn_tau):
+            pval, pidx = ops.sinkhorn_unbalanced(feat1, feat2, alpha, self.sinkhorn_iters, self.sinkhorn_tau, topk=10)[:2]
+        elif self.sinkhorn_iters > 0:
             pval, pidx, _, _ = ops.sinkhorn(feat1, feat2, alpha, self.sinkhorn_iters, topk=10)
         else:
             pval, pidx, _, _ = ops.softcorr(feat1, feat2, alpha, topk=10, stats=False)
@@ -247,7 +267,9 @@ class GraphDeformLoss_Neural(nn.Module):
             else:
                 cd_warp, cd_self = tm[1] + tm[2], tm[3] + tm[4]
             return (terms[:, 0] if with_map else None), cd_warp, terms[:, 5].sum(), cd_self, None
-        if self.sinkhorn_iters > 0:
+        if self.sinkhorn_iters > 0 and _relaxed(self.sinkhorn_tau):
+            pval, pidx, _ = nn_ops.sinkhorn_unbalanced_topk(feat1, feat2, alpha, self.sinkhorn_iters, self.sinkhorn_tau, topk=10)
+        elif self.sinkhorn_iters > 0:
             pval, pidx = nn_ops.sinkhorn_topk(feat1, feat2, alpha, self.sinkhorn_iters, 10)
         else:
             pval, pidx = nn_ops.softcorr_topk(feat1, feat2, alpha, 10)

@@ -46,6 +46,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
+from dvm import ops  # noqa: E402
 from dvm.dist import FlatGradBucket, shard_range  # noqa: E402
 from models.loss import GraphDeformLoss_Neural, GraphDeformLoss_Neural_Partial  # noqa: E402
 from models.model import Deformer, Uni3FC, join_side_streams  # noqa: E402
@@ -223,6 +224,9 @@ def main(argv=None):
                     help="train under the Sinkhorn-normalised correspondence: T row / column normalisations in place of the row softmax "
                          "(criterion.sinkhorn_iters = T, nn_ops.sinkhorn_topk; not in the reference; the criterion leaves its native "
                          "nodes for the per-op path).  0: the reference's operator")
+    ap.add_argument("--sinkhorn-tau", type=ops.tau_pair, default=None, metavar="R[,C]",
+                    help="with --sinkhorn: the unbalanced operator's damping factors (criterion.sinkhorn_tau = (tau_row, tau_col), each in "
+                         "(0, 1]; nn_ops.sinkhorn_unbalanced_topk) — source points without a partner keep little mass.  Default: balanced")
     ap.add_argument("--graph", action="store_true", help="timing mode, one rank: capture the whole step (forward, criterion, backward, "
                     "Adam) into ONE HIP graph and replay it — ~2000 kernel launches per step become one graph launch")
     ap.add_argument("--sync-stats", action="store_true", help="DDP: BatchNorm statistics and the positional encoding's min/max "
@@ -242,6 +246,8 @@ def main(argv=None):
                     "configurations with with_dino = False, whose visual features are rendered and back-projected on the fly "
                     "(train_partial.py:72, 98-104); default: the seeded random initialisation (parity unpinned)")
     args = ap.parse_args(argv)
+    if args.sinkhorn_tau is not None and args.sinkhorn <= 0:
+        ap.error("--sinkhorn-tau needs --sinkhorn T with T > 0")
     cfg = copy.deepcopy(PARTIAL_CFG if args.partial else FULL_CFG)
     if args.config:
         import yaml
@@ -321,6 +327,7 @@ def main(argv=None):
     if args.sinkhorn < 0:
         ap.error("--sinkhorn must not be negative")
     crit.sinkhorn_iters = int(args.sinkhorn)
+    crit.sinkhorn_tau = args.sinkhorn_tau
     if args.graph_cache:
         import collections
         crit.graph_cache = collections.OrderedDict()   # least-recently-used shapes are dropped beyond crit.graph_cache_max
@@ -510,7 +517,7 @@ def main(argv=None):
                                            "note": "algorithmic matrix flops of the whole step per GPU over the step time; the step is "
                                                    "~900 small launches, bound by the latency of its kernel chain (network forward -> criterion -> backward), not by the matrix pipe"},
                               "points": N, "points_target": M, "criterion": type(crit).__name__, "alpha": float(alpha),
-                              "sinkhorn_iters": crit.sinkhorn_iters, "hip_graph": use_graph, "graph_cache": bool(args.graph_cache),
+                              "sinkhorn_iters": crit.sinkhorn_iters, "sinkhorn_tau": crit.sinkhorn_tau, "hip_graph": use_graph, "graph_cache": bool(args.graph_cache),
                               "sync_stats": (None if not (args.sync_stats and dist_on) else
                                              {"native_node": getattr(net, "sync_stats", None) is not None,
                                               "native_calls": net.__dict__.get("native_train_calls", 0),
@@ -567,7 +574,7 @@ def main(argv=None):
                 save_ckpt(net, dfm, args.ckpt_dir, cfg["expname"], "val_best")
     if rank == 0:
         print(json.dumps({"epochs": epochs, "history": history, "best_val": best_val, "criterion": type(crit).__name__,
-                          "sinkhorn_iters": crit.sinkhorn_iters,
+                          "sinkhorn_iters": crit.sinkhorn_iters, "sinkhorn_tau": crit.sinkhorn_tau,
                           "ckpt": list(ckpt_paths(args.ckpt_dir, cfg["expname"], "val_best"))}))
     if dist_on:
         dist.destroy_process_group()

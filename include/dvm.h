@@ -216,6 +216,56 @@ int dvm_sinkhorn_bwd_f32(const float *f1, const float *f2, int B, int N, int M, 
                          const float *g_val, float *d_f1, float *d_f2, int variant, void *ws, size_t ws_bytes,
                          void *stream);
 
+/* Unbalanced (KL-relaxed) Sinkhorn correspondence: relaxed marginals, per-point weights, the mass of every row.  NOT in the
+ * reference.  The balanced operator above gives every source row mass 1, also a row that has no partner (partial shapes);
+ * here every potential update is damped by tau = rho / (rho + 1/alpha) in (0, 1], and the final row step leaves a row whose
+ * matches are all expensive with a small mass.  S as above; tau_row, tau_col in (0, 1]; log_a [B,N] (NULL = 0) and
+ * log_b [B,M] (NULL = the constant log(N/M)) are the log weights of the two sides.  With T = n_iter, v^0 = 0, for t = 1..T:
+ *   m^t_i = -LSE_j(S_ij + v^(t-1)_j)     u^t_i = tau_row (log_a_i + m^t_i)
+ *   n^t_j = -LSE_i(S_ij + u^t_i)         v^t_j = tau_col (log_b_j + n^t_j)
+ * and the final row step
+ *   m^f_i = -LSE_j(S_ij + v^T_j)     u^f_i = tau_row (log_a_i + m^f_i)     L_ij = S_ij + v^T_j
+ *   P_ij = exp(S_ij + u^f_i + v^T_j)     row_lmass_i = u^f_i - m^f_i = log sum_j P_ij
+ * pi_val / pi_idx [B,N,topk]: the topk largest of each row of P ranked by L; ranking, tie rule and the (0, 0) slots beyond M
+ * as in dvm_sinkhorn_fwd_f32; no renormalisation.  row_lmax, row_sum (of L, as above), row_lmass [B,N], u = u^f [B,N],
+ * v = v^T [B,M] may each be NULL.  The mass is returned as a logarithm: at alpha = 100 on unnormalised features it is e^-100
+ * and smaller; pi_val may then be 0, it is never NaN or Inf.  tau_row = tau_col = 1 with both weights NULL is
+ * dvm_sinkhorn_fwd_f32, bit for bit (and row_lmass = 0).  Every potential is formed as tau * (log weight + normaliser), a sum
+ * and then a product in fp32.
+ * dvm_sinkhorn_ub_fwd_hist_f32 is the same run, keeping the normalisers:
+ *   rn_hist [B,T+1,N] = m^1 .. m^T, m^f      cn_hist [B,T+1,M] = 0, n^1 .. n^T
+ * (the potentials are re-made from them by the expression above wherever they are needed: u / tau - log_a is not the same
+ * number in fp32); its pi_val, pi_idx, row_* equal dvm_sinkhorn_ub_fwd_f32's bit for bit.
+ * dvm_sinkhorn_ub_bwd_f32: the exact gradient of the unrolled operator.  Given g_val [B,N,topk] = dL/d pi_val, g_lmass [B,N]
+ * = dL/d row_lmass (NULL = 0), the forward's pi_val, pi_idx, row_lmass and the two histories, with gp_t = g_t val_t,
+ * G_i = sum_t gp_t, R^f_ij = exp(S_ij + m^f_i + v^T_j) and H_i = tau_row G_i - (1 - tau_row) g_lmass_i:
+ *   Sbar_ij = [j = idx_t] gp_t - H_i R^f_ij - sum_t ( nbar^t_j Q^t_ij + mbar^t_i R^t_ij )
+ *   Q^t_ij = exp(S_ij + u^t_i + n^t_j)     R^t_ij = exp(S_ij + m^t_i + v^(t-1)_j)
+ *   vbar^T_j = sum_i ([j = idx_t] gp_t - H_i R^f_ij)     nbar^t = tau_col vbar^t     ubar^t_i = -sum_j nbar^t_j Q^t_ij
+ *   mbar^t = tau_row ubar^t     vbar^(t-1)_j = -sum_i mbar^t_i R^t_ij
+ *   d_log_a_i = tau_row (G_i + g_lmass_i) + sum_t mbar^t_i     d_log_b_j = sum_t nbar^t_j
+ * d_f1 [B,N,d], d_f2 [B,M,d] from W = neg_alpha Sbar / D as in dvm_sinkhorn_bwd_f32 (entries with D = 0 contribute 0);
+ * d_log_a [B,N], d_log_b [B,M] may be NULL.  All are overwritten.  Every exponent is that of a probability, built from the
+ * step's own normaliser.  Structure, limits (n_iter <= 32), variants and guarantees (no float atomics, no host
+ * synchronisation, capturable, the same bits from run to run) as dvm_sinkhorn_bwd_f32.  At tau = 1 this is the balanced
+ * gradient computed from the normalisers; it is not bit-equal to dvm_sinkhorn_bwd_f32. */
+size_t dvm_sinkhorn_ub_workspace_bytes(int B, int N, int M, int d);
+int dvm_sinkhorn_ub_fwd_f32(const float *f1, const float *f2, int B, int N, int M, int d, float neg_alpha, int n_iter, int topk,
+                            float tau_row, float tau_col, const float *log_a, const float *log_b, float *pi_val,
+                            int32_t *pi_idx, float *row_lmax, float *row_sum, float *row_lmass, float *u, float *v, int variant,
+                            void *ws, size_t ws_bytes, void *stream);
+size_t dvm_sinkhorn_ub_hist_workspace_bytes(int B, int N, int M, int d);
+int dvm_sinkhorn_ub_fwd_hist_f32(const float *f1, const float *f2, int B, int N, int M, int d, float neg_alpha, int n_iter,
+                                 int topk, float tau_row, float tau_col, const float *log_a, const float *log_b, float *pi_val,
+                                 int32_t *pi_idx, float *row_lmax, float *row_sum, float *row_lmass, float *rn_hist,
+                                 float *cn_hist, int variant, void *ws, size_t ws_bytes, void *stream);
+size_t dvm_sinkhorn_ub_bwd_workspace_bytes(int B, int N, int M, int d, int n_iter);
+int dvm_sinkhorn_ub_bwd_f32(const float *f1, const float *f2, int B, int N, int M, int d, float neg_alpha, int n_iter, int topk,
+                            float tau_row, float tau_col, const float *log_a, const float *log_b, const float *pi_val,
+                            const int32_t *pi_idx, const float *row_lmass, const float *rn_hist, const float *cn_hist,
+                            const float *g_val, const float *g_lmass, float *d_f1, float *d_f2, float *d_log_a, float *d_log_b,
+                            int variant, void *ws, size_t ws_bytes, void *stream);
+
 /* Backward of dvm_softcorr_fwd_f32 (autograd through models/loss.py:110-114 + the top-k keep of
  * 1339-1347): given g_val [B,N,topk] = dL/d pi_val and the forward's outputs (pi_val, pi_idx, row_smax,
  * row_sum), writes d_f1 [B,N,d] and d_f2 [B,M,d] (overwritten, not accumulated).  The dense N x M term is

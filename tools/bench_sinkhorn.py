@@ -7,7 +7,12 @@ from the shapes.  Prints one JSON line per alpha (and keeps it in --out).
 yardsticks that do not depend on them, from the same run: t_fwd = ops.sinkhorn(n_iter) and t_scb = ops.softcorr_bwd(variant=2).
 The expectation t_bwd <= 1.25 (t_fwd + (1 + x) t_scb) is stated with x = 0.049 * 2 n_iter (profiles/notes_sinkhorn.md 2b).
 
-    python tools/bench_sinkhorn.py [--B 64] [--N 2048] [--M 2048] [--n-iter 5] [--alphas 100,10] [--rounds 3] [--backward] [--out FILE]
+--tau R[,C] adds the unbalanced operator at those factors as one more candidate of the same run: ops.sinkhorn_unbalanced beside
+ops.sinkhorn, or with --backward ops.sinkhorn_unbalanced_bwd / _hist beside ops.sinkhorn_bwd / _hist.  It adds no sweep, so the
+expectation is a ratio of at most 1.05 (profiles/notes_sinkhorn.md 2c).
+
+    python tools/bench_sinkhorn.py [--B 64] [--N 2048] [--M 2048] [--n-iter 5] [--alphas 100,10] [--rounds 3] [--backward] [--tau R[,C]]
+                                   [--out FILE]
 """
 import argparse
 import json
@@ -45,6 +50,7 @@ def main(argv=None):
     ap.add_argument("--alphas", default="100,10")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--backward", action="store_true")
+    ap.add_argument("--tau", type=ops.tau_pair, default=None, metavar="R[,C]")
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
     assert torch.cuda.is_available(), "bench_sinkhorn needs the MI355X: there is no CPU path to time"
@@ -63,6 +69,11 @@ def main(argv=None):
                "hist": lambda: ops.sinkhorn_hist(f1, f2, alpha, args.n_iter),
                "fwd": lambda: ops.sinkhorn(f1, f2, alpha, args.n_iter),
                "scb": lambda: ops.softcorr_bwd(f1, f2, alpha, sval, sidx, smax, ssum, gv, variant=2)}
+        if args.tau:
+            uval, uidx, _, _, ulm, rn, cn = ops.sinkhorn_unbalanced_hist(f1, f2, alpha, args.n_iter, tau=args.tau)
+            glm = torch.randn(args.B, args.N, generator=g).to(dev)
+            fns["ub_bwd"] = lambda: ops.sinkhorn_unbalanced_bwd(f1, f2, alpha, args.n_iter, args.tau, None, None, uval, uidx, ulm, rn, cn, gv, glm)
+            fns["ub_hist"] = lambda: ops.sinkhorn_unbalanced_hist(f1, f2, alpha, args.n_iter, tau=args.tau)
         reps = {}
         for k, fn in fns.items():
             fn()
@@ -79,11 +90,16 @@ def main(argv=None):
                     t_fwd_ms=t["fwd"] * 1e3, t_scb_ms=t["scb"] * 1e3, x=x, expected_t_bwd_max_ms=expected * 1e3,
                     expectation_held=bool(t["bwd"] <= expected), rounds_ms={k: [round(v * 1e3, 3) for v in vs] for k, vs in best.items()},
                     reps=reps)
+        if args.tau:
+            line.update(tau=args.tau, t_ub_bwd_ms=t["ub_bwd"] * 1e3, t_ub_hist_ms=t["ub_hist"] * 1e3, ub_bwd_ratio=t["ub_bwd"] / t["bwd"],
+                        ub_hist_ratio=t["ub_hist"] / t["hist"], ub_expected_ratio_max=1.05)
         print(json.dumps(line))
         lines.append(line)
     for alpha in [float(x) for x in args.alphas.split(",")] if not args.backward else []:
         fns = {"sinkhorn": lambda: ops.sinkhorn(f1, f2, alpha, args.n_iter), "sinkhorn0": lambda: ops.sinkhorn(f1, f2, alpha, 0),
                "softcorr_v2": lambda: ops.softcorr(f1, f2, alpha, variant=2)}
+        if args.tau:
+            fns["unbalanced"] = lambda: ops.sinkhorn_unbalanced(f1, f2, alpha, args.n_iter, tau=args.tau)
         reps = {}
         for k, fn in fns.items():   # warm-up, and the repetition count that fills MIN_S
             fn()
@@ -102,6 +118,9 @@ def main(argv=None):
                     potential_sweep_ms=per_sweep * 1e3, matrix_bound_per_sweep_ms=bound * 1e3,
                     potential_sweep_share_of_fp32_matrix_bound=bound / per_sweep,
                     softcorr_v2_share_of_fp32_matrix_bound=bound / t["softcorr_v2"])
+        if args.tau:
+            line.update(tau=args.tau, t_unbalanced_ms=t["unbalanced"] * 1e3, unbalanced_ratio=t["unbalanced"] / t["sinkhorn"],
+                        ub_expected_ratio_max=1.05)
         print(json.dumps(line))
         lines.append(line)
     if args.out:
