@@ -917,8 +917,8 @@ __global__ __launch_bounds__(256) void n2p_attention_kernel(const float *__restr
 // ============================================================== K10: dist loss term
 // per (b, anchor n): x_j = |feat[idx_j] - feat[a_n]|_2, y_j = dist[b, idx_j, a_n], j < k;
 // term = 1 - |cos(x, y)|;  out[b] = sum_n term.   One wave per (b, n), k <= 512: lane l keeps x_j, y_j of j = l + 64 u, u < 8, in
-// xs[u] / ys[u] (0 past k).  Where they come from is the only difference between the forms of the forward and of the backward
-// weights; the cosine and the weight are written once, below, so that the forms agree bit for bit.
+// xs[u] / ys[u] (0 past k).  The forward works in float32; the backward weights form x_j again in float64 (see dist_x_f64_128), in
+// the same lane layout, and differ among their forms only in where y_j comes from, so that the forms agree bit for bit.
 enum DistRows { DIST_ROWS_128, DIST_ROWS_GENERIC, DIST_ROWS_SAVED };   // C == 128 half-wave form | any C % 4 == 0 | the forward's xsave
 
 // any C % 4 == 0: a lane streams its own rows, 16 bytes per instruction
@@ -1010,16 +1010,89 @@ __device__ __forceinline__ float dist_cos(const float (&xs)[8], const float (&ys
     nx = fmaxf(sqrt_rn(sxx), 1e-8f), ny = fmaxf(sqrt_rn(syy), 1e-8f);
     return sxy / (nx * ny);
 }
+// The backward weights in float64.  y_j / (|x||y|) - cos x_j / |x|^2 cancels where cos(x, y) is near 1, and the float32 rounding of x_j
+// itself is then amplified by 1 / (1 - cos) (per-row errors of 1e-5 .. 7e-4 of the feature gradient's row maximum at N = 64 .. 516,
+// profiles/notes_wgrad_elements.md).  So the backward forms x_j again from the feature rows — differences, squares, sum and root in
+// float64, exact up to the last root — and W is rounded to float32 once.  The forward's term stays on its float32 x_j, bit for bit.
+__device__ __forceinline__ double dist_sq4_f64(const f32x4 &p, const f32x4 &q, double s2) {
+    const double d0 = (double)p.x - (double)q.x, d1 = (double)p.y - (double)q.y, d2 = (double)p.z - (double)q.z, d3 = (double)p.w - (double)q.w;
+    s2 = fma(d0, d0, s2);
+    s2 = fma(d1, d1, s2);
+    s2 = fma(d2, d2, s2);
+    return fma(d3, d3, s2);
+}
+// any C % 4 == 0: dist_rows_generic's walk
+__device__ __forceinline__ void dist_x_f64_generic(const float *__restrict__ featb, int C, int a, const int32_t *__restrict__ ix, int k, int lane,
+                                                   double (&xd)[8]) {
+    const float *fa = featb + (size_t)a * C;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+        const int j = lane + 64 * u;
+        xd[u] = 0.0;
+        if (j < k) {
+            const float *fv = featb + (size_t)ix[j] * C;
+            double s2 = 0.0;
+            for (int c = 0; c < C; c += 4) s2 = dist_sq4_f64(*(const f32x4 *)(fv + c), *(const f32x4 *)(fa + c), s2);
+            xd[u] = sqrt(s2);
+        }
+    }
+}
+// C = 128: dist_rows128's walk (a 32-lane half reads one whole row, lane j % 64 keeps x_j)
+__device__ __forceinline__ void dist_x_f64_128(const float *__restrict__ featb, int a, const int32_t *__restrict__ ix, int k, int lane,
+                                               double (&xd)[8]) {
+    const int half = lane >> 5, l = lane & 31;
+    const f32x4 q = *(const f32x4 *)(featb + (size_t)a * 128 + 4 * l);
+    int ixl[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+        const int j = lane + 64 * u;
+        ixl[u] = ix[j < k ? j : k - 1];
+        xd[u] = 0.0;
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+        if (64 * u >= k) break;
+#pragma unroll 4
+        for (int jj = 0; jj < 64; jj += 2) {
+            if (64 * u + jj >= k) break;
+            const int j = 64 * u + jj + half;
+            const int v0 = __builtin_amdgcn_readlane(ixl[u], jj), v1 = __builtin_amdgcn_readlane(ixl[u], jj + 1);
+            const int v = half ? v1 : v0;
+            double s2 = dist_sq4_f64(*(const f32x4 *)(featb + (size_t)v * 128 + 4 * l), q, 0.0);
+#pragma unroll
+            for (int o = 16; o > 0; o >>= 1) s2 += __shfl_xor(s2, o, 64);   // within the 32-lane half
+            const double x = j < k ? sqrt(s2) : 0.0;
+            const double o = __shfl_xor(x, 32, 64);
+            if (lane == jj) xd[u] = half ? o : x;
+            if (lane == jj + 1) xd[u] = half ? x : o;
+        }
+    }
+}
+__device__ __forceinline__ double dist_cos(const double (&xs)[8], const float (&ys)[8], double &nx, double &ny) {
+    double sxy = 0.0, sxx = 0.0, syy = 0.0;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+        const double y = (double)ys[u];
+        sxy = fma(xs[u], y, sxy);
+        sxx = fma(xs[u], xs[u], sxx);
+        syy = fma(y, y, syy);
+    }
+    sxy = wave_sum(sxy);
+    sxx = wave_sum(sxx);
+    syy = wave_sum(syy);
+    nx = fmax(sqrt(sxx), 1e-8), ny = fmax(sqrt(syy), 1e-8);   // the same floor as the float32 cosine
+    return sxy / (nx * ny);
+}
 // W[b, n, idx_j] = g * d term / d x_j / x_j for x_j > 0, with d term / d x_j = -sgn(cos) (y_j / (|x||y|) - cos x_j / |x|^2): an anchor's
 // coefficients once, then a weight per (x_j, y_j)
-struct DistWeight {
-    float g, inv, cx;
-    __device__ __forceinline__ DistWeight(float gterm, float cosv, float nx, float ny) {
-        const float sg = cosv > 0.f ? -1.f : (cosv < 0.f ? 1.f : 0.f);  // d(1 - |cos|)/d cos
-        g = gterm * sg;
-        inv = 1.f / (nx * ny), cx = cosv / (nx * nx);
+struct DistWeightF64 {
+    double g, inv, cx;
+    __device__ __forceinline__ DistWeightF64(float gterm, double cosv, double nx, double ny) {
+        const double sg = cosv > 0.0 ? -1.0 : (cosv < 0.0 ? 1.0 : 0.0);
+        g = (double)gterm * sg;
+        inv = 1.0 / (nx * ny), cx = cosv / (nx * nx);
     }
-    __device__ __forceinline__ float operator()(float x, float y) const { return g * (y * inv - cx * x) / x; }
+    __device__ __forceinline__ float operator()(double x, double y) const { return (float)(g * (y * inv - cx * x) / x); }
 };
 
 // the forward: one partial per workgroup of 4 anchors, the four terms added pairwise (r0 + r1) + (r2 + r3) — NOT the map term's order
@@ -1057,11 +1130,12 @@ __global__ __launch_bounds__(256) void dist_loss_kernel(const float *__restrict_
 //     d feat      = diag(colsum W) feat - W^T feat[anchors]
 //     d feat[a_n] += rowsum(W)_n feat[a_n] - (W feat)_n
 // (k = 500 neighbours x 128 channels per anchor as atomics would be 0.5 G atomics per shape batch).
-// W [B][nA][N] must be zero-filled by the caller.  One wave per (b, n), k <= 512.  x_j, y_j are recomputed from the feature rows, or,
-// DIST_ROWS_SAVED, read from what the forward kept (`rows` = its xsave: no second pass over the feature rows), and then also the row
-// sums rs [B][nA] = sum_v W[b, n, v] (in lane order + a wave reduction).  gterm read at gterm[b * gstride].
+// W [B][nA][N] must be zero-filled by the caller.  One wave per (b, n), k <= 512.  x_j is formed in float64 from the feature rows
+// (dist_x_f64_*, see above); y_j is read from the distance matrix or, DIST_ROWS_SAVED, from what the forward kept (`dist` = its xsave:
+// the node's backward has no distance matrix), and then also the row sums rs [B][nA] = sum_v W[b, n, v] of the ROUNDED weights (float64,
+// lane order + a wave reduction, rounded once).  gterm read at gterm[b * gstride].
 template <DistRows ROWS>
-__global__ __launch_bounds__(256) void dist_loss_bwd_weights_kernel(const float *__restrict__ rows /* feat, or xsave */, const float *__restrict__ dist,
+__global__ __launch_bounds__(256) void dist_loss_bwd_weights_kernel(const float *__restrict__ feat, const float *__restrict__ dist /* or xsave */,
                                                                     const int32_t *__restrict__ anchors,
                                                                     const int32_t *__restrict__ idx, const float *__restrict__ gterm,
                                                                     int gstride, int N, int C, int nA, int k, float *__restrict__ W,
@@ -1071,35 +1145,34 @@ __global__ __launch_bounds__(256) void dist_loss_bwd_weights_kernel(const float 
     const int b = blockIdx.y;
     if (n >= nA) return;
     const int32_t *ix = idx + ((size_t)b * nA + n) * k;
-    float xs[8], ys[8], nx, ny;
-    if (ROWS == DIST_ROWS_128) {
-        dist_rows128(rows + (size_t)b * N * 128, dist + (size_t)b * N * N, N, anchors[n], ix, k, lane, xs, ys);
-    } else if (ROWS == DIST_ROWS_GENERIC) {
-        dist_rows_generic(rows + (size_t)b * N * C, dist + (size_t)b * N * N, N, C, anchors[n], ix, k, lane, xs, ys);
-    } else {
-        const float *xr = rows + ((size_t)b * nA + n) * k * 2;
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int j = lane + 64 * u;
-            xs[u] = j < k ? xr[j] : 0.f, ys[u] = j < k ? xr[k + j] : 0.f;
-        }
-    }
-    const float cosv = dist_cos(xs, ys, nx, ny);
-    const DistWeight weight(gterm[(size_t)b * gstride], cosv, nx, ny);
-    float *Wr = W + ((size_t)b * nA + n) * N;
-    float acc = 0.f;
+    const int a = anchors[n];
+    double xd[8], nx, ny;
+    float ys[8];
+    if (ROWS == DIST_ROWS_GENERIC) dist_x_f64_generic(feat + (size_t)b * N * C, C, a, ix, k, lane, xd);
+    else dist_x_f64_128(feat + (size_t)b * N * 128, a, ix, k, lane, xd);
+    const float *yr = ROWS == DIST_ROWS_SAVED ? dist + ((size_t)b * nA + n) * k * 2 + k : dist + (size_t)b * N * N + a;
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
         const int j = lane + 64 * u;
-        if (j < k && xs[u] > 0.f) {
-            const float wv = weight(xs[u], ys[u]);
+        ys[u] = 0.f;
+        if (j < k) ys[u] = ROWS == DIST_ROWS_SAVED ? yr[j] : yr[(size_t)ix[j] * N];
+    }
+    const double cosv = dist_cos(xd, ys, nx, ny);
+    const DistWeightF64 weight(gterm[(size_t)b * gstride], cosv, nx, ny);
+    float *Wr = W + ((size_t)b * nA + n) * N;
+    double acc = 0.0;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+        const int j = lane + 64 * u;
+        if (j < k && xd[u] > 0.0) {
+            const float wv = weight(xd[u], (double)ys[u]);
             Wr[ix[j]] = wv;
-            acc += wv;
+            acc += (double)wv;
         }
     }
     if (ROWS == DIST_ROWS_SAVED) {
         acc = wave_sum(acc);
-        if (lane == 0) rs[(size_t)b * nA + n] = acc;
+        if (lane == 0) rs[(size_t)b * nA + n] = (float)acc;
     }
 }
 
@@ -1391,12 +1464,13 @@ int launch_dist_loss_fwd(const float *feat, const float *dist, const int32_t *an
     launch_reduce_partials(partial, B, nblk, 1.f, out, out_stride, out_off, s);
     return DVM_OK;
 }
-// W [B][nA][N] (zeroed here) and its row sums from the forward's xsave; gterm read at gterm[b * gstride]
-void launch_dist_loss_bwd_weights_saved(const float *xsave, const int32_t *idx, const float *gterm, int gstride, int B, int N, int nA, int k, float *W,
-                                        float *rs, hipStream_t s) {
+// W [B][nA][N] (zeroed here) and its row sums: x_j in float64 from feat [B][N][128], y_j from the forward's xsave; gterm read at
+// gterm[b * gstride]
+void launch_dist_loss_bwd_weights_saved(const float *feat, const int32_t *anchors, const float *xsave, const int32_t *idx, const float *gterm,
+                                        int gstride, int B, int N, int nA, int k, float *W, float *rs, hipStream_t s) {
     (void)hipMemsetAsync(W, 0, (size_t)B * nA * N * sizeof(float), s);
-    hipLaunchKernelGGL(dist_loss_bwd_weights_kernel<DIST_ROWS_SAVED>, dim3((nA + 3) / 4, B), dim3(256), 0, s, xsave, (const float *)nullptr,
-                       (const int32_t *)nullptr, idx, gterm, gstride, N, 0, nA, k, W, rs);
+    hipLaunchKernelGGL(dist_loss_bwd_weights_kernel<DIST_ROWS_SAVED>, dim3((nA + 3) / 4, B), dim3(256), 0, s, feat, xsave, anchors, idx, gterm,
+                       gstride, N, 128, nA, k, W, rs);
 }
 }  // namespace dvm
 

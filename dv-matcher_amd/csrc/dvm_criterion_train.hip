@@ -529,7 +529,7 @@ int crit_bwd(const char *who, const Dims &d, Sides io, const DistIn &di, const f
             const float *fs = io.feat_s + so * N * CT_C, *fa = w.fa + so * nA * CT_C;
             const int32_t *an = side ? di.anchors2 : di.anchors1;
             float *dd = w.ddist + so * N * CT_C;
-            launch_dist_loss_bwd_weights_saved(w.xsave + so * nA * d.kd * 2, w.didx + so * nA * d.kd, g_terms + so * CT_TERMS + 6, CT_TERMS, B, N, nA, d.kd,
+            launch_dist_loss_bwd_weights_saved(fs, an, w.xsave + so * nA * d.kd * 2, w.didx + so * nA * d.kd, g_terms + so * CT_TERMS + 6, CT_TERMS, B, N, nA, d.kd,
                                                w.W, w.rs, ds);
             (void)hipMemsetAsync(w.c1, 0, (size_t)B * N * CT_C * sizeof(float), ds);
             launch_wgrad_batched(w.W, fa, B, nA, N, CT_C, w.c1, ds);                 // C1[b] = W[b]^T fa[b]      [N][C]

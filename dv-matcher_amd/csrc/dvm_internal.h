@@ -10,9 +10,9 @@ namespace dvm {
 // dvm_dist_loss_fwd_f32 with the sum at out[b * out_stride + out_off]; idx_out, xsave ([B][nA][k] x 2: x_j, y_j), fa_out: NULL or kept for the backward
 int launch_dist_loss_fwd(const float *feat, const float *dist, const int32_t *anchors, int B, int N, int C, int nA, int k, float *out, int out_stride,
                          int out_off, int32_t *idx_out, float *xsave, float *fa_out, void *ws, size_t ws_bytes, hipStream_t s);
-// W [B][nA][N] (zeroed here) and its row sums from the forward's xsave; gterm read at gterm[b * gstride]
-void launch_dist_loss_bwd_weights_saved(const float *xsave, const int32_t *idx, const float *gterm, int gstride, int B, int N, int nA, int k, float
-                                        *W, float *rs, hipStream_t s);
+// W [B][nA][N] (zeroed here) and its row sums: x_j in float64 from feat [B][N][128], y_j from the forward's xsave; gterm read at gterm[b * gstride]
+void launch_dist_loss_bwd_weights_saved(const float *feat, const int32_t *anchors, const float *xsave, const int32_t *idx, const float *gterm,
+                                        int gstride, int B, int N, int nA, int k, float *W, float *rs, hipStream_t s);
 
 // ---- dvm_bn.hip
 int launch_bn_running_update(float *const *rm, float *const *rv, const float *const *mean, const float *const *var, const int *C, int count, float
