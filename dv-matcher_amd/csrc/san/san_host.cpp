@@ -141,6 +141,23 @@ int main() {
 #undef UBH
 #undef UBB
     }
+    // the rank term: sized without any N x N / M x M array, refused over its row limit before any launch
+    {
+        const int nmax = dvm_rank_term_max_n();
+        const size_t rb = dvm_rank_term_workspace_bytes(2, 300, 170, 10);
+        std::vector<char> rws(rb);
+        EXPECT(nmax >= 8192 && rb >= (size_t)4 * 2 * (2 * 170 + 1 + 300 * 10) + 8 * 2 * 300 && rb < (size_t)64 * 1024);
+        EXPECT(dvm_rank_term_workspace_bytes(1, nmax, 1 << 20, 16) > 0 && dvm_rank_term_workspace_bytes(1, nmax + 1, 64, 1) == 0);
+        EXPECT(dvm_rank_term_workspace_bytes(0, 8, 8, 4) == 0 && dvm_rank_term_workspace_bytes(1, 8, 8, 17) == 0);
+        EXPECT(dvm_rank_term_f32(nullptr, idummy, 2, 300, 170, 10, dummy, nullptr, rws.data(), rb, nullptr) == DVM_EINVAL);
+        EXPECT(strstr(dvm_last_error(), "null pointer") != nullptr);
+        EXPECT(dvm_rank_term_f32(dummy, idummy, 2, 300, 170, 17, dummy, dummy, rws.data(), rb, nullptr) == DVM_EINVAL);
+        EXPECT(dvm_rank_term_f32(dummy, idummy, 1, nmax + 1, 64, 1, dummy, nullptr, rws.data(), rb, nullptr) == DVM_EINVAL);
+        EXPECT(strstr(dvm_last_error(), "N=") != nullptr);
+        EXPECT(dvm_rank_term_f32(dummy, idummy, 2, 300, 170, 10, dummy, dummy, rws.data(), rb - 1, nullptr) == DVM_ENOSPACE);
+        EXPECT(strstr(dvm_last_error(), "workspace") != nullptr);
+        EXPECT(dvm_rank_term_f32(dummy, idummy, 2, 300, 170, 10, dummy, nullptr, nullptr, 0, nullptr) == DVM_ENOSPACE);
+    }
     EXPECT(dvm_linear_f32(nullptr, dummy, 1, 4, 4, 4, 0, nullptr, nullptr, nullptr, nullptr, 1.f, dummy, nullptr) == DVM_EINVAL);
     EXPECT(dvm_linear_f32(dummy, dummy, 1, 4, 4, 4, 0, nullptr, nullptr, dummy, nullptr, 1.f, dummy, nullptr) == DVM_EINVAL);               // alpha without beta
     EXPECT(dvm_linear_f32(dummy, dummy, 1, 4, 100000, 4, 0, nullptr, nullptr, nullptr, nullptr, 1.f, dummy, nullptr) == DVM_EINVAL);        // K too large
@@ -213,6 +230,7 @@ int main() {
         SHORT(dvm_n2p_core_bwd_workspace_bytes(B, N, 16), dvm_n2p_core_bwd_f32(F, I, F, F, B, N, d, 16, 4, F, ws, q - 1, nullptr));
         SHORT(dvm_dist_loss_workspace_bytes(B, N, d, 16, k), dvm_dist_loss_fwd_f32(F, F, I, B, N, d, 16, k, F, I, ws, q - 1, nullptr));
         SHORT(dvm_map_term_workspace_bytes(B, N), dvm_map_term_f32(F, F, I, I, F, I, B, N, M, 16, 10, F, ws, q - 1, nullptr));
+        SHORT(dvm_rank_term_workspace_bytes(B, N, M, 10), dvm_rank_term_f32(F, I, B, N, M, 10, F, F, ws, q - 1, nullptr));
         SHORT(dvm_pair_direction_workspace_bytes(B, N, M),
               dvm_pair_direction_fwd_f32(F, F, F, F, B, N, M, -1.f, I, F, F, F, F, F, F, F, F, F, F, 1, F, F, I, F, ws, q - 1, nullptr));
         SHORT(dvm_pair_workspace_bytes(B, N, M),

@@ -577,6 +577,30 @@ class _SparseApply(torch.autograd.Function):
         return dval, None, dV
 
 
+class _RankTerm(torch.autograd.Function):
+    """||P P^T - I||_F per batch element of the sparse top-k P on the HIP kernel (dvm_rank_term_f32): the forward call returns the
+    gradient as well (the residual row is in LDS then), and the backward only scales it."""
+
+    @staticmethod
+    def forward(ctx, val, idx, M):
+        loss, g_val = ops.rank_term(val, idx, M, grad=True)
+        ctx.save_for_backward(g_val)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        g_val, = ctx.saved_tensors
+        return g_val * gout[:, None, None], None, None
+
+
+def rank_term(val, idx, M):
+    """(B,) ||P P^T - I||_F of the sparse top-k correspondence val / idx (B,N,k) with M columns, with autograd w.r.t. val (0 where
+    the term is 0).  Without grad it is ops.rank_term: no gradient is formed."""
+    if not (torch.is_grad_enabled() and val.requires_grad):
+        return ops.rank_term(val, idx, M)
+    return _RankTerm.apply(val, idx, M)
+
+
 class _DistLoss(torch.autograd.Function):
     """dist-loss term (models/loss.py:1351-1396) per batch element: fused HIP forward; the backward builds the
     sparse (anchor, point) weights with a HIP kernel and finishes with two library GEMMs per batch."""

@@ -737,6 +737,32 @@ def map_term(verts12, verts2, idx11, idx22, pi_val, pi_idx):
     return out
 
 
+def rank_term_max_n():
+    """The largest N dvm_rank_term_f32 takes (a row of P P^T must fit LDS); models.loss.rank_term falls back to torch beyond it."""
+    return int(_lib.load().dvm_rank_term_max_n())
+
+
+def rank_term(pi_val, pi_idx, M, grad=False):
+    """||P P^T - I_N||_F per batch element for the sparse top-k P (pi_val / pi_idx (B,N,k), M columns; indices in [0, M),
+    distinct within a row) -> loss (B,), and with grad=True also g_val (B,N,k) = d loss[b] / d pi_val (0 where loss[b] == 0).
+    dvm_rank_term_f32: row by row over the reversed column lists, no dense matrix, no float atomics.  Takes no part in autograd
+    itself (nn_ops.rank_term is the node)."""
+    _need_gpu(pi_val, pi_idx)
+    pi_val, pi_idx = _f(pi_val), _i(pi_idx)
+    B, N, topk = pi_val.shape
+    if tuple(pi_idx.shape) != (B, N, topk):
+        raise ValueError("rank_term: pi_idx must have pi_val's shape %s, got %s" % ((B, N, topk), tuple(pi_idx.shape)))
+    lib = _lib.load()
+    dev = pi_val.device
+    loss = torch.empty(B, dtype=torch.float32, device=dev)
+    g_val = torch.empty_like(pi_val) if grad else None
+    nb = lib.dvm_rank_term_workspace_bytes(B, N, int(M), topk)
+    ws = workspace(nb, dev, "rank")
+    check(lib.dvm_rank_term_f32(_p(pi_val), _p(pi_idx), B, N, int(M), topk, _p(loss), _p(g_val), _p(ws), nb, _stream()),
+          "dvm_rank_term_f32")
+    return (loss, g_val) if grad else loss
+
+
 def pair_direction(wl, feat1, feat2, verts1, verts2, alpha, fps_start, with_map=True, out=None):
     """Config-2 path for B pairs, one direction. Returns dict(warped, verts12, T12, losses[B,6])."""
     _need_gpu(feat1, feat2, verts1, verts2, fps_start, *wl)

@@ -135,13 +135,26 @@ def sinkhorn_pi_unbalanced(x, y, alpha=100, n_iter=5, topk=10, tau=(1.0, 1.0), l
     return SparsePi(val, idx, y.shape[1], log_mass=lmass)
 
 
-def rank_term(pval, pidx, M):
-    """||P P^T - I||_F per batch element for the sparse top-k correspondence P (val/idx (B,N,k), M columns) —
-    models/loss.py:1427-1433 — without the dense (B,N,M) P or the (B,N,N) product:
+class _SafeSqrt(torch.autograd.Function):
+    """sqrt(x) for x >= 0 whose gradient at x == 0 is 0 (torch.norm's subgradient at zero), not inf."""
+
+    @staticmethod
+    def forward(ctx, x):
+        r = torch.sqrt(x)
+        ctx.save_for_backward(r)
+        return r
+
+    @staticmethod
+    def backward(ctx, g):
+        r, = ctx.saved_tensors
+        return torch.where(r > 0, g / (2 * r).clamp_min(torch.finfo(r.dtype).tiny), torch.zeros_like(g))
+
+
+def _rank_term_torch(pval, pidx, M):
+    """rank_term with plain torch ops, for what the kernel does not take (CPU tensors, other dtypes, N over its limit):
         ||P P^T - I||_F^2 = ||P^T P||_F^2 - sum_i d_i^2 + sum_i (d_i - 1)^2,   d_i = sum_t val[i,t]^2 = (P P^T)_ii,
     with G = P^T P (M x M) accumulated from the k x k outer product of every row.  Accumulated in float64: for a
-    near-permutation P the two large terms cancel.  Differentiable w.r.t. pval (plain torch ops; the term is off in every
-    shipped config, so it has no kernel of its own)."""
+    near-permutation P the two large terms cancel.  The gradient where the term is 0 is 0, as the kernel's."""
     B, N, k = pval.shape
     v = pval.double()
     i = pidx.long()
@@ -150,7 +163,19 @@ def rank_term(pval, pidx, M):
     G = torch.zeros(B, M * M, dtype=torch.float64, device=pval.device).scatter_add_(1, flat, outer)
     d = (v * v).sum(-1)
     frob2 = (G * G).sum(1) - (d * d).sum(1) + ((d - 1) ** 2).sum(1)
-    return torch.sqrt(frob2.clamp_min(0)).float()
+    return _SafeSqrt.apply(frob2.clamp_min(0)).float()
+
+
+def rank_term(pval, pidx, M):
+    """||P P^T - I||_F per batch element for the sparse top-k correspondence P (val/idx (B,N,k), M columns) —
+    models/loss.py:1427-1433 — without the dense (B,N,M) P or the (B,N,N) product.  Differentiable w.r.t. pval; the gradient
+    where the term is 0 (an exact permutation) is 0.  CUDA float32 input within the kernel's limits (N <= ops.rank_term_max_n(),
+    k <= 16) runs on dvm_rank_term_f32 (nn_ops.rank_term: row by row, no dense array, no float atomics); anything else on the
+    torch formula of _rank_term_torch, which forms an M x M float64 matrix."""
+    if (pval.is_cuda and pval.dtype == torch.float32 and pval.dim() == 3 and pval.shape[0] >= 1 and 1 <= pval.shape[1] <= ops.rank_term_max_n()
+            and 1 <= pval.shape[2] <= 16 and M >= 1):
+        return nn_ops.rank_term(pval, pidx, M)
+    return _rank_term_torch(pval, pidx, M)
 
 
 class GraphDeformLoss_Neural(nn.Module):

@@ -326,6 +326,31 @@ int dvm_softcorr_apply_bwd_f32(const float *pi_val, const int32_t *pi_idx, const
                                int N, int M, int topk, int C, float *d_val, float *d_V, void *ws, size_t ws_bytes,
                                void *stream);
 
+/* The rank term of the criterion — models/loss.py:1427-1433: loss[b] = ||P P^T - I_N||_F for the sparse top-k correspondence
+ * P [N,M] given as pi_val / pi_idx [B,N,topk], and (g_val != NULL) g_val [B,N,topk] = d loss[b] / d pi_val.
+ * PRECONDITION: the indices of a row lie in [0, M) and are distinct within the row — what every top-k producer of this library
+ * emits (softcorr, sinkhorn, their unbalanced forms).  Repeated slots are harmless only where their value is 0 (the (0, 0) slots
+ * of a row with M < topk); an index outside [0, M) contributes nothing.  Values need not be normalised.
+ * Neither P^T P nor P P^T is formed.  With S = P P^T,
+ *   F^2 = sum_i [ (S_ii - 1)^2 + sum_{i' != i} S_ii'^2 ]
+ * is evaluated row by row: nothing cancels.  Row i of S is non-zero only at rows that share a column with row i; the entries of
+ * every column come from the reversed lists of dvm_softcorr_apply_bwd_f32.  One workgroup per row keeps the row of S in LDS
+ * (fp32, every entry an fma chain of at most topk terms in slot order), reduces its squared residual in float64, and for the
+ * gradient sums  dF^2 / d pi_val[i,t] = 4 sum_i' (S - I)[i,i'] P[i', pi_idx[i,t]]  over the column's list in 64-bit fixed point
+ * (units of 2^-50 of the list's largest term, found by a first walk: the float64 terms added as integers, so the order of the
+ * lists, which integer atomics set, cannot reach the result; quantisation at most N 2^-50 of that term).  Row sums
+ * are reduced per batch element in float64, fixed order; loss = sqrt(F^2) and g_val = (dF^2 / d pi_val) / (2 loss).  Where
+ * loss[b] == 0 (an exact permutation) g_val[b] is 0, torch.norm's gradient at zero.
+ * Work: sum_j c_j^2 for the column counts c_j (with g_val: three walks of the lists instead of one), N LDS words per row.  Memory: the workspace only,
+ * 4 B (2 M + N topk) + 8 B N bytes — no N x N, M x M or N x M array.  No float atomics, no host synchronisation, capturable, the
+ * same bits from run to run and for a batch element alone or in a batch.
+ * Limits: N <= dvm_rank_term_max_n() (8192, the criterion's own gate: the row must fit LDS), any M, topk <= 16,
+ * B <= 65535.  Outside them dvm_rank_term_workspace_bytes returns 0 and dvm_rank_term_f32 DVM_EINVAL, before any launch. */
+int dvm_rank_term_max_n(void);
+size_t dvm_rank_term_workspace_bytes(int B, int N, int M, int topk);
+int dvm_rank_term_f32(const float *pi_val, const int32_t *pi_idx, int B, int N, int M, int topk, float *loss,
+                      float *g_val /* may be NULL */, void *ws, size_t ws_bytes, void *stream);
+
 /* farthest_point_sample — lib/deformation_graph_point.py:18-33 with the random
  * start index made an input.  xyz [B,N,3], start [B] -> out [B,npoint]. */
 int dvm_fps_f32(const float *xyz, int B, int N, int npoint, const int32_t *start, int32_t *out, void *stream);

@@ -1,0 +1,105 @@
+"""The rank term alone, forward plus backward (models.loss.rank_term(...).sum().backward()): the HIP kernel's route against the
+torch formula it replaced (models.loss._rank_term_torch: a dense B x M x M float64 Gram matrix filled by scatter_add_ atomics),
+on the pval / pidx that ops.softcorr gives on randn features.  Both are timed in one process, alternating, with warm-up and
+device events around windows of at least MIN_S seconds of work each; the peak memory of one step of each is read from torch's
+allocator.  Prints one JSON line per (shape, alpha) (and keeps them in --out; profiles/notes_rank.md).
+
+    python tools/bench_rank.py [--shapes 8x2048,2x4995] [--alphas 10,100] [--rounds 5] [--out FILE]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "dv-matcher_amd"))
+sys.path.insert(0, ROOT)
+import torch  # noqa: E402
+
+import models.loss as ml  # noqa: E402
+from dvm import ops  # noqa: E402
+
+MIN_S = 0.3
+
+
+def window(fn, reps):
+    """Seconds per call over `reps` back-to-back calls, by device events."""
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) * 1e-3 / reps
+
+
+def peak_of(fn):
+    """Bytes by which one call raises the allocator's peak."""
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    fn()
+    torch.cuda.synchronize()
+    return torch.cuda.max_memory_allocated() - base
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", default="8x2048,2x4995", help="BxN[,BxN...] (M = N)")
+    ap.add_argument("--alphas", default="10,100")
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args(argv)
+    assert torch.cuda.is_available(), "bench_rank needs the MI355X: there is no CPU path to time"
+    dev = torch.device("cuda", 0)
+    lines = []
+    for shape in args.shapes.split(","):
+        B, N = (int(x) for x in shape.split("x"))
+        g = torch.Generator().manual_seed(0)
+        f1 = torch.randn(B, N, 128, generator=g).to(dev)
+        f2 = torch.randn(B, N, 128, generator=g).to(dev)
+        for alpha in [float(x) for x in args.alphas.split(",")]:
+            val, idx, _, _ = ops.softcorr(f1, f2, alpha)
+            col_counts = torch.zeros(B, N, dtype=torch.int64, device=dev).scatter_add_(1, idx.long().flatten(1), torch.ones(B, N * 10, dtype=torch.int64, device=dev))
+            v = val.clone().requires_grad_(True)
+
+            def step(term):
+                v.grad = None
+                term(v, idx, N).sum().backward()
+
+            fns = {"kernel": lambda: step(ml.rank_term), "torch": lambda: step(ml._rank_term_torch)}
+            step(ml.rank_term)
+            gk, lk = v.grad.clone(), ml.rank_term(v.detach(), idx, N)
+            step(ml._rank_term_torch)
+            gt, lt = v.grad.clone(), ml._rank_term_torch(v.detach(), idx, N)
+            reps, peak = {}, {}
+            for k, fn in fns.items():   # warm-up, and the repetition count that fills MIN_S
+                fn()
+                torch.cuda.synchronize()
+                reps[k] = max(3, int(MIN_S / window(fn, 3)) + 1)
+                peak[k] = peak_of(fn)
+            rounds = {k: [] for k in fns}
+            for _ in range(args.rounds):   # alternate the candidates; report every round
+                for k, fn in fns.items():
+                    rounds[k].append(window(fn, reps[k]))
+            med = {k: statistics.median(x) for k, x in rounds.items()}
+            line = dict(B=B, N=N, M=N, k=10, alpha=alpha, t_kernel_ms=med["kernel"] * 1e3, t_torch_ms=med["torch"] * 1e3,
+                        speedup=med["torch"] / med["kernel"],
+                        spread_ms={k: (max(x) - min(x)) * 1e3 for k, x in rounds.items()},
+                        rounds_ms={k: [round(t * 1e3, 4) for t in x] for k, x in rounds.items()}, reps=reps,
+                        peak_bytes=peak, largest_column=int(col_counts.max()), sum_cj2=int((col_counts * col_counts).sum()),
+                        loss_kernel=lk.tolist(), loss_torch=lt.tolist(),
+                        grad_max_abs_diff=float((gk - gt).abs().max()), grad_max_abs=float(gt.abs().max()))
+            print(json.dumps(line))
+            lines.append(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            for line in lines:
+                f.write(json.dumps(line) + "\n")
+
+
+if __name__ == "__main__":
+    main()
