@@ -194,6 +194,36 @@ struct KBest {
     }
 };
 
+// The two half-lanes of a 64-lane wave that share a row (lane, lane ^ 32) fold their lists into one; both end with the row's.
+template <int K>
+__device__ __forceinline__ void merge_halves(KBest<K, float> &kb) {
+    float ok[K];
+    int oi[K];
+#pragma unroll
+    for (int t = 0; t < K; ++t) {
+        ok[t] = __shfl_xor(kb.key[t], 32, 64);
+        oi[t] = __shfl_xor(kb.idx[t], 32, 64);
+    }
+#pragma unroll
+    for (int t = 0; t < K; ++t) kb.insert_lex(ok[t], oi[t]);
+}
+
+// A lane's flagged candidates (bit r of mask: entry r of its 16, parked at stage[r * 64], the [r][lane] layout), in ascending r:
+// body(act, bpos, staged value), act false once this lane has run out (bpos 0 then: the body makes that a no-op, e.g. by
+// inserting +inf).  Counted, wave-uniform trip count: a `while (__any(mask))` loop makes the compiler copy a whole top-k list —
+// 60 v_mov — around a structurised exit on every iteration.  The body must be branch-free for the same reason: it keeps the list
+// in its registers instead of copying it around a divergent region.
+template <class Body>
+__device__ __forceinline__ void for_each_flagged(unsigned mask, const float *stage, Body body) {
+    const int iters = (int)__reduce_max_sync(~0ull, (unsigned)__popc(mask));
+    for (int it = 0; it < iters; ++it) {
+        const bool act = mask != 0;
+        const int bpos = act ? (__ffs(mask) - 1) : 0;
+        mask &= mask - 1;
+        body(act, bpos, stage[bpos * 64]);
+    }
+}
+
 // The same list for NON-NEGATIVE float keys, each (key, index) pair packed into one double — high word the key's bit pattern,
 // low word the index: such doubles order like (key, index) pairs, so a compare-swap of the insertion is v_min_f64 + v_max_f64
 // instead of two compares, their combination and four selects (the idiom of the soft-correspondence sweeps).  insert_lex below

@@ -1,12 +1,19 @@
-// dvm_dist_tile.h — the fp32 squared-distance tile of the soft-correspondence family, defined once.
+// dvm_dist_tile.h — the fp32 squared-distance tile of the soft-correspondence family and the frame around it, defined once.
 //
-// Users: softcorr_mfma_kernel (dvm_softcorr.hip), sinkhorn_mfma_kernel (dvm_sinkhorn.hip), skb_sweep_mfma_kernel and
-// skb_apply_mfma_kernel (dvm_sinkhorn_bwd.hip), softcorr_bwd_mfma_kernel (dvm_softcorr_bwd.hip) and their scalar
-// cross-check forms.  The operators are correct only if every one of them forms the same S_ij bit for bit (Sinkhorn at
+// Users:
+//   sweeps (SW_* geometry, row_frame, two_role_sweep)    softcorr_mfma_kernel (dvm_softcorr.hip), sinkhorn_mfma_kernel
+//                                                        (dvm_sinkhorn.hip), skb_sweep_mfma_kernel (dvm_sinkhorn_bwd.hip; no frame)
+//   phase B (BW_* geometry and the phase-B pieces)       softcorr_bwd_mfma_kernel (dvm_softcorr_bwd.hip), skb_apply_mfma_kernel
+//                                                        (dvm_sinkhorn_bwd.hip); each keeps its own prologue and tile loop
+//   scalar sweeps (scalar_frame, scalar_sweep)           softcorr_scalar_kernel, sinkhorn_scalar_kernel, skb_sweep_scalar_kernel;
+//                                                        softcorr_dense_kernel (the frame only)
+//   scalar phase B (wave_row_*)                          softcorr_bwd_scalar_kernel, skb_apply_scalar_kernel
+// The operators are correct only if every one of them forms the same S_ij bit for bit (Sinkhorn at
 // n_iter = 0 is pinned to dvm_softcorr_fwd_f32, phase A of the Sinkhorn backward to the forward, a row step to its
-// transpose, the two phase-B kernels to each other), so the tile lives here and nowhere else.  Everything below is a
-// stateless __device__ __forceinline__ piece; argument structs, sidecar planes, epilogues, __launch_bounds__ and
-// launchers belong to the kernels.  (The fp16 pass A, dvm_softcorr_f16.h, is a different tile.)
+// transpose, the two phase-B kernels to each other) and only if their workgroup geometries agree, so the tile, the
+// geometry, a lane's view of its row and the sweep loops live here and nowhere else.  Everything below is a constant or a
+// stateless __device__ __forceinline__ piece; argument structs, sidecar planes, epilogue arithmetic, __launch_bounds__
+// and launchers belong to the kernels.  (The fp16 pass A, dvm_softcorr_f16.h, is a different tile.)
 //
 // The distance.  Squared distances are the matmul form of torch.cdist, [-2a, |a|^2, 1] . [b, 1, |b|^2], evaluated as a
 // k-ordered fp32 fma chain; v_mfma_f32_32x32x2_f32 computes exactly that chain, so the matrix-core and the scalar forms
@@ -125,6 +132,39 @@ __device__ __forceinline__ float sqdist(float acc, float nq, float nk) {
     return d2 > 0.f ? d2 : 0.f;
 }
 
+// Geometry of the three sweeps: a workgroup owns 256 query rows.
+constexpr int SW_QW = 32;                  // queries per wave
+constexpr int SW_WAVES = 8;                // waves 0-3 and 4-7 pair up on the 4 SIMDs (two per SIMD)
+constexpr int SW_QB = SW_QW * SW_WAVES;    // 256 queries per workgroup
+constexpr int SW_THREADS = 64 * SW_WAVES;
+constexpr int SW_LD_PER_THREAD = KT * D / 4 / SW_THREADS;   // float4 loads per thread per tile = 4
+constexpr int SW_STAGE = 16 * 64;          // floats per wave of a top-k epilogue's staging block: a sub-tile's 16 values of each lane, [r][lane]
+
+// A lane's view of its query row.  lid: the logical block id within the launch's group; tiles: blocks of SW_QB rows per entry;
+// feat [B][rows][D], norms [B][rows].
+struct RowFrame {
+    int b, tile;               // entry, block of SW_QB rows of the entry
+    int tid, lane, wave, r32, h;
+    int row, rc;               // the lane's row of the entry; clamped to the entry's last row (row >= rows: nothing is stored)
+    const float *p;            // features of row rc
+    float q[D / 2];            // its B-operand fragment
+    float nrm;                 // |row|^2
+};
+__device__ __forceinline__ void row_frame(RowFrame &f, int lid, int tiles, int rows, const float *feat, const float *norms) {
+    f.b = lid / tiles, f.tile = lid % tiles;
+    f.tid = threadIdx.x, f.lane = f.tid & 63, f.wave = f.tid >> 6;
+    f.r32 = f.lane & 31, f.h = f.lane >> 5;
+    f.row = f.tile * SW_QB + f.wave * SW_QW + f.r32;
+    f.rc = f.row < rows ? f.row : rows - 1;
+    f.p = feat + ((size_t)f.b * rows + f.rc) * D;
+    load_query_frag(f.p, f.h, f.q);
+    f.nrm = norms[(size_t)f.b * rows + f.rc];
+}
+// ... of a launch with one group: the logical block id is the hardware one, remapped
+__device__ __forceinline__ void row_frame(RowFrame &f, int tiles, int rows, const float *feat, const float *norms) {
+    row_frame(f, xcd_remap(blockIdx.x, gridDim.x), tiles, rows, feat, norms);
+}
+
 // The two-role loop over the ntiles key tiles of a sweep; role = wave >> 2, wave-uniform.  The kernel supplies
 //   issue(t) / commit(buf)   tile t and its sidecar planes into registers / from them into buffer buf,
 //   chain(buf, sub)          the distance chain of a sub-tile plus everything its epilogue needs from LDS,
@@ -154,6 +194,11 @@ __device__ __forceinline__ void two_role_sweep(int ntiles, int role, Issue issue
 // ------------------------------------------------------------------------------------------------ phase B
 // Shared by softcorr_bwd_mfma_kernel and skb_apply_mfma_kernel: WAVES waves own 32 WAVES "outer" rows in registers,
 // "inner" rows stream through the tile.  Group 0 is the df1 pass (outer = f1 rows), group 1 the df2 pass.
+constexpr int BW_WAVES = 4;
+constexpr int BW_OB = 32 * BW_WAVES;       // 128 outer rows per workgroup
+constexpr int BW_THREADS = 64 * BW_WAVES;
+constexpr int BW_LD_PER_THREAD = KT * D / 4 / BW_THREADS;   // float4 loads per thread per tile = 8
+constexpr int BW_MASK = 64 * BW_WAVES;     // skip-mask words per tile (skip_mask_load)
 
 // the norm expansion's v is redone from the exact difference below this share of |f_o|^2 + |f_i|^2; both kernels (and
 // their scalar forms) must take the redo on the same entries
@@ -319,6 +364,49 @@ __device__ __forceinline__ void scalar_dist_chain(const float *q, const float *k
                 }
             }
         }
+    }
+}
+
+// A thread's query row: workgroup blockIdx.x of entry blockIdx.y owns blockDim.x consecutive rows of feat [B][N][d].
+struct ScalarFrame {
+    int b, i, ic;      // entry, row, row clamped to the entry's last (i >= N: nothing is stored)
+    const float *q;    // features of row ic
+    float na;          // |row|^2
+};
+__device__ __forceinline__ ScalarFrame scalar_frame(const float *feat, const float *norms, int N, int d) {
+    ScalarFrame f;
+    f.b = blockIdx.y;
+    f.i = blockIdx.x * blockDim.x + threadIdx.x;
+    f.ic = f.i < N ? f.i : N - 1;
+    f.q = feat + ((size_t)f.b * N + f.ic) * d;
+    f.na = norms[(size_t)f.b * N + f.ic];
+    return f;
+}
+// dynamic LDS of a scalar sweep with `planes` sidecar planes of the kernel's own next to the norms
+constexpr size_t scalar_sweep_lds_bytes(int d, int planes) { return (size_t)(SC_KT * d + (1 + planes) * SC_KT) * sizeof(float); }
+
+// The loop over the M keys of entry f.b (keys [B][M][d], knorms [B][M]) in tiles of SC_KT.  LDS: [SC_KT][d] keys, the [SC_KT]
+// plane of their norms (+inf past the end: a padding key is at distance +inf), then the kernel's planes.  The kernel supplies
+//   fill(j, in, side)           key j = j0 + threadIdx.x (in: j < M) of threads < SC_KT: its planes' values to side[p * SC_KT], p = 1 ..
+//   epilogue(j0, acc, kn)       on acc[j] = the chain of key j0 + j; kn[j] its norm, kn[p * SC_KT + j] its plane p.
+template <class Fill, class Epilogue>
+__device__ __forceinline__ void scalar_sweep(const ScalarFrame &f, const float *keys, const float *knorms, int M, int d, Fill fill, Epilogue epilogue) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float *kt = smem;
+    float *kn = smem + SC_KT * d;
+    const float *kbase = keys + (size_t)f.b * M * d;
+    for (int j0 = 0; j0 < M; j0 += SC_KT) {
+        __syncthreads();
+        scalar_stage_keys(kt, kbase, j0, M, d);
+        if (threadIdx.x < SC_KT) {
+            const int j = j0 + threadIdx.x;
+            kn[threadIdx.x] = j < M ? knorms[(size_t)f.b * M + j] : INFINITY;
+            fill(j, j < M, kn + threadIdx.x);
+        }
+        __syncthreads();
+        float acc[SC_KT];
+        scalar_dist_chain(f.q, kt, d, acc);
+        epilogue(j0, acc, kn);
     }
 }
 

@@ -145,4 +145,28 @@ int launch_softcorr_f16(const float *f1, const float *f2, const float *n1, const
                         *val12, int32_t *idx12, float *smax12, float *sum12, float *val21, int32_t *idx21, float *smax21, float *sum21, const int
                         *amax, void *ws, size_t ws_bytes, hipStream_t s, int *fuse_slots = nullptr);
 
+// ---- the fp32 soft-correspondence family's entry points (dvm_softcorr.hip, dvm_softcorr_bwd.hip, dvm_sinkhorn.hip,
+// dvm_sinkhorn_bwd.hip): the checks of the arguments they share, in the order every entry tests them; `who` names the entry.
+// ptrs: the entry's own "all required pointers given".  variant in 0..variant_max.  n_iter_max < 0: no upper limit (and the
+// defaults pass for an entry without n_iter or tau).
+static inline int softcorr_family_check(const char *who, bool ptrs, int B, int N, int M, int d, int topk, float neg_alpha, int variant,
+                                        int variant_max, int n_iter = 0, int n_iter_max = -1, float tau_row = 1.f, float tau_col = 1.f) {
+    DVM_REQUIRE(ptrs, "%s: null pointer", who);
+    DVM_REQUIRE(B >= 1 && N >= 1 && M >= 1, "%s: empty input (B=%d N=%d M=%d)", who, B, N, M);
+    DVM_REQUIRE(d >= 4 && d % 4 == 0 && d <= 512, "%s: d=%d unsupported (need d%%4==0, 4<=d<=512)", who, d);
+    DVM_REQUIRE(topk >= 1 && topk <= 16, "%s: topk=%d unsupported (1..16)", who, topk);
+    if (n_iter_max < 0)
+        DVM_REQUIRE(n_iter >= 0, "%s: n_iter=%d must not be negative", who, n_iter);
+    else
+        DVM_REQUIRE(n_iter >= 0 && n_iter <= n_iter_max, "%s: n_iter=%d unsupported (0..%d)", who, n_iter, n_iter_max);
+    DVM_REQUIRE(neg_alpha < 0.f, "%s: neg_alpha must be negative (got %g)", who, (double)neg_alpha);
+    DVM_REQUIRE(tau_row > 0.f && tau_row <= 1.f && tau_col > 0.f && tau_col <= 1.f, "%s: tau=(%g, %g) outside (0, 1]", who, (double)tau_row,
+                (double)tau_col);
+    if (variant_max == 1)
+        DVM_REQUIRE(variant == 0 || variant == 1, "%s: bad variant %d (0 = auto, 1 = scalar)", who, variant);
+    else
+        DVM_REQUIRE(variant >= 0 && variant <= variant_max, "%s: bad variant %d", who, variant);
+    return DVM_OK;
+}
+
 }  // namespace dvm

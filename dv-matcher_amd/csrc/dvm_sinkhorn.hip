@@ -8,9 +8,9 @@
 // is the reference's operator (v = 0, one row softmax): that case is pinned to dvm_softcorr_fwd_f32, which is pinned to
 // the reference.
 //
-// One kernel does every step: a workgroup owns 256 "query" rows (8 waves x 32), streams all "key" rows through a
-// double-buffered, k-deinterleaved LDS tile together with the keys' |.|^2 and potential, forms the squared-distance tile
-// on the fp32 matrix cores (the k-ordered fma chain of torch.cdist's matmul form: the tile of dvm_dist_tile.h) and keeps
+// One kernel does every step: a workgroup owns 256 "query" rows and streams all "key" rows through the distance tile of
+// dvm_dist_tile.h (layout, chain, geometry, row frame and sweep loops are defined there; the top-k list's half-lane merge
+// and flagged-candidate loop next to KBest in dvm_common.h) together with the keys' |.|^2 and potential, and keeps
 // an online (max, sum) of L per query row in registers.  The row step is (queries, keys, potential) = (f1, f2, v), the
 // column step the same kernel with (f2, f1, u): every potential is owned by one lane pair, so there are no float atomics
 // and two runs give the same bits.  The N x M matrix is never written to HBM; the potentials (4 (N + M) bytes per entry)
@@ -131,52 +131,39 @@ __device__ __forceinline__ void store_potential(const SKArgs &a, int b, int i, s
 // matrix-core kernel and the path for d != 128; not tuned.  SWAP: the queries are f2 (column step), see sqdist.
 template <bool FINAL, bool SWAP, int TOPK>
 __global__ __launch_bounds__(128) void sinkhorn_scalar_kernel(const SKArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];   // [SC_KT][d] keys + [SC_KT] norms + [SC_KT] potentials
-    const int N = a.N, M = a.M, d = a.d;
-    float *kt = smem;
-    float *kn = smem + SC_KT * d;
-    float *kp = kn + SC_KT;
-    const int b = blockIdx.y;
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const int ic = i < N ? i : N - 1;
-    const float *q = a.q + ((size_t)b * N + ic) * d;
-    const float na = a.nq[(size_t)b * N + ic];
-    const float *kbase = a.k + (size_t)b * M * d;
+    // one sidecar plane: the keys' potentials
+    const int N = a.N, M = a.M;
+    const ScalarFrame f = scalar_frame(a.q, a.nq, N, a.d);
+    const int b = f.b, i = f.i;
+    const float na = f.na;
     const bool hasv = a.pot != nullptr;
     const float neg_alpha = a.neg_alpha;
     LseState st;
     st.init();
     KBest<TOPK, float> kb;
     if (FINAL) kb.init(INFINITY);
-    for (int j0 = 0; j0 < M; j0 += SC_KT) {
-        __syncthreads();
-        scalar_stage_keys(kt, kbase, j0, M, d);
-        if (threadIdx.x < SC_KT) {
-            const int j = j0 + threadIdx.x;
-            kn[threadIdx.x] = j < M ? a.nk[(size_t)b * M + j] : INFINITY;
-            kp[threadIdx.x] = (j < M && hasv) ? a.pot[(size_t)b * a.pot_bs + j] : 0.f;
-        }
-        __syncthreads();
-        float acc[SC_KT];
-        scalar_dist_chain(q, kt, d, acc);
-        float Lv[SC_KT], dv[SC_KT];
-        float tmax = -INFINITY;
+    scalar_sweep(
+        f, a.k, a.nk, M, a.d, [&](int j, bool in, float *side) { side[SC_KT] = (in && hasv) ? a.pot[(size_t)b * a.pot_bs + j] : 0.f; },
+        [&](int j0, const float (&acc)[SC_KT], const float *kn) {
+            const float *kp = kn + SC_KT;
+            float Lv[SC_KT], dv[SC_KT];
+            float tmax = -INFINITY;
 #pragma unroll
-        for (int j = 0; j < SC_KT; ++j) {
-            dv[j] = sqrt_rn(sqdist<SWAP>(acc[j], na, kn[j]));
-            Lv[j] = dv[j] * neg_alpha + kp[j];
-            tmax = fmaxf(tmax, Lv[j]);
-        }
-        st.rescale(tmax);
-        const float sh = st.shift();
-        float ls = 0.f;
+            for (int j = 0; j < SC_KT; ++j) {
+                dv[j] = sqrt_rn(sqdist<SWAP>(acc[j], na, kn[j]));
+                Lv[j] = dv[j] * neg_alpha + kp[j];
+                tmax = fmaxf(tmax, Lv[j]);
+            }
+            st.rescale(tmax);
+            const float sh = st.shift();
+            float ls = 0.f;
 #pragma unroll
-        for (int j = 0; j < SC_KT; ++j) {
-            ls += __builtin_amdgcn_exp2f((Lv[j] - sh) * LOG2E);
-            if (FINAL) kb.insert(hasv ? -Lv[j] : dv[j], j0 + j);
-        }
-        st.l += (double)ls;
-    }
+            for (int j = 0; j < SC_KT; ++j) {
+                ls += __builtin_amdgcn_exp2f((Lv[j] - sh) * LOG2E);
+                if (FINAL) kb.insert(hasv ? -Lv[j] : dv[j], j0 + j);
+            }
+            st.l += (double)ls;
+        });
     if (i < N) {
         const size_t row = (size_t)b * N + i;
         if (FINAL)
@@ -190,43 +177,30 @@ __global__ __launch_bounds__(128) void sinkhorn_scalar_kernel(const SKArgs a) {
 }
 
 // -------------------------------------------------------------- matrix-core variant (d == 128)
-// Tile, LDS layout and the two-role phase structure: dvm_dist_tile.h.  The online (max, sum) and the top-k list need no
-// cross-lane traffic until the two half-lanes of a query merge at the end.
-constexpr int SK_QW = 32;             // queries per wave
-constexpr int SK_WAVES = 8;
-constexpr int SK_QB = SK_QW * SK_WAVES;   // 256 queries per workgroup
-constexpr int SK_THREADS = 64 * SK_WAVES;
-constexpr int SK_LD_PER_THREAD = KT * D / 4 / SK_THREADS;   // float4 loads per thread per tile = 8
+// Tile, LDS layout, geometry and the two-role phase structure: dvm_dist_tile.h.  The online (max, sum) and the top-k list
+// need no cross-lane traffic until the two half-lanes of a query merge at the end.
 constexpr int SK_TILE_FLOATS = ROWS_FLOATS + 2 * KT;        // keys + their norms + their potentials
-constexpr int SK_STAGE = 16 * 64;   // final row sweep, floats per wave: this sub-tile's 16 ranking keys of each lane, [r][lane]
 constexpr size_t SK_LDS_BYTES = (size_t)2 * SK_TILE_FLOATS * sizeof(float);
-constexpr size_t SK_LDS_BYTES_FINAL = SK_LDS_BYTES + (size_t)SK_WAVES * SK_STAGE * sizeof(float);
+// final row sweep: + per wave the staging block of this sub-tile's 16 ranking keys of each lane
+constexpr size_t SK_LDS_BYTES_FINAL = SK_LDS_BYTES + (size_t)SW_WAVES * SW_STAGE * sizeof(float);
 
 // FINAL: the last row sweep (top-k, pi_val / pi_idx / row_lmax / row_sum / u); HASV (FINAL only): rank by -L, else by d.
 template <bool FINAL, bool HASV, bool SWAP, int TOPK>
-__global__ __launch_bounds__(SK_THREADS, 2) void sinkhorn_mfma_kernel(const SKArgs a) {
-    // [2] x { [KT][LDK] keys, [KT] norms, [KT] potentials }; FINAL: + [SK_WAVES][16][64] ranking keys
+__global__ __launch_bounds__(SW_THREADS, 2) void sinkhorn_mfma_kernel(const SKArgs a) {
+    // [2] x { [KT][LDK] keys, [KT] norms, [KT] potentials }; FINAL: + [SW_WAVES][16][64] ranking keys
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float *const stage = smem + 2 * SK_TILE_FLOATS + (threadIdx.x >> 6) * SK_STAGE + (threadIdx.x & 63);   // this lane's column
+    float *const stage = smem + 2 * SK_TILE_FLOATS + (threadIdx.x >> 6) * SW_STAGE + (threadIdx.x & 63);   // this lane's column
 
-    const int lid = xcd_remap(blockIdx.x, gridDim.x);
     const int N = a.N, M = a.M;
-    const int b = lid / a.tiles;
-    const int qt = lid % a.tiles;
     const float neg_alpha = a.neg_alpha;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r32 = lane & 31, h = lane >> 5;
+    RowFrame f;   // this lane's query row
+    row_frame(f, a.tiles, N, a.q, a.nq);
+    const int b = f.b, tid = f.tid, r32 = f.r32, h = f.h, qrow = f.row;
+    const float na = f.nrm;
 
     const float *kbase = a.k + (size_t)b * M * D;
     const float *knb = a.nk + (size_t)b * M;
     const float *kpb = a.pot ? a.pot + (size_t)b * a.pot_bs : nullptr;
-
-    // this lane's query row and its B-operand fragment
-    const int qrow = qt * SK_QB + wave * SK_QW + r32;
-    const int qrc = qrow < N ? qrow : N - 1;
-    float q[D / 2];
-    load_query_frag(a.q + ((size_t)b * N + qrc) * D, h, q);
-    const float na = a.nq[(size_t)b * N + qrc];
 
     LseState st;
     st.init();
@@ -234,12 +208,12 @@ __global__ __launch_bounds__(SK_THREADS, 2) void sinkhorn_mfma_kernel(const SKAr
     if (FINAL) kb.init(INFINITY);
 
     const int ntiles = (M + KT - 1) / KT;
-    f32x4 pre[SK_LD_PER_THREAD];
+    f32x4 pre[SW_LD_PER_THREAD];
     float pren = 0.f;   // threads 0..63: a key's norm; threads 64..127: a key's potential
 
     auto issue_loads = [&](int t) {
         const int j0 = t * KT;
-        issue_tile<SK_THREADS>(kbase, j0, M, tid, pre);
+        issue_tile<SW_THREADS>(kbase, j0, M, tid, pre);
         if (tid < KT)
             pren = (j0 + tid < M) ? knb[j0 + tid] : INFINITY;
         else if (tid < 2 * KT)
@@ -247,7 +221,7 @@ __global__ __launch_bounds__(SK_THREADS, 2) void sinkhorn_mfma_kernel(const SKAr
     };
     auto commit_loads = [&](int buf) {
         float *kt = smem + buf * SK_TILE_FLOATS;
-        commit_tile<SK_THREADS>(kt, tid, pre);
+        commit_tile<SW_THREADS>(kt, tid, pre);
         if (tid < 2 * KT) kt[ROWS_FLOATS + tid] = pren;   // norms, then potentials
     };
 
@@ -256,7 +230,7 @@ __global__ __launch_bounds__(SK_THREADS, 2) void sinkhorn_mfma_kernel(const SKAr
     float nbv[16], pv[16];
     auto mfma_chain = [&](int buf, int sub) {
         const float *kt = smem + buf * SK_TILE_FLOATS;
-        dist_chain(kt, sub, r32, h, q, acc);
+        dist_chain(kt, sub, r32, h, f.q, acc);
         lane_scalars(kt + ROWS_FLOATS, sub, h, nbv);
         lane_scalars(kt + ROWS_FLOATS + KT, sub, h, pv);
     };
@@ -285,23 +259,17 @@ __global__ __launch_bounds__(SK_THREADS, 2) void sinkhorn_mfma_kernel(const SKAr
         for (int r = 0; r < 16; ++r) ls += __builtin_amdgcn_exp2f((Lv[r] - sh) * LOG2E);
         st.l += (double)ls;
         if (FINAL) {
-            // candidates that beat this lane's current worst, in ascending column order; a counted, wave-uniform loop
-            // with a branch-free body keeps the list in its registers
-            const int iters = (int)__reduce_max_sync(~0ull, (unsigned)__popc(mask));
-            for (int it = 0; it < iters; ++it) {
-                const bool act = mask != 0;
-                const int bpos = act ? (__ffs(mask) - 1) : 0;
-                mask &= mask - 1;
-                const float key = act ? stage[bpos * 64] : INFINITY;
-                kb.insert_nb(key, t * KT + sub * 32 + lane_key(bpos, h));
-            }
+            // candidates that beat this lane's current worst, in ascending column order
+            for_each_flagged(mask, stage, [&](bool act, int bpos, float key) {
+                kb.insert_nb(act ? key : INFINITY, t * KT + sub * 32 + lane_key(bpos, h));
+            });
         }
     };
 
     // the 16-entry list leaves no room for the next tile's 32 prefetch registers next to it: that variant loads the tile after
     // its epilogues (the other wave of the SIMD covers the latency) instead of spilling
     constexpr bool LATE_LOADS = FINAL && TOPK > 10;
-    const int role = __builtin_amdgcn_readfirstlane(wave >> 2);
+    const int role = __builtin_amdgcn_readfirstlane(f.wave >> 2);
     two_role_sweep<LATE_LOADS>(ntiles, role, issue_loads, commit_loads, mfma_chain, epilogue);
 
     // merge the two half-lanes that share a query (lane, lane ^ 32); the lower lane writes the row
@@ -310,17 +278,7 @@ __global__ __launch_bounds__(SK_THREADS, 2) void sinkhorn_mfma_kernel(const SKAr
         const double ol = __shfl_xor(st.l, 32, 64);
         st.merge(om, ol);
     }
-    if (FINAL) {
-        float ok[TOPK];
-        int oi[TOPK];
-#pragma unroll
-        for (int t = 0; t < TOPK; ++t) {
-            ok[t] = __shfl_xor(kb.key[t], 32, 64);
-            oi[t] = __shfl_xor(kb.idx[t], 32, 64);
-        }
-#pragma unroll
-        for (int t = 0; t < TOPK; ++t) kb.insert_lex(ok[t], oi[t]);
-    }
+    if (FINAL) merge_halves(kb);
     if (h == 0 && qrow < N) {
         const size_t row = (size_t)b * N + qrow;
         if (FINAL)
@@ -337,12 +295,12 @@ template <bool FINAL, bool HASV, bool SWAP, int TOPK>
 void launch_mfma(const SKArgs &a, int B, hipStream_t s) {
     const size_t lds = FINAL ? SK_LDS_BYTES_FINAL : SK_LDS_BYTES;
     ensure_dyn_lds((const void *)sinkhorn_mfma_kernel<FINAL, HASV, SWAP, TOPK>, (int)lds);
-    hipLaunchKernelGGL((sinkhorn_mfma_kernel<FINAL, HASV, SWAP, TOPK>), dim3((unsigned)(B * a.tiles)), dim3(SK_THREADS), lds, s, a);
+    hipLaunchKernelGGL((sinkhorn_mfma_kernel<FINAL, HASV, SWAP, TOPK>), dim3((unsigned)(B * a.tiles)), dim3(SW_THREADS), lds, s, a);
 }
 
 template <bool FINAL, bool SWAP, int TOPK>
 void launch_scalar(const SKArgs &a, int B, hipStream_t s) {
-    const size_t lds = (size_t)(SC_KT * a.d + 2 * SC_KT) * sizeof(float);
+    const size_t lds = scalar_sweep_lds_bytes(a.d, 1);
     ensure_dyn_lds((const void *)sinkhorn_scalar_kernel<FINAL, SWAP, TOPK>, 66 * 1024);
     hipLaunchKernelGGL((sinkhorn_scalar_kernel<FINAL, SWAP, TOPK>), dim3((a.N + 127) / 128, B), dim3(128), lds, s, a);
 }
@@ -350,7 +308,7 @@ void launch_scalar(const SKArgs &a, int B, hipStream_t s) {
 // one potential sweep: out [B][Nq] = add - LSE_keys(S + pot)
 void launch_sweep(bool mfma, bool swap, SKArgs a, int B, hipStream_t s) {
     if (mfma) {
-        a.tiles = (a.N + SK_QB - 1) / SK_QB;
+        a.tiles = (a.N + SW_QB - 1) / SW_QB;
         if (swap)
             launch_mfma<false, true, true, 1>(a, B, s);
         else
@@ -366,7 +324,7 @@ void launch_sweep(bool mfma, bool swap, SKArgs a, int B, hipStream_t s) {
 template <int TOPK>
 void launch_final(bool mfma, SKArgs a, int B, hipStream_t s) {
     if (mfma) {
-        a.tiles = (a.N + SK_QB - 1) / SK_QB;
+        a.tiles = (a.N + SW_QB - 1) / SW_QB;
         if (a.pot)
             launch_mfma<true, true, false, TOPK>(a, B, s);
         else
@@ -459,13 +417,8 @@ DVM_EXPORT size_t dvm_sinkhorn_workspace_bytes(int B, int N, int M, int d) {
 DVM_EXPORT int dvm_sinkhorn_fwd_f32(const float *f1, const float *f2, int B, int N, int M, int d, float neg_alpha, int n_iter,
                                     int topk, float *pi_val, int32_t *pi_idx, float *row_lmax, float *row_sum, float *u, float *v,
                                     int variant, void *ws, size_t ws_bytes, void *stream) {
-    DVM_REQUIRE(f1 && f2 && pi_val && pi_idx, "dvm_sinkhorn_fwd_f32: null pointer");
-    DVM_REQUIRE(B >= 1 && N >= 1 && M >= 1, "dvm_sinkhorn_fwd_f32: empty input (B=%d N=%d M=%d)", B, N, M);
-    DVM_REQUIRE(d >= 4 && d % 4 == 0 && d <= 512, "dvm_sinkhorn_fwd_f32: d=%d unsupported (need d%%4==0, 4<=d<=512)", d);
-    DVM_REQUIRE(topk >= 1 && topk <= 16, "dvm_sinkhorn_fwd_f32: topk=%d unsupported (1..16)", topk);
-    DVM_REQUIRE(n_iter >= 0, "dvm_sinkhorn_fwd_f32: n_iter=%d must not be negative", n_iter);
-    DVM_REQUIRE(neg_alpha < 0.f, "dvm_sinkhorn_fwd_f32: neg_alpha must be negative (got %g)", (double)neg_alpha);
-    DVM_REQUIRE(variant == 0 || variant == 1, "dvm_sinkhorn_fwd_f32: bad variant %d (0 = auto, 1 = scalar)", variant);
+    const int rc = softcorr_family_check("dvm_sinkhorn_fwd_f32", f1 && f2 && pi_val && pi_idx, B, N, M, d, topk, neg_alpha, variant, 1, n_iter);
+    if (rc != DVM_OK) return rc;
     SinkhornWs w;
     if (!carve_ws(ws, ws_bytes, "dvm_sinkhorn_fwd_f32", w, carve_sinkhorn, B, N, M, true)) return DVM_ENOSPACE;
     hipStream_t s = (hipStream_t)stream;
@@ -485,13 +438,9 @@ DVM_EXPORT size_t dvm_sinkhorn_hist_workspace_bytes(int B, int N, int M, int d) 
 DVM_EXPORT int dvm_sinkhorn_fwd_hist_f32(const float *f1, const float *f2, int B, int N, int M, int d, float neg_alpha, int n_iter,
                                          int topk, float *pi_val, int32_t *pi_idx, float *row_lmax, float *row_sum, float *u_hist,
                                          float *v_hist, int variant, void *ws, size_t ws_bytes, void *stream) {
-    DVM_REQUIRE(f1 && f2 && pi_val && pi_idx && u_hist && v_hist, "dvm_sinkhorn_fwd_hist_f32: null pointer");
-    DVM_REQUIRE(B >= 1 && N >= 1 && M >= 1, "dvm_sinkhorn_fwd_hist_f32: empty input (B=%d N=%d M=%d)", B, N, M);
-    DVM_REQUIRE(d >= 4 && d % 4 == 0 && d <= 512, "dvm_sinkhorn_fwd_hist_f32: d=%d unsupported (need d%%4==0, 4<=d<=512)", d);
-    DVM_REQUIRE(topk >= 1 && topk <= 16, "dvm_sinkhorn_fwd_hist_f32: topk=%d unsupported (1..16)", topk);
-    DVM_REQUIRE(n_iter >= 0, "dvm_sinkhorn_fwd_hist_f32: n_iter=%d must not be negative", n_iter);
-    DVM_REQUIRE(neg_alpha < 0.f, "dvm_sinkhorn_fwd_hist_f32: neg_alpha must be negative (got %g)", (double)neg_alpha);
-    DVM_REQUIRE(variant == 0 || variant == 1, "dvm_sinkhorn_fwd_hist_f32: bad variant %d (0 = auto, 1 = scalar)", variant);
+    const int rc = softcorr_family_check("dvm_sinkhorn_fwd_hist_f32", f1 && f2 && pi_val && pi_idx && u_hist && v_hist, B, N, M, d, topk,
+                                         neg_alpha, variant, 1, n_iter);
+    if (rc != DVM_OK) return rc;
     SinkhornWs w;
     if (!carve_ws(ws, ws_bytes, "dvm_sinkhorn_fwd_hist_f32", w, carve_sinkhorn, B, N, M, false)) return DVM_ENOSPACE;
     hipStream_t s = (hipStream_t)stream;
@@ -502,19 +451,10 @@ DVM_EXPORT int dvm_sinkhorn_fwd_hist_f32(const float *f1, const float *f2, int B
 }
 
 // ---------------------------------------------------------------------------------------- unbalanced (KL-relaxed) entries
-// the argument checks the two entries share; the message names the entry
+// the argument checks the two entries share: the family's, with the tau pair (tested after neg_alpha, before variant)
 static int sinkhorn_ub_check(const char *who, const void *f1, const void *f2, const void *pi_val, const void *pi_idx, int B, int N, int M, int d,
                              float neg_alpha, int n_iter, int topk, float tau_row, float tau_col, int variant) {
-    DVM_REQUIRE(f1 && f2 && pi_val && pi_idx, "%s: null pointer", who);
-    DVM_REQUIRE(B >= 1 && N >= 1 && M >= 1, "%s: empty input (B=%d N=%d M=%d)", who, B, N, M);
-    DVM_REQUIRE(d >= 4 && d % 4 == 0 && d <= 512, "%s: d=%d unsupported (need d%%4==0, 4<=d<=512)", who, d);
-    DVM_REQUIRE(topk >= 1 && topk <= 16, "%s: topk=%d unsupported (1..16)", who, topk);
-    DVM_REQUIRE(n_iter >= 0, "%s: n_iter=%d must not be negative", who, n_iter);
-    DVM_REQUIRE(neg_alpha < 0.f, "%s: neg_alpha must be negative (got %g)", who, (double)neg_alpha);
-    DVM_REQUIRE(tau_row > 0.f && tau_row <= 1.f && tau_col > 0.f && tau_col <= 1.f, "%s: tau=(%g, %g) outside (0, 1]", who, (double)tau_row,
-                (double)tau_col);
-    DVM_REQUIRE(variant == 0 || variant == 1, "%s: bad variant %d (0 = auto, 1 = scalar)", who, variant);
-    return DVM_OK;
+    return softcorr_family_check(who, f1 && f2 && pi_val && pi_idx, B, N, M, d, topk, neg_alpha, variant, 1, n_iter, -1, tau_row, tau_col);
 }
 
 // both entries: |f1|^2, |f2|^2 and the current potentials of the two sides (the caller's u / v where given)

@@ -32,7 +32,8 @@
 // No float atomics and no host synchronisation anywhere, n_iter = 0 included (it runs prep, colgather, pack and phase B
 // with one term; dvm_softcorr_bwd_f32's atomics are not used).  variant 1 runs scalar forms of phase A and B (any
 // d % 4 == 0, d <= 512; untuned): the cross-check of the matrix-core kernels and the path for d != 128.
-// Every kernel here forms its distances with dvm_dist_tile.h.
+// Every kernel here forms its distances with dvm_dist_tile.h, which also owns the workgroup geometries and the sweep loops
+// (two_role_sweep, scalar_sweep): what is here are the argument structs, the planes and the epilogues.
 //
 // dvm_sinkhorn_ub_bwd_f32 is the same structure for the unbalanced operator (the formulas are in include/dvm.h).  Its history
 // holds the normalisers m^t, n^t; skb_ub_pots_kernel re-makes the potentials u^t, v^t from them by the forward's expression.
@@ -275,65 +276,50 @@ struct SAArgs {
 // scalar form: the scalar sweep of dvm_dist_tile.h (one thread per query row, keys through LDS in tiles of 32)
 template <bool SWAP, bool MASKED>
 __global__ __launch_bounds__(128) void skb_sweep_scalar_kernel(const SAArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];   // [SC_KT][d] keys + norms + potentials + coefficients
-    const int N = a.N, M = a.M, d = a.d;
-    float *kt = smem;
-    float *kn = smem + SC_KT * d;
-    float *kp = kn + SC_KT;
-    float *kc = kp + SC_KT;
-    const int b = blockIdx.y;
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const int ic = i < N ? i : N - 1;
-    const float *q = a.q + ((size_t)b * N + ic) * d;
-    const float na = a.nq[(size_t)b * N + ic];
+    // two sidecar planes: the keys' potentials and coefficients
+    const int N = a.N, M = a.M;
+    const ScalarFrame f = scalar_frame(a.q, a.nq, N, a.d);
+    const int b = f.b, i = f.i, ic = f.ic;
+    const float na = f.na;
     const float pq = a.potq[(size_t)b * a.potq_bs + ic] + a.add;
-    const float *kbase = a.k + (size_t)b * M * d;
     const float neg_alpha = a.neg_alpha;
     double sum = 0.0;
-    for (int j0 = 0; j0 < M; j0 += SC_KT) {
-        __syncthreads();
-        scalar_stage_keys(kt, kbase, j0, M, d);
-        if (threadIdx.x < SC_KT) {
-            const int j = j0 + threadIdx.x;
-            kn[threadIdx.x] = j < M ? a.nk[(size_t)b * M + j] : INFINITY;
-            kp[threadIdx.x] = j < M ? a.potk[(size_t)b * a.potk_bs + j] : 0.f;
-            kc[threadIdx.x] = j < M ? a.coefk[(size_t)b * a.coefk_bs + j] : 0.f;
-        }
-        __syncthreads();
-        float acc[SC_KT];
-        scalar_dist_chain(q, kt, d, acc);
-        float ls = 0.f;
+    scalar_sweep(
+        f, a.k, a.nk, M, a.d,
+        [&](int j, bool in, float *side) {
+            side[SC_KT] = in ? a.potk[(size_t)b * a.potk_bs + j] : 0.f;
+            side[2 * SC_KT] = in ? a.coefk[(size_t)b * a.coefk_bs + j] : 0.f;
+        },
+        [&](int j0, const float (&acc)[SC_KT], const float *kn) {
+            const float *kp = kn + SC_KT, *kc = kn + 2 * SC_KT;
+            float ls = 0.f;
 #pragma unroll
-        for (int j = 0; j < SC_KT; ++j) {
-            const float L = sqrt_rn(sqdist<SWAP>(acc[j], na, kn[j])) * neg_alpha + kp[j];
-            float term = kc[j] * __builtin_amdgcn_exp2f((L + pq) * LOG2E);
-            if (MASKED) {
-                const int key = j0 + j < M ? j0 + j : M - 1;
-                const uint32_t word = a.bits[((size_t)b * M + key) * a.wpr + (ic >> 5)];
-                term = ((word >> (ic & 31)) & 1u) ? 0.f : term;
+            for (int j = 0; j < SC_KT; ++j) {
+                const float L = sqrt_rn(sqdist<SWAP>(acc[j], na, kn[j])) * neg_alpha + kp[j];
+                float term = kc[j] * __builtin_amdgcn_exp2f((L + pq) * LOG2E);
+                if (MASKED) {
+                    const int key = j0 + j < M ? j0 + j : M - 1;
+                    const uint32_t word = a.bits[((size_t)b * M + key) * a.wpr + (ic >> 5)];
+                    term = ((word >> (ic & 31)) & 1u) ? 0.f : term;
+                }
+                ls += term;
             }
-            ls += term;
-        }
-        sum += (double)ls;
-    }
+            sum += (double)ls;
+        });
     if (i < N) {
         float *o = a.out + (size_t)b * a.out_bs + i;
         *o = (float)((MASKED ? (double)*o : 0.0) - sum) * a.scale;
     }
 }
 
-// matrix-core form (d == 128): tile, LDS layout and the two-role phase structure of dvm_dist_tile.h
-constexpr int SK_QW = 32;
-constexpr int SK_WAVES = 8;
-constexpr int SK_QB = SK_QW * SK_WAVES;
-constexpr int SK_THREADS = 64 * SK_WAVES;
-constexpr int SK_LD_PER_THREAD = KT * D / 4 / SK_THREADS;
-constexpr int SA_TILE_FLOATS = ROWS_FLOATS + 3 * KT + KT * SK_WAVES;   // keys + {norm, potential, coefficient} + mask words [key][wave]
+// matrix-core form (d == 128): tile, LDS layout, geometry and the two-role phase structure of dvm_dist_tile.h
+constexpr int SA_TILE_FLOATS = ROWS_FLOATS + 3 * KT + KT * SW_WAVES;   // keys + {norm, potential, coefficient} + mask words [key][wave]
 constexpr size_t SA_LDS_BYTES = (size_t)2 * SA_TILE_FLOATS * sizeof(float);
 
 template <bool SWAP, bool MASKED>
-__global__ __launch_bounds__(SK_THREADS, 2) void skb_sweep_mfma_kernel(const SAArgs a) {
+__global__ __launch_bounds__(SW_THREADS, 2) void skb_sweep_mfma_kernel(const SAArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
+    // (its own prologue, not row_frame: with the frame the backward benchmarks came out slower than the two runs before it differ)
     const int lid = xcd_remap(blockIdx.x, gridDim.x);
     const int N = a.N, M = a.M;
     const int b = lid / a.tiles;
@@ -349,7 +335,7 @@ __global__ __launch_bounds__(SK_THREADS, 2) void skb_sweep_mfma_kernel(const SAA
     const uint32_t *bits = a.bits;
     const int wpr = a.wpr;
 
-    const int qrow = qt * SK_QB + wave * SK_QW + r32;
+    const int qrow = qt * SW_QB + wave * SW_QW + r32;
     const int qrc = qrow < N ? qrow : N - 1;
     float q[D / 2];
     load_query_frag(a.q + ((size_t)b * N + qrc) * D, h, q);
@@ -358,24 +344,24 @@ __global__ __launch_bounds__(SK_THREADS, 2) void skb_sweep_mfma_kernel(const SAA
     double sum = 0.0;
 
     const int ntiles = (M + KT - 1) / KT;
-    f32x4 pre[SK_LD_PER_THREAD];
+    f32x4 pre[SW_LD_PER_THREAD];
     float pren = 0.f;   // threads 0..63: a key's norm; 64..127: its potential; 128..191: its coefficient
     uint32_t prem = 0;  // MASKED: the word of key tid / 8 for the 32 queries of wave tid % 8
 
     auto issue_loads = [&](int t) __attribute__((always_inline)) {
         const int j0 = t * KT;
-        issue_tile<SK_THREADS>(kbase, j0, M, tid, pre);
+        issue_tile<SW_THREADS>(kbase, j0, M, tid, pre);
         if (tid < KT)
             pren = (j0 + tid < M) ? knb[j0 + tid] : INFINITY;
         else if (tid < 2 * KT)
             pren = (j0 + tid - KT < M) ? kpb[j0 + tid - KT] : 0.f;
         else if (tid < 3 * KT)
             pren = (j0 + tid - 2 * KT < M) ? kcb[j0 + tid - 2 * KT] : 0.f;
-        if (MASKED) prem = skip_mask_load<SK_WAVES>(1, bits, wpr, b, qt, j0, N, M, tid);   // queries = columns: the df2 layout
+        if (MASKED) prem = skip_mask_load<SW_WAVES>(1, bits, wpr, b, qt, j0, N, M, tid);   // queries = columns: the df2 layout
     };
     auto commit_loads = [&](int buf) __attribute__((always_inline)) {
         float *kt = smem + buf * SA_TILE_FLOATS;
-        commit_tile<SK_THREADS>(kt, tid, pre);
+        commit_tile<SW_THREADS>(kt, tid, pre);
         if (tid < 3 * KT) kt[ROWS_FLOATS + tid] = pren;
         if (MASKED) ((uint32_t *)kt)[ROWS_FLOATS + 3 * KT + tid] = prem;
     };
@@ -389,7 +375,7 @@ __global__ __launch_bounds__(SK_THREADS, 2) void skb_sweep_mfma_kernel(const SAA
         lane_scalars(kt + ROWS_FLOATS, sub, h, nbv);
         lane_scalars(kt + ROWS_FLOATS + KT, sub, h, pv);
         lane_scalars(kt + ROWS_FLOATS + 2 * KT, sub, h, cv);
-        if (MASKED) skip = skip_mask_lane<SK_WAVES>(1, (const uint32_t *)(kt + ROWS_FLOATS + 3 * KT), wave, r32, sub, h);
+        if (MASKED) skip = skip_mask_lane<SW_WAVES>(1, (const uint32_t *)(kt + ROWS_FLOATS + 3 * KT), wave, r32, sub, h);
     };
     auto epilogue = [&](int, int) __attribute__((always_inline)) {
         float ls = 0.f;
@@ -415,22 +401,17 @@ __global__ __launch_bounds__(SK_THREADS, 2) void skb_sweep_mfma_kernel(const SAA
 template <bool SWAP, bool MASKED>
 void launch_sweep_t(bool mfma, SAArgs a, int B, hipStream_t s) {
     if (mfma) {
-        a.tiles = (a.N + SK_QB - 1) / SK_QB;
+        a.tiles = (a.N + SW_QB - 1) / SW_QB;
         ensure_dyn_lds((const void *)skb_sweep_mfma_kernel<SWAP, MASKED>, (int)SA_LDS_BYTES);
-        hipLaunchKernelGGL((skb_sweep_mfma_kernel<SWAP, MASKED>), dim3((unsigned)(B * a.tiles)), dim3(SK_THREADS), SA_LDS_BYTES, s, a);
+        hipLaunchKernelGGL((skb_sweep_mfma_kernel<SWAP, MASKED>), dim3((unsigned)(B * a.tiles)), dim3(SW_THREADS), SA_LDS_BYTES, s, a);
     } else {
-        const size_t lds = (size_t)(SC_KT * a.d + 3 * SC_KT) * sizeof(float);
+        const size_t lds = scalar_sweep_lds_bytes(a.d, 2);
         ensure_dyn_lds((const void *)skb_sweep_scalar_kernel<SWAP, MASKED>, 66 * 1024);
         hipLaunchKernelGGL((skb_sweep_scalar_kernel<SWAP, MASKED>), dim3((a.N + 127) / 128, B), dim3(128), lds, s, a);
     }
 }
 
 // ------------------------------------------------------------------------------------------------ phase B
-constexpr int BW_WAVES = 4;
-constexpr int BW_OB = 32 * BW_WAVES;
-constexpr int BW_THREADS = 64 * BW_WAVES;
-constexpr int BW_LD_PER_THREAD = KT * D / 4 / BW_THREADS;
-constexpr int BW_MASK = 64 * BW_WAVES;   // skip-mask words per tile (skip_mask_load)
 constexpr int BW_FIXED_FLOATS = ROWS_FLOATS + KT + BW_MASK;   // rows + norms + mask; the K2 planes [K2][KT] follow
 
 // group 0: df1 (outer = f1 rows, inner = f2 rows); group 1: df2 (outer = f2 rows, inner = f1 rows)
@@ -448,6 +429,7 @@ struct PBArgs {
 };
 
 // UB: the unbalanced operator's planes (skb_ub_pack_kernel): R^t takes its two potentials from the third group
+// (its own prologue and loop, as softcorr_bwd_mfma_kernel and for the same reason: 256 VGPRs with spills)
 template <int grp, bool UB>
 __global__ __launch_bounds__(BW_THREADS, 2) void skb_apply_mfma_kernel(const PBArgs args) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -655,8 +637,7 @@ struct SkbWs {
     float *n1, *n2, *G, *esp, *wsp, *ubar, *vbar, *tabR, *tabC, *Graw, *upot, *vpot;
     uint32_t *bits;
 };
-SkbWs skb_carve(Arena &ar, int B, int N, int M, int n_iter, int topk, bool ub = false) {
-    SkbWs w;
+size_t skb_carve(Arena &ar, int B, int N, int M, int n_iter, int topk, bool ub, SkbWs &w) {
     const size_t T = (size_t)n_iter, P = ub ? 3 : 2;
     w.n1 = ar.take<float>((size_t)B * N);
     w.n2 = ar.take<float>((size_t)B * M);
@@ -671,7 +652,7 @@ SkbWs skb_carve(Arena &ar, int B, int N, int M, int n_iter, int topk, bool ub = 
     w.Graw = ub ? ar.take<float>((size_t)B * N) : nullptr;
     w.upot = ub ? ar.take<float>((size_t)B * N * (T ? T : 1)) : nullptr;
     w.vpot = ub ? ar.take<float>((size_t)B * M * (T + 1)) : nullptr;
-    return w;
+    return ar.off;
 }
 
 }  // namespace
@@ -682,9 +663,7 @@ using namespace dvm;
 DVM_EXPORT size_t dvm_sinkhorn_bwd_workspace_bytes(int B, int N, int M, int d, int n_iter) {
     (void)d;
     if (B < 1 || N < 1 || M < 1 || n_iter < 0 || n_iter > SKB_MAX_ITER) return 0;
-    Arena ar(nullptr, 0);
-    (void)skb_carve(ar, B, N, M, n_iter, 16);
-    return ar.off;
+    return null_carve<SkbWs>(skb_carve, B, N, M, n_iter, 16, false);   // (sized for the longest list)
 }
 
 // what the unbalanced entry adds to the run below
@@ -789,16 +768,11 @@ static int skb_run(const SkbWs &w, const float *f1, const float *f2, int B, int 
 DVM_EXPORT int dvm_sinkhorn_bwd_f32(const float *f1, const float *f2, int B, int N, int M, int d, float neg_alpha, int n_iter, int topk,
                                     const float *pi_val, const int32_t *pi_idx, const float *u_hist, const float *v_hist,
                                     const float *g_val, float *d_f1, float *d_f2, int variant, void *ws, size_t ws_bytes, void *stream) {
-    DVM_REQUIRE(f1 && f2 && pi_val && pi_idx && u_hist && v_hist && g_val && d_f1 && d_f2, "dvm_sinkhorn_bwd_f32: null pointer");
-    DVM_REQUIRE(B >= 1 && N >= 1 && M >= 1, "dvm_sinkhorn_bwd_f32: empty input (B=%d N=%d M=%d)", B, N, M);
-    DVM_REQUIRE(d >= 4 && d % 4 == 0 && d <= 512, "dvm_sinkhorn_bwd_f32: d=%d unsupported (need d%%4==0, 4<=d<=512)", d);
-    DVM_REQUIRE(topk >= 1 && topk <= 16, "dvm_sinkhorn_bwd_f32: topk=%d unsupported (1..16)", topk);
-    DVM_REQUIRE(n_iter >= 0 && n_iter <= SKB_MAX_ITER, "dvm_sinkhorn_bwd_f32: n_iter=%d unsupported (0..%d)", n_iter, SKB_MAX_ITER);
-    DVM_REQUIRE(neg_alpha < 0.f, "dvm_sinkhorn_bwd_f32: neg_alpha must be negative (got %g)", (double)neg_alpha);
-    DVM_REQUIRE(variant == 0 || variant == 1, "dvm_sinkhorn_bwd_f32: bad variant %d (0 = auto, 1 = scalar)", variant);
-    Arena ar(ws, ws_bytes);
-    const SkbWs w = skb_carve(ar, B, N, M, n_iter, topk);
-    if (!arena_fits(ar, "dvm_sinkhorn_bwd_f32")) return DVM_ENOSPACE;
+    const int rc = softcorr_family_check("dvm_sinkhorn_bwd_f32", f1 && f2 && pi_val && pi_idx && u_hist && v_hist && g_val && d_f1 && d_f2, B, N,
+                                         M, d, topk, neg_alpha, variant, 1, n_iter, SKB_MAX_ITER);
+    if (rc != DVM_OK) return rc;
+    SkbWs w;
+    if (!carve_ws(ws, ws_bytes, "dvm_sinkhorn_bwd_f32", w, skb_carve, B, N, M, n_iter, topk, false)) return DVM_ENOSPACE;
     return skb_run(w, f1, f2, B, N, M, d, neg_alpha, n_iter, topk, pi_val, pi_idx, u_hist, v_hist, g_val, d_f1, d_f2, variant == 0 && d == D,
                    nullptr, (hipStream_t)stream);
 }
@@ -806,9 +780,7 @@ DVM_EXPORT int dvm_sinkhorn_bwd_f32(const float *f1, const float *f2, int B, int
 DVM_EXPORT size_t dvm_sinkhorn_ub_bwd_workspace_bytes(int B, int N, int M, int d, int n_iter) {
     (void)d;
     if (B < 1 || N < 1 || M < 1 || n_iter < 0 || n_iter > SKB_MAX_ITER) return 0;
-    Arena ar(nullptr, 0);
-    (void)skb_carve(ar, B, N, M, n_iter, 16, true);
-    return ar.off;
+    return null_carve<SkbWs>(skb_carve, B, N, M, n_iter, 16, true);
 }
 
 DVM_EXPORT int dvm_sinkhorn_ub_bwd_f32(const float *f1, const float *f2, int B, int N, int M, int d, float neg_alpha, int n_iter, int topk,
@@ -816,18 +788,12 @@ DVM_EXPORT int dvm_sinkhorn_ub_bwd_f32(const float *f1, const float *f2, int B, 
                                        const int32_t *pi_idx, const float *row_lmass, const float *rn_hist, const float *cn_hist,
                                        const float *g_val, const float *g_lmass, float *d_f1, float *d_f2, float *d_log_a, float *d_log_b,
                                        int variant, void *ws, size_t ws_bytes, void *stream) {
-    DVM_REQUIRE(f1 && f2 && pi_val && pi_idx && row_lmass && rn_hist && cn_hist && g_val && d_f1 && d_f2, "dvm_sinkhorn_ub_bwd_f32: null pointer");
-    DVM_REQUIRE(B >= 1 && N >= 1 && M >= 1, "dvm_sinkhorn_ub_bwd_f32: empty input (B=%d N=%d M=%d)", B, N, M);
-    DVM_REQUIRE(d >= 4 && d % 4 == 0 && d <= 512, "dvm_sinkhorn_ub_bwd_f32: d=%d unsupported (need d%%4==0, 4<=d<=512)", d);
-    DVM_REQUIRE(topk >= 1 && topk <= 16, "dvm_sinkhorn_ub_bwd_f32: topk=%d unsupported (1..16)", topk);
-    DVM_REQUIRE(n_iter >= 0 && n_iter <= SKB_MAX_ITER, "dvm_sinkhorn_ub_bwd_f32: n_iter=%d unsupported (0..%d)", n_iter, SKB_MAX_ITER);
-    DVM_REQUIRE(neg_alpha < 0.f, "dvm_sinkhorn_ub_bwd_f32: neg_alpha must be negative (got %g)", (double)neg_alpha);
-    DVM_REQUIRE(tau_row > 0.f && tau_row <= 1.f && tau_col > 0.f && tau_col <= 1.f, "dvm_sinkhorn_ub_bwd_f32: tau=(%g, %g) outside (0, 1]",
-                (double)tau_row, (double)tau_col);
-    DVM_REQUIRE(variant == 0 || variant == 1, "dvm_sinkhorn_ub_bwd_f32: bad variant %d (0 = auto, 1 = scalar)", variant);
-    Arena ar(ws, ws_bytes);
-    const SkbWs w = skb_carve(ar, B, N, M, n_iter, topk, true);
-    if (!arena_fits(ar, "dvm_sinkhorn_ub_bwd_f32")) return DVM_ENOSPACE;
+    const int rc = softcorr_family_check("dvm_sinkhorn_ub_bwd_f32",
+                                         f1 && f2 && pi_val && pi_idx && row_lmass && rn_hist && cn_hist && g_val && d_f1 && d_f2, B, N, M, d, topk,
+                                         neg_alpha, variant, 1, n_iter, SKB_MAX_ITER, tau_row, tau_col);
+    if (rc != DVM_OK) return rc;
+    SkbWs w;
+    if (!carve_ws(ws, ws_bytes, "dvm_sinkhorn_ub_bwd_f32", w, skb_carve, B, N, M, n_iter, topk, true)) return DVM_ENOSPACE;
     const SkbUb ub{tau_row, tau_col, log_a, log_b, row_lmass, g_lmass, d_log_a, d_log_b};
     return skb_run(w, f1, f2, B, N, M, d, neg_alpha, n_iter, topk, pi_val, pi_idx, rn_hist, cn_hist, g_val, d_f1, d_f2, variant == 0 && d == D,
                    &ub, (hipStream_t)stream);

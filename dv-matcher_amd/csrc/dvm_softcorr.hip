@@ -8,7 +8,9 @@
 // arg-max map are bit-exact integers.
 //
 // One workgroup owns 256 query rows (8 waves x 32) and sweeps all M keys through the distance tile of
-// dvm_dist_tile.h, which defines the layout, the chain and the two-role phase structure.
+// dvm_dist_tile.h, which defines the layout, the chain, the workgroup geometry, a lane's row frame and the sweep loops
+// (two_role_sweep, scalar_sweep); the top-k list's half-lane merge and flagged-candidate loop are next to KBest in
+// dvm_common.h.  What is here: the row norms, the epilogues, the launchers and the entry points.
 #include <stdlib.h>
 
 #include "dvm_dist_tile.h"
@@ -101,32 +103,24 @@ struct RowState {
             smax = new_smax;
         }
     }
-    __device__ __forceinline__ void merge(const RowState &o) {
-        float m = fmaxf(smax, o.smax);
-        float a = (smax == -INFINITY) ? 0.f : l * exp2f((smax - m) * LOG2E);
-        float b = (o.smax == -INFINITY) ? 0.f : o.l * exp2f((o.smax - m) * LOG2E);
-        l = a + b;
-        smax = m;
-#pragma unroll
-        for (int t = 0; t < TOPK; ++t) kb.insert_lex(o.kb.key[t], o.kb.idx[t]);
-    }
 };
 
+// a finished row: the list, smax = max of s and l = sum exp(s - smax)
 template <int TOPK>
-__device__ __forceinline__ void store_row(const RowState<TOPK> &st, int topk, int M, float neg_alpha, float *val,
+__device__ __forceinline__ void store_row(const KBest<TOPK, float> &kb, float smax, float l, int topk, int M, float neg_alpha, float *val,
                                           int32_t *idx, float *row_smax, float *row_sum) {
-    float inv = 1.0f / st.l;
+    float inv = 1.0f / l;
 #pragma unroll
     for (int t = 0; t < TOPK; ++t) {
         if (t < topk) {
             bool live = t < M;
-            float s = st.kb.key[t] * neg_alpha;
-            val[t] = live ? exp2f((s - st.smax) * LOG2E) * inv : 0.f;
-            idx[t] = live ? st.kb.idx[t] : 0;
+            float s = kb.key[t] * neg_alpha;
+            val[t] = live ? exp2f((s - smax) * LOG2E) * inv : 0.f;
+            idx[t] = live ? kb.idx[t] : 0;
         }
     }
-    if (row_smax) *row_smax = st.smax;
-    if (row_sum) *row_sum = st.l;
+    if (row_smax) *row_smax = smax;
+    if (row_sum) *row_sum = l;
 }
 
 // ------------------------------------------------------------ scalar variant
@@ -139,44 +133,32 @@ __global__ __launch_bounds__(128) void softcorr_scalar_kernel(const float *__res
                                                               int N, int M, int d, float neg_alpha, int topk,
                                                               float *__restrict__ pi_val, int32_t *__restrict__ pi_idx,
                                                               float *__restrict__ row_smax, float *__restrict__ row_sum) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];  // [SC_KT][d] keys + [SC_KT] norms
-    float *kt = smem;
-    float *kn = smem + SC_KT * d;
-    const int b = blockIdx.y;
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const int ic = i < N ? i : N - 1;
-    const float *q = f1 + ((size_t)b * N + ic) * d;
-    const float na = n1[(size_t)b * N + ic];
-    const float *kbase = f2 + (size_t)b * M * d;
+    const ScalarFrame f = scalar_frame(f1, n1, N, d);
+    const float na = f.na;
     RowState<TOPK> st;
     st.init();
-    for (int j0 = 0; j0 < M; j0 += SC_KT) {
-        __syncthreads();
-        scalar_stage_keys(kt, kbase, j0, M, d);
-        if (threadIdx.x < SC_KT) kn[threadIdx.x] = (j0 + threadIdx.x < M) ? n2[(size_t)b * M + j0 + threadIdx.x] : INFINITY;
-        __syncthreads();
-        float acc[SC_KT];
-        scalar_dist_chain(q, kt, d, acc);
-        // epilogue: distances, online softmax, top-k
-        float dd[SC_KT];
-        float tmin = INFINITY;
+    scalar_sweep(
+        f, f2, n2, M, d, [](int, bool, float *) {},
+        [&](int j0, const float (&acc)[SC_KT], const float *kn) {   // distances, online softmax, top-k
+            float dd[SC_KT];
+            float tmin = INFINITY;
 #pragma unroll
-        for (int j = 0; j < SC_KT; ++j) {
-            dd[j] = sqrt_rn(sqdist<false>(acc[j], na, kn[j]));
-            tmin = fminf(tmin, dd[j]);
-        }
-        st.rescale(tmin * neg_alpha);
+            for (int j = 0; j < SC_KT; ++j) {
+                dd[j] = sqrt_rn(sqdist<false>(acc[j], na, kn[j]));
+                tmin = fminf(tmin, dd[j]);
+            }
+            st.rescale(tmin * neg_alpha);
 #pragma unroll
-        for (int j = 0; j < SC_KT; ++j) {
-            float s = dd[j] * neg_alpha;
-            st.l += exp2f((s - st.smax) * LOG2E);
-            st.kb.insert(dd[j], j0 + j);
-        }
-    }
-    if (i < N) {
-        size_t row = (size_t)b * N + i;
-        store_row<TOPK>(st, topk, M, neg_alpha, pi_val + row * topk, pi_idx + row * topk, row_smax ? row_smax + row : nullptr,
-                        row_sum ? row_sum + row : nullptr);
+            for (int j = 0; j < SC_KT; ++j) {
+                float s = dd[j] * neg_alpha;
+                st.l += exp2f((s - st.smax) * LOG2E);
+                st.kb.insert(dd[j], j0 + j);
+            }
+        });
+    if (f.i < N) {
+        size_t row = (size_t)f.b * N + f.i;
+        store_row<TOPK>(st.kb, st.smax, st.l, topk, M, neg_alpha, pi_val + row * topk, pi_idx + row * topk,
+                        row_smax ? row_smax + row : nullptr, row_sum ? row_sum + row : nullptr);
     }
 }
 
@@ -189,16 +171,16 @@ __global__ __launch_bounds__(128) void softcorr_dense_kernel(const float *__rest
                                                              const float *__restrict__ n1, const float *__restrict__ n2,
                                                              const float *__restrict__ row_smax, const float *__restrict__ row_sum,
                                                              int N, int M, int d, float neg_alpha, float *__restrict__ P) {
+    // (its own loop and chain, one key at a time: scalar_sweep's 32 accumulators would cost it 3 of its 8 waves per SIMD)
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *kt = smem;
     float *kn = smem + SC_KT * d;
-    const int b = blockIdx.y;
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const int ic = i < N ? i : N - 1;
-    const float *q = f1 + ((size_t)b * N + ic) * d;
-    const float na = n1[(size_t)b * N + ic];
-    const float smax = row_smax[(size_t)b * N + ic];
-    const float inv = 1.0f / row_sum[(size_t)b * N + ic];
+    const ScalarFrame f = scalar_frame(f1, n1, N, d);
+    const int b = f.b, i = f.i;
+    const float *q = f.q;
+    const float na = f.na;
+    const float smax = row_smax[(size_t)b * N + f.ic];
+    const float inv = 1.0f / row_sum[(size_t)b * N + f.ic];
     const float *kbase = f2 + (size_t)b * M * d;
     for (int j0 = 0; j0 < M; j0 += SC_KT) {
         __syncthreads();
@@ -221,13 +203,8 @@ __global__ __launch_bounds__(128) void softcorr_dense_kernel(const float *__rest
 }
 
 // -------------------------------------------------------------- MFMA variant
-constexpr int MF_QW = 32;              // queries per wave
-constexpr int MF_WAVES = 8;             // waves 0-3 and 4-7 pair up on the 4 SIMDs (two per SIMD)
-constexpr int MF_QB = MF_QW * MF_WAVES;  // 256 queries per workgroup
-constexpr int MF_THREADS = 64 * MF_WAVES;
-constexpr int MF_LD_PER_THREAD = KT * D / 4 / MF_THREADS;  // float4 loads per thread per tile = 8
-constexpr int MF_STAGE = 16 * 64;  // floats per wave: this sub-tile's 16 squared distances of each lane, [r][lane]
-constexpr size_t MF_LDS_BYTES = ((size_t)2 * (ROWS_FLOATS + KT) + (size_t)MF_WAVES * MF_STAGE) * sizeof(float);
+// [2] x { keys, norms } + per wave the staging block of this sub-tile's 16 squared distances of each lane
+constexpr size_t MF_LDS_BYTES = ((size_t)2 * (ROWS_FLOATS + KT) + (size_t)SW_WAVES * SW_STAGE) * sizeof(float);
 
 __device__ __forceinline__ float select16(const float (&v)[16], int b) {
     float a0 = (b & 1) ? v[1] : v[0], a1 = (b & 1) ? v[3] : v[2], a2 = (b & 1) ? v[5] : v[4], a3 = (b & 1) ? v[7] : v[6];
@@ -242,7 +219,7 @@ __device__ __forceinline__ float select16(const float (&v)[16], int b) {
 // (f2 -> f1)), each with its own query/key tensors and outputs.
 struct SCGroup {
     const float *q, *k, *nq, *nk;  // queries [B][N][128], keys [B][M][128], their |.|^2
-    int N, M, tiles;               // tiles = ceil(N / MF_QB)
+    int N, M, tiles;               // tiles = ceil(N / SW_QB)
     float *val;
     int32_t *idx;
     float *smax, *sum;
@@ -261,33 +238,26 @@ struct SCArgs {
 // with the correctly rounded sqrt and the reference's rounding sequence (s = d*neg_alpha, s - c)
 // inside a compacted, wave-uniform loop, so the ranking and the dominant terms stay exact.
 template <int TOPK, bool LEAN>
-__global__ __launch_bounds__(MF_THREADS, 2) void softcorr_mfma_kernel(const SCArgs args) {
+__global__ __launch_bounds__(SW_THREADS, 2) void softcorr_mfma_kernel(const SCArgs args) {
     // __launch_bounds__(512, 2): two waves per SIMD, i.e. ONE 512-thread workgroup per CU
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *const ktile0 = smem;                    // [2][KT][LDK]
     float *const knorm0 = smem + 2 * ROWS_FLOATS;  // [2][KT]
-    float *const stage = knorm0 + 2 * KT + (threadIdx.x >> 6) * MF_STAGE + (threadIdx.x & 63);  // this lane's column
+    float *const stage = knorm0 + 2 * KT + (threadIdx.x >> 6) * SW_STAGE + (threadIdx.x & 63);  // this lane's column
 
     int lid = xcd_remap(blockIdx.x, gridDim.x);
     const int grp = lid >= args.blocks0 ? 1 : 0;
     lid -= grp ? args.blocks0 : 0;
     const SCGroup &G = args.g[grp];
     const int N = G.N, M = G.M;
-    const int b = lid / G.tiles;
-    const int qt = lid % G.tiles;
     const float neg_alpha = args.neg_alpha;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r32 = lane & 31, h = lane >> 5;
+    RowFrame f;   // this lane's query row
+    row_frame(f, lid, G.tiles, N, G.q, G.nq);
+    const int b = f.b, tid = f.tid, r32 = f.r32, h = f.h;
+    const float na = f.nrm;
 
     const float *kbase = G.k + (size_t)b * M * D;
     const float *knb = G.nk + (size_t)b * M;
-
-    // this lane's query row and its B-operand fragment
-    const int qrow = qt * MF_QB + wave * MF_QW + r32;
-    const int qrc = qrow < N ? qrow : N - 1;
-    float q[D / 2];
-    load_query_frag(G.q + ((size_t)b * N + qrc) * D, h, q);
-    const float na = G.nq[(size_t)b * N + qrc];
 
     KBest<TOPK, float> kb;  // keyed on the correctly rounded distance
     kb.init(INFINITY);
@@ -297,16 +267,16 @@ __global__ __launch_bounds__(MF_THREADS, 2) void softcorr_mfma_kernel(const SCAr
     const float a2 = neg_alpha * LOG2E;
 
     const int ntiles = (M + KT - 1) / KT;
-    f32x4 pre[MF_LD_PER_THREAD];
+    f32x4 pre[SW_LD_PER_THREAD];
     float pren = 0.f;
 
     auto issue_loads = [&](int t) {
         const int j0 = t * KT;
-        issue_tile<MF_THREADS>(kbase, j0, M, tid, pre);
+        issue_tile<SW_THREADS>(kbase, j0, M, tid, pre);
         if (tid < KT) pren = (j0 + tid < M) ? knb[j0 + tid] : INFINITY;
     };
     auto commit_loads = [&](int buf) {
-        commit_tile<MF_THREADS>(ktile0 + buf * ROWS_FLOATS, tid, pre);
+        commit_tile<SW_THREADS>(ktile0 + buf * ROWS_FLOATS, tid, pre);
         if (tid < KT) knorm0[buf * KT + tid] = pren;
     };
 
@@ -314,7 +284,7 @@ __global__ __launch_bounds__(MF_THREADS, 2) void softcorr_mfma_kernel(const SCAr
     f32x16 acc;
     float nbv[16];
     auto mfma_chain = [&](int buf, int sub) {
-        dist_chain(ktile0 + buf * ROWS_FLOATS, sub, r32, h, q, acc);
+        dist_chain(ktile0 + buf * ROWS_FLOATS, sub, r32, h, f.q, acc);
         lane_scalars(knorm0 + buf * KT, sub, h, nbv);
     };
 
@@ -364,16 +334,8 @@ __global__ __launch_bounds__(MF_THREADS, 2) void softcorr_mfma_kernel(const SCAr
             }
             l += lsum;
         }
-        // Branch-free body (inactive lanes process +inf, a no-op): keeps the top-k registers in place
-        // instead of copying them around a divergent region every iteration.
-        // (counted, wave-uniform trip count: a `while (__any(mask))` loop makes the compiler copy the whole list — 60
-        // v_mov — around a structurised exit on every iteration)
-        const int iters = (int)__reduce_max_sync(~0ull, (unsigned)__popc(mask));
-        for (int it = 0; it < iters; ++it) {
-            const bool act = mask != 0;
-            const int bpos = act ? (__ffs(mask) - 1) : 0;
-            mask &= mask - 1;
-            float v2 = stage[bpos * 64];
+        // the exact path of the flagged candidates (inactive lanes process +inf, a no-op)
+        for_each_flagged(mask, stage, [&](bool act, int bpos, float v2) {
             v2 = act ? (v2 > 0.f ? v2 : 0.f) : INFINITY;
             const float de = sqrt_rn(v2);
             const float s = de * neg_alpha;  // -inf for inactive lanes
@@ -389,7 +351,7 @@ __global__ __launch_bounds__(MF_THREADS, 2) void softcorr_mfma_kernel(const SCAr
                 l += __builtin_amdgcn_exp2f((s - cref) * LOG2E) - __builtin_amdgcn_exp2f(fmaf(dfast, a2, -c2));
             }
             kb.insert_nb(de, t * KT + sub * 32 + lane_key(bpos, h));
-        }
+        });
         // bounds for the next sub-tile.  Top-k: the row's k-th best is at most min(a_k, b_k, max(a_m, b_m))
         // with a, b the sorted lists of the two half-lanes and m = k/2 (2m elements lie below that max).
         {
@@ -407,7 +369,7 @@ __global__ __launch_bounds__(MF_THREADS, 2) void softcorr_mfma_kernel(const SCAr
         }
     };
 
-    const int role = __builtin_amdgcn_readfirstlane(wave >> 2);
+    const int role = __builtin_amdgcn_readfirstlane(f.wave >> 2);
     two_role_sweep<false>(ntiles, role, issue_loads, commit_loads, mfma_chain, epilogue);
 
     // merge the two half-lanes that share a query (lane, lane^32)
@@ -418,35 +380,15 @@ __global__ __launch_bounds__(MF_THREADS, 2) void softcorr_mfma_kernel(const SCAr
         float bb = (co == -INFINITY) ? 0.f : lo * exp2f((co - cm) * LOG2E);
         l = a + bb;
         cref = cm;
-        float ok[TOPK];
-        int oi[TOPK];
-#pragma unroll
-        for (int t = 0; t < TOPK; ++t) {
-            ok[t] = __shfl_xor(kb.key[t], 32, 64);
-            oi[t] = __shfl_xor(kb.idx[t], 32, 64);
-        }
-#pragma unroll
-        for (int t = 0; t < TOPK; ++t) kb.insert_lex(ok[t], oi[t]);
+        merge_halves(kb);
     }
-    if (h == 0 && qrow < N) {
-        const size_t row = (size_t)b * N + qrow;
+    if (h == 0 && f.row < N) {
+        const size_t row = (size_t)b * N + f.row;
         const int topk = args.topk;
         const float smax = kb.key[0] * neg_alpha;                  // exact max of s
         const float lsm = l * exp2f((cref - smax) * LOG2E);        // sum exp(s - smax)
-        const float inv = 1.0f / lsm;
-        float *val = G.val + row * topk;
-        int32_t *idx = G.idx + row * topk;
-#pragma unroll
-        for (int t = 0; t < TOPK; ++t) {
-            if (t < topk) {
-                bool live = t < M;
-                float s = kb.key[t] * neg_alpha;
-                val[t] = live ? exp2f((s - smax) * LOG2E) * inv : 0.f;
-                idx[t] = live ? kb.idx[t] : 0;
-            }
-        }
-        if (G.smax) G.smax[row] = smax;
-        if (G.sum) G.sum[row] = lsm;
+        store_row<TOPK>(kb, smax, lsm, topk, M, neg_alpha, G.val + row * topk, G.idx + row * topk, G.smax ? G.smax + row : nullptr,
+                        G.sum ? G.sum + row : nullptr);
     }
 }
 
@@ -459,9 +401,9 @@ static void launch_softcorr_mfma(SCArgs &a, int blocks, hipStream_t s) {
     const float alpha = -a.neg_alpha;
     a.cutw = 20.f / alpha;
     if (alpha >= LEAN_MIN_ALPHA)
-        hipLaunchKernelGGL((softcorr_mfma_kernel<TOPK, true>), dim3(blocks), dim3(MF_THREADS), MF_LDS_BYTES, s, a);
+        hipLaunchKernelGGL((softcorr_mfma_kernel<TOPK, true>), dim3(blocks), dim3(SW_THREADS), MF_LDS_BYTES, s, a);
     else
-        hipLaunchKernelGGL((softcorr_mfma_kernel<TOPK, false>), dim3(blocks), dim3(MF_THREADS), MF_LDS_BYTES, s, a);
+        hipLaunchKernelGGL((softcorr_mfma_kernel<TOPK, false>), dim3(blocks), dim3(SW_THREADS), MF_LDS_BYTES, s, a);
 }
 
 // K == 128 only: also maxes the bit pattern of max |x| into the 256 slots of `absmax_slots` (zero them first);
@@ -545,12 +487,8 @@ DVM_EXPORT size_t dvm_softcorr_workspace_bytes(int B, int N, int M, int d) {
 DVM_EXPORT int dvm_softcorr_fwd_f32(const float *f1, const float *f2, int B, int N, int M, int d, float neg_alpha,
                                     int topk, float *pi_val, int32_t *pi_idx, float *row_smax, float *row_sum,
                                     int variant, void *ws, size_t ws_bytes, void *stream) {
-    DVM_REQUIRE(f1 && f2 && pi_val && pi_idx, "dvm_softcorr_fwd_f32: null pointer");
-    DVM_REQUIRE(B >= 1 && N >= 1 && M >= 1, "dvm_softcorr_fwd_f32: empty input (B=%d N=%d M=%d)", B, N, M);
-    DVM_REQUIRE(d >= 4 && d % 4 == 0 && d <= 512, "dvm_softcorr_fwd_f32: d=%d unsupported (need d%%4==0, 4<=d<=512)", d);
-    DVM_REQUIRE(topk >= 1 && topk <= 16, "dvm_softcorr_fwd_f32: topk=%d unsupported (1..16)", topk);
-    DVM_REQUIRE(neg_alpha < 0.f, "dvm_softcorr_fwd_f32: neg_alpha must be negative (got %g)", (double)neg_alpha);
-    DVM_REQUIRE(variant >= 0 && variant <= 3, "dvm_softcorr_fwd_f32: bad variant %d", variant);
+    const int rc0 = softcorr_family_check("dvm_softcorr_fwd_f32", f1 && f2 && pi_val && pi_idx, B, N, M, d, topk, neg_alpha, variant, 3);
+    if (rc0 != DVM_OK) return rc0;
     DVM_REQUIRE(variant < 2 || d == D, "dvm_softcorr_fwd_f32: the matrix-core variants need d == 128");
     DVM_REQUIRE(variant != 3 || topk <= 10, "dvm_softcorr_fwd_f32: the bf16 variant keeps 12 candidates (topk <= 10)");
     if (variant == 0 && d == D && topk <= 10) variant = 3;   // auto: the fp16-split sweep (variants 1 / 2: the `variant` argument)
@@ -577,7 +515,7 @@ DVM_EXPORT int dvm_softcorr_fwd_f32(const float *f1, const float *f2, int B, int
     prof_begin(s);
     if (mfma) {
         SCArgs a;
-        a.g[0] = SCGroup{f1, f2, n1, n2, N, M, (N + MF_QB - 1) / MF_QB, pi_val, pi_idx, row_smax, row_sum};
+        a.g[0] = SCGroup{f1, f2, n1, n2, N, M, (N + SW_QB - 1) / SW_QB, pi_val, pi_idx, row_smax, row_sum};
         a.g[1] = a.g[0];
         a.blocks0 = B * a.g[0].tiles;
         a.neg_alpha = neg_alpha;
@@ -588,7 +526,7 @@ DVM_EXPORT int dvm_softcorr_fwd_f32(const float *f1, const float *f2, int B, int
             launch_softcorr_mfma<16>(a, a.blocks0, s);
     } else {
         dim3 grid((N + 127) / 128, B);
-        size_t lds = (size_t)(SC_KT * d + SC_KT) * sizeof(float);
+        size_t lds = scalar_sweep_lds_bytes(d, 0);
         ensure_dyn_lds((const void *)softcorr_scalar_kernel<10>, 66 * 1024);
         ensure_dyn_lds((const void *)softcorr_scalar_kernel<16>, 66 * 1024);
         if (topk <= 10)
@@ -634,7 +572,7 @@ DVM_EXPORT int dvm_softcorr_dense_f32(const float *f1, const float *f2, int B, i
     int rc = dvm_softcorr_fwd_f32(f1, f2, B, N, M, d, neg_alpha, 1, w.v1, w.i1, smax, ssum, 0, ws, w.sc_bytes, stream);
     if (rc != DVM_OK) return rc;
     const float *n1 = w.sc.n1, *n2 = w.sc.n2;
-    size_t lds = (size_t)(SC_KT * d + SC_KT) * sizeof(float);
+    size_t lds = scalar_sweep_lds_bytes(d, 0);
     (void)hipFuncSetAttribute((const void *)softcorr_dense_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 66 * 1024);
     hipLaunchKernelGGL(softcorr_dense_kernel<0>, dim3((N + 127) / 128, B), dim3(128), lds, (hipStream_t)stream, f1, f2, n1, n2, smax,
                        ssum, N, M, d, neg_alpha, P);

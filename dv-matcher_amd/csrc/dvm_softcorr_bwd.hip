@@ -20,7 +20,8 @@
 // is permuted consistently on the B side), so W never touches LDS.  Where the expansion cancels
 // (v < TAU (|f_o|^2 + |f_i|^2): a cluster of columns near one query, more than its top-k) the entry's D is
 // redone from the exact difference in a wave-uniform branch that ordinary features never take.
-// The tile, the redo, the skip mask, the apply chain and the output loop are the phase-B pieces of dvm_dist_tile.h.
+// The geometry, the tile, the redo, the skip mask, the apply chain and the output loop are the phase-B pieces of
+// dvm_dist_tile.h.
 #include <algorithm>
 
 #include "dvm_dist_tile.h"
@@ -30,11 +31,6 @@ namespace {
 
 using namespace dtile;
 
-constexpr int BW_WAVES = 4;
-constexpr int BW_OB = 32 * BW_WAVES;  // outer rows per workgroup
-constexpr int BW_THREADS = 64 * BW_WAVES;
-constexpr int BW_LD_PER_THREAD = KT * D / 4 / BW_THREADS;  // 8 float4 per thread per tile
-constexpr int BW_MASK = 64 * BW_WAVES;                     // skip-mask words per tile (skip_mask_load)
 constexpr int BW_TILE_FLOATS = ROWS_FLOATS + 3 * KT + BW_MASK;  // rows + {norm, c2, coef} + mask
 constexpr size_t BW_LDS_BYTES = ((size_t)2 * BW_TILE_FLOATS + BW_OB) * sizeof(float);
 
@@ -57,6 +53,8 @@ struct SBArgs {
     float a2;     // neg_alpha * log2(e)
 };
 
+// (its own prologue and loop, not a frame and a loop shared with skb_apply_mfma_kernel: both kernels sit at 256 VGPRs with spills,
+// and any change in their text moved the spill counts up)
 __global__ __launch_bounds__(BW_THREADS, 2) void softcorr_bwd_mfma_kernel(const SBArgs args) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *const rsum = smem + 2 * BW_TILE_FLOATS;  // [BW_OB]
@@ -320,12 +318,9 @@ DVM_EXPORT int dvm_softcorr_bwd_f32(const float *f1, const float *f2, int B, int
                                     const float *pi_val, const int32_t *pi_idx, const float *row_smax, const float *row_sum,
                                     const float *g_val, float *d_f1, float *d_f2, int variant, void *ws, size_t ws_bytes,
                                     void *stream) {
-    DVM_REQUIRE(f1 && f2 && pi_val && pi_idx && row_smax && row_sum && g_val && d_f1 && d_f2, "dvm_softcorr_bwd_f32: null pointer");
-    DVM_REQUIRE(B >= 1 && N >= 1 && M >= 1, "dvm_softcorr_bwd_f32: empty input (B=%d N=%d M=%d)", B, N, M);
-    DVM_REQUIRE(d >= 4 && d % 4 == 0 && d <= 512, "dvm_softcorr_bwd_f32: d=%d unsupported (need d%%4==0, 4<=d<=512)", d);
-    DVM_REQUIRE(topk >= 1 && topk <= 16, "dvm_softcorr_bwd_f32: topk=%d unsupported (1..16)", topk);
-    DVM_REQUIRE(neg_alpha < 0.f, "dvm_softcorr_bwd_f32: neg_alpha must be negative (got %g)", (double)neg_alpha);
-    DVM_REQUIRE(variant >= 0 && variant <= 2, "dvm_softcorr_bwd_f32: bad variant %d", variant);
+    const int rc = softcorr_family_check("dvm_softcorr_bwd_f32", f1 && f2 && pi_val && pi_idx && row_smax && row_sum && g_val && d_f1 && d_f2, B,
+                                         N, M, d, topk, neg_alpha, variant, 2);
+    if (rc != DVM_OK) return rc;
     DVM_REQUIRE(variant != 2 || d == D, "dvm_softcorr_bwd_f32: MFMA variant needs d == 128");
     SoftcorrBwdWs w;
     if (!carve_ws(ws, ws_bytes, "dvm_softcorr_bwd_f32", w, carve_softcorr_bwd, B, N, M)) return DVM_ENOSPACE;

@@ -236,6 +236,15 @@ def test_softcorr_dense_rows_sum_to_one(ops):
     np.testing.assert_allclose(host(P.sum(-1)), 1.0, rtol=1e-5)
     ref = torch.softmax(torch.cdist(f1, f2) * ops.neg_alpha_f32(12.5), -1)
     np.testing.assert_allclose(host(P), host(ref), rtol=0, atol=1e-5)
+    # d = 36: not a multiple of the scalar chain's 32-wide register chunk; two key tiles, the second ragged
+    f1, f2 = torch.randn(2, 70, 36, generator=g).cuda(), torch.randn(2, 45, 36, generator=g).cuda()
+    P = ops.softcorr_dense(f1, f2, 12.5)
+    np.testing.assert_allclose(host(P.sum(-1)), 1.0, rtol=1e-5)
+    ref = torch.softmax(torch.cdist(f1, f2) * ops.neg_alpha_f32(12.5), -1)
+    np.testing.assert_allclose(host(P), host(ref), rtol=0, atol=1e-5)
+    # the sparse operator's scalar form makes exp2f((s - smax) * log2e) * (1 / sum) from the same distance bits: the same values
+    val, idx = ops.softcorr(f1, f2, 12.5, variant=1)[:2]
+    assert np.array_equal(host(torch.gather(P, 2, idx.long())), host(val))
 
 
 def test_training_driver_runs():
