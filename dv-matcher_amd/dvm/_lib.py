@@ -6,166 +6,72 @@ tensor is not on a HIP device, every op raises.  Build with
 """
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 SO_PATH = os.path.join(CSRC, "libdvm_hip.so")
+HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "dvm.h")
 
 _lib = None
-
-c_int, c_float, c_size_t, c_void_p = ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_void_p
-
-# name -> (restype, [argtypes])  — mirrors include/dvm.h one to one
-_P = c_void_p
-SIGNATURES = {
-    "dvm_abi_version": (c_int, []),
-    "dvm_last_error": (ctypes.c_char_p, []),
-    "dvm_device_count": (c_int, []),
-    "dvm_profile_enable": (c_int, [c_int]),
-    "dvm_profile_select": (c_int, [ctypes.c_uint]),
-    "dvm_profile_read": (c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_int)]),
-    "dvm_profile_read_kernel": (c_int, [c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_int)]),
-    "dvm_profile_kernel_name": (ctypes.c_char_p, [c_int]),
-    "dvm_profile_disable": (c_int, []),
-    "dvm_rownorm2_f32": (c_int, [_P, c_int, c_int, _P, _P]),
-    "dvm_linear_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_float, _P, _P]),
-    "dvm_linear_prefix_f32": (c_int, [_P, c_int, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_float, _P, _P]),
-    "dvm_linear_scaled_residual_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, c_float, _P, _P, _P]),
-    "dvm_linear_wgrad_f32": (c_int, [_P, _P, ctypes.c_long, c_int, c_int, _P, _P]),
-    "dvm_bn_pm_workspace_bytes": (c_size_t, [ctypes.c_long, c_int]),
-    "dvm_bn_act_train_fwd_pm_f32": (c_int, [_P, _P, _P, _P, ctypes.c_long, c_int, c_float, c_float, c_float, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
-    "dvm_bn_act_train_bwd_pm_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, ctypes.c_long, c_int, c_float, _P, _P, _P, c_int, _P, c_size_t, _P]),
-    "dvm_softcorr_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "dvm_softcorr_fwd_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_float, c_int, _P, _P, _P, _P, c_int, _P,
-                                     c_size_t, _P]),
-    "dvm_sinkhorn_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "dvm_sinkhorn_fwd_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_float, c_int, c_int, _P, _P, _P, _P, _P, _P, c_int,
-                                     _P, c_size_t, _P]),
-    "dvm_sinkhorn_hist_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "dvm_sinkhorn_fwd_hist_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_float, c_int, c_int, _P, _P, _P, _P, _P, _P, c_int,
-                                          _P, c_size_t, _P]),
-    "dvm_sinkhorn_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
-    "dvm_sinkhorn_bwd_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_float, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, c_int,
-                                     _P, c_size_t, _P]),
-    "dvm_sinkhorn_ub_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "dvm_sinkhorn_ub_fwd_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_float, c_float, _P, _P, _P, _P, _P, _P, _P,
-                                        _P, _P, c_int, _P, c_size_t, _P]),
-    "dvm_sinkhorn_ub_hist_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "dvm_sinkhorn_ub_fwd_hist_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_float, c_float, _P, _P, _P, _P, _P, _P,
-                                             _P, _P, _P, c_int, _P, c_size_t, _P]),
-    "dvm_sinkhorn_ub_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
-    "dvm_sinkhorn_ub_bwd_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_float, c_float, _P, _P, _P, _P, _P, _P, _P,
-                                        _P, _P, _P, _P, _P, _P, c_int, _P, c_size_t, _P]),
-    "dvm_softcorr_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "dvm_softcorr_bwd_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_float, c_int, _P, _P, _P, _P, _P, _P, _P, c_int,
-                                     _P, c_size_t, _P]),
-    "dvm_n2p_core_fwd_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
-    "dvm_n2p_core_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "dvm_n2p_core_bwd_f32": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
-    "dvm_softcorr_apply_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "dvm_softcorr_apply_bwd_f32": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
-    "dvm_rank_term_max_n": (c_int, []),
-    "dvm_rank_term_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "dvm_rank_term_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
-    "dvm_dist_loss_bwd_weights_f32": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
-    "dvm_rot6d_bwd_f32": (c_int, [_P, _P, c_int, _P, _P]),
-    "dvm_dg_warp_arap_bwd_f32": (c_int, [_P, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "dvm_chamfer_bwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
-    "dvm_sa_attention_train_fwd_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "dvm_sa_attention_train_fwd_f32": (c_int, [_P, _P, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
-    "dvm_sa_attention_bwd_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "dvm_sa_attention_bwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, _P, _P, _P, c_size_t, _P]),
-    "dvm_pair_set_overlap": (c_int, [c_int]),
-    "dvm_pair_init": (c_int, [_P]),
-    "dvm_uni3fc_fwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "dvm_uni3fc_fwd_f32": (c_int, [_P, _P, c_int, c_int, _P, c_int, c_int, _P, _P, _P, c_size_t, _P]),
-    "dvm_uni3fc_train_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "dvm_uni3fc_train_fwd_f32": (c_int, [_P, _P, c_int, c_int, _P, c_int, c_int, c_float, c_float, c_int, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
-    "dvm_uni3fc_train_running_stats_f32": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_float, _P, c_size_t, _P]),
-    "dvm_bn_act_train_fwd_pm_var_f32": (c_int, [_P, _P, _P, _P, ctypes.c_long, c_int, c_int, c_float, c_float, c_float, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
-    "dvm_bn_pm_groups_workspace_bytes": (c_size_t, [ctypes.c_long, c_int, c_int]),
-    "dvm_bn_act_train_bwd_pm_groups_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, ctypes.c_long, c_int, c_int, c_float, _P, _P, _P, c_int, _P, c_size_t, _P]),
-    "dvm_uni3fc_train_bwd_f32": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P, _P, c_int, c_int, c_int, _P, c_size_t, _P]),
-    # the same calls with the caller's collective for cross-rank statistics (dvm_collective *: passed as a pointer)
-    "dvm_uni3fc_train_fwd_sync_f32": (c_int, [_P, _P, c_int, c_int, _P, c_int, c_int, c_float, c_float, c_int, c_int, _P, _P, _P, _P, _P, c_size_t, _P, _P]),
-    "dvm_uni3fc_train_bwd_sync_f32": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P, _P, c_int, c_int, c_int, _P, c_size_t, _P, _P]),
-    "dvm_bn_pm_sync_bytes": (c_size_t, [c_int, c_int]),
-    "dvm_bn_act_train_fwd_pm_sync_f32": (c_int, [_P, _P, _P, _P, ctypes.c_long, c_int, c_int, c_float, c_float, c_float, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P, _P, _P]),
-    "dvm_bn_act_train_bwd_pm_sync_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, ctypes.c_long, c_int, c_int, c_float, _P, _P, _P, c_int, _P, c_size_t, _P, _P, _P]),
-    "dvm_pos_encoding_sync_f32": (c_int, [_P, c_int, c_int, _P, _P, c_size_t, _P, _P, _P]),
-    "dvm_criterion_train_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
-    "dvm_criterion_train_fwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float, _P, c_int, c_int, _P, _P, _P, _P, c_int,
-                                            c_int, _P, _P, c_size_t, _P]),
-    "dvm_criterion_train_bwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P, c_int, c_int, _P, _P, c_int,
-                                            c_int, _P, _P, c_size_t, _P]),
-    "dvm_criterion_dir_train_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
-    "dvm_criterion_dir_train_fwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, _P, c_int, c_int, _P,
-                                                _P, c_size_t, _P]),
-    "dvm_criterion_dir_train_bwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P, c_int,
-                                                c_int, _P, _P, _P, c_size_t, _P]),
-    "dvm_linear_wgrad_workspace_bytes": (c_size_t, [ctypes.c_long, c_int, c_int]),
-    "dvm_linear_wgrad_ws_f32": (c_int, [_P, _P, ctypes.c_long, c_int, c_int, _P, _P, c_size_t, _P]),
-    "dvm_set_deterministic": (c_int, [c_int]),
-    "dvm_get_deterministic": (c_int, []),
-    "dvm_k1_last_routes": (c_int, [_P]),
-    "dvm_pair_destroy": (c_int, []),
-    "dvm_argmin_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
-    "dvm_argmin_exact_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
-    "dvm_argmin_pair_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
-    "dvm_knn_cdist_workspace_bytes": (c_size_t, [c_int] * 4),
-    "dvm_knn_cdist_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
-    "dvm_knn_neg_workspace_bytes": (c_size_t, [c_int] * 5),
-    "dvm_knn_neg_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
-    "dvm_softcorr_dense_workspace_bytes": (c_size_t, [c_int] * 4),
-    "dvm_softcorr_dense_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P, c_size_t, _P]),
-    "dvm_deformer_mlp_workspace_bytes": (c_size_t, [c_int]),
-    "dvm_deformer_mlp_fwd_f32": (c_int, [_P, c_int] + [_P] * 8 + [_P, _P, c_size_t, _P]),
-    "dvm_pos_encoding_workspace_bytes": (c_size_t, []),
-    "dvm_pos_encoding_f32": (c_int, [_P, c_int, c_int, _P, _P, c_size_t, _P]),
-    "dvm_pos_encoding_minmax_f32": (c_int, [_P, _P, c_int, c_int, _P, _P]),
-    "dvm_bn_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "dvm_bn_act_train_fwd_f32": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_float, c_float, c_float, _P, _P, _P, _P, _P, _P,
-                                         c_size_t, _P]),
-    "dvm_bn_act_train_bwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_float, _P, _P, _P, _P, c_size_t, _P]),
-    "dvm_graph_geodesics_f64": (c_int, [_P, _P, c_int, c_int, _P, _P]),
-    "dvm_proj2img_workspace_bytes": (c_size_t, [c_int]),
-    "dvm_proj2img_f32": (c_int, [_P, c_int, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
-    "dvm_i2p_f32": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P]),
-    "dvm_adaptive_conv_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P]),
-    "dvm_bicubic_resize_pad_f32": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P]),
-    "dvm_jbu_kernel_f32": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
-    "dvm_sa_attention_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "dvm_sa_attention_fwd_f32": (c_int, [_P, _P, c_int, c_int, _P, _P, c_size_t, _P]),
-    "dvm_n2p_attention_fwd_f32": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
-    "dvm_dist_loss_workspace_bytes": (c_size_t, [c_int] * 5),
-    "dvm_dist_loss_fwd_f32": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
-    "dvm_softcorr_apply_f32": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
-    "dvm_fps_f32": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P]),
-    "dvm_dg_build_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "dvm_dg_build_f32": (c_int, [_P, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
-    "dvm_rot6d_f32": (c_int, [_P, c_int, _P, _P]),
-    "dvm_dg_warp_arap_fwd_f32": (c_int, [_P, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "dvm_dg_warp_arap_graph_f32": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "dvm_chamfer_workspace_bytes": (c_size_t, [c_int] * 3),
-    "dvm_chamfer_fwd_f32": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
-    "dvm_deformer_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "dvm_deformer_fwd_f32": (c_int, [_P] * 9 + [c_int] * 6 + [_P] * 10 + [_P, c_int, _P, c_size_t, _P]),
-    "dvm_map_term_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "dvm_map_term_f32": (c_int, [_P] * 6 + [c_int] * 5 + [_P, _P, c_size_t, _P]),
-    "dvm_pair_direction_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "dvm_pair_direction_fwd_f32": (c_int, [_P] * 4 + [c_int] * 3 + [c_float, _P] + [_P] * 10 + [c_int] + [_P] * 4 +
-                                   [_P, c_size_t, _P]),
-    "dvm_pair_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "dvm_pair_fwd_f32": (c_int, [_P] * 4 + [c_int] * 3 + [c_float, _P, _P] + [_P] * 10 + [c_int] + [_P] * 8 +
-                         [_P, c_size_t, _P]),
-    "dvm_pair_fwd_cached_f32": (c_int, [_P] * 4 + [c_int] * 3 + [c_float, _P, _P] + [_P] * 10 + [c_int] + [_P] * 8 +
-                                [_P, c_size_t, c_int, _P]),
-    "dvm_pair_geometry_f32": (c_int, [_P, _P] + [c_int] * 3 + [_P, _P, c_int, _P, c_size_t, _P]),
-}
 
 
 class DvmError(RuntimeError):
     pass
+
+
+_SCALARS = {"int": ctypes.c_int, "long": ctypes.c_long, "unsigned": ctypes.c_uint, "unsigned int": ctypes.c_uint,
+            "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t}
+_DECL = re.compile(r"([\w\s*]+?)\b(dvm_\w+)\s*\(([^()]*)\)")
+
+
+def _ctype(text, param):
+    """The ctypes type of a return type, or of a parameter with or without its name, as the header spells it.  Every pointer
+    parameter is a c_void_p (device pointers, host tables and byref() objects all pass); a type not listed here raises."""
+    if "*" in text:
+        if param:
+            return ctypes.c_void_p
+        if text.split() == ["const", "char", "*"]:
+            return ctypes.c_char_p
+    else:
+        words = [w for w in text.split() if w != "const"]
+        for n in (len(words), len(words) - 1) if param else (len(words),):   # the whole text, then without the parameter's name
+            if " ".join(words[:n]) in _SCALARS:
+                return _SCALARS[" ".join(words[:n])]
+    raise DvmError("include/dvm.h: no ctypes type for the %s `%s`" % ("parameter" if param else "return type", " ".join(text.split())))
+
+
+def parse_header(src):
+    """name -> (restype, [argtypes]) of every `ret dvm_name(args);` in the text of a C header.  Comments, preprocessor lines,
+    typedefs and structs are skipped; any other statement that is not such a declaration raises."""
+    src = re.sub(r"/\*.*?\*/|//[^\n]*", " ", src, flags=re.S)
+    src = re.sub(r"^[ \t]*#.*$", "", src, flags=re.M)
+    src = re.sub(r'extern\s*"C"\s*\{', "", src)
+    src = re.sub(r"\{[^{}]*\}", "", src).replace("}", "")          # struct bodies; the closing brace of extern "C"
+    table = {}
+    for stmt in src.split(";"):
+        stmt = " ".join(stmt.replace("*", " * ").split())
+        if not stmt or stmt.split()[0] in ("typedef", "struct"):
+            continue
+        m = _DECL.fullmatch(stmt)
+        if m is None:
+            raise DvmError("include/dvm.h: cannot read the declaration `%s`" % stmt)
+        ret, name, args = m.groups()
+        args = [] if args.strip() in ("", "void") else args.split(",")
+        table[name] = (_ctype(ret, False), [_ctype(a, True) for a in args])
+    return table
+
+
+def _header_text():
+    try:
+        with open(HEADER) as f:
+            return f.read()
+    except OSError as e:
+        raise DvmError("the C ABI's header was not found at %s (%s): the ctypes prototypes are derived from it" % (HEADER, e))
+
+
+# name -> (restype, [argtypes]): include/dvm.h, read when this module is imported
+SIGNATURES = parse_header(_header_text())
 
 
 def load():

@@ -52,6 +52,11 @@ def _p(t):
     return None if t is None else t.data_ptr()
 
 
+def _new(dev, *shape, dtype=torch.float32):
+    """An uninitialised output tensor on `dev`: fp32, or the int32 of the index outputs."""
+    return torch.empty(shape, dtype=dtype, device=dev)
+
+
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
 
@@ -80,6 +85,22 @@ def scratch(nbytes, device):
     return torch.empty(int(nbytes), dtype=torch.uint8, device=device)
 
 
+def _call(name, *args):
+    """The entry point `name` of the library on torch's current stream: `args` are its arguments in front of the last one, the
+    stream.  A failure raises under `name`."""
+    check(getattr(_lib.load(), name)(*args, _stream()), name)
+
+
+def _call_ws(name, args, dev, tag, size_query, *size_args, null_if_empty=False):
+    """_call for an entry whose arguments end (.., ws, ws_bytes, stream): the size is what `size_query(*size_args)` answers, the
+    buffer workspace(size, dev, tag).  A size of 0 still passes the (256-byte minimum) buffer, except with null_if_empty: those
+    entries read ws == NULL as "no workspace" and must get it."""
+    lib = _lib.load()
+    nb = getattr(lib, size_query)(*size_args)
+    ws = None if null_if_empty and not nb else workspace(nb, dev, tag)
+    check(getattr(lib, name)(*args, _p(ws), nb, _stream()), name)
+
+
 def neg_alpha_f32(alpha):
     """`-alpha * distance`: ATen casts the python/numpy scalar to fp32 (models/loss.py:112)."""
     return float(torch.tensor(-float(alpha), dtype=torch.float32).item())
@@ -89,8 +110,8 @@ def rownorm2(x):
     _need_gpu(x)
     x = _f(x)
     rows, K = x.numel() // x.shape[-1], x.shape[-1]
-    out = torch.empty(x.shape[:-1], dtype=torch.float32, device=x.device)
-    check(_lib.load().dvm_rownorm2_f32(_p(x), rows, K, _p(out), _stream()), "dvm_rownorm2_f32")
+    out = _new(x.device, *x.shape[:-1])
+    _call("dvm_rownorm2_f32", _p(x), rows, K, _p(out))
     return out
 
 
@@ -124,7 +145,7 @@ def linear(x, w, bias=None, res=None, bn=None, slope=1.0, channel_major=False, o
     if Kx != K:
         raise DvmError("linear: x has %d input channels, w expects %d" % (Kx, K))
     if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+        out = _new(x.device, *shape)
     elif tuple(out.shape) != tuple(shape) or not out.is_contiguous() or out.dtype != torch.float32:
         raise DvmError("linear: bad `out`")
     bias = None if bias is None else _f(bias)
@@ -140,15 +161,14 @@ def linear(x, w, bias=None, res=None, bn=None, slope=1.0, channel_major=False, o
         r = _f(r)
         if tuple(r.shape) != tuple(shape):
             raise DvmError("linear: post residual shape %s != output shape %s" % (tuple(r.shape), tuple(shape)))
-        check(_lib.load().dvm_linear_scaled_residual_f32(_p(x), _p(w), B, N, K, Co, 1 if channel_major else 0, _p(bias), float(scale),
-                                                         _p(r), _p(out), _stream()), "dvm_linear_scaled_residual_f32")
-        return out
-    if Cg:
-        check(_lib.load().dvm_linear_prefix_f32(_p(prefix), Cg, _p(x), _p(w), B, N, K, Co, _p(bias), _p(res), _p(al), _p(be),
-                                                float(slope), _p(out), _stream()), "dvm_linear_prefix_f32")
-        return out
-    check(_lib.load().dvm_linear_f32(_p(x), _p(w), B, N, K, Co, 1 if channel_major else 0, _p(bias), _p(res), _p(al), _p(be),
-                                     float(slope), _p(out), _stream()), "dvm_linear_f32")
+        _call("dvm_linear_scaled_residual_f32", _p(x), _p(w), B, N, K, Co, 1 if channel_major else 0, _p(bias), float(scale),
+              _p(r), _p(out))
+    elif Cg:
+        _call("dvm_linear_prefix_f32", _p(prefix), Cg, _p(x), _p(w), B, N, K, Co, _p(bias), _p(res), _p(al), _p(be),
+              float(slope), _p(out))
+    else:
+        _call("dvm_linear_f32", _p(x), _p(w), B, N, K, Co, 1 if channel_major else 0, _p(bias), _p(res), _p(al), _p(be),
+              float(slope), _p(out))
     return out
 
 
@@ -177,23 +197,21 @@ def linear_wgrad(gy, x, out=None):
         dW = out
         if dW.dtype != torch.float32 or not dW.is_contiguous() or dW.numel() != Co * K:
             raise ValueError("linear_wgrad: out must be a contiguous float32 tensor of %d x %d elements" % (Co, K))
-    lib = _lib.load()
-    if lib.dvm_get_deterministic():   # per-chunk partial tiles added in chunk order (needs scratch)
-        nb = lib.dvm_linear_wgrad_workspace_bytes(R, Co, K)
-        ws = workspace(nb, gy.device, "wgrad")
-        check(lib.dvm_linear_wgrad_ws_f32(_p(gy), _p(x), R, Co, K, _p(dW), _p(ws), nb, _stream()), "dvm_linear_wgrad_ws_f32")
+    args = (_p(gy), _p(x), R, Co, K, _p(dW))
+    if _lib.load().dvm_get_deterministic():   # per-chunk partial tiles added in chunk order (needs scratch)
+        _call_ws("dvm_linear_wgrad_ws_f32", args, gy.device, "wgrad", "dvm_linear_wgrad_workspace_bytes", R, Co, K)
     else:
-        check(lib.dvm_linear_wgrad_f32(_p(gy), _p(x), R, Co, K, _p(dW), _stream()), "dvm_linear_wgrad_f32")
+        _call("dvm_linear_wgrad_f32", *args)
     return dW
 
 
 _bn_pm_sizes = {}
 
 
-def _bn_pm_bytes(lib, R, C):
+def _bn_pm_bytes(R, C):
     nb = _bn_pm_sizes.get((R, C))
     if nb is None:
-        nb = _bn_pm_sizes[(R, C)] = lib.dvm_bn_pm_workspace_bytes(R, C)
+        nb = _bn_pm_sizes[(R, C)] = _lib.load().dvm_bn_pm_workspace_bytes(R, C)
     return nb
 
 
@@ -205,13 +223,12 @@ def bn_act_train_fwd_pm(x, res, gamma, beta, eps, slope, momentum, running_mean=
     R = x.numel() // C
     res = None if res is None else _f(res)
     y = torch.empty_like(x)
-    mean = torch.empty(C, dtype=torch.float32, device=x.device)
+    mean = _new(x.device, C)
     invstd = torch.empty_like(mean)
-    lib = _lib.load()
-    nb = _bn_pm_bytes(lib, R, C)
+    nb = _bn_pm_bytes(R, C)
     ws = workspace(nb, x.device, "bn_pm")
-    check(lib.dvm_bn_act_train_fwd_pm_f32(_p(x), _p(res), _p(gamma), _p(beta), R, C, float(eps), float(slope), float(momentum), _p(y), _p(mean),
-                                          _p(invstd), _p(running_mean), _p(running_var), _p(ws), nb, _stream()), "dvm_bn_act_train_fwd_pm_f32")
+    _call("dvm_bn_act_train_fwd_pm_f32", _p(x), _p(res), _p(gamma), _p(beta), R, C, float(eps), float(slope), float(momentum), _p(y),
+          _p(mean), _p(invstd), _p(running_mean), _p(running_var), _p(ws), nb)
     return y, mean, invstd
 
 
@@ -223,18 +240,17 @@ def bn_act_train_bwd_pm(dy, y, x, res, gamma, mean, invstd, slope, grads=None):
     R = x.numel() // C
     dx = torch.empty_like(x)
     if grads is None:
-        dgamma = torch.empty(C, dtype=torch.float32, device=x.device)
+        dgamma = _new(x.device, C)
         dbeta = torch.empty_like(dgamma)
     else:
         dgamma, dbeta = grads
         for t in grads:
             if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != C:
                 raise ValueError("bn_act_train_bwd_pm: grads must be contiguous float32 tensors of %d elements" % C)
-    lib = _lib.load()
-    nb = _bn_pm_bytes(lib, R, C)
+    nb = _bn_pm_bytes(R, C)
     ws = workspace(nb, x.device, "bn_pm")
-    check(lib.dvm_bn_act_train_bwd_pm_f32(_p(dy), _p(y), _p(x), _p(res), _p(gamma), _p(mean), _p(invstd), R, C, float(slope), _p(dx), _p(dgamma),
-                                          _p(dbeta), int(grads is not None), _p(ws), nb, _stream()), "dvm_bn_act_train_bwd_pm_f32")
+    _call("dvm_bn_act_train_bwd_pm_f32", _p(dy), _p(y), _p(x), _p(res), _p(gamma), _p(mean), _p(invstd), R, C, float(slope), _p(dx),
+          _p(dgamma), _p(dbeta), int(grads is not None), _p(ws), nb)
     return dx, dgamma, dbeta
 
 
@@ -244,15 +260,13 @@ def softcorr(f1, f2, alpha, topk=10, variant=0, stats=True):
     f1, f2 = _f(f1), _f(f2)
     B, N, d = f1.shape
     M = f2.shape[1]
-    lib = _lib.load()
-    val = torch.empty(B, N, topk, dtype=torch.float32, device=f1.device)
-    idx = torch.empty(B, N, topk, dtype=torch.int32, device=f1.device)
-    smax = torch.empty(B, N, dtype=torch.float32, device=f1.device) if stats else None
-    ssum = torch.empty(B, N, dtype=torch.float32, device=f1.device) if stats else None
-    nb = lib.dvm_softcorr_workspace_bytes(B, N, M, d)
-    ws = workspace(nb, f1.device, "softcorr")
-    check(lib.dvm_softcorr_fwd_f32(_p(f1), _p(f2), B, N, M, d, neg_alpha_f32(alpha), topk, _p(val), _p(idx), _p(smax),
-                                   _p(ssum), variant, _p(ws), nb, _stream()), "dvm_softcorr_fwd_f32")
+    dev = f1.device
+    val = _new(dev, B, N, topk)
+    idx = _new(dev, B, N, topk, dtype=torch.int32)
+    smax = _new(dev, B, N) if stats else None
+    ssum = _new(dev, B, N) if stats else None
+    _call_ws("dvm_softcorr_fwd_f32", (_p(f1), _p(f2), B, N, M, d, neg_alpha_f32(alpha), topk, _p(val), _p(idx), _p(smax), _p(ssum),
+                                      variant), dev, "softcorr", "dvm_softcorr_workspace_bytes", B, N, M, d)
     return val, idx, smax, ssum
 
 
@@ -269,18 +283,14 @@ def sinkhorn(f1, f2, alpha, n_iter, topk=10, variant=0, potentials=False):
     f1, f2 = _f(f1), _f(f2)
     B, N, d = f1.shape
     M = f2.shape[1]
-    lib = _lib.load()
     dev = f1.device
-    val = torch.empty(B, N, topk, dtype=torch.float32, device=dev)
-    idx = torch.empty(B, N, topk, dtype=torch.int32, device=dev)
-    lmax = torch.empty(B, N, dtype=torch.float32, device=dev)
-    lsum = torch.empty(B, N, dtype=torch.float32, device=dev)
-    u = torch.empty(B, N, dtype=torch.float32, device=dev) if potentials else None
-    v = torch.empty(B, M, dtype=torch.float32, device=dev) if potentials else None
-    nb = lib.dvm_sinkhorn_workspace_bytes(B, N, M, d)
-    ws = workspace(nb, dev, "sinkhorn")
-    check(lib.dvm_sinkhorn_fwd_f32(_p(f1), _p(f2), B, N, M, d, neg_alpha_f32(alpha), int(n_iter), topk, _p(val), _p(idx), _p(lmax),
-                                   _p(lsum), _p(u), _p(v), variant, _p(ws), nb, _stream()), "dvm_sinkhorn_fwd_f32")
+    val = _new(dev, B, N, topk)
+    idx = _new(dev, B, N, topk, dtype=torch.int32)
+    lmax, lsum = _new(dev, B, N), _new(dev, B, N)
+    u = _new(dev, B, N) if potentials else None
+    v = _new(dev, B, M) if potentials else None
+    _call_ws("dvm_sinkhorn_fwd_f32", (_p(f1), _p(f2), B, N, M, d, neg_alpha_f32(alpha), int(n_iter), topk, _p(val), _p(idx), _p(lmax),
+                                      _p(lsum), _p(u), _p(v), variant), dev, "sinkhorn", "dvm_sinkhorn_workspace_bytes", B, N, M, d)
     return (val, idx, lmax, lsum, u, v) if potentials else (val, idx, lmax, lsum)
 
 
@@ -294,18 +304,15 @@ def sinkhorn_hist(f1, f2, alpha, n_iter, topk=10, variant=0):
     B, N, d = f1.shape
     M = f2.shape[1]
     n_iter = int(n_iter)
-    lib = _lib.load()
     dev = f1.device
-    val = torch.empty(B, N, topk, dtype=torch.float32, device=dev)
-    idx = torch.empty(B, N, topk, dtype=torch.int32, device=dev)
-    lmax = torch.empty(B, N, dtype=torch.float32, device=dev)
-    lsum = torch.empty(B, N, dtype=torch.float32, device=dev)
-    u_hist = torch.empty(B, max(n_iter, 0) + 1, N, dtype=torch.float32, device=dev)
-    v_hist = torch.empty(B, max(n_iter, 0) + 1, M, dtype=torch.float32, device=dev)
-    nb = lib.dvm_sinkhorn_hist_workspace_bytes(B, N, M, d)
-    ws = workspace(nb, dev, "sinkhorn_hist")
-    check(lib.dvm_sinkhorn_fwd_hist_f32(_p(f1), _p(f2), B, N, M, d, neg_alpha_f32(alpha), n_iter, topk, _p(val), _p(idx), _p(lmax),
-                                        _p(lsum), _p(u_hist), _p(v_hist), variant, _p(ws), nb, _stream()), "dvm_sinkhorn_fwd_hist_f32")
+    val = _new(dev, B, N, topk)
+    idx = _new(dev, B, N, topk, dtype=torch.int32)
+    lmax, lsum = _new(dev, B, N), _new(dev, B, N)
+    u_hist = _new(dev, B, max(n_iter, 0) + 1, N)
+    v_hist = _new(dev, B, max(n_iter, 0) + 1, M)
+    _call_ws("dvm_sinkhorn_fwd_hist_f32", (_p(f1), _p(f2), B, N, M, d, neg_alpha_f32(alpha), n_iter, topk, _p(val), _p(idx), _p(lmax),
+                                           _p(lsum), _p(u_hist), _p(v_hist), variant),
+             dev, "sinkhorn_hist", "dvm_sinkhorn_hist_workspace_bytes", B, N, M, d)
     return val, idx, lmax, lsum, u_hist, v_hist
 
 
@@ -314,7 +321,7 @@ def sinkhorn_bwd(f1, f2, alpha, n_iter, val, idx, u_hist, v_hist, gval, variant=
     val / idx / u_hist / v_hist are sinkhorn_hist's outputs for the same f1, f2, alpha, n_iter.  No float atomics: two calls give
     the same bits."""
     _need_gpu(f1, f2, gval)
-    f1, f2, gval, val, u_hist, v_hist = _f(f1), _f(f2), _f(gval), _f(val), _f(u_hist), _f(v_hist)
+    f1, f2, gval, val, idx, u_hist, v_hist = _f(f1), _f(f2), _f(gval), _f(val), _i(idx), _f(u_hist), _f(v_hist)
     B, N, d = f1.shape
     M = f2.shape[1]
     n_iter = int(n_iter)
@@ -322,13 +329,10 @@ def sinkhorn_bwd(f1, f2, alpha, n_iter, val, idx, u_hist, v_hist, gval, variant=
     if n_iter >= 0 and (tuple(u_hist.shape) != (B, n_iter + 1, N) or tuple(v_hist.shape) != (B, n_iter + 1, M)):
         raise ValueError("sinkhorn_bwd: u_hist / v_hist must be (B, n_iter + 1, N) / (B, n_iter + 1, M), got %s / %s"
                          % (tuple(u_hist.shape), tuple(v_hist.shape)))
-    lib = _lib.load()
     df1, df2 = torch.empty_like(f1), torch.empty_like(f2)
-    nb = lib.dvm_sinkhorn_bwd_workspace_bytes(B, N, M, d, n_iter)
-    ws = workspace(nb, f1.device, "sinkhorn_bwd")
-    check(lib.dvm_sinkhorn_bwd_f32(_p(f1), _p(f2), B, N, M, d, neg_alpha_f32(alpha), n_iter, topk, _p(val), _p(idx.contiguous()),
-                                   _p(u_hist), _p(v_hist), _p(gval), _p(df1), _p(df2), variant, _p(ws), nb, _stream()),
-          "dvm_sinkhorn_bwd_f32")
+    _call_ws("dvm_sinkhorn_bwd_f32", (_p(f1), _p(f2), B, N, M, d, neg_alpha_f32(alpha), n_iter, topk, _p(val), _p(idx), _p(u_hist),
+                                      _p(v_hist), _p(gval), _p(df1), _p(df2), variant),
+             f1.device, "sinkhorn_bwd", "dvm_sinkhorn_bwd_workspace_bytes", B, N, M, d, n_iter)
     return df1, df2
 
 
@@ -378,17 +382,14 @@ def sinkhorn_unbalanced(f1, f2, alpha, n_iter, tau=(1.0, 1.0), log_a=None, log_b
     M = f2.shape[1]
     tr, tc = tau_pair(tau)
     log_a, log_b = _log_weight(log_a, B, N, "log_a"), _log_weight(log_b, B, M, "log_b")
-    lib = _lib.load()
     dev = f1.device
-    val = torch.empty(B, N, topk, dtype=torch.float32, device=dev)
-    idx = torch.empty(B, N, topk, dtype=torch.int32, device=dev)
-    lmax, lsum, lmass, u = (torch.empty(B, N, dtype=torch.float32, device=dev) for _ in range(4))
-    v = torch.empty(B, M, dtype=torch.float32, device=dev)
-    nb = lib.dvm_sinkhorn_ub_workspace_bytes(B, N, M, d)
-    ws = workspace(nb, dev, "sinkhorn_ub")
-    check(lib.dvm_sinkhorn_ub_fwd_f32(_p(f1), _p(f2), B, N, M, d, neg_alpha_f32(alpha), int(n_iter), topk, tr, tc, _p(log_a), _p(log_b),
-                                      _p(val), _p(idx), _p(lmax), _p(lsum), _p(lmass), _p(u), _p(v), variant, _p(ws), nb, _stream()),
-          "dvm_sinkhorn_ub_fwd_f32")
+    val = _new(dev, B, N, topk)
+    idx = _new(dev, B, N, topk, dtype=torch.int32)
+    lmax, lsum, lmass, u = (_new(dev, B, N) for _ in range(4))
+    v = _new(dev, B, M)
+    _call_ws("dvm_sinkhorn_ub_fwd_f32", (_p(f1), _p(f2), B, N, M, d, neg_alpha_f32(alpha), int(n_iter), topk, tr, tc, _p(log_a), _p(log_b),
+                                         _p(val), _p(idx), _p(lmax), _p(lsum), _p(lmass), _p(u), _p(v), variant),
+             dev, "sinkhorn_ub", "dvm_sinkhorn_ub_workspace_bytes", B, N, M, d)
     return val, idx, lmax, lsum, lmass, u, v
 
 
@@ -404,18 +405,15 @@ def sinkhorn_unbalanced_hist(f1, f2, alpha, n_iter, tau=(1.0, 1.0), log_a=None, 
     n_iter = int(n_iter)
     tr, tc = tau_pair(tau)
     log_a, log_b = _log_weight(log_a, B, N, "log_a"), _log_weight(log_b, B, M, "log_b")
-    lib = _lib.load()
     dev = f1.device
-    val = torch.empty(B, N, topk, dtype=torch.float32, device=dev)
-    idx = torch.empty(B, N, topk, dtype=torch.int32, device=dev)
-    lmax, lsum, lmass = (torch.empty(B, N, dtype=torch.float32, device=dev) for _ in range(3))
-    rn_hist = torch.empty(B, max(n_iter, 0) + 1, N, dtype=torch.float32, device=dev)
-    cn_hist = torch.empty(B, max(n_iter, 0) + 1, M, dtype=torch.float32, device=dev)
-    nb = lib.dvm_sinkhorn_ub_hist_workspace_bytes(B, N, M, d)
-    ws = workspace(nb, dev, "sinkhorn_ub_hist")
-    check(lib.dvm_sinkhorn_ub_fwd_hist_f32(_p(f1), _p(f2), B, N, M, d, neg_alpha_f32(alpha), n_iter, topk, tr, tc, _p(log_a), _p(log_b),
-                                           _p(val), _p(idx), _p(lmax), _p(lsum), _p(lmass), _p(rn_hist), _p(cn_hist), variant, _p(ws), nb,
-                                           _stream()), "dvm_sinkhorn_ub_fwd_hist_f32")
+    val = _new(dev, B, N, topk)
+    idx = _new(dev, B, N, topk, dtype=torch.int32)
+    lmax, lsum, lmass = (_new(dev, B, N) for _ in range(3))
+    rn_hist = _new(dev, B, max(n_iter, 0) + 1, N)
+    cn_hist = _new(dev, B, max(n_iter, 0) + 1, M)
+    _call_ws("dvm_sinkhorn_ub_fwd_hist_f32", (_p(f1), _p(f2), B, N, M, d, neg_alpha_f32(alpha), n_iter, topk, tr, tc, _p(log_a), _p(log_b),
+                                              _p(val), _p(idx), _p(lmax), _p(lsum), _p(lmass), _p(rn_hist), _p(cn_hist), variant),
+             dev, "sinkhorn_ub_hist", "dvm_sinkhorn_ub_hist_workspace_bytes", B, N, M, d)
     return val, idx, lmax, lsum, lmass, rn_hist, cn_hist
 
 
@@ -425,6 +423,7 @@ def sinkhorn_unbalanced_bwd(f1, f2, alpha, n_iter, tau, log_a, log_b, val, idx, 
     cn_hist are sinkhorn_unbalanced_hist's outputs for the same inputs.  No float atomics: two calls give the same bits."""
     _need_gpu(f1, f2, gval, glmass, log_a, log_b)
     f1, f2, gval, val, lmass, rn_hist, cn_hist = _f(f1), _f(f2), _f(gval), _f(val), _f(lmass), _f(rn_hist), _f(cn_hist)
+    idx = _i(idx)
     B, N, d = f1.shape
     M = f2.shape[1]
     n_iter = int(n_iter)
@@ -435,15 +434,12 @@ def sinkhorn_unbalanced_bwd(f1, f2, alpha, n_iter, tau, log_a, log_b, val, idx, 
     if n_iter >= 0 and (tuple(rn_hist.shape) != (B, n_iter + 1, N) or tuple(cn_hist.shape) != (B, n_iter + 1, M)):
         raise ValueError("sinkhorn_unbalanced_bwd: rn_hist / cn_hist must be (B, n_iter + 1, N) / (B, n_iter + 1, M), got %s / %s"
                          % (tuple(rn_hist.shape), tuple(cn_hist.shape)))
-    lib = _lib.load()
     df1, df2 = torch.empty_like(f1), torch.empty_like(f2)
-    dla = torch.empty(B, N, dtype=torch.float32, device=f1.device)
-    dlb = torch.empty(B, M, dtype=torch.float32, device=f1.device)
-    nb = lib.dvm_sinkhorn_ub_bwd_workspace_bytes(B, N, M, d, n_iter)
-    ws = workspace(nb, f1.device, "sinkhorn_ub_bwd")
-    check(lib.dvm_sinkhorn_ub_bwd_f32(_p(f1), _p(f2), B, N, M, d, neg_alpha_f32(alpha), n_iter, topk, tr, tc, _p(log_a), _p(log_b), _p(val),
-                                      _p(idx.contiguous()), _p(lmass), _p(rn_hist), _p(cn_hist), _p(gval), _p(glmass), _p(df1), _p(df2),
-                                      _p(dla), _p(dlb), variant, _p(ws), nb, _stream()), "dvm_sinkhorn_ub_bwd_f32")
+    dla, dlb = _new(f1.device, B, N), _new(f1.device, B, M)
+    _call_ws("dvm_sinkhorn_ub_bwd_f32", (_p(f1), _p(f2), B, N, M, d, neg_alpha_f32(alpha), n_iter, topk, tr, tc, _p(log_a), _p(log_b), _p(val),
+                                         _p(idx), _p(lmass), _p(rn_hist), _p(cn_hist), _p(gval), _p(glmass), _p(df1), _p(df2), _p(dla),
+                                         _p(dlb), variant),
+             f1.device, "sinkhorn_ub_bwd", "dvm_sinkhorn_ub_bwd_workspace_bytes", B, N, M, d, n_iter)
     return df1, df2, dla, dlb
 
 
@@ -452,45 +448,38 @@ def softcorr_bwd(f1, f2, alpha, val, idx, smax, ssum, gval, variant=0):
     the same f1, f2, alpha: a row's in-range columns must be distinct (repeated slots carry val 0, as softcorr writes them at
     M < topk), since each slot's entry takes both terms of dL/dS."""
     _need_gpu(f1, f2, gval)
-    f1, f2, gval, val = _f(f1), _f(f2), _f(gval), _f(val)
+    f1, f2, gval, val, idx = _f(f1), _f(f2), _f(gval), _f(val), _i(idx)
     B, N, d = f1.shape
     M = f2.shape[1]
     topk = val.shape[-1]
-    lib = _lib.load()
     df1, df2 = torch.empty_like(f1), torch.empty_like(f2)
-    nb = lib.dvm_softcorr_bwd_workspace_bytes(B, N, M, d)
-    ws = workspace(nb, f1.device, "softcorr_bwd")
-    check(lib.dvm_softcorr_bwd_f32(_p(f1), _p(f2), B, N, M, d, neg_alpha_f32(alpha), topk, _p(val), _p(idx.contiguous()),
-                                   _p(smax), _p(ssum), _p(gval), _p(df1), _p(df2), variant, _p(ws), nb, _stream()),
-          "dvm_softcorr_bwd_f32")
+    _call_ws("dvm_softcorr_bwd_f32", (_p(f1), _p(f2), B, N, M, d, neg_alpha_f32(alpha), topk, _p(val), _p(idx), _p(smax), _p(ssum),
+                                      _p(gval), _p(df1), _p(df2), variant),
+             f1.device, "softcorr_bwd", "dvm_softcorr_bwd_workspace_bytes", B, N, M, d)
     return df1, df2
 
 
 def n2p_core_fwd(qkv, idx, heads=4):
     """qkv (B,N,3C), idx (B,N,K) int32 -> out (B,N,C), attn (B,N,K,heads)."""
     _need_gpu(qkv, idx)
-    qkv = _f(qkv)
+    qkv, idx = _f(qkv), _i(idx)
     B, N, C3 = qkv.shape
     C, K = C3 // 3, idx.shape[-1]
-    out = torch.empty(B, N, C, dtype=torch.float32, device=qkv.device)
-    attn = torch.empty(B, N, K, heads, dtype=torch.float32, device=qkv.device)
-    check(_lib.load().dvm_n2p_core_fwd_f32(_p(qkv), _p(idx.contiguous()), B, N, C, K, heads, _p(out), _p(attn), _stream()),
-          "dvm_n2p_core_fwd_f32")
+    out = _new(qkv.device, B, N, C)
+    attn = _new(qkv.device, B, N, K, heads)
+    _call("dvm_n2p_core_fwd_f32", _p(qkv), _p(idx), B, N, C, K, heads, _p(out), _p(attn))
     return out, attn
 
 
 def n2p_core_bwd(qkv, idx, attn, gout, heads=4):
     """-> d_qkv (B,N,3C)."""
     _need_gpu(qkv, idx, attn, gout)
-    qkv, gout = _f(qkv), _f(gout)
+    qkv, idx, gout = _f(qkv), _i(idx), _f(gout)
     B, N, C3 = qkv.shape
     C, K = C3 // 3, idx.shape[-1]
     dqkv = torch.empty_like(qkv)
-    lib = _lib.load()
-    nb = lib.dvm_n2p_core_bwd_workspace_bytes(B, N, K)
-    ws = workspace(nb, qkv.device, "n2p_bwd")
-    check(lib.dvm_n2p_core_bwd_f32(_p(qkv), _p(idx.contiguous()), _p(attn), _p(gout), B, N, C, K, heads, _p(dqkv), _p(ws), nb,
-                                   _stream()), "dvm_n2p_core_bwd_f32")
+    _call_ws("dvm_n2p_core_bwd_f32", (_p(qkv), _p(idx), _p(attn), _p(gout), B, N, C, K, heads, _p(dqkv)),
+             qkv.device, "n2p_bwd", "dvm_n2p_core_bwd_workspace_bytes", B, N, K)
     return dqkv
 
 
@@ -501,13 +490,13 @@ def argmin_exact(f1, f2, want_dist=False, screen=True):
     f1, f2 = _f(f1), _f(f2)
     B, N, d = f1.shape
     M = f2.shape[1]
-    lib = _lib.load()
-    T = torch.empty(B, N, dtype=torch.int32, device=f1.device)
-    dm = torch.empty(B, N, dtype=torch.float32, device=f1.device) if want_dist else None
-    nb = lib.dvm_argmin_workspace_bytes(B, N, M, d, 0) if screen else 0
-    ws = workspace(nb, f1.device, "argmin") if nb else None
-    check(lib.dvm_argmin_exact_f32(_p(f1), _p(f2), B, N, M, d, _p(T), _p(dm), _p(ws) if nb else None, nb, _stream()),
-          "dvm_argmin_exact_f32")
+    T = _new(f1.device, B, N, dtype=torch.int32)
+    dm = _new(f1.device, B, N) if want_dist else None
+    args = (_p(f1), _p(f2), B, N, M, d, _p(T), _p(dm))
+    if screen:
+        _call_ws("dvm_argmin_exact_f32", args, f1.device, "argmin", "dvm_argmin_workspace_bytes", B, N, M, d, 0, null_if_empty=True)
+    else:
+        _call("dvm_argmin_exact_f32", *args, None, 0)   # no workspace: every column
     return (T, dm) if want_dist else T
 
 
@@ -517,13 +506,10 @@ def argmin_pair(f1, f2):
     f1, f2 = _f(f1), _f(f2)
     B, N, d = f1.shape
     M = f2.shape[1]
-    lib = _lib.load()
-    T12 = torch.empty(B, N, dtype=torch.int32, device=f1.device)
-    T21 = torch.empty(B, M, dtype=torch.int32, device=f1.device)
-    nb = lib.dvm_argmin_workspace_bytes(B, N, M, d, 1)
-    ws = workspace(nb, f1.device, "argmin") if nb else None
-    check(lib.dvm_argmin_pair_f32(_p(f1), _p(f2), B, N, M, d, _p(T12), _p(T21), None, None, _p(ws) if nb else None, nb, _stream()),
-          "dvm_argmin_pair_f32")
+    T12 = _new(f1.device, B, N, dtype=torch.int32)
+    T21 = _new(f1.device, B, M, dtype=torch.int32)
+    _call_ws("dvm_argmin_pair_f32", (_p(f1), _p(f2), B, N, M, d, _p(T12), _p(T21), None, None),
+             f1.device, "argmin", "dvm_argmin_workspace_bytes", B, N, M, d, 1, null_if_empty=True)
     return T12, T21
 
 
@@ -532,11 +518,8 @@ def knn_cdist(x, y, k):
     x, y = _f(x), _f(y)
     B, N, C = x.shape
     M = y.shape[1]
-    idx = torch.empty(B, N, k, dtype=torch.int32, device=x.device)
-    lib = _lib.load()
-    nb = lib.dvm_knn_cdist_workspace_bytes(B, N, M, C)
-    ws = workspace(nb, x.device, "knn_cdist")
-    check(lib.dvm_knn_cdist_f32(_p(x), _p(y), B, N, M, C, k, _p(idx), _p(ws), nb, _stream()), "dvm_knn_cdist_f32")
+    idx = _new(x.device, B, N, k, dtype=torch.int32)
+    _call_ws("dvm_knn_cdist_f32", (_p(x), _p(y), B, N, M, C, k, _p(idx)), x.device, "knn_cdist", "dvm_knn_cdist_workspace_bytes", B, N, M, C)
     return idx
 
 
@@ -545,9 +528,8 @@ def apply(pi_val, pi_idx, V):
     pi_val, pi_idx, V = _f(pi_val), _i(pi_idx), _f(V)
     B, N, topk = pi_val.shape
     M, C = V.shape[1], V.shape[2]
-    out = torch.empty(B, N, C, dtype=torch.float32, device=V.device)
-    check(_lib.load().dvm_softcorr_apply_f32(_p(pi_val), _p(pi_idx), _p(V), B, N, M, topk, C, _p(out), _stream()),
-          "dvm_softcorr_apply_f32")
+    out = _new(V.device, B, N, C)
+    _call("dvm_softcorr_apply_f32", _p(pi_val), _p(pi_idx), _p(V), B, N, M, topk, C, _p(out))
     return out
 
 
@@ -559,11 +541,12 @@ def apply_bwd(pi_val, pi_idx, V, gout, atomics=False):
     M, C = V.shape[1], V.shape[2]
     dval = torch.empty_like(pi_val)
     dV = torch.empty_like(V)
-    lib = _lib.load()
-    nb = 0 if atomics else lib.dvm_softcorr_apply_bwd_workspace_bytes(B, N, M, topk)
-    ws = workspace(nb, V.device, "apply_bwd") if nb else None
-    check(lib.dvm_softcorr_apply_bwd_f32(_p(pi_val), _p(pi_idx), _p(V), _p(gout), B, N, M, topk, C, _p(dval), _p(dV),
-                                         _p(ws) if nb else None, nb, _stream()), "dvm_softcorr_apply_bwd_f32")
+    args = (_p(pi_val), _p(pi_idx), _p(V), _p(gout), B, N, M, topk, C, _p(dval), _p(dV))
+    if atomics:
+        _call("dvm_softcorr_apply_bwd_f32", *args, None, 0)
+    else:
+        _call_ws("dvm_softcorr_apply_bwd_f32", args, V.device, "apply_bwd", "dvm_softcorr_apply_bwd_workspace_bytes", B, N, M, topk,
+                 null_if_empty=True)
     return dval, dV
 
 
@@ -571,8 +554,8 @@ def fps(xyz, npoint, start):
     _need_gpu(xyz, start)
     xyz, start = _f(xyz), _i(start)
     B, N, _ = xyz.shape
-    out = torch.empty(B, npoint, dtype=torch.int32, device=xyz.device)
-    check(_lib.load().dvm_fps_f32(_p(xyz), B, N, npoint, _p(start), _p(out), _stream()), "dvm_fps_f32")
+    out = _new(xyz.device, B, npoint, dtype=torch.int32)
+    _call("dvm_fps_f32", _p(xyz), B, N, npoint, _p(start), _p(out))
     return out
 
 
@@ -583,18 +566,14 @@ def dg_build(xyz, start):
     B, N, _ = xyz.shape
     Nn = N // 2
     dev = xyz.device
-    lib = _lib.load()
-    out = dict(nodes_idx=torch.empty(B, Nn, dtype=torch.int32, device=dev),
-               one_ring=torch.empty(B, Nn, 9, dtype=torch.int32, device=dev),
-               infl_idx=torch.empty(B, N, 3, dtype=torch.int32, device=dev),
-               dists=torch.empty(B, N, 3, dtype=torch.float32, device=dev),
-               weights=torch.empty(B, N, 3, dtype=torch.float32, device=dev),
-               sigma=torch.empty(B, dtype=torch.float64, device=dev))
-    nb = lib.dvm_dg_build_workspace_bytes(B, N)
-    ws = workspace(nb, dev, "dg_build")
-    check(lib.dvm_dg_build_f32(_p(xyz), B, N, _p(start), _p(out["nodes_idx"]), _p(out["one_ring"]), _p(out["infl_idx"]),
-                               _p(out["dists"]), _p(out["weights"]), _p(out["sigma"]), _p(ws), nb, _stream()),
-          "dvm_dg_build_f32")
+    out = dict(nodes_idx=_new(dev, B, Nn, dtype=torch.int32),
+               one_ring=_new(dev, B, Nn, 9, dtype=torch.int32),
+               infl_idx=_new(dev, B, N, 3, dtype=torch.int32),
+               dists=_new(dev, B, N, 3),
+               weights=_new(dev, B, N, 3),
+               sigma=_new(dev, B, dtype=torch.float64))
+    _call_ws("dvm_dg_build_f32", (_p(xyz), B, N, _p(start), _p(out["nodes_idx"]), _p(out["one_ring"]), _p(out["infl_idx"]),
+                                  _p(out["dists"]), _p(out["weights"]), _p(out["sigma"])), dev, "dg_build", "dvm_dg_build_workspace_bytes", B, N)
     return out
 
 
@@ -603,8 +582,8 @@ def rot6d(d6):
     _need_gpu(d6)
     d6 = _f(d6)
     rows = d6.numel() // 6
-    R = torch.empty(*d6.shape[:-1], 3, 3, dtype=torch.float32, device=d6.device)
-    check(_lib.load().dvm_rot6d_f32(_p(d6), rows, _p(R), _stream()), "dvm_rot6d_f32")
+    R = _new(d6.device, *d6.shape[:-1], 3, 3)
+    _call("dvm_rot6d_f32", _p(d6), rows, _p(R))
     return R
 
 
@@ -612,7 +591,7 @@ def rot6d_bwd(d6, gR):
     _need_gpu(d6, gR)
     d6, gR = _f(d6), _f(gR)
     out = torch.empty_like(d6)
-    check(_lib.load().dvm_rot6d_bwd_f32(_p(d6), _p(gR), d6.numel() // 6, _p(out), _stream()), "dvm_rot6d_bwd_f32")
+    _call("dvm_rot6d_bwd_f32", _p(d6), _p(gR), d6.numel() // 6, _p(out))
     return out
 
 
@@ -622,9 +601,8 @@ def dg_warp_arap_bwd(xyz, g, R, T, gw, ga):
     xyz, R, T, gw, ga = _f(xyz), _f(R), _f(T), _f(gw), _f(ga)
     B, N, _ = xyz.shape
     dR, dT = torch.empty_like(R), torch.empty_like(T)
-    check(_lib.load().dvm_dg_warp_arap_bwd_f32(_p(xyz), B, N, _p(_i(g["nodes_idx"])), _p(_i(g["one_ring"])),
-                                               _p(_i(g["infl_idx"])), _p(_f(g["weights"])), _p(R), _p(T), _p(gw), _p(ga),
-                                               _p(dR), _p(dT), _stream()), "dvm_dg_warp_arap_bwd_f32")
+    _call("dvm_dg_warp_arap_bwd_f32", _p(xyz), B, N, _p(_i(g["nodes_idx"])), _p(_i(g["one_ring"])), _p(_i(g["infl_idx"])),
+          _p(_f(g["weights"])), _p(R), _p(T), _p(gw), _p(ga), _p(dR), _p(dT))
     return dR, dT
 
 
@@ -634,8 +612,7 @@ def chamfer_bwd(a, b, i1, i2, g1, g2):
     B, N, _ = a.shape
     M = b.shape[1]
     da, db = torch.empty_like(a), torch.empty_like(b)
-    check(_lib.load().dvm_chamfer_bwd_f32(_p(a), _p(b), _p(_i(i1)), _p(_i(i2)), _p(g1), _p(g2), B, N, M, _p(da), _p(db),
-                                          _stream()), "dvm_chamfer_bwd_f32")
+    _call("dvm_chamfer_bwd_f32", _p(a), _p(b), _p(_i(i1)), _p(_i(i2)), _p(g1), _p(g2), B, N, M, _p(da), _p(db))
     return da, db
 
 
@@ -645,12 +622,9 @@ def dg_warp_arap(xyz, g, R, T):
     xyz, R, T = _f(xyz), _f(R), _f(T)
     B, N, _ = xyz.shape
     dev = xyz.device
-    warped = torch.empty(B, N, 3, dtype=torch.float32, device=dev)
-    arap = torch.empty(B, dtype=torch.float32, device=dev)
-    sr = torch.empty(B, dtype=torch.float32, device=dev)
-    check(_lib.load().dvm_dg_warp_arap_fwd_f32(_p(xyz), B, N, _p(_i(g["nodes_idx"])), _p(_i(g["one_ring"])),
-                                               _p(_i(g["infl_idx"])), _p(_f(g["weights"])), _p(R), _p(T), _p(warped),
-                                               _p(arap), _p(sr), _stream()), "dvm_dg_warp_arap_fwd_f32")
+    warped, arap, sr = _new(dev, B, N, 3), _new(dev, B), _new(dev, B)
+    _call("dvm_dg_warp_arap_fwd_f32", _p(xyz), B, N, _p(_i(g["nodes_idx"])), _p(_i(g["one_ring"])), _p(_i(g["infl_idx"])),
+          _p(_f(g["weights"])), _p(R), _p(T), _p(warped), _p(arap), _p(sr))
     return warped, arap, sr
 
 
@@ -663,12 +637,9 @@ def dg_warp_arap_graph(xyz, g, R, T):
     nodes, ring = _i(g["nodes_idx"]), _i(g["one_ring"])
     Nn, K = nodes.shape[1], ring.shape[2]
     dev = xyz.device
-    warped = torch.empty(B, N, 3, dtype=torch.float32, device=dev)
-    arap = torch.empty(B, dtype=torch.float32, device=dev)
-    sr = torch.empty(B, dtype=torch.float32, device=dev)
-    check(_lib.load().dvm_dg_warp_arap_graph_f32(_p(xyz), B, N, Nn, K, _p(nodes), _p(ring), _p(_i(g["infl_idx"])),
-                                                 _p(_f(g["weights"])), _p(R), _p(T), _p(warped), _p(arap), _p(sr), _stream()),
-          "dvm_dg_warp_arap_graph_f32")
+    warped, arap, sr = _new(dev, B, N, 3), _new(dev, B), _new(dev, B)
+    _call("dvm_dg_warp_arap_graph_f32", _p(xyz), B, N, Nn, K, _p(nodes), _p(ring), _p(_i(g["infl_idx"])), _p(_f(g["weights"])),
+          _p(R), _p(T), _p(warped), _p(arap), _p(sr))
     return warped, arap, sr
 
 
@@ -678,15 +649,10 @@ def chamfer(a, b, want_idx=True):
     B, N, _ = a.shape
     M = b.shape[1]
     dev = a.device
-    d1 = torch.empty(B, N, dtype=torch.float32, device=dev)
-    d2 = torch.empty(B, M, dtype=torch.float32, device=dev)
-    i1 = torch.empty(B, N, dtype=torch.int32, device=dev) if want_idx else None
-    i2 = torch.empty(B, M, dtype=torch.int32, device=dev) if want_idx else None
-    lib = _lib.load()
-    nb = lib.dvm_chamfer_workspace_bytes(B, N, M)
-    ws = workspace(nb, dev, "chamfer")
-    check(lib.dvm_chamfer_fwd_f32(_p(a), _p(b), B, N, M, _p(d1), _p(d2), _p(i1), _p(i2), _p(ws), nb, _stream()),
-          "dvm_chamfer_fwd_f32")
+    d1, d2 = _new(dev, B, N), _new(dev, B, M)
+    i1 = _new(dev, B, N, dtype=torch.int32) if want_idx else None
+    i2 = _new(dev, B, M, dtype=torch.int32) if want_idx else None
+    _call_ws("dvm_chamfer_fwd_f32", (_p(a), _p(b), B, N, M, _p(d1), _p(d2), _p(i1), _p(i2)), dev, "chamfer", "dvm_chamfer_workspace_bytes", B, N, M)
     return d1, d2, i1, i2
 
 
@@ -712,13 +678,10 @@ def deformer(wl, feat1, feat2, verts1, verts12, idx11, idx22, pi_val, pi_idx, fp
     B, N, _ = feat1.shape
     M = feat2.shape[1]
     Nn, k, topk = fps1.shape[1], idx11.shape[2], pi_val.shape[2]
-    lib = _lib.load()
-    out = torch.empty(B, Nn, 9, dtype=torch.float32, device=feat1.device)
-    nb = lib.dvm_deformer_workspace_bytes(B, N, M, Nn)
-    ws = workspace(nb, feat1.device, "deformer")
-    check(lib.dvm_deformer_fwd_f32(_p(feat1), _p(feat2), _p(verts1), _p(verts12), _p(idx11), _p(idx22), _p(pi_val),
-                                   _p(pi_idx), _p(fps1), B, N, M, Nn, k, topk, *[_p(w) for w in wl], _p(out), variant,
-                                   _p(ws), nb, _stream()), "dvm_deformer_fwd_f32")
+    out = _new(feat1.device, B, Nn, 9)
+    _call_ws("dvm_deformer_fwd_f32", (_p(feat1), _p(feat2), _p(verts1), _p(verts12), _p(idx11), _p(idx22), _p(pi_val), _p(pi_idx), _p(fps1),
+                                      B, N, M, Nn, k, topk, *[_p(w) for w in wl], _p(out), variant),
+             feat1.device, "deformer", "dvm_deformer_workspace_bytes", B, N, M, Nn)
     return out
 
 
@@ -728,12 +691,9 @@ def map_term(verts12, verts2, idx11, idx22, pi_val, pi_idx):
     idx11, idx22, pi_idx = _i(idx11), _i(idx22), _i(pi_idx)
     B, N, _ = verts12.shape
     M, k, topk = verts2.shape[1], idx11.shape[2], pi_val.shape[2]
-    lib = _lib.load()
-    out = torch.empty(B, dtype=torch.float32, device=verts12.device)
-    nb = lib.dvm_map_term_workspace_bytes(B, N)
-    ws = workspace(nb, verts12.device, "map")
-    check(lib.dvm_map_term_f32(_p(verts12), _p(verts2), _p(idx11), _p(idx22), _p(pi_val), _p(pi_idx), B, N, M, k, topk,
-                               _p(out), _p(ws), nb, _stream()), "dvm_map_term_f32")
+    out = _new(verts12.device, B)
+    _call_ws("dvm_map_term_f32", (_p(verts12), _p(verts2), _p(idx11), _p(idx22), _p(pi_val), _p(pi_idx), B, N, M, k, topk, _p(out)),
+             verts12.device, "map", "dvm_map_term_workspace_bytes", B, N)
     return out
 
 
@@ -752,15 +712,21 @@ def rank_term(pi_val, pi_idx, M, grad=False):
     B, N, topk = pi_val.shape
     if tuple(pi_idx.shape) != (B, N, topk):
         raise ValueError("rank_term: pi_idx must have pi_val's shape %s, got %s" % ((B, N, topk), tuple(pi_idx.shape)))
-    lib = _lib.load()
     dev = pi_val.device
-    loss = torch.empty(B, dtype=torch.float32, device=dev)
+    loss = _new(dev, B)
     g_val = torch.empty_like(pi_val) if grad else None
-    nb = lib.dvm_rank_term_workspace_bytes(B, N, int(M), topk)
-    ws = workspace(nb, dev, "rank")
-    check(lib.dvm_rank_term_f32(_p(pi_val), _p(pi_idx), B, N, int(M), topk, _p(loss), _p(g_val), _p(ws), nb, _stream()),
-          "dvm_rank_term_f32")
+    _call_ws("dvm_rank_term_f32", (_p(pi_val), _p(pi_idx), B, N, int(M), topk, _p(loss), _p(g_val)),
+             dev, "rank", "dvm_rank_term_workspace_bytes", B, N, int(M), topk)
     return (loss, g_val) if grad else loss
+
+
+def _pair_out(B, n, dev):
+    """One direction's outputs of the pair calls: dict(warped, verts12, T12, losses[B,6])."""
+    return dict(warped=_new(dev, B, n, 3), verts12=_new(dev, B, n, 3), T12=_new(dev, B, n, dtype=torch.int32), losses=_new(dev, B, 6))
+
+
+def _pair_out_ptrs(o):
+    return _p(o["warped"]), _p(o["verts12"]), _p(o["T12"]), _p(o["losses"])
 
 
 def pair_direction(wl, feat1, feat2, verts1, verts2, alpha, fps_start, with_map=True, out=None):
@@ -770,18 +736,11 @@ def pair_direction(wl, feat1, feat2, verts1, verts2, alpha, fps_start, with_map=
     B, N, _ = feat1.shape
     M = feat2.shape[1]
     dev = feat1.device
-    lib = _lib.load()
     if out is None:
-        out = dict(warped=torch.empty(B, N, 3, dtype=torch.float32, device=dev),
-                   verts12=torch.empty(B, N, 3, dtype=torch.float32, device=dev),
-                   T12=torch.empty(B, N, dtype=torch.int32, device=dev),
-                   losses=torch.empty(B, 6, dtype=torch.float32, device=dev))
-    nb = lib.dvm_pair_direction_workspace_bytes(B, N, M)
-    ws = workspace(nb, dev, "pair")
-    check(lib.dvm_pair_direction_fwd_f32(_p(feat1), _p(feat2), _p(verts1), _p(verts2), B, N, M, neg_alpha_f32(alpha),
-                                         _p(fps_start), *[_p(w) for w in wl], int(with_map), _p(out["warped"]),
-                                         _p(out["verts12"]), _p(out["T12"]), _p(out["losses"]), _p(ws), nb, _stream()),
-          "dvm_pair_direction_fwd_f32")
+        out = _pair_out(B, N, dev)
+    _call_ws("dvm_pair_direction_fwd_f32", (_p(feat1), _p(feat2), _p(verts1), _p(verts2), B, N, M, neg_alpha_f32(alpha), _p(fps_start),
+                                            *[_p(w) for w in wl], int(with_map), *_pair_out_ptrs(out)),
+             dev, "pair", "dvm_pair_direction_workspace_bytes", B, N, M)
     return out
 
 
@@ -791,11 +750,8 @@ def knn_neg(a, b, k):
     a, b = _f(a), _f(b)
     B, N, C = a.shape
     M = b.shape[1]
-    lib = _lib.load()
-    idx = torch.empty(B, N, k, dtype=torch.int32, device=a.device)
-    nb = lib.dvm_knn_neg_workspace_bytes(B, N, M, C, k)
-    ws = workspace(nb, a.device, "knn_neg")
-    check(lib.dvm_knn_neg_f32(_p(a), _p(b), B, N, M, C, k, _p(idx), _p(ws), nb, _stream()), "dvm_knn_neg_f32")
+    idx = _new(a.device, B, N, k, dtype=torch.int32)
+    _call_ws("dvm_knn_neg_f32", (_p(a), _p(b), B, N, M, C, k, _p(idx)), a.device, "knn_neg", "dvm_knn_neg_workspace_bytes", B, N, M, C, k)
     return idx
 
 
@@ -804,12 +760,9 @@ def softcorr_dense(f1, f2, alpha):
     f1, f2 = _f(f1), _f(f2)
     B, N, d = f1.shape
     M = f2.shape[1]
-    lib = _lib.load()
-    P = torch.empty(B, N, M, dtype=torch.float32, device=f1.device)
-    nb = lib.dvm_softcorr_dense_workspace_bytes(B, N, M, d)
-    ws = workspace(nb, f1.device, "softcorr_dense")
-    check(lib.dvm_softcorr_dense_f32(_p(f1), _p(f2), B, N, M, d, neg_alpha_f32(alpha), _p(P), _p(ws), nb, _stream()),
-          "dvm_softcorr_dense_f32")
+    P = _new(f1.device, B, N, M)
+    _call_ws("dvm_softcorr_dense_f32", (_p(f1), _p(f2), B, N, M, d, neg_alpha_f32(alpha), _p(P)),
+             f1.device, "softcorr_dense", "dvm_softcorr_dense_workspace_bytes", B, N, M, d)
     return P
 
 
@@ -818,12 +771,8 @@ def deformer_mlp(wl, z):
     _need_gpu(z, *wl)
     z = _f(z)
     rows = z.numel() // 262
-    lib = _lib.load()
-    out = torch.empty(*z.shape[:-1], 9, dtype=torch.float32, device=z.device)
-    nb = lib.dvm_deformer_mlp_workspace_bytes(rows)
-    ws = workspace(nb, z.device, "mlp")
-    check(lib.dvm_deformer_mlp_fwd_f32(_p(z), rows, *[_p(w) for w in wl[2:]], _p(out), _p(ws), nb, _stream()),
-          "dvm_deformer_mlp_fwd_f32")
+    out = _new(z.device, *z.shape[:-1], 9)
+    _call_ws("dvm_deformer_mlp_fwd_f32", (_p(z), rows, *[_p(w) for w in wl[2:]], _p(out)), z.device, "mlp", "dvm_deformer_mlp_workspace_bytes", rows)
     return out
 
 
@@ -832,16 +781,13 @@ def pos_encoding(x, minmax=None):
     _need_gpu(x)
     x = _f(x)
     B, _, N = x.shape
-    lib = _lib.load()
-    out = torch.empty(B, 384, N, dtype=torch.float32, device=x.device)
+    out = _new(x.device, B, 384, N)
     if minmax is not None:
         _need_gpu(minmax)
         mm = _f(minmax).reshape(2)
-        check(lib.dvm_pos_encoding_minmax_f32(_p(x), _p(mm), B, N, _p(out), _stream()), "dvm_pos_encoding_minmax_f32")
-        return out
-    nb = lib.dvm_pos_encoding_workspace_bytes()
-    ws = workspace(nb, x.device, "posenc")
-    check(lib.dvm_pos_encoding_f32(_p(x), B, N, _p(out), _p(ws), nb, _stream()), "dvm_pos_encoding_f32")
+        _call("dvm_pos_encoding_minmax_f32", _p(x), _p(mm), B, N, _p(out))
+    else:
+        _call_ws("dvm_pos_encoding_f32", (_p(x), B, N, _p(out)), x.device, "posenc", "dvm_pos_encoding_workspace_bytes")
     return out
 
 
@@ -851,19 +797,16 @@ def bn_act_train_fwd(x, res, gamma, beta, eps, slope, momentum, running_mean=Non
     _need_gpu(x)
     x = _f(x)
     res = None if res is None else _f(res)
+    gamma = None if gamma is None else _f(gamma)
+    beta = None if beta is None else _f(beta)
     B, C, N = x.shape
-    lib = _lib.load()
     y = torch.empty_like(x)
-    mean = torch.empty(C, dtype=torch.float32, device=x.device)
-    invstd = torch.empty(C, dtype=torch.float32, device=x.device)
-    nb = lib.dvm_bn_workspace_bytes(B, C, N)
-    ws = workspace(nb, x.device, "bn")
-    opt = lambda t: None if t is None else _p(t)  # noqa: E731
+    mean, invstd = _new(x.device, C), _new(x.device, C)
     if running_mean is not None:
         assert running_mean.is_contiguous() and running_var.is_contiguous() and running_mean.dtype == torch.float32
-    check(lib.dvm_bn_act_train_fwd_f32(_p(x), opt(res), opt(None if gamma is None else _f(gamma)), opt(None if beta is None else _f(beta)),
-                                       B, C, N, float(eps), float(slope), float(momentum), _p(y), _p(mean), _p(invstd),
-                                       opt(running_mean), opt(running_var), _p(ws), nb, _stream()), "dvm_bn_act_train_fwd_f32")
+    _call_ws("dvm_bn_act_train_fwd_f32", (_p(x), _p(res), _p(gamma), _p(beta), B, C, N, float(eps), float(slope), float(momentum), _p(y),
+                                          _p(mean), _p(invstd), _p(running_mean), _p(running_var)),
+             x.device, "bn", "dvm_bn_workspace_bytes", B, C, N)
     return y, mean, invstd
 
 
@@ -872,16 +815,12 @@ def bn_act_train_bwd(dy, y, x, res, gamma, mean, invstd, slope):
     _need_gpu(dy, y, x)
     dy, y, x = _f(dy), _f(y), _f(x)
     res = None if res is None else _f(res)
+    gamma = None if gamma is None else _f(gamma)
     B, C, N = x.shape
-    lib = _lib.load()
     dx = torch.empty_like(x)
-    dgamma = torch.empty(C, dtype=torch.float32, device=x.device)
-    dbeta = torch.empty(C, dtype=torch.float32, device=x.device)
-    nb = lib.dvm_bn_workspace_bytes(B, C, N)
-    ws = workspace(nb, x.device, "bn")
-    check(lib.dvm_bn_act_train_bwd_f32(_p(dy), _p(y), _p(x), None if res is None else _p(res), None if gamma is None else _p(_f(gamma)),
-                                       _p(mean), _p(invstd), B, C, N, float(slope), _p(dx), _p(dgamma), _p(dbeta), _p(ws), nb,
-                                       _stream()), "dvm_bn_act_train_bwd_f32")
+    dgamma, dbeta = _new(x.device, C), _new(x.device, C)
+    _call_ws("dvm_bn_act_train_bwd_f32", (_p(dy), _p(y), _p(x), _p(res), _p(gamma), _p(mean), _p(invstd), B, C, N, float(slope), _p(dx),
+                                          _p(dgamma), _p(dbeta)), x.device, "bn", "dvm_bn_workspace_bytes", B, C, N)
     return dx, dgamma, dbeta
 
 
@@ -890,8 +829,8 @@ def graph_geodesics(nbr, w):
     _need_gpu(nbr, w)
     nbr, w = nbr.contiguous().int(), w.contiguous().double()
     N, K = nbr.shape
-    D = torch.empty(N, N, dtype=torch.float64, device=nbr.device)
-    check(_lib.load().dvm_graph_geodesics_f64(_p(nbr), _p(w), N, K, _p(D), _stream()), "dvm_graph_geodesics_f64")
+    D = _new(nbr.device, N, N, dtype=torch.float64)
+    _call("dvm_graph_geodesics_f64", _p(nbr), _p(w), N, K, _p(D))
     return D
 
 
@@ -900,14 +839,10 @@ def proj2img(pts):
     _need_gpu(pts)
     pts = _f(pts)
     B, N, _ = pts.shape
-    lib = _lib.load()
     dev = pts.device
-    img = torch.empty(B, 3, 224, 224, dtype=torch.float32, device=dev)
-    pc_min, grid, off = (torch.empty(B, 2, dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.float32, device=dev),
-                         torch.empty(B, 2, dtype=torch.float32, device=dev))
-    nb = lib.dvm_proj2img_workspace_bytes(B)
-    ws = workspace(nb, dev, "proj2img")
-    check(lib.dvm_proj2img_f32(_p(pts), B, N, _p(img), _p(pc_min), _p(grid), _p(off), _p(ws), nb, _stream()), "dvm_proj2img_f32")
+    img = _new(dev, B, 3, 224, 224)
+    pc_min, grid, off = _new(dev, B, 2), _new(dev, B), _new(dev, B, 2)
+    _call_ws("dvm_proj2img_f32", (_p(pts), B, N, _p(img), _p(pc_min), _p(grid), _p(off)), dev, "proj2img", "dvm_proj2img_workspace_bytes", B)
     return img, pc_min, grid, off
 
 
@@ -918,10 +853,10 @@ def i2p(pts, f, pc_min, grid, offsets, normalize=False, out=None, col=0):
     B, N, _ = pts.shape
     C, H, W = f.shape[1:]
     if out is None:
-        out, col = torch.empty(B, N, C, dtype=torch.float32, device=pts.device), 0
+        out, col = _new(pts.device, B, N, C), 0
     assert out.is_contiguous() and out.dtype == torch.float32 and out.shape[:2] == (B, N) and col + C <= out.shape[2]
-    check(_lib.load().dvm_i2p_f32(_p(pts), _p(f), _p(pc_min), _p(grid), _p(offsets), B, N, C, H, W, int(bool(normalize)),
-                                  ctypes.c_void_p(out.data_ptr() + 4 * col), out.shape[2], _stream()), "dvm_i2p_f32")
+    _call("dvm_i2p_f32", _p(pts), _p(f), _p(pc_min), _p(grid), _p(offsets), B, N, C, H, W, int(bool(normalize)),
+          ctypes.c_void_p(out.data_ptr() + 4 * col), out.shape[2])
     return out
 
 
@@ -939,9 +874,8 @@ def adaptive_conv(x_padded, kernel, tap_major=False):
         ok = d == dd
     if not ok or Hp != H + d - 1 or Wp != W + d - 1 or kernel.shape[0] != B:
         raise DvmError("adaptive_conv: shapes %s and %s do not match" % (tuple(x_padded.shape), tuple(kernel.shape)))
-    out = torch.empty(B, C, H, W, dtype=torch.float32, device=x_padded.device)
-    check(_lib.load().dvm_adaptive_conv_f32(_p(x_padded), _p(kernel), B, C, H, W, d, 1 if tap_major else 0, _p(out), _stream()),
-          "dvm_adaptive_conv_f32")
+    out = _new(x_padded.device, B, C, H, W)
+    _call("dvm_adaptive_conv_f32", _p(x_padded), _p(kernel), B, C, H, W, d, 1 if tap_major else 0, _p(out))
     return out
 
 
@@ -952,8 +886,8 @@ def bicubic_resize_pad(x, size, pad=0):
     x = _f(x)
     B, C, Hi, Wi = x.shape
     Ho, Wo = size
-    out = torch.empty(B, C, Ho + 2 * pad, Wo + 2 * pad, dtype=torch.float32, device=x.device)
-    check(_lib.load().dvm_bicubic_resize_pad_f32(_p(x), B * C, Hi, Wi, Ho, Wo, pad, _p(out), _stream()), "dvm_bicubic_resize_pad_f32")
+    out = _new(x.device, B, C, Ho + 2 * pad, Wo + 2 * pad)
+    _call("dvm_bicubic_resize_pad_f32", _p(x), B * C, Hi, Wi, Ho, Wo, pad, _p(out))
     return out
 
 
@@ -962,9 +896,8 @@ def jbu_kernel(proj, range_temp, sigma_spatial, d=7):
     _need_gpu(proj, range_temp, sigma_spatial)
     proj = _f(proj)
     B, Kd, H, W = proj.shape
-    out = torch.empty(B, d * d, H, W, dtype=torch.float32, device=proj.device)
-    check(_lib.load().dvm_jbu_kernel_f32(_p(proj), _p(_f(range_temp)), _p(_f(sigma_spatial)), B, Kd, H, W, d, _p(out), _stream()),
-          "dvm_jbu_kernel_f32")
+    out = _new(proj.device, B, d * d, H, W)
+    _call("dvm_jbu_kernel_f32", _p(proj), _p(_f(range_temp)), _p(_f(sigma_spatial)), B, Kd, H, W, d, _p(out))
     return out
 
 
@@ -973,11 +906,8 @@ def sa_attention_pm(p, v):
     _need_gpu(p, v)
     p, v = _f(p), _f(v)
     B, N, _ = p.shape
-    lib = _lib.load()
-    xr = torch.empty(B, N, 64, dtype=torch.float32, device=p.device)
-    nb = lib.dvm_sa_attention_workspace_bytes(B, N)
-    ws = workspace(nb, p.device, "sa")
-    check(lib.dvm_sa_attention_fwd_f32(_p(p), _p(v), B, N, _p(xr), _p(ws), nb, _stream()), "dvm_sa_attention_fwd_f32")
+    xr = _new(p.device, B, N, 64)
+    _call_ws("dvm_sa_attention_fwd_f32", (_p(p), _p(v), B, N, _p(xr)), p.device, "sa", "dvm_sa_attention_workspace_bytes", B, N)
     return xr
 
 
@@ -986,14 +916,10 @@ def sa_attention_train_fwd(p, v):
     _need_gpu(p, v)
     p, v = _f(p), _f(v)
     B, N, _ = p.shape
-    xr = torch.empty(B, N, 64, dtype=torch.float32, device=p.device)
-    stats = torch.empty(B, N, 2, dtype=torch.float32, device=p.device)
-    cinv = torch.empty(B, N, dtype=torch.float32, device=p.device)
-    lib = _lib.load()
-    nb = lib.dvm_sa_attention_train_fwd_workspace_bytes(B, N)
-    ws = workspace(nb, p.device, "sa_train") if nb else None
-    check(lib.dvm_sa_attention_train_fwd_f32(_p(p), _p(v), B, N, _p(xr), _p(stats), _p(cinv), _p(ws) if nb else None, nb, _stream()),
-          "dvm_sa_attention_train_fwd_f32")
+    dev = p.device
+    xr, stats, cinv = _new(dev, B, N, 64), _new(dev, B, N, 2), _new(dev, B, N)
+    _call_ws("dvm_sa_attention_train_fwd_f32", (_p(p), _p(v), B, N, _p(xr), _p(stats), _p(cinv)),
+             dev, "sa_train", "dvm_sa_attention_train_fwd_workspace_bytes", B, N, null_if_empty=True)
     return xr, stats, cinv
 
 
@@ -1003,11 +929,8 @@ def sa_attention_bwd(p, v, xr, stats, cinv, gxr):
     p, v, gxr = _f(p), _f(v), _f(gxr)
     B, N, _ = p.shape
     dp, dv = torch.empty_like(p), torch.empty_like(v)
-    lib = _lib.load()
-    nb = lib.dvm_sa_attention_bwd_workspace_bytes(B, N)
-    ws = workspace(nb, p.device, "sa_bwd")
-    check(lib.dvm_sa_attention_bwd_f32(_p(p), _p(v), _p(xr), _p(stats), _p(cinv), _p(gxr), B, N, _p(dp), _p(dv), _p(ws), nb,
-                                       _stream()), "dvm_sa_attention_bwd_f32")
+    _call_ws("dvm_sa_attention_bwd_f32", (_p(p), _p(v), _p(xr), _p(stats), _p(cinv), _p(gxr), B, N, _p(dp), _p(dv)),
+             p.device, "sa_bwd", "dvm_sa_attention_bwd_workspace_bytes", B, N)
     return dp, dv
 
 
@@ -1022,9 +945,8 @@ def n2p_attention_pm(q, kp, vp, idx, heads=4):
     q, kp, vp, idx = _f(q), _f(kp), _f(vp), _i(idx)
     B, N, C = q.shape
     K = idx.shape[2]
-    out = torch.empty(B, N, C, dtype=torch.float32, device=q.device)
-    check(_lib.load().dvm_n2p_attention_fwd_f32(_p(q), _p(kp), _p(vp), _p(idx), B, N, C, K, heads, _p(out), _stream()),
-          "dvm_n2p_attention_fwd_f32")
+    out = _new(q.device, B, N, C)
+    _call("dvm_n2p_attention_fwd_f32", _p(q), _p(kp), _p(vp), _p(idx), B, N, C, K, heads, _p(out))
     return out
 
 
@@ -1045,13 +967,10 @@ def dist_loss(feat, dist, anchors, k, want_idx=False):
     feat, dist, anchors = _f(feat), _f(dist), _i(anchors)
     B, N, C = feat.shape
     nA = anchors.shape[0]
-    lib = _lib.load()
-    out = torch.empty(B, dtype=torch.float32, device=feat.device)
-    idx = torch.empty(B, nA, k, dtype=torch.int32, device=feat.device) if want_idx else None
-    nb = lib.dvm_dist_loss_workspace_bytes(B, N, C, nA, k)
-    ws = workspace(nb, feat.device, "dist")
-    check(lib.dvm_dist_loss_fwd_f32(_p(feat), _p(dist), _p(anchors), B, N, C, nA, k, _p(out), _p(idx), _p(ws), nb,
-                                    _stream()), "dvm_dist_loss_fwd_f32")
+    out = _new(feat.device, B)
+    idx = _new(feat.device, B, nA, k, dtype=torch.int32) if want_idx else None
+    _call_ws("dvm_dist_loss_fwd_f32", (_p(feat), _p(dist), _p(anchors), B, N, C, nA, k, _p(out), _p(idx)),
+             feat.device, "dist", "dvm_dist_loss_workspace_bytes", B, N, C, nA, k)
     return (out, idx) if want_idx else out
 
 
@@ -1061,9 +980,8 @@ def dist_loss_bwd_weights(feat, dist, anchors, idx, gout):
     feat, dist, anchors, idx, gout = _f(feat), _f(dist), _i(anchors), _i(idx), _f(gout)
     B, N, C = feat.shape
     nA, k = idx.shape[1], idx.shape[2]
-    W = torch.empty(B, nA, N, dtype=torch.float32, device=feat.device)
-    check(_lib.load().dvm_dist_loss_bwd_weights_f32(_p(feat), _p(dist), _p(anchors), _p(idx), _p(gout), B, N, C, nA, k, _p(W),
-                                                    _stream()), "dvm_dist_loss_bwd_weights_f32")
+    W = _new(feat.device, B, nA, N)
+    _call("dvm_dist_loss_bwd_weights_f32", _p(feat), _p(dist), _p(anchors), _p(idx), _p(gout), B, N, C, nA, k, _p(W))
     return W
 
 
@@ -1073,7 +991,6 @@ U3_NWEIGHTS = 101
 def uni3fc_weight_table(tensors):
     """The host array of DVM_U3_NWEIGHTS device pointers dvm_uni3fc_fwd_f32 takes (order: include/dvm.h) from a list of
     fp32 CUDA tensors; returns (kept-alive tensors, ctypes array)."""
-    import ctypes
     ts = [_f(t) for t in tensors]
     if len(ts) != U3_NWEIGHTS:
         raise DvmError("uni3fc_weight_table: %d tensors, expected %d" % (len(ts), U3_NWEIGHTS))
@@ -1081,27 +998,30 @@ def uni3fc_weight_table(tensors):
     return ts, (ctypes.c_void_p * U3_NWEIGHTS)(*[t.data_ptr() for t in ts])
 
 
+def _ensure_pair_ctx(dev):
+    """-> (device index, stream), with the library's helper streams / events for it made (once, outside the compute call)."""
+    ctx = (dev.index, _stream())
+    if ctx not in _pair_ctx:
+        _call("dvm_pair_init")
+        _pair_ctx.add(ctx)
+    return ctx
+
+
 def uni3fc_forward(table, x, dino, k=40):
     """LG-Net's eval-mode forward in ONE native call (dvm_uni3fc_fwd_f32): x (B,3,N), dino (B,N,1152) -> feat (B,N,128),
     tmp (B,N,64).  `table` = uni3fc_weight_table(...)."""
-    import ctypes
     _need_gpu(x, dino)
     x, dino = _f(x), _f(dino)
     B, _, N = x.shape
     if tuple(dino.shape) != (B, N, 1152):
         raise DvmError("uni3fc_forward: dino features %s, expected %s" % (tuple(dino.shape), (B, N, 1152)))
-    lib = _lib.load()
     dev = x.device
-    feat = torch.empty(B, N, 128, dtype=torch.float32, device=dev)
-    tmp = torch.empty(B, N, 64, dtype=torch.float32, device=dev)
-    nb = lib.dvm_uni3fc_fwd_workspace_bytes(B, N, int(k))
+    feat, tmp = _new(dev, B, N, 128), _new(dev, B, N, 64)
+    nb = _lib.load().dvm_uni3fc_fwd_workspace_bytes(B, N, int(k))
     ws = workspace(nb, dev, "uni3fc")
-    ctx = (dev.index, _stream())
-    if ctx not in _pair_ctx:   # helper stream / events for this (device, stream): made once, outside the compute call
-        check(lib.dvm_pair_init(_stream()), "dvm_pair_init")
-        _pair_ctx.add(ctx)
-    check(lib.dvm_uni3fc_fwd_f32(_p(x), _p(dino), B, N, ctypes.cast(table[1], ctypes.c_void_p), U3_NWEIGHTS, int(k), _p(feat), _p(tmp),
-                                 _p(ws), nb, _stream()), "dvm_uni3fc_fwd_f32")
+    _ensure_pair_ctx(dev)
+    _call("dvm_uni3fc_fwd_f32", _p(x), _p(dino), B, N, ctypes.cast(table[1], ctypes.c_void_p), U3_NWEIGHTS, int(k), _p(feat), _p(tmp),
+          _p(ws), nb)
     return feat, tmp
 
 
@@ -1112,13 +1032,6 @@ def _ptr_table(tensors, n):
     if len(tensors) != n:
         raise DvmError("pointer table: %d tensors, expected %d" % (len(tensors), n))
     return (ctypes.c_void_p * n)(*[None if t is None else t.data_ptr() for t in tensors])
-
-
-def _ensure_pair_ctx(dev):
-    ctx = (dev.index, _stream())
-    if ctx not in _pair_ctx:   # helper stream / events for this (device, stream): made once, outside the compute call
-        check(_lib.load().dvm_pair_init(_stream()), "dvm_pair_init")
-        _pair_ctx.add(ctx)
 
 
 def knn_tap():
@@ -1133,11 +1046,14 @@ def knn_tap():
     return None if inspect.isfunction(fn) else (fn if hasattr(fn, "log") and hasattr(fn, "forced") else None)
 
 
-def _coll_check(coll, rc, what):
+def _call_sync(name, coll, *args):
+    """_call for a *_sync_f32 entry, `args` ending with the collective it is handed (coll.bind(..), or None): an exception that
+    the collective's all-reduce raised during the call is reported in place of the return code."""
+    rc = getattr(_lib.load(), name)(*args, _stream())
     if coll is not None and coll.error is not None:
         err, coll.error = coll.error, None
-        raise DvmError("%s: the collective failed: %r" % (what, err))
-    check(rc, what)
+        raise DvmError("%s: the collective failed: %r" % (name, err))
+    check(rc, name)
 
 
 def uni3fc_train_forward(params, x, dino, k, eps, momentum, defer_stats=False, groups=1, coll=None):
@@ -1149,18 +1065,16 @@ def uni3fc_train_forward(params, x, dino, k, eps, momentum, defer_stats=False, g
     B, _, N = x.shape
     if tuple(dino.shape) != (B, N, 1152):
         raise DvmError("uni3fc_train_forward: dino features %s, expected %s" % (tuple(dino.shape), (B, N, 1152)))
-    lib = _lib.load()
     dev = x.device
-    feat = torch.empty(B, N, 128, dtype=torch.float32, device=dev)
-    tmp = torch.empty(B, N, 64, dtype=torch.float32, device=dev)
-    nb = lib.dvm_uni3fc_train_workspace_bytes(B, N, int(k))
+    feat, tmp = _new(dev, B, N, 128), _new(dev, B, N, 64)
+    nb = _lib.load().dvm_uni3fc_train_workspace_bytes(B, N, int(k))
     arena = scratch(nb, dev)
     _ensure_pair_ctx(dev)
     table = _ptr_table(params, U3_TRAIN_NPARAMS)
     tap = knn_tap()
     forced = logs = ftab = ltab = None
     if tap is not None:
-        logs = [torch.empty(B, N, int(k), dtype=torch.int32, device=dev) for _ in range(7)]
+        logs = [_new(dev, B, N, int(k), dtype=torch.int32) for _ in range(7)]
         ltab = ctypes.cast(_ptr_table(logs, 7), ctypes.c_void_p)
         if tap.forced is not None:
             import numpy as np
@@ -1169,9 +1083,9 @@ def uni3fc_train_forward(params, x, dino, k, eps, momentum, defer_stats=False, g
                 raise DvmError("uni3fc_train_forward: forced neighbour sets must be (B, N, k)")
             ftab = ctypes.cast(_ptr_table(forced, 7), ctypes.c_void_p)
     # coll (dvm.dist.TorchCollective): BatchNorm statistics and the position-encoding range over ALL ranks of a data-parallel step
-    _coll_check(coll, lib.dvm_uni3fc_train_fwd_sync_f32(_p(x), _p(dino), B, N, ctypes.cast(table, ctypes.c_void_p), U3_TRAIN_NPARAMS, int(k), float(eps),
-                                                        float(momentum), int(groups), 1 if defer_stats else 0, ftab, ltab, _p(feat), _p(tmp), _p(arena), nb,
-                                                        coll.bind(arena) if coll is not None else None, _stream()), "dvm_uni3fc_train_fwd_f32")
+    _call_sync("dvm_uni3fc_train_fwd_sync_f32", coll, _p(x), _p(dino), B, N, ctypes.cast(table, ctypes.c_void_p), U3_TRAIN_NPARAMS, int(k),
+               float(eps), float(momentum), int(groups), 1 if defer_stats else 0, ftab, ltab, _p(feat), _p(tmp), _p(arena), nb,
+               coll.bind(arena) if coll is not None else None)
     if tap is not None:
         tap.log.extend(logs)
         if forced is not None:
@@ -1188,6 +1102,10 @@ def _graph_c(g):
     return {"nodes_idx": _i(g["nodes_idx"]), "one_ring": _i(g["one_ring"]), "infl_idx": _i(g["infl_idx"]), "weights": _f(g["weights"])}
 
 
+def _graph_ptrs(g):
+    return _p(g["nodes_idx"]), _p(g["one_ring"]), _p(g["infl_idx"]), _p(g["weights"])
+
+
 def criterion_train_forward(params, feat, verts, g, knn_idx, alpha, topk=10, with_map=True, dist=None):
     """The training criterion for B pairs as ONE native call (dvm_criterion_train_fwd_f32).  feat (2B,N,128), verts (2B,N,3): the B first
     shapes followed by the B second shapes; g = their batched graph dict (dg_build), knn_idx (2B,N,k) their xyz-kNN; params: the
@@ -1198,23 +1116,21 @@ def criterion_train_forward(params, feat, verts, g, knn_idx, alpha, topk=10, wit
     feat, verts, knn_idx, g = _f(feat), _f(verts), _i(knn_idx), _graph_c(g)
     P, N, C = feat.shape
     k = knn_idx.shape[-1]
-    lib = _lib.load()
-    terms = torch.empty(P, 7, dtype=torch.float32, device=feat.device)
+    terms = _new(feat.device, P, 7)
     d1, d2, a1, a2, kd = dist if dist is not None else (None, None, None, None, 0)
     nA = 0 if dist is None else int(a1.numel())
     if dist is not None and not (d1.dtype is torch.float32 and d1.is_contiguous() and d2.dtype is torch.float32 and d2.is_contiguous()
                                  and a1.dtype is torch.int32 and a2.dtype is torch.int32 and tuple(d1.shape) == (P // 2, N, N)
                                  and tuple(d2.shape) == (P // 2, N, N) and a2.numel() == nA):
         raise DvmError("criterion_train_forward: dist term inputs must be contiguous fp32 (B,N,N) matrices and int32 anchor lists of one length")
-    nb = lib.dvm_criterion_train_workspace_bytes(P // 2, N, k, topk, nA, int(kd))
+    nb = _lib.load().dvm_criterion_train_workspace_bytes(P // 2, N, k, topk, nA, int(kd))
     arena = scratch(nb, feat.device)
     if nA:
         _ensure_pair_ctx(feat.device)
     table = _ptr_table(params, CRIT_TRAIN_NPARAMS)
-    check(lib.dvm_criterion_train_fwd_f32(_p(feat), _p(verts), _p(g["nodes_idx"]), _p(g["one_ring"]), _p(g["infl_idx"]), _p(g["weights"]), _p(knn_idx),
-                                          P // 2, N, C, k, topk, neg_alpha_f32(alpha), ctypes.cast(table, ctypes.c_void_p), CRIT_TRAIN_NPARAMS,
-                                          1 if with_map else 0, _p(d1), _p(d2), _p(a1), _p(a2), nA, int(kd), _p(terms), _p(arena), nb, _stream()),
-          "dvm_criterion_train_fwd_f32")
+    _call("dvm_criterion_train_fwd_f32", _p(feat), _p(verts), *_graph_ptrs(g), _p(knn_idx), P // 2, N, C, k, topk, neg_alpha_f32(alpha),
+          ctypes.cast(table, ctypes.c_void_p), CRIT_TRAIN_NPARAMS, 1 if with_map else 0, _p(d1), _p(d2), _p(a1), _p(a2), nA, int(kd),
+          _p(terms), _p(arena), nb)
     return terms, arena
 
 
@@ -1224,17 +1140,15 @@ def criterion_train_backward(params, grads, g_terms, feat, verts, g, knn_idx, al
     feat, verts, knn_idx, g = _f(feat), _f(verts), _i(knn_idx), _graph_c(g)
     P, N, C = feat.shape
     k = knn_idx.shape[-1]
-    lib = _lib.load()
     d_feat = torch.empty_like(feat)
     _, _, a1, a2, kd = dist if dist is not None else (None, None, None, None, 0)
     nA = 0 if dist is None else int(a1.numel())
     if nA:
         _ensure_pair_ctx(feat.device)
     ptab, gtab = _ptr_table(params, CRIT_TRAIN_NPARAMS), _ptr_table(grads, CRIT_TRAIN_NPARAMS)
-    check(lib.dvm_criterion_train_bwd_f32(_p(_f(g_terms)), _p(feat), _p(verts), _p(g["nodes_idx"]), _p(g["one_ring"]), _p(g["infl_idx"]), _p(g["weights"]),
-                                          _p(knn_idx), P // 2, N, C, k, topk, neg_alpha_f32(alpha), ctypes.cast(ptab, ctypes.c_void_p),
-                                          ctypes.cast(gtab, ctypes.c_void_p), CRIT_TRAIN_NPARAMS, 1 if with_map else 0, _p(a1), _p(a2), nA, int(kd),
-                                          _p(d_feat), _p(arena), arena.numel(), _stream()), "dvm_criterion_train_bwd_f32")
+    _call("dvm_criterion_train_bwd_f32", _p(_f(g_terms)), _p(feat), _p(verts), *_graph_ptrs(g), _p(knn_idx), P // 2, N, C, k, topk,
+          neg_alpha_f32(alpha), ctypes.cast(ptab, ctypes.c_void_p), ctypes.cast(gtab, ctypes.c_void_p), CRIT_TRAIN_NPARAMS,
+          1 if with_map else 0, _p(a1), _p(a2), nA, int(kd), _p(d_feat), _p(arena), arena.numel())
     return d_feat
 
 
@@ -1247,15 +1161,13 @@ def criterion_dir_train_forward(params, feat_s, feat_t, verts_s, verts_t, g, knn
     knn_s, knn_t, g = _i(knn_s), _i(knn_t), _graph_c(g)
     P, N, C = feat_s.shape
     M, k = feat_t.shape[1], knn_s.shape[-1]
-    lib = _lib.load()
-    terms = torch.empty(P, 7, dtype=torch.float32, device=feat_s.device)
-    nb = lib.dvm_criterion_dir_train_workspace_bytes(P, N, M, k, topk)
+    terms = _new(feat_s.device, P, 7)
+    nb = _lib.load().dvm_criterion_dir_train_workspace_bytes(P, N, M, k, topk)
     arena = scratch(nb, feat_s.device)
     table = _ptr_table(params, CRIT_TRAIN_NPARAMS)
-    check(lib.dvm_criterion_dir_train_fwd_f32(_p(feat_s), _p(feat_t), _p(verts_s), _p(verts_t), _p(g["nodes_idx"]), _p(g["one_ring"]), _p(g["infl_idx"]),
-                                              _p(g["weights"]), _p(knn_s), _p(knn_t), P, N, M, C, k, topk, neg_alpha_f32(alpha),
-                                              ctypes.cast(table, ctypes.c_void_p), CRIT_TRAIN_NPARAMS, 1 if with_map else 0, _p(terms), _p(arena), nb,
-                                              _stream()), "dvm_criterion_dir_train_fwd_f32")
+    _call("dvm_criterion_dir_train_fwd_f32", _p(feat_s), _p(feat_t), _p(verts_s), _p(verts_t), *_graph_ptrs(g), _p(knn_s), _p(knn_t),
+          P, N, M, C, k, topk, neg_alpha_f32(alpha), ctypes.cast(table, ctypes.c_void_p), CRIT_TRAIN_NPARAMS, 1 if with_map else 0,
+          _p(terms), _p(arena), nb)
     return terms, arena
 
 
@@ -1266,24 +1178,20 @@ def criterion_dir_train_backward(params, grads, g_terms, feat_s, feat_t, verts_s
     knn_s, knn_t, g = _i(knn_s), _i(knn_t), _graph_c(g)
     P, N, C = feat_s.shape
     M, k = feat_t.shape[1], knn_s.shape[-1]
-    lib = _lib.load()
     d_s, d_t = torch.empty_like(feat_s), torch.empty_like(feat_t)
     ptab, gtab = _ptr_table(params, CRIT_TRAIN_NPARAMS), _ptr_table(grads, CRIT_TRAIN_NPARAMS)
-    check(lib.dvm_criterion_dir_train_bwd_f32(_p(_f(g_terms)), _p(feat_s), _p(feat_t), _p(verts_s), _p(verts_t), _p(g["nodes_idx"]), _p(g["one_ring"]),
-                                              _p(g["infl_idx"]), _p(g["weights"]), _p(knn_s), _p(knn_t), P, N, M, C, k, topk, neg_alpha_f32(alpha),
-                                              ctypes.cast(ptab, ctypes.c_void_p), ctypes.cast(gtab, ctypes.c_void_p), CRIT_TRAIN_NPARAMS,
-                                              1 if with_map else 0, _p(d_s), _p(d_t), _p(arena), arena.numel(), _stream()),
-          "dvm_criterion_dir_train_bwd_f32")
+    _call("dvm_criterion_dir_train_bwd_f32", _p(_f(g_terms)), _p(feat_s), _p(feat_t), _p(verts_s), _p(verts_t), *_graph_ptrs(g),
+          _p(knn_s), _p(knn_t), P, N, M, C, k, topk, neg_alpha_f32(alpha), ctypes.cast(ptab, ctypes.c_void_p),
+          ctypes.cast(gtab, ctypes.c_void_p), CRIT_TRAIN_NPARAMS, 1 if with_map else 0, _p(d_s), _p(d_t), _p(arena), arena.numel())
     return d_s, d_t
 
 
 def uni3fc_train_running_stats(params, arena, B, N, k, momentum, groups=1):
     """The 26 running-statistics updates of a forward that ran with defer_stats=True (dvm_uni3fc_train_running_stats_f32), on the
     current stream."""
-    lib = _lib.load()
     table = _ptr_table(params, U3_TRAIN_NPARAMS)
-    check(lib.dvm_uni3fc_train_running_stats_f32(ctypes.cast(table, ctypes.c_void_p), U3_TRAIN_NPARAMS, int(B), int(N), int(k), int(groups), float(momentum),
-                                                 _p(arena), arena.numel(), _stream()), "dvm_uni3fc_train_running_stats_f32")
+    _call("dvm_uni3fc_train_running_stats_f32", ctypes.cast(table, ctypes.c_void_p), U3_TRAIN_NPARAMS, int(B), int(N), int(k), int(groups),
+          float(momentum), _p(arena), arena.numel())
 
 
 def uni3fc_train_backward(params, grads, dino, feat, tmp, arena, g_feat, g_tmp, k, groups=1, coll=None):
@@ -1291,14 +1199,13 @@ def uni3fc_train_backward(params, grads, dino, feat, tmp, arena, g_feat, g_tmp, 
     running statistics)."""
     _need_gpu(g_feat, dino)
     B, N, _ = feat.shape
-    lib = _lib.load()
     _ensure_pair_ctx(feat.device)
     g_feat = _f(g_feat)
     g_tmp = None if g_tmp is None else _f(g_tmp)
     ptab, gtab = _ptr_table(params, U3_TRAIN_NPARAMS), _ptr_table(grads, U3_TRAIN_NPARAMS)
-    _coll_check(coll, lib.dvm_uni3fc_train_bwd_sync_f32(_p(g_feat), _p(g_tmp), _p(dino), _p(feat), _p(tmp), B, N, ctypes.cast(ptab, ctypes.c_void_p),
-                                                        ctypes.cast(gtab, ctypes.c_void_p), U3_TRAIN_NPARAMS, int(k), int(groups), _p(arena), arena.numel(),
-                                                        coll.bind(arena) if coll is not None else None, _stream()), "dvm_uni3fc_train_bwd_f32")
+    _call_sync("dvm_uni3fc_train_bwd_sync_f32", coll, _p(g_feat), _p(g_tmp), _p(dino), _p(feat), _p(tmp), B, N,
+               ctypes.cast(ptab, ctypes.c_void_p), ctypes.cast(gtab, ctypes.c_void_p), U3_TRAIN_NPARAMS, int(k), int(groups), _p(arena),
+               arena.numel(), coll.bind(arena) if coll is not None else None)
 
 
 class GeometryCache:
@@ -1341,33 +1248,19 @@ def pair_forward(wl, feat1, feat2, verts1, verts2, alpha, start1, start2, with_m
     B, N, _ = feat1.shape
     M = feat2.shape[1]
     dev = feat1.device
-    lib = _lib.load()
-
-    def alloc(n):
-        return dict(warped=torch.empty(B, n, 3, dtype=torch.float32, device=dev),
-                    verts12=torch.empty(B, n, 3, dtype=torch.float32, device=dev),
-                    T12=torch.empty(B, n, dtype=torch.int32, device=dev),
-                    losses=torch.empty(B, 6, dtype=torch.float32, device=dev))
-    o12, o21 = out if out is not None else (alloc(N), alloc(M))
-    nb = lib.dvm_pair_workspace_bytes(B, N, M)
-    ctx = (dev.index, _stream())
-    if ctx not in _pair_ctx:   # helper streams / events for this (device, stream): made once, outside the compute call
-        check(lib.dvm_pair_init(_stream()), "dvm_pair_init")
-        _pair_ctx.add(ctx)
-    if cache is not None:
-        if key is None:
-            raise DvmError("pair_forward: a GeometryCache needs the key of this batch's geometry (shape ids + FPS starts)")
-        ws, reuse = cache.lookup((key, B, N, M, bool(with_map), ctx), nb, dev)
-        check(lib.dvm_pair_fwd_cached_f32(_p(feat1), _p(feat2), _p(verts1), _p(verts2), B, N, M, neg_alpha_f32(alpha), _p(start1),
-                                          _p(start2), *[_p(w) for w in wl], int(with_map), _p(o12["warped"]), _p(o12["verts12"]),
-                                          _p(o12["T12"]), _p(o12["losses"]), _p(o21["warped"]), _p(o21["verts12"]), _p(o21["T12"]),
-                                          _p(o21["losses"]), _p(ws), nb, reuse, _stream()), "dvm_pair_fwd_cached_f32")
+    o12, o21 = out if out is not None else (_pair_out(B, N, dev), _pair_out(B, M, dev))
+    nb = _lib.load().dvm_pair_workspace_bytes(B, N, M)
+    ctx = _ensure_pair_ctx(dev)
+    args = (_p(feat1), _p(feat2), _p(verts1), _p(verts2), B, N, M, neg_alpha_f32(alpha), _p(start1), _p(start2), *[_p(w) for w in wl],
+            int(with_map), *_pair_out_ptrs(o12), *_pair_out_ptrs(o21))
+    if cache is None:
+        ws = workspace(nb, dev, "pair2")
+        _call("dvm_pair_fwd_f32", *args, _p(ws), nb)
         return o12, o21
-    ws = workspace(nb, dev, "pair2")
-    check(lib.dvm_pair_fwd_f32(_p(feat1), _p(feat2), _p(verts1), _p(verts2), B, N, M, neg_alpha_f32(alpha), _p(start1),
-                               _p(start2), *[_p(w) for w in wl], int(with_map), _p(o12["warped"]), _p(o12["verts12"]),
-                               _p(o12["T12"]), _p(o12["losses"]), _p(o21["warped"]), _p(o21["verts12"]), _p(o21["T12"]),
-                               _p(o21["losses"]), _p(ws), nb, _stream()), "dvm_pair_fwd_f32")
+    if key is None:
+        raise DvmError("pair_forward: a GeometryCache needs the key of this batch's geometry (shape ids + FPS starts)")
+    ws, reuse = cache.lookup((key, B, N, M, bool(with_map), ctx), nb, dev)
+    _call("dvm_pair_fwd_cached_f32", *args, _p(ws), nb, reuse)   # `reuse` stands between the size and the stream
     return o12, o21
 
 
@@ -1397,13 +1290,12 @@ class PairPipeline:
     def __init__(self, wl, B, N, M, with_map=True, depth=2, device=None):
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
         self.wl, self.B, self.N, self.M, self.with_map, self.dev = wl, int(B), int(N), int(M), bool(with_map), dev
-        lib = _lib.load()
-        self.nb = lib.dvm_pair_workspace_bytes(self.B, self.N, self.M)
+        self.nb = _lib.load().dvm_pair_workspace_bytes(self.B, self.N, self.M)
         self.ws = [scratch(max(int(self.nb), 256), dev) for _ in range(depth)]
         self.free = [None] * depth           # event: the stage-2 call that last used the workspace has finished
         self.geo = torch.cuda.Stream(device=dev)
         with torch.cuda.stream(self.geo):
-            check(lib.dvm_pair_init(_stream()), "dvm_pair_init")      # the geometry stream's own helper stream / events
+            _call("dvm_pair_init")           # the geometry stream's own helper stream / events
         self.n = 0
         self.slot_gen = [0] * depth          # which prefetch last wrote the workspace (a ticket is valid while it is the one)
         self.schedule = "geometry first" if 2 * self.B <= _cu_count() else "features first"
@@ -1447,8 +1339,8 @@ class PairPipeline:
         if self.free[slot] is not None:
             self.geo.wait_event(self.free[slot])        # the workspace's previous consumer is done
         with torch.cuda.stream(self.geo):
-            check(_lib.load().dvm_pair_geometry_f32(_p(verts1), _p(verts2), self.B, self.N, self.M, _p(start1), _p(start2),
-                                                    int(self.with_map), _p(self.ws[slot]), self.nb, _stream()), "dvm_pair_geometry_f32")
+            _call("dvm_pair_geometry_f32", _p(verts1), _p(verts2), self.B, self.N, self.M, _p(start1), _p(start2), int(self.with_map),
+                  _p(self.ws[slot]), self.nb)
             ready = torch.cuda.Event()
             ready.record()
         return dict(pipe=self, slot=slot, gen=self.n, ready=ready, verts1=verts1, verts2=verts2, start1=start1, start2=start2)
@@ -1460,28 +1352,19 @@ class PairPipeline:
         B, N, M, dev = self.B, self.N, self.M, self.dev
         if tuple(feat1.shape) != (B, N, 128) or tuple(feat2.shape) != (B, M, 128):
             raise DvmError("PairPipeline.forward: features %s / %s, built for B=%d N=%d M=%d" % (tuple(feat1.shape), tuple(feat2.shape), B, N, M))
-        lib = _lib.load()
-
-        def alloc(n):
-            return dict(warped=torch.empty(B, n, 3, dtype=torch.float32, device=dev),
-                        verts12=torch.empty(B, n, 3, dtype=torch.float32, device=dev),
-                        T12=torch.empty(B, n, dtype=torch.int32, device=dev),
-                        losses=torch.empty(B, 6, dtype=torch.float32, device=dev))
         if ticket.get("pipe") is not self:
             raise DvmError("PairPipeline.forward: the ticket was issued by another pipeline (its geometry is in that pipeline's workspace)")
         slot = ticket["slot"]
         if self.slot_gen[slot] != ticket["gen"]:
             raise DvmError("PairPipeline.forward: this ticket's workspace has been rewritten by a later prefetch (%d workspaces rotate: "
                            "consume a ticket before %d further prefetches)" % (len(self.ws), len(self.ws)))
-        o12, o21 = out if out is not None else (alloc(N), alloc(M))
+        o12, o21 = out if out is not None else (_pair_out(B, N, dev), _pair_out(B, M, dev))
         _ensure_pair_ctx(dev)
         cur = torch.cuda.current_stream(dev)
         cur.wait_event(ticket["ready"])
-        check(lib.dvm_pair_fwd_cached_f32(_p(feat1), _p(feat2), _p(ticket["verts1"]), _p(ticket["verts2"]), B, N, M, neg_alpha_f32(alpha),
-                                          _p(ticket["start1"]), _p(ticket["start2"]), *[_p(w) for w in self.wl], int(self.with_map),
-                                          _p(o12["warped"]), _p(o12["verts12"]), _p(o12["T12"]), _p(o12["losses"]), _p(o21["warped"]),
-                                          _p(o21["verts12"]), _p(o21["T12"]), _p(o21["losses"]), _p(self.ws[slot]), self.nb, 1, _stream()),
-              "dvm_pair_fwd_cached_f32")
+        _call("dvm_pair_fwd_cached_f32", _p(feat1), _p(feat2), _p(ticket["verts1"]), _p(ticket["verts2"]), B, N, M, neg_alpha_f32(alpha),
+              _p(ticket["start1"]), _p(ticket["start2"]), *[_p(w) for w in self.wl], int(self.with_map), *_pair_out_ptrs(o12),
+              *_pair_out_ptrs(o21), _p(self.ws[slot]), self.nb, 1)
         ev = torch.cuda.Event()
         ev.record(cur)
         self.free[slot] = ev

@@ -33,6 +33,87 @@ def test_ctypes_table_matches_header():
     assert sorted(_lib.SIGNATURES) == header_symbols()
 
 
+HEADER_FORMS = """
+/* a declaration inside a comment:
+ * int dvm_in_a_comment(int x);
+ */
+#ifndef DVM_SAMPLE_H
+#define DVM_SAMPLE_VERSION 1
+extern "C" {
+typedef int (*dvm_callback_fn)(void *user, void *buf, size_t count, void *stream);
+typedef struct dvm_thing {
+    dvm_callback_fn call;
+    void *user;
+} dvm_thing;
+// int dvm_in_a_line_comment(void);
+int dvm_multi_line(const float *x, int B, float slope,
+                   int32_t *idx /* may be NULL */, void *ws,
+                   size_t ws_bytes,
+                   void *stream);
+size_t dvm_scalars(long R, size_t n, unsigned mask, unsigned int mask2, double scale, double *out);
+int dvm_tables(const float *const *rows, const dvm_thing *thing, const double *w, int);
+const char *dvm_text(void);
+int dvm_no_arguments();
+}
+#endif
+"""
+
+
+def test_header_parser_forms():
+    """Every form of declaration the header may use, on a literal header: the exact tuples, and no default for a type the parser
+    does not know."""
+    from ctypes import c_char_p, c_double, c_float, c_int, c_long, c_size_t, c_uint, c_void_p as P
+    from dvm import _lib
+    got = _lib.parse_header(HEADER_FORMS)
+    assert got == {
+        "dvm_multi_line": (c_int, [P, c_int, c_float, P, P, c_size_t, P]),
+        "dvm_scalars": (c_size_t, [c_long, c_size_t, c_uint, c_uint, c_double, P]),
+        "dvm_tables": (c_int, [P, P, P, c_int]),
+        "dvm_text": (c_char_p, []),
+        "dvm_no_arguments": (c_int, []),
+    }
+    assert list(got) == ["dvm_multi_line", "dvm_scalars", "dvm_tables", "dvm_text", "dvm_no_arguments"]
+    for bad in ("int dvm_bad(short x);",            # a scalar parameter type without a ctypes entry
+                "int dvm_bad(int a, uint64_t n);",
+                "char dvm_bad(void);",              # return types
+                "float *dvm_bad(int n);",
+                "int dvm_bad(int (*fn)(int));",     # not a form the parser reads
+                "int dvm_some_global;"):
+        with pytest.raises(_lib.DvmError):
+            _lib.parse_header(bad)
+
+
+def test_header_entries_against_hand_written_types():
+    """Five entries of the real header against types written out here by hand (the derived table is otherwise only ever compared
+    with itself): long and size_t among ints, unsigned, a char * return, the longest list."""
+    from ctypes import c_char_p, c_float, c_int, c_long, c_size_t, c_uint, c_void_p as P
+    from dvm import _lib
+    S = _lib.SIGNATURES
+    bn = S["dvm_bn_act_train_fwd_pm_f32"]
+    assert bn == (c_int, [P, P, P, P, c_long, c_int, c_float, c_float, c_float, P, P, P, P, P, P, c_size_t, P])
+    assert len(bn[1]) == 17 and bn[1][4] is c_long and bn[1][15] is c_size_t
+    assert S["dvm_linear_wgrad_f32"] == (c_int, [P, P, c_long, c_int, c_int, P, P])
+    assert S["dvm_profile_select"] == (c_int, [c_uint])
+    assert S["dvm_last_error"] == (c_char_p, [])
+    de = S["dvm_deformer_fwd_f32"]
+    assert de == (c_int, [P] * 9 + [c_int] * 6 + [P] * 10 + [P, c_int, P, c_size_t, P]) and len(de[1]) == 30
+
+
+def test_loaded_prototypes_are_the_table():
+    from dvm import _lib
+    lib = _lib.load()
+    for name, (res, args) in _lib.SIGNATURES.items():
+        fn = getattr(lib, name)
+        assert fn.restype is res and list(fn.argtypes) == args, name
+
+
+def test_missing_header_is_reported(monkeypatch, tmp_path):
+    from dvm import _lib
+    monkeypatch.setattr(_lib, "HEADER", str(tmp_path / "include" / "dvm.h"))
+    with pytest.raises(_lib.DvmError, match="dvm.h"):
+        _lib._header_text()
+
+
 def test_loads_and_reports_without_gpu():
     from dvm import _lib
     lib = _lib.load()

@@ -86,6 +86,43 @@ def test_softcorr_bwd_split_and_full_size(ops):
     assert rel(a1, b1) < 2e-5 and rel(a2, b2) < 2e-5, (rel(a1, b1), rel(a2, b2))
 
 
+def _index_forms(idx):
+    """A contiguous int32 index tensor on the device as int64, and as a strided int32 view of the same values."""
+    view = torch.stack([idx, idx.flip(-1)], -1)[..., 0]
+    assert view.is_cuda and view.dtype == torch.int32 and not view.is_contiguous() and torch.equal(view, idx)
+    return [("int64", idx.long()), ("strided int32", view)]
+
+
+def test_index_tensors_are_converted_not_reinterpreted(ops):
+    """softcorr_bwd and the N2P core read their index tensor as contiguous int32.  Handed int64, or an int32 view that is not
+    contiguous, they give what the contiguous int32 tensor gives (read as it lies, every second int64 word is a 0 and the view's
+    rows are interleaved).  Shapes: the smallest of this file's softcorr_bwd cases, and of its N2P cases the smallest and the
+    smallest with more than one neighbour per row.  Bars: softcorr_bwd sums with float atomics, so two calls are compared at this
+    file's 1e-4; the N2P forward has no atomics and is compared bit for bit, its backward goes through the per-row check of
+    test_gpu_backward_adversarial.py for every form and is compared with the int32 call at this file's 1e-5."""
+    from test_gpu_backward_adversarial import n2p_check
+    g = torch.Generator().manual_seed(5)
+    f1, f2 = torch.randn(1, 70, 36, generator=g).cuda(), torch.randn(1, 90, 36, generator=g).cuda()
+    gval = torch.randn(1, 70, 10, generator=g).cuda()
+    val, idx, smax, ssum = ops.softcorr(f1, f2, 2.0)
+    base = ops.softcorr_bwd(f1, f2, 2.0, val, idx, smax, ssum, gval)
+    for name, alt in _index_forms(idx):
+        got = ops.softcorr_bwd(f1, f2, 2.0, val, alt, smax, ssum, gval)
+        assert rel(got[0], base[0]) < 1e-4 and rel(got[1], base[1]) < 1e-4, (name, rel(got[0], base[0]), rel(got[1], base[1]))
+    for C, K, N in ((64, 1, 9), (64, 5, 33)):
+        g = torch.Generator().manual_seed(C + K)
+        qkv = torch.randn(2, N, 3 * C, generator=g)
+        idx = torch.randint(0, N, (2, N, K), generator=g, dtype=torch.int32).cuda()
+        gout = torch.randn(2, N, C, generator=g)
+        out, attn = ops.n2p_core_fwd(qkv.cuda(), idx, 4)
+        base = n2p_check(ops, qkv, idx, gout)
+        for name, alt in _index_forms(idx):
+            o, a = ops.n2p_core_fwd(qkv.cuda(), alt, 4)
+            assert torch.equal(o, out) and torch.equal(a, attn), (name, C, K, N)
+            got = n2p_check(ops, qkv, alt, gout)
+            assert rel(got, base) < 1e-5, (name, C, K, N, rel(got, base))
+
+
 @pytest.mark.parametrize("C,K,N", [(64, 40, 300), (128, 40, 257), (128, 7, 50), (64, 64, 130), (64, 5, 33), (64, 1, 9), (128, 1, 5)])
 def test_n2p_core_fwd_bwd_vs_fp64_autograd(ops, C, K, N):
     B, H = 2, 4
