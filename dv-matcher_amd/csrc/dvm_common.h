@@ -441,6 +441,17 @@ __device__ __forceinline__ double wave_sum(double v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+// The order-free sum of the rank and cycle terms' gradients (dvm_rank.hip, dvm_cycle.hip): the terms of a reversed list come in the
+// order integer atomics set, so they are added as 64-bit integers in units of 2^(unit_exp - FIX_BITS), unit_exp = ilogb(m) + 1 for the
+// largest |term| m of the list (a first walk; a maximum is order-free too).  Every term is below 2^FIX_BITS units, a list holds at most
+// 2^13 of them; the quantisation is at most half a unit per term.
+constexpr int FIX_BITS = 50;
+// one term of such a list: (s - delta) v in float64, s an fp32 entry of the product, delta = 1 on the diagonal
+__device__ __forceinline__ double resid_term(float s, bool diag, float v) { return ((double)s - (diag ? 1.0 : 0.0)) * (double)v; }
+__device__ __forceinline__ int fix_unit_exp(double m) { return m > 0.0 && m < INFINITY ? ilogb(m) + 1 : 0; }
+__device__ __forceinline__ long long fix_quant(double term, int unit_exp) { return __double2ll_rn(ldexp(term, FIX_BITS - unit_exp)); }
+__device__ __forceinline__ double fix_value(long long q, int unit_exp) { return ldexp((double)q, unit_exp - FIX_BITS); }
+
 // Sum of one double per thread of a 256-THREAD workgroup, returned in every thread: the fixed tree red[t] += red[t + o],
 // o = 128, 64, .. 1, a barrier per level.  Every fixed-order fp64 reduction of the loss scalars ends in this one tree (the
 // map term's and the dist term's four-wave block sums are other orders and stay with their kernels).

@@ -119,6 +119,10 @@ int *launch_mlp_planes_f16(const void *zp, int rows, const float *W0, const floa
 size_t mlp_zplane_bytes(int rows);   // bytes of the plane form of `rows` z rows (padded to whole 64-row blocks)
 size_t mlp_zplane_row_bytes();   // MH_SZ
 
+// ---- dvm_rank.hip
+// f2 [B] = F^2 -> loss [B] = F and (g_val != NULL) g_val [B][E] *= num / F, 0 where F == 0: the last step of a Frobenius-norm term
+void launch_frob_finish(const float *f2, int B, size_t E, double num, float *loss, float *g_val, hipStream_t s);
+
 // ---- dvm_sa_f16.hip: fp16x2-split kernels of the SA attention core
 size_t sa_f16_carve(Arena &ar, int B, int N, _Float16 *&pp, _Float16 *&vp);   // the split planes of p and v, carved from the caller's arena
 void launch_sa_split_f16(const float *p, const float *v, int B, int N, _Float16 *pp, _Float16 *vp, hipStream_t s);

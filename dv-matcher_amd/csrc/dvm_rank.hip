@@ -23,11 +23,11 @@ namespace dvm {
 constexpr int RANK_MAX_N = 8192;    // the criterion's own gate; the row of S takes N fp32 words of LDS (32 KB at the limit)
 constexpr int RANK_THREADS = 256;   // block_tree_sum's width
 
-// ilogb(m) + 1 for the largest |term| m of slot t (the maximum over the workgroup's waves): every term of the slot is below 2^that
+// fix_unit_exp of the largest |term| of slot t (the maximum over the workgroup's waves): every term of the slot is below 2^that
 __device__ __forceinline__ int rank_unit_exp(const double (*gmax)[16], int t) {
     double m = gmax[0][t];
     for (int w = 1; w < RANK_THREADS / WAVE; ++w) m = fmax(m, gmax[w][t]);
-    return m > 0.0 && m < INFINITY ? ilogb(m) + 1 : 0;
+    return fix_unit_exp(m);
 }
 
 template <int K, bool GRAD>
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(RANK_THREADS) void rank_row_kernel(const float *__r
             const int end = send[t];
             for (int e = sbeg[t] + tid; e < end; e += RANK_THREADS) {
                 const int en = ed[e], r = en / topk;
-                mx[t] = fmax(mx[t], fabs(((double)S[r] - (r == i ? 1.0 : 0.0)) * (double)vb[en]));
+                mx[t] = fmax(mx[t], fabs(resid_term(S[r], r == i, vb[en])));
             }
         }
 #pragma unroll
@@ -100,11 +100,11 @@ __global__ __launch_bounds__(RANK_THREADS) void rank_row_kernel(const float *__r
     for (int t = 0; t < K; ++t) {
         Q[t] = 0;
         if (t < topk) {
-            const int sh = 50 - rank_unit_exp(gmax, t);
+            const int ue = rank_unit_exp(gmax, t);
             const int end = send[t];
             for (int e = sbeg[t] + tid; e < end; e += RANK_THREADS) {
                 const int en = ed[e], r = en / topk;
-                Q[t] += __double2ll_rn(ldexp(((double)S[r] - (r == i ? 1.0 : 0.0)) * (double)vb[en], sh));
+                Q[t] += fix_quant(resid_term(S[r], r == i, vb[en]), ue);
             }
         }
 #pragma unroll
@@ -115,19 +115,24 @@ __global__ __launch_bounds__(RANK_THREADS) void rank_row_kernel(const float *__r
     if (tid < topk) {
         long long q = 0;
         for (int w = 0; w < RANK_THREADS / WAVE; ++w) q += qred[w][tid];
-        g_val[(size_t)b * E + (size_t)i * topk + tid] = (float)(4.0 * ldexp((double)q, rank_unit_exp(gmax, tid) - 50));
+        g_val[(size_t)b * E + (size_t)i * topk + tid] = (float)(4.0 * fix_value(q, rank_unit_exp(gmax, tid)));
     }
 }
 
-// f2 [B] = F^2 -> loss [B] = F; g_val [B][E] = dF^2 / d pi_val -> dF / d pi_val = g_val / (2 F), 0 where F == 0
-__global__ void rank_finish_kernel(const float *__restrict__ f2, size_t E, float *__restrict__ loss, float *__restrict__ g_val) {
+// f2 [B] = F^2 -> loss [B] = F; g_val [B][E] *= num / F, 0 where F == 0 (num = 1/2: g_val = dF^2 / d pi_val -> dF / d pi_val)
+__global__ void rank_finish_kernel(const float *__restrict__ f2, size_t E, double num, float *__restrict__ loss, float *__restrict__ g_val) {
     const int b = blockIdx.y;
     const double F = sqrt((double)f2[b]);
     if (blockIdx.x == 0 && threadIdx.x == 0) loss[b] = (float)F;
     if (g_val == nullptr) return;
-    const double sc = F > 0.0 ? 0.5 / F : 0.0;
+    const double sc = F > 0.0 ? num / F : 0.0;
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < E; e += (size_t)gridDim.x * blockDim.x)
         g_val[(size_t)b * E + e] = (float)((double)g_val[(size_t)b * E + e] * sc);
+}
+
+void launch_frob_finish(const float *f2, int B, size_t E, double num, float *loss, float *g_val, hipStream_t s) {
+    const unsigned fblocks = g_val ? (unsigned)((E + 1023) / 1024) : 1u;
+    hipLaunchKernelGGL(rank_finish_kernel, dim3(fblocks, B), dim3(256), 0, s, f2, E, num, loss, g_val);
 }
 
 }  // namespace dvm
@@ -181,8 +186,7 @@ DVM_EXPORT int dvm_rank_term_f32(const float *pi_val, const int32_t *pi_idx, int
         RANK_LAUNCH(16, true);
 #undef RANK_LAUNCH
     launch_reduce_partials(w.partial, B, N, 1.f, w.f2, 1, 0, s);
-    const unsigned fblocks = g_val ? (unsigned)((E + 1023) / 1024) : 1u;
-    hipLaunchKernelGGL(rank_finish_kernel, dim3(fblocks, B), dim3(256), 0, s, w.f2, E, loss, g_val);
+    launch_frob_finish(w.f2, B, E, 0.5, loss, g_val, s);
     DVM_CHECK_LAUNCH("rank_term");
     return DVM_OK;
 }

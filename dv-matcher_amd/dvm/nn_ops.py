@@ -601,6 +601,30 @@ def rank_term(val, idx, M):
     return _RankTerm.apply(val, idx, M)
 
 
+class _CycleTerm(torch.autograd.Function):
+    """||P12 P21 - I||_F per batch element of a pair's two sparse correspondences on the HIP kernel (dvm_cycle_term_f32): the forward
+    call returns both gradients as well (the residual row is in LDS then), and the backward only scales them."""
+
+    @staticmethod
+    def forward(ctx, val12, idx12, val21, idx21):
+        loss, g12, g21 = ops.cycle_term(val12, idx12, val21, idx21, grad=True)
+        ctx.save_for_backward(g12, g21)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        g12, g21 = ctx.saved_tensors
+        return g12 * gout[:, None, None], None, g21 * gout[:, None, None], None
+
+
+def cycle_term(val12, idx12, val21, idx21):
+    """(B,) ||P12 P21 - I||_F of the sparse top-k correspondences val12 / idx12 (B,N,k12) and val21 / idx21 (B,M,k21), with autograd
+    w.r.t. val12 and val21 (0 where the term is 0).  Without grad it is ops.cycle_term: no gradient is formed."""
+    if not (torch.is_grad_enabled() and (val12.requires_grad or val21.requires_grad)):
+        return ops.cycle_term(val12, idx12, val21, idx21)
+    return _CycleTerm.apply(val12, idx12, val21, idx21)
+
+
 class _DistLoss(torch.autograd.Function):
     """dist-loss term (models/loss.py:1351-1396) per batch element: fused HIP forward; the backward builds the
     sparse (anchor, point) weights with a HIP kernel and finishes with two library GEMMs per batch."""

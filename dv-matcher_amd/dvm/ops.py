@@ -720,6 +720,34 @@ def rank_term(pi_val, pi_idx, M, grad=False):
     return (loss, g_val) if grad else loss
 
 
+def cycle_term_max_n():
+    """The largest N dvm_cycle_term_f32 takes (a row of P12 P21 must fit LDS); models.loss.cycle_term falls back to torch beyond it."""
+    return int(_lib.load().dvm_cycle_term_max_n())
+
+
+def cycle_term(val12, idx12, val21, idx21, grad=False):
+    """||P12 P21 - I_N||_F per batch element for the sparse top-k P12 (val12 / idx12 (B,N,k12), columns in [0, M)) and P21 (val21 /
+    idx21 (B,M,k21), columns in [0, N)); indices distinct within a row -> loss (B,), and with grad=True also g12 (B,N,k12) =
+    d loss[b] / d val12 and g21 (B,M,k21) = d loss[b] / d val21 (both 0 where loss[b] == 0).  dvm_cycle_term_f32: row by row, no
+    dense matrix, no float atomics.  Takes no part in autograd itself (nn_ops.cycle_term is the node)."""
+    _need_gpu(val12, idx12, val21, idx21)
+    val12, idx12, val21, idx21 = _f(val12), _i(idx12), _f(val21), _i(idx21)
+    if val12.dim() != 3 or val21.dim() != 3 or val12.shape[0] != val21.shape[0]:
+        raise ValueError("cycle_term: val12 (B,N,k12) and val21 (B,M,k21) must share B, got %s and %s" % (tuple(val12.shape), tuple(val21.shape)))
+    if idx12.shape != val12.shape or idx21.shape != val21.shape:
+        raise ValueError("cycle_term: idx12 / idx21 must have the shapes of val12 / val21, %s / %s, got %s / %s"
+                         % (tuple(val12.shape), tuple(val21.shape), tuple(idx12.shape), tuple(idx21.shape)))
+    B, N, k12 = val12.shape
+    M, k21 = val21.shape[1], val21.shape[2]
+    dev = val12.device
+    loss = _new(dev, B)
+    g12 = torch.empty_like(val12) if grad else None
+    g21 = torch.empty_like(val21) if grad else None
+    _call_ws("dvm_cycle_term_f32", (_p(val12), _p(idx12), _p(val21), _p(idx21), B, N, M, k12, k21, _p(loss), _p(g12), _p(g21)),
+             dev, "cycle", "dvm_cycle_term_workspace_bytes", B, N, M, k12, k21)
+    return (loss, g12, g21) if grad else loss
+
+
 def _pair_out(B, n, dev):
     """One direction's outputs of the pair calls: dict(warped, verts12, T12, losses[B,6])."""
     return dict(warped=_new(dev, B, n, 3), verts12=_new(dev, B, n, 3), T12=_new(dev, B, n, dtype=torch.int32), losses=_new(dev, B, 6))

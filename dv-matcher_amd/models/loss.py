@@ -178,6 +178,31 @@ def rank_term(pval, pidx, M):
     return _rank_term_torch(pval, pidx, M)
 
 
+def _cycle_term_torch(pval12, pidx12, pval21, pidx21):
+    """cycle_term with plain torch ops, for what the kernel does not take (CPU tensors, other dtypes, N over its limit): the
+    definition in float64 on dense arrays (P12 N x M, P21 M x N, their N x N product), rounded once to fp32.  The gradient where
+    the term is 0 is 0, as the kernel's."""
+    B, N, _ = pval12.shape
+    M = pval21.shape[1]
+    P12 = torch.zeros(B, N, M, dtype=torch.float64, device=pval12.device).scatter_add(-1, pidx12.long(), pval12.double())
+    P21 = torch.zeros(B, M, N, dtype=torch.float64, device=pval21.device).scatter_add(-1, pidx21.long(), pval21.double())
+    R = torch.bmm(P12, P21)
+    R.diagonal(dim1=1, dim2=2).sub_(1.0)
+    return _SafeSqrt.apply(R.square().flatten(1).sum(1)).float()
+
+
+def cycle_term(pval12, pidx12, pval21, pidx21):
+    """||P12 P21 - I_N||_F per batch element for the two sparse top-k correspondences of a pair, P12 (val/idx (B,N,k12), M columns)
+    and P21 (val/idx (B,M,k21), N columns): 0 where the two maps are mutual inverses; N != M is allowed (not in the reference).
+    Differentiable w.r.t. both pval; the gradient where the term is 0 is 0.  CUDA float32 input within the kernel's limits
+    (N <= ops.cycle_term_max_n(), k <= 16) runs on dvm_cycle_term_f32 (nn_ops.cycle_term: row by row, no dense array, no float
+    atomics); anything else on the torch formula of _cycle_term_torch, which forms dense float64 arrays."""
+    if (all(p.is_cuda and p.dtype == torch.float32 and p.dim() == 3 and 1 <= p.shape[2] <= 16 for p in (pval12, pval21))
+            and pval12.shape[0] >= 1 and 1 <= pval12.shape[1] <= ops.cycle_term_max_n() and pval21.shape[1] >= 1):
+        return nn_ops.cycle_term(pval12, pidx12, pval21, pidx21)
+    return _cycle_term_torch(pval12, pidx12, pval21, pidx21)
+
+
 class GraphDeformLoss_Neural(nn.Module):
     partial_variant = False
 
@@ -207,6 +232,11 @@ class GraphDeformLoss_Neural(nn.Module):
         # with sinkhorn_iters > 0: (tau_row, tau_col) of the unbalanced operator (ops.sinkhorn_unbalanced: rows without a partner
         # keep little mass); None or (1, 1) = the balanced operator, on exactly the paths of sinkhorn_iters alone
         self.sinkhorn_tau = None
+        # opt-in: weight of the cycle term ||Pi12 Pi21 - I||_F (cycle_term; not in the reference), which ties the two directions'
+        # correspondences together and, unlike the rank term, takes N != M.  0 = off, on exactly the paths above; > 0 takes the
+        # paths w_rank > 0 takes (the term stays on the per-op path)
+        self.w_cycle = 0
+        self.cycle_loss = 0
 
     def _identity6(self, device):
         """[1,0,0,0,1,0]: the identity rotation in the 6D parametrisation (models/loss.py:1258-1262), made once per device."""
@@ -275,7 +305,7 @@ class GraphDeformLoss_Neural(nn.Module):
         instead of batch scalars (for a caller that has merged several calls into one batch)."""
         B, N, _ = verts1.shape
         M = verts2.shape[1]
-        if (self.native_train and self.sinkhorn_iters <= 0 and not per_pair and not self.dump and self.w_rank <= 0 and feat1.is_cuda and feat1.dtype == torch.float32
+        if (self.native_train and self.sinkhorn_iters <= 0 and not per_pair and not self.dump and self.w_rank <= 0 and self.w_cycle <= 0 and feat1.is_cuda and feat1.dtype == torch.float32
                 and feat2.dtype == torch.float32 and feat1.shape[-1] == 128 and 64 <= N <= 8192 and 64 <= M <= 8192 and self.k_deform <= 16
                 and idx11.shape[-1] == self.k_deform and all(torch.is_tensor(g1[k]) for k in ("nodes_idx", "one_ring", "infl_idx", "weights"))
                 and all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() for p in deformer.parameters())):
@@ -464,7 +494,7 @@ class GraphDeformLoss_Neural(nn.Module):
         native_dist = False
         if self.w_deform > 0 or not self.partial_variant:
             g1, g2, idx11, idx22 = geometry if geometry is not None else self.geometry(verts1, verts2, fps_starts, shape_ids)
-            merged = (train and N == M and not self.dump and not self.partial_variant and self.w_rank <= 0
+            merged = (train and N == M and not self.dump and not self.partial_variant and self.w_rank <= 0 and self.w_cycle <= 0
                       and all(torch.is_tensor(g1[k]) for k in g1))
             native = (merged and self.native_train and self.sinkhorn_iters <= 0 and feat1.is_cuda and feat1.dtype == torch.float32 and feat1.shape[-1] == 128 and N % 4 == 0
                       and 64 <= N <= 8192 and self.k_deform <= 16 and idx11.shape[-1] == self.k_deform
@@ -555,6 +585,11 @@ class GraphDeformLoss_Neural(nn.Module):
                                   rank_term(ex21["pval"], ex21["pidx"], N).mean()) * self.w_rank / 2
                 loss = loss + self.rank_loss
                 self._mean_part = self._mean_part + self.rank_loss
+            if self.w_cycle > 0:
+                self.cycle_loss = (cycle_term(ex12["pval"], ex12["pidx"], ex21["pval"], ex21["pidx"]).mean() +
+                                   cycle_term(ex21["pval"], ex21["pidx"], ex12["pval"], ex12["pidx"]).mean()) * self.w_cycle / 2
+                loss = loss + self.cycle_loss
+                self._mean_part = self._mean_part + self.cycle_loss
         return loss, self.dist_loss, self.deform_loss, self.map_loss, self.self_rec_loss
 
     def data_parallel_loss(self, fraction):

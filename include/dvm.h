@@ -351,6 +351,35 @@ size_t dvm_rank_term_workspace_bytes(int B, int N, int M, int topk);
 int dvm_rank_term_f32(const float *pi_val, const int32_t *pi_idx, int B, int N, int M, int topk, float *loss,
                       float *g_val /* may be NULL */, void *ws, size_t ws_bytes, void *stream);
 
+/* The cycle term of a pair's two correspondences (not in the reference, whose loss terms each look at one direction):
+ * loss[b] = ||P12 P21 - I_N||_F for the sparse top-k P12 [N,M] given as val12 / idx12 [B,N,k12] (columns in [0, M)) and
+ * P21 [M,N] given as val21 / idx21 [B,M,k21] (columns in [0, N)); N != M is allowed.  With C = P12 P21 (N x N), R = C - I_N and
+ * F = ||R||_F, the gradients (g12, g21: both NULL or both given) are
+ *   g12[i,t] = d F / d val12[i,t] = (1/F) sum_s R[i, idx21[j,s]] val21[j,s],   j = idx12[i,t]
+ *   g21[j,s] = d F / d val21[j,s] = (1/F) sum_{(i,t): idx12[i,t] = j} val12[i,t] R[i, idx21[j,s]]
+ * and both are exactly 0 where F == 0 (the two maps are mutual inverses), torch.norm's gradient at zero.
+ * PRECONDITION: the indices of a row are distinct within the row — what every top-k producer of this library emits.  An index
+ * outside its range contributes nothing (to C or to either gradient; it never becomes an address), and a slot whose value is 0
+ * is skipped when C is formed, so the repeated (0, 0) slots of a row with fewer columns than topk are harmless.  Values need not
+ * be normalised.
+ * No dense array is formed.  One workgroup per row i keeps row i of C in LDS (fp32, every entry an fma chain of at most k12 terms
+ * in slot order: C[i,c] += val12[i,t] val21[j,s] at c = idx21[j,s]), reduces the squared residual in float64 and, for the
+ * gradients, adds g12[i,t]'s k21 terms in slot order in float64 and leaves the k12 k21 entries C[i, idx21[idx12[i,t], s]] in the
+ * workspace.  g21 needs one of them from every row that picks column j: one wave per column walks the reversed list of idx12
+ * (as dvm_softcorr_apply_bwd_f32's) and sums in 64-bit fixed point, units of 2^-50 of the list's largest term, found by a first
+ * walk, so the order of the list, which integer atomics set, cannot reach the result (as dvm_rank_term_f32's gradient).  Row
+ * sums are reduced per batch element in float64, fixed order; loss = sqrt(F^2), both gradients are scaled by 1 / F.
+ * The loss-only call builds no lists and leaves no samples, and gives the loss bits of the call with gradients.
+ * Memory: the workspace only, 4 B (2 M + N k12) + 8 B N + 4 B N k12 k21 bytes — no N x N, N x M or M x M array.  No float
+ * atomics, no host synchronisation, capturable, the same bits from run to run and for a batch element alone or in a batch.
+ * Limits: N <= dvm_cycle_term_max_n() (8192: the row must fit LDS), any M, 1 <= k12, k21 <= 16, B <= 65535.  Outside them
+ * dvm_cycle_term_workspace_bytes returns 0 and dvm_cycle_term_f32 DVM_EINVAL, before any launch. */
+int dvm_cycle_term_max_n(void);
+size_t dvm_cycle_term_workspace_bytes(int B, int N, int M, int k12, int k21);
+int dvm_cycle_term_f32(const float *val12, const int32_t *idx12, const float *val21, const int32_t *idx21, int B, int N, int M,
+                       int k12, int k21, float *loss, float *g12 /* may be NULL */, float *g21 /* may be NULL */, void *ws,
+                       size_t ws_bytes, void *stream);
+
 /* farthest_point_sample — lib/deformation_graph_point.py:18-33 with the random
  * start index made an input.  xyz [B,N,3], start [B] -> out [B,npoint]. */
 int dvm_fps_f32(const float *xyz, int B, int N, int npoint, const int32_t *start, int32_t *out, void *stream);
