@@ -12,13 +12,11 @@
 // (k-deinterleaved so an MFMA A-fragment is one ds_read_b128 per 4 k-steps), weights pre-packed
 // into the MFMA B-fragment order so each k-step is one coalesced 256-B load per wave.  The
 // accumulation is the same k-ordered fma chain as the oracle's (and torch's CPU addmm).
-#include "dvm_common.h"
+#include "dvm_mfma_tile.h"
 #include "dvm_mlp_f16.h"
 
 namespace dvm {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int DF_C = 128;
 
@@ -363,7 +361,7 @@ __device__ __forceinline__ void mlp_store(const f32x16 &acc, const float *__rest
     const float bv = o < O ? bias[o] : 0.f;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        int node = (r & 3) + 8 * (r >> 2) + 4 * h;
+        int node = lane_key(r, h);
         float v = acc[r] + bv;
         v = act ? elu1(v) : v;
         if (o < O) dst[node * stride + (o & 1) * half + (o >> 1)] = v;
@@ -421,7 +419,7 @@ __global__ __launch_bounds__(ML_THREADS) void mlp_mfma_kernel(const float *__res
         const float bv = o < 9 ? b3[o] : 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            int node = (r & 3) + 8 * (r >> 2) + 4 * h;
+            int node = lane_key(r, h);
             if (o < 9 && row0 + node < rows) out[(size_t)(row0 + node) * 9 + o] = acc[r] + bv;
         }
     }

@@ -40,12 +40,10 @@
 // two_role_sweep below is that loop.
 #pragma once
 
-#include "dvm_common.h"
+#include "dvm_mfma_tile.h"
 
 namespace dvm {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr float LOG2E = 1.4426950408889634f;
 
@@ -57,7 +55,6 @@ constexpr int LDK = D + 4;           // padded row (floats)
 constexpr int ROWS_FLOATS = KT * LDK;   // the key rows of one tile; a kernel's [KT] sidecar planes follow
 
 // entry r of half h of an accumulator <-> key of the 32-key sub-tile
-__device__ __forceinline__ int lane_key(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
 // B-operand fragment of a lane's own row: q[s] = -2 * row[2s + h]
 __device__ __forceinline__ void load_query_frag(const float *row, int h, float (&q)[D / 2]) {

@@ -20,14 +20,12 @@
 // are far below their limits: the kernel is bound by MFMA issue.
 #include <stdint.h>
 
-#include "dvm_common.h"
+#include "dvm_mfma_tile.h"
 
 #include <stdlib.h>
 
 namespace dvm {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int GK = 32;       // k-step
 constexpr int GLD = GK + 4;  // LDS row stride of a [row][evens | odds] tile
@@ -649,7 +647,7 @@ __global__ __launch_bounds__(256, 2) void linear_wgrad_kernel(const float *__res
     const int k = k0 + wj * 32 + r32;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int co = co0 + wi * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+        const int co = co0 + wi * 32 + lane_key(r, h);
         if (co < Co && k < K) {
             if (DET)
                 dW[((size_t)blockIdx.y * Co + co) * K + k] = acc[r];   // dW = the scratch: [chunk][Co][K]

@@ -1,12 +1,13 @@
 // dvm_internal.h — every dvm:: function that one translation unit of libdvm_hip.so defines and another one calls, declared
-// ONCE, grouped by the file that defines it; default arguments appear here and nowhere else.  Included at the end of
+// ONCE, grouped by the file that defines it (with the workspace struct or constants its callers need); default arguments appear
+// here and nowhere else.  Included at the end of
 // dvm_common.h: no .hip file declares a function it does not define.  (The K1 sweep's launchers, whose signatures need its
 // argument structs, are in dvm_softcorr_f16.h; set_error / prof_* / options and their kin, defined in dvm_api.cpp, in dvm_common.h.)
 #pragma once
 
 namespace dvm {
 
-// ---- dvm_backbone.hip
+// ---- dvm_dist_loss.hip
 // dvm_dist_loss_fwd_f32 with the sum at out[b * out_stride + out_off]; idx_out, xsave ([B][nA][k] x 2: x_j, y_j), fa_out: NULL or kept for the backward
 int launch_dist_loss_fwd(const float *feat, const float *dist, const int32_t *anchors, int B, int N, int C, int nA, int k, float *out, int out_stride,
                          int out_off, int32_t *idx_out, float *xsave, float *fa_out, void *ws, size_t ws_bytes, hipStream_t s);
@@ -97,6 +98,15 @@ void launch_grid_infl(const float *xyz, int B, int N, const GridBuf &gnodes, con
                       hipStream_t s);
 void launch_grid_chamfer(const GridBuf *gq, const GridBuf *gb, float *const *dout, int32_t *const *iout, int ngroups, int B, hipStream_t s);
 
+// ---- dvm_knn.hip
+// idx [B][N][k] = the k largest of s_ij = -|a_i - b_j|^2 per row of a [B][N][C] against bq [B][M][C], ties to the lower column; na, nb, S: scratch
+int launch_knn_neg(const float *a, const float *bq, int B, int N, int M, int C, int k, int32_t *idx, float *na, float *nb, float *S, hipStream_t s);
+// that scratch: the norms of both sides and the scores [B][N][M]
+struct KnnNegWs {
+    float *na, *nb, *S;
+};
+size_t carve_knn_neg(Arena &ar, int B, int N, int M, KnnNegWs &w);
+
 // ---- dvm_loss_bwd.hip
 void launch_dg_warp_arap_bwd(const float *xyz, int B, int N, const int32_t *nodes_idx, const int32_t *ring, const int32_t *infl_idx, const float
                              *weights, const float *R, const float *T, const float *g_warped, const float *g_arap, int garap_stride, float *d_R, float
@@ -122,6 +132,9 @@ size_t mlp_zplane_row_bytes();   // MH_SZ
 // ---- dvm_rank.hip
 // f2 [B] = F^2 -> loss [B] = F and (g_val != NULL) g_val [B][E] *= num / F, 0 where F == 0: the last step of a Frobenius-norm term
 void launch_frob_finish(const float *f2, int B, size_t E, double num, float *loss, float *g_val, hipStream_t s);
+
+// ---- the SA attention core (dvm_sa.hip, dvm_sa_bwd.hip): channels of p and of v, padded p row of the staged tiles (floats)
+constexpr int SA_P = 16, SA_C = 64, SA_LDP = 20;
 
 // ---- dvm_sa_f16.hip: fp16x2-split kernels of the SA attention core
 size_t sa_f16_carve(Arena &ar, int B, int N, _Float16 *&pp, _Float16 *&vp);   // the split planes of p and v, carved from the caller's arena

@@ -9,12 +9,10 @@
 // same accuracy class as an fp32 chain (reference models/model.py:433-452, 476-477; floats only, no
 // integer output depends on it).  Activations live pre-split in LDS (three bf16 planes per node),
 // weights are pre-split and packed in B-fragment order, one 16-B load per lane, plane and k-step.
-#include "dvm_common.h"
+#include "dvm_mfma_tile.h"
 
 namespace dvm {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int MB_NODES = 32, MB_WAVES = 8, MB_THREADS = 64 * MB_WAVES;
@@ -104,7 +102,7 @@ __device__ __forceinline__ void mlp_store_bf16(const f32x16 &acc, const float *_
     const float bv = bias[o];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int node = (r & 3) + 8 * (r >> 2) + 4 * hh;
+        const int node = lane_key(r, hh);
         __bf16 h, m, l;
         split3(elu_fast(acc[r] + bv), h, m, l);
         char *p = dst + node * stride + 2 * o;
@@ -175,7 +173,7 @@ __global__ __launch_bounds__(MB_THREADS) void mlp_bf16x3_kernel(const float *__r
         const float bv = o < 9 ? b3[o] : 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int node = (r & 3) + 8 * (r >> 2) + 4 * hh;
+            const int node = lane_key(r, hh);
             if (o < 9 && row0 + node < rows) out[(size_t)(row0 + node) * 9 + o] = acc[r] + bv;
         }
     }

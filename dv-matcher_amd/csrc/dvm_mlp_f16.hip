@@ -19,13 +19,11 @@
 // (reference models/model.py:433-452, 476-477; floats only, no integer output depends on it)
 #include <stdlib.h>
 
-#include "dvm_common.h"
+#include "dvm_mfma_tile.h"
 #include "dvm_mlp_f16.h"
 
 namespace dvm {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 namespace {

@@ -1,5 +1,5 @@
 // dvm_sa_f16.hip — SA_Layer attention core (models/model.py:113-121) with both contractions on the 16-bit matrix cores.
-// The fp32-MFMA kernels (dvm_backbone.hip) spend 40 matrix instructions of 64 cycles per 32x32 tile; here every
+// The fp32-MFMA kernels (dvm_sa.hip) spend 40 matrix instructions of 64 cycles per 32x32 tile; here every
 // operand is split into two fp16 planes (x = h + m, |x - h - m| <= 2^-22 |x|) and each contraction runs as three
 // products hh + hm + mh of the 32x32x16 fp16 instruction, accumulated in fp32:
 //   E tile      : p has 16 channels = exactly one k-step            -> 3 instructions (was 8 of the fp32 kind)
@@ -12,12 +12,10 @@
 //                                             back as the B operand with k-slot (step s, half hh, j) = register 8s + j,
 //                                             and V^T is stored with its keys permuted to the same slots
 //                                             (pos = 16 s + 8 hh + j), so nothing moves between the two contractions.
-#include "dvm_common.h"
+#include "dvm_mfma_tile.h"
 
 namespace dvm {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
@@ -97,7 +95,7 @@ __global__ __launch_bounds__(256) void sa_rowstats_f16_kernel(const _Float16 *__
         float tmax = -INFINITY;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int j = j0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+            const int j = j0 + lane_key(r, h);
             const float e = j < N ? acc[r] : -INFINITY;
             acc[r] = e;
             tmax = fmaxf(tmax, e);
@@ -240,7 +238,7 @@ __global__ __launch_bounds__(256) void sa_apply_f16_kernel(const _Float16 *__res
             const float *src = red + r * 64 + lane;
             const float sum = (src[0] + src[32 * 64]) + (src[2 * 32 * 64] + src[3 * 32 * 64]);
             const int rr = r & 15;
-            o[(r >> 4) * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * h] = sum * inv;
+            o[(r >> 4) * 32 + lane_key(rr, h)] = sum * inv;
         }
     }
 }

@@ -321,7 +321,7 @@ __global__ __launch_bounds__(64 * W, 8 / W) void softcorr_coarse_kernel(const HC
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             v[r] = (__float_as_uint(acc[r]) << 4) + ((unsigned)r - (HC_KBASE << 4));   // one v_lshl_add_u32
-            if (mask_pads) v[r] = jb + (r & 3) + 8 * (r >> 2) < M ? v[r] : (HC_REMOVED | r);
+            if (mask_pads) v[r] = jb + lane_key(r, 0) < M ? v[r] : (HC_REMOVED | r);
         }
     };
     const unsigned h4 = (unsigned)h << 4;

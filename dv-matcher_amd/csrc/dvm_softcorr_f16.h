@@ -1,13 +1,11 @@
 // dvm_softcorr_f16.h — what the two translation units of the fp16-split soft-correspondence sweep share
 // (dvm_softcorr_f16.hip: splitting, first form of pass A, pass B, launchers; dvm_softcorr_coarse.hip: the one-plane screen).
 #pragma once
-#include "dvm_common.h"
+#include "dvm_mfma_tile.h"
 
 namespace dvm {
 namespace k1 {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 

@@ -632,7 +632,7 @@ def test_n2p_core_poisoned_scratch(ops, monkeypatch, deterministic, C, K, N):
     assert rel(got["out[2]"], x.grad) < 1e-5
 
 
-@pytest.mark.parametrize("B,N", [(2, 300), (3, 77), (1, 1000)])
+@pytest.mark.parametrize("B,N", [(2, 300), (3, 77), (1, 1000), (1, 1100)])
 def test_sa_attention_poisoned_scratch(ops, monkeypatch, deterministic, B, N):
     """Eval and training forms and the backward, against tests/test_gpu_backward.py::test_sa_core_fwd_bwd_vs_fp64_autograd's
     fp64 formulation (models/model.py:113-121)."""

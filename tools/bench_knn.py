@@ -1,5 +1,6 @@
-"""Feature-space self-kNN (dvm_knn_neg_f32, k = 40): the fp16-sweep path (a is b) against the dense N x N path (b a copy of a:
-the library cannot know they are equal) — same indices, time per call."""
+"""Feature-space self-kNN (dvm_knn_neg_f32, k = 40), time per call.  Both calls take the same route through launch_knn_neg (row
+norms, fp32 score tiles into the N x N score matrix, top-k per row); with `a is b` the library computes one set of row norms, with
+b a copy of a (the library cannot know they are equal) two — same indices either way."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "dv-matcher_amd"))
@@ -26,4 +27,4 @@ for kind in ("randn", "relu", "clustered", "duplicates"):
         same = bool(torch.equal(a, b))
         bad = int((a != b).any(-1).sum())
         t1, t2 = timeit(lambda: ops.knn_neg(x, x, 40)), timeit(lambda: ops.knn_neg(x, y, 40))
-        print("%-10s B=%d N=%d C=%d: equal %s (%d rows differ)   sweep path %.1f us   dense path %.1f us" % (kind, B, N, C, same, bad, t1 * 1e6, t2 * 1e6))
+        print("%-10s B=%d N=%d C=%d: equal %s (%d rows differ)   a is b %.1f us   b a copy %.1f us" % (kind, B, N, C, same, bad, t1 * 1e6, t2 * 1e6))
