@@ -625,6 +625,32 @@ def cycle_term(val12, idx12, val21, idx21):
     return _CycleTerm.apply(val12, idx12, val21, idx21)
 
 
+class _DistortionTerm(torch.autograd.Function):
+    """||P D2 P^T - D1||_F per batch element of the sparse top-k P on the HIP kernel (dvm_distortion_term_f32): the forward call
+    returns the gradient in val as well (the residual row is in LDS then), and the backward only scales it.  The distance matrices
+    are constants."""
+
+    @staticmethod
+    def forward(ctx, val, idx, dist_src, dist_tgt):
+        loss, g_val = ops.distortion_term(val, idx, dist_src, dist_tgt, grad=True)
+        ctx.save_for_backward(g_val)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        g_val, = ctx.saved_tensors
+        return g_val * gout[:, None, None], None, None, None
+
+
+def distortion_term(val, idx, dist_src, dist_tgt):
+    """(B,) ||P D2 P^T - D1||_F of the sparse top-k correspondence val / idx (B,N,k) against the symmetric distance matrices
+    dist_src (B,N,N) and dist_tgt (B,M,M), with autograd w.r.t. val only (0 where the term is 0).  Without grad it is
+    ops.distortion_term: no gradient is formed."""
+    if not (torch.is_grad_enabled() and val.requires_grad):
+        return ops.distortion_term(val, idx, dist_src, dist_tgt)
+    return _DistortionTerm.apply(val, idx, dist_src, dist_tgt)
+
+
 class _DistLoss(torch.autograd.Function):
     """dist-loss term (models/loss.py:1351-1396) per batch element: fused HIP forward; the backward builds the
     sparse (anchor, point) weights with a HIP kernel and finishes with two library GEMMs per batch."""

@@ -748,6 +748,35 @@ def cycle_term(val12, idx12, val21, idx21, grad=False):
     return (loss, g12, g21) if grad else loss
 
 
+def distortion_term_max_n():
+    """The largest N and M dvm_distortion_term_f32 takes (the rows it keeps must fit LDS); models.loss.distortion_term falls back to
+    torch beyond it."""
+    return int(_lib.load().dvm_distortion_term_max_n())
+
+
+def distortion_term(val, idx, dist_src, dist_tgt, grad=False):
+    """||P D2 P^T - D1||_F per batch element for the sparse top-k P (val / idx (B,N,k), columns in [0, M), distinct within a row),
+    D1 = dist_src (B,N,N) and D2 = dist_tgt (B,M,M), both SYMMETRIC (not checked) -> loss (B,), and with grad=True also g_val
+    (B,N,k) = d loss[b] / d val (0 where loss[b] == 0).  dvm_distortion_term_f32: row by row, no dense product, no float atomics.
+    Takes no part in autograd itself (nn_ops.distortion_term is the node)."""
+    _need_gpu(val, idx, dist_src, dist_tgt)
+    val, idx, dist_src, dist_tgt = _f(val), _i(idx), _f(dist_src), _f(dist_tgt)
+    if val.dim() != 3 or idx.shape != val.shape:
+        raise ValueError("distortion_term: val and idx must share a shape (B,N,k), got %s and %s" % (tuple(val.shape), tuple(idx.shape)))
+    B, N, topk = val.shape
+    if dist_src.dim() != 3 or tuple(dist_src.shape) != (B, N, N):
+        raise ValueError("distortion_term: dist_src must be %s, got %s" % ((B, N, N), tuple(dist_src.shape)))
+    if dist_tgt.dim() != 3 or dist_tgt.shape[0] != B or dist_tgt.shape[1] != dist_tgt.shape[2]:
+        raise ValueError("distortion_term: dist_tgt must be (%d,M,M), got %s" % (B, tuple(dist_tgt.shape)))
+    M = dist_tgt.shape[1]
+    dev = val.device
+    loss = _new(dev, B)
+    g_val = torch.empty_like(val) if grad else None
+    _call_ws("dvm_distortion_term_f32", (_p(val), _p(idx), _p(dist_src), _p(dist_tgt), B, N, M, topk, _p(loss), _p(g_val)),
+             dev, "distortion", "dvm_distortion_term_workspace_bytes", B, N, M, topk)
+    return (loss, g_val) if grad else loss
+
+
 def _pair_out(B, n, dev):
     """One direction's outputs of the pair calls: dict(warped, verts12, T12, losses[B,6])."""
     return dict(warped=_new(dev, B, n, 3), verts12=_new(dev, B, n, 3), T12=_new(dev, B, n, dtype=torch.int32), losses=_new(dev, B, 6))

@@ -203,6 +203,39 @@ def cycle_term(pval12, pidx12, pval21, pidx21):
     return _cycle_term_torch(pval12, pidx12, pval21, pidx21)
 
 
+def _symmetrised(dist):
+    """(D + D^T) / 2 of a batch of square matrices: exactly symmetric in fp32 (the sum commutes, the halving is exact)."""
+    return 0.5 * (dist + dist.transpose(1, 2))
+
+
+def _distortion_term_torch(pval, pidx, dist_src, dist_tgt):
+    """distortion_term with plain torch ops, for what the kernel does not take (CPU tensors, other dtypes, N or M over its limit):
+    the definition in float64 on dense arrays (P N x M, P D2 N x M, the N x N product), rounded once to fp32.  The distance matrices
+    are constants; the gradient where the term is 0 is 0, as the kernel's."""
+    B, N, _ = pval.shape
+    M = dist_tgt.shape[1]
+    P = torch.zeros(B, N, M, dtype=torch.float64, device=pval.device).scatter_add(-1, pidx.long(), pval.double())
+    R = torch.bmm(torch.bmm(P, dist_tgt.detach().double()), P.transpose(1, 2)) - dist_src.detach().double()
+    return _SafeSqrt.apply(R.square().flatten(1).sum(1)).float()
+
+
+def distortion_term(pval, pidx, dist_src, dist_tgt, symmetric=False):
+    """||P D2 P^T - D1||_F per batch element for the sparse top-k correspondence P (val/idx (B,N,k), M columns), the source shape's
+    distance matrix D1 = dist_src (B,N,N) and the target's D2 = dist_tgt (B,M,M): the metric distortion of the map, 0 for an
+    isometry; N != M is allowed (not in the reference).  The term is defined on symmetric matrices: symmetric=False takes
+    (D + D^T) / 2 of both first (heat-method geodesics and a matmul-form cdist are symmetric only to rounding), symmetric=True is
+    the caller's promise that they already are, bit for bit.  Differentiable w.r.t. pval only; the gradient where the term is 0 is
+    0.  CUDA float32 input within the kernel's limits (N, M <= ops.distortion_term_max_n(), k <= 16) runs on
+    dvm_distortion_term_f32 (nn_ops.distortion_term: row by row, no dense product, no float atomics); anything else on the torch
+    formula of _distortion_term_torch, which forms dense float64 arrays."""
+    if not symmetric:
+        dist_src, dist_tgt = _symmetrised(dist_src), _symmetrised(dist_tgt)
+    if (all(t.is_cuda and t.dtype == torch.float32 and t.dim() == 3 for t in (pval, dist_src, dist_tgt)) and pval.shape[0] >= 1
+            and 1 <= pval.shape[2] <= 16 and all(1 <= n <= ops.distortion_term_max_n() for n in (pval.shape[1], dist_tgt.shape[1]))):
+        return nn_ops.distortion_term(pval, pidx, dist_src, dist_tgt)
+    return _distortion_term_torch(pval, pidx, dist_src, dist_tgt)
+
+
 class GraphDeformLoss_Neural(nn.Module):
     partial_variant = False
 
@@ -237,6 +270,11 @@ class GraphDeformLoss_Neural(nn.Module):
         # paths w_rank > 0 takes (the term stays on the per-op path)
         self.w_cycle = 0
         self.cycle_loss = 0
+        # opt-in: weight of the geodesic distortion term ||Pi D_target Pi^T - D_source||_F of both directions (distortion_term; not
+        # in the reference), on the symmetrised dist1 / dist2 the criterion is handed anyway; N != M is allowed.  0 = off, on
+        # exactly the paths above; > 0 takes the paths w_cycle > 0 takes
+        self.w_distortion = 0
+        self.distortion_loss = 0
 
     def _identity6(self, device):
         """[1,0,0,0,1,0]: the identity rotation in the 6D parametrisation (models/loss.py:1258-1262), made once per device."""
@@ -305,7 +343,7 @@ class GraphDeformLoss_Neural(nn.Module):
         instead of batch scalars (for a caller that has merged several calls into one batch)."""
         B, N, _ = verts1.shape
         M = verts2.shape[1]
-        if (self.native_train and self.sinkhorn_iters <= 0 and not per_pair and not self.dump and self.w_rank <= 0 and self.w_cycle <= 0 and feat1.is_cuda and feat1.dtype == torch.float32
+        if (self.native_train and self.sinkhorn_iters <= 0 and not per_pair and not self.dump and self.w_rank <= 0 and self.w_cycle <= 0 and self.w_distortion <= 0 and feat1.is_cuda and feat1.dtype == torch.float32
                 and feat2.dtype == torch.float32 and feat1.shape[-1] == 128 and 64 <= N <= 8192 and 64 <= M <= 8192 and self.k_deform <= 16
                 and idx11.shape[-1] == self.k_deform and all(torch.is_tensor(g1[k]) for k in ("nodes_idx", "one_ring", "infl_idx", "weights"))
                 and all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() for p in deformer.parameters())):
@@ -459,6 +497,8 @@ class GraphDeformLoss_Neural(nn.Module):
         self._sum_part = self._mean_part = 0
         B, N, _ = verts1.shape
         M = verts2.shape[1]
+        if self.w_distortion > 0 and (dist1 is None or dist2 is None):
+            raise ValueError("w_distortion > 0 needs both distance matrices (dist1, dist2)")
         train = torch.is_grad_enabled() and (feat1.requires_grad or feat2.requires_grad or
                                              any(p.requires_grad for p in deformer.parameters()))
         dist_term = self._dist_term_train if train else self._dist_term
@@ -495,7 +535,7 @@ class GraphDeformLoss_Neural(nn.Module):
         if self.w_deform > 0 or not self.partial_variant:
             g1, g2, idx11, idx22 = geometry if geometry is not None else self.geometry(verts1, verts2, fps_starts, shape_ids)
             merged = (train and N == M and not self.dump and not self.partial_variant and self.w_rank <= 0 and self.w_cycle <= 0
-                      and all(torch.is_tensor(g1[k]) for k in g1))
+                      and self.w_distortion <= 0 and all(torch.is_tensor(g1[k]) for k in g1))
             native = (merged and self.native_train and self.sinkhorn_iters <= 0 and feat1.is_cuda and feat1.dtype == torch.float32 and feat1.shape[-1] == 128 and N % 4 == 0
                       and 64 <= N <= 8192 and self.k_deform <= 16 and idx11.shape[-1] == self.k_deform
                       and all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() for p in deformer.parameters()))
@@ -590,6 +630,12 @@ class GraphDeformLoss_Neural(nn.Module):
                                    cycle_term(ex21["pval"], ex21["pidx"], ex12["pval"], ex12["pidx"]).mean()) * self.w_cycle / 2
                 loss = loss + self.cycle_loss
                 self._mean_part = self._mean_part + self.cycle_loss
+            if self.w_distortion > 0:
+                sym1, sym2 = _symmetrised(dist1), _symmetrised(dist2)   # once per call, for both directions
+                self.distortion_loss = (distortion_term(ex12["pval"], ex12["pidx"], sym1, sym2, symmetric=True).mean() +
+                                        distortion_term(ex21["pval"], ex21["pidx"], sym2, sym1, symmetric=True).mean()) * self.w_distortion / 2
+                loss = loss + self.distortion_loss
+                self._mean_part = self._mean_part + self.distortion_loss
         return loss, self.dist_loss, self.deform_loss, self.map_loss, self.self_rec_loss
 
     def data_parallel_loss(self, fraction):

@@ -230,6 +230,10 @@ def main(argv=None):
     ap.add_argument("--w-cycle", type=float, default=0.0, metavar="W",
                     help="weight of the cycle term ||Pi12 Pi21 - I||_F between the two directions' correspondences (criterion.w_cycle = W, "
                          "models.loss.cycle_term; not in the reference; the criterion leaves its native nodes for the per-op path).  0: off")
+    ap.add_argument("--w-distortion", type=float, default=0.0, metavar="W",
+                    help="weight of the geodesic distortion term ||Pi D_target Pi^T - D_source||_F of both directions (criterion.w_distortion = W, "
+                         "models.loss.distortion_term on the symmetrised distance matrices; not in the reference; the criterion leaves its "
+                         "native nodes for the per-op path).  0: off")
     ap.add_argument("--graph", action="store_true", help="timing mode, one rank: capture the whole step (forward, criterion, backward, "
                     "Adam) into ONE HIP graph and replay it — ~2000 kernel launches per step become one graph launch")
     ap.add_argument("--sync-stats", action="store_true", help="DDP: BatchNorm statistics and the positional encoding's min/max "
@@ -334,6 +338,9 @@ def main(argv=None):
     if args.w_cycle < 0:
         ap.error("--w-cycle must not be negative")
     crit.w_cycle = args.w_cycle
+    if args.w_distortion < 0:
+        ap.error("--w-distortion must not be negative")
+    crit.w_distortion = args.w_distortion
     if args.graph_cache:
         import collections
         crit.graph_cache = collections.OrderedDict()   # least-recently-used shapes are dropped beyond crit.graph_cache_max
@@ -523,7 +530,7 @@ def main(argv=None):
                                            "note": "algorithmic matrix flops of the whole step per GPU over the step time; the step is "
                                                    "~900 small launches, bound by the latency of its kernel chain (network forward -> criterion -> backward), not by the matrix pipe"},
                               "points": N, "points_target": M, "criterion": type(crit).__name__, "alpha": float(alpha),
-                              "sinkhorn_iters": crit.sinkhorn_iters, "sinkhorn_tau": crit.sinkhorn_tau, "w_cycle": crit.w_cycle, "hip_graph": use_graph, "graph_cache": bool(args.graph_cache),
+                              "sinkhorn_iters": crit.sinkhorn_iters, "sinkhorn_tau": crit.sinkhorn_tau, "w_cycle": crit.w_cycle, "w_distortion": crit.w_distortion, "hip_graph": use_graph, "graph_cache": bool(args.graph_cache),
                               "sync_stats": (None if not (args.sync_stats and dist_on) else
                                              {"native_node": getattr(net, "sync_stats", None) is not None,
                                               "native_calls": net.__dict__.get("native_train_calls", 0),
@@ -580,7 +587,7 @@ def main(argv=None):
                 save_ckpt(net, dfm, args.ckpt_dir, cfg["expname"], "val_best")
     if rank == 0:
         print(json.dumps({"epochs": epochs, "history": history, "best_val": best_val, "criterion": type(crit).__name__,
-                          "sinkhorn_iters": crit.sinkhorn_iters, "sinkhorn_tau": crit.sinkhorn_tau, "w_cycle": crit.w_cycle,
+                          "sinkhorn_iters": crit.sinkhorn_iters, "sinkhorn_tau": crit.sinkhorn_tau, "w_cycle": crit.w_cycle, "w_distortion": crit.w_distortion,
                           "ckpt": list(ckpt_paths(args.ckpt_dir, cfg["expname"], "val_best"))}))
     if dist_on:
         dist.destroy_process_group()

@@ -380,6 +380,37 @@ int dvm_cycle_term_f32(const float *val12, const int32_t *idx12, const float *va
                        int k12, int k21, float *loss, float *g12 /* may be NULL */, float *g21 /* may be NULL */, void *ws,
                        size_t ws_bytes, void *stream);
 
+/* The geodesic distortion term of a correspondence (not in the reference, which uses the two distance matrices only for its
+ * anchor-sampled cosine): loss[b] = ||P D2 P^T - D1||_F for the sparse top-k P [N,M] given as pi_val / pi_idx [B,N,topk] (columns in
+ * [0, M)), the source shape's distance matrix D1 = dist_src [B,N,N] and the target's D2 = dist_tgt [B,M,M]; N != M is allowed.
+ * With S = P D2 P^T (N x N), R = S - D1 and F = ||R||_F the gradient (g_val != NULL) is
+ *   g_val[i,t] = d F / d pi_val[i,t] = (2/F) sum_m D2[c,m] q_i[m],   c = pi_idx[i,t],   q_i[m] = sum_{(j,s): pi_idx[j,s] = m} pi_val[j,s] R[i,j]
+ * (the halves of the derivative that come from row i and from column i of S are equal), exactly 0 where F == 0 (an exact
+ * isometry), torch.norm's gradient at zero.  The distance matrices are constants: no gradient is formed for them.
+ * PRECONDITIONS: D1 and D2 are finite and SYMMETRIC (the entry does not symmetrise and does not check; the formula above is the
+ * gradient only then); the indices of a row are distinct within the row — what every top-k producer of this library emits.  An
+ * index outside [0, M) contributes nothing (to S or to the gradient, whose element for that slot is 0; it never becomes an
+ * address), and a slot whose value is 0 adds nothing to S.  Values need not be normalised.
+ * No dense product is formed.  One workgroup per row i: u_i[m] = sum_t pi_val[i,t] D2[pi_idx[i,t], m] in LDS (fp32, an fma chain in
+ * slot order over topk coalesced rows of D2), then S[i,j] = sum_s pi_val[j,s] u_i[pi_idx[j,s]] for every j (an fma chain in slot
+ * order), the residual against the row of D1 and its squared sum in float64.  For the gradient the residual row stays in LDS
+ * (fp32) and q_i is summed there in 64-bit fixed point, units of 2^-50 of every column's largest term, found by a first sweep: LDS
+ * integer maxima and integer adds, which commute, so no order of arrival can reach the result (as the fixed-point sums of
+ * dvm_rank_term_f32, without the reversed lists); topk more rows of D2 are then dotted with q_i in float64.  Row sums are
+ * reduced per batch element in float64, fixed order; loss = sqrt(F^2), the gradient is scaled by 2 / F.  The loss-only call
+ * keeps no residual row and gives the loss bits of the call with gradients.
+ * Work per row: 2 topk rows of D2 (topk without g_val), one sweep over P (three with g_val), one row of D1.
+ * Memory: the workspace only, 8 B N + 4 B bytes — no N x N, N x M or M x M array.  LDS per workgroup: 12 M + 4 N bytes with
+ * g_val, 4 M without.  No float atomics, no host synchronisation, capturable, the same bits from run to run and for a batch
+ * element alone or in a batch.
+ * Limits: N, M <= dvm_distortion_term_max_n() (8192: the rows must fit LDS), 1 <= topk <= 16, B <= 65535.  Outside them
+ * dvm_distortion_term_workspace_bytes returns 0 and dvm_distortion_term_f32 DVM_EINVAL, before any launch. */
+int dvm_distortion_term_max_n(void);
+size_t dvm_distortion_term_workspace_bytes(int B, int N, int M, int topk);
+int dvm_distortion_term_f32(const float *pi_val, const int32_t *pi_idx, const float *dist_src /* [B,N,N] */,
+                            const float *dist_tgt /* [B,M,M] */, int B, int N, int M, int topk, float *loss /* [B] */,
+                            float *g_val /* [B,N,topk], may be NULL */, void *ws, size_t ws_bytes, void *stream);
+
 /* farthest_point_sample — lib/deformation_graph_point.py:18-33 with the random
  * start index made an input.  xyz [B,N,3], start [B] -> out [B,npoint]. */
 int dvm_fps_f32(const float *xyz, int B, int N, int npoint, const int32_t *start, int32_t *out, void *stream);
