@@ -14,6 +14,7 @@
 #include <type_traits>
 
 #include "dvm_common.h"
+#include "dvm_mlp_f16.h"
 
 namespace dvm {
 
@@ -529,6 +530,8 @@ struct ChGridArgs {
                                  // walked, certified by the walk, waves that scanned, lanes served by a scan, exact fallback lanes
 };
 typedef float f32x16_g __attribute__((ext_vector_type(16)));
+typedef _Float16 f16x8_g __attribute__((ext_vector_type(8)));
+typedef unsigned u32x4_g __attribute__((ext_vector_type(4)));
 
 // the target's points [s_begin, s_end) in storage order with the reference's arithmetic (difference form, lower original index on
 // exact ties; !WANT_IDX: the minimum alone, `bs` untouched)
@@ -553,6 +556,41 @@ __device__ __forceinline__ void chamfer_exact_scan(const GridView &g, const Metr
     }
 }
 
+// Float minimum / median as the instructions themselves, and the minimum of a matrix-core accumulator.  Written as fminf trees
+// the compiler puts a canonicalising v_max x, x in front of every matrix-core output (it cannot know that the matrix cores return
+// quiet NaNs only) - one extra instruction per accumulator register.  The hardware minimum passes over a quiet NaN operand as
+// fminf does; the median is used on numbers only.
+__device__ __forceinline__ float fmin2i(float a, float b) {
+    float r;
+    asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+// min(acc[0..15], inf): eight three-input minima.  NaN entries are passed over; sixteen of them give `inf`.
+// The compiler does not count the matrix instruction's latency in front of a register read inside an asm statement (it follows
+// the MFMA at once, with the wait states behind the statement: seen in the assembly).  acc[15] therefore goes through one
+// instruction of the compiler's own, which gets the wait states, and the statement depends on its result.
+__device__ __forceinline__ float acc_min16(const f32x16_g &acc, float inf) {
+    const float last = __builtin_canonicalizef(acc[15]);
+    float r0, r1, r2;
+    asm("v_min3_f32 %0, %3, %4, %5\n\t"
+        "v_min3_f32 %1, %6, %7, %8\n\t"
+        "v_min3_f32 %2, %9, %10, %11\n\t"
+        "v_min3_f32 %0, %0, %1, %2\n\t"
+        "v_min3_f32 %1, %12, %13, %14\n\t"
+        "v_min3_f32 %2, %15, %16, %17\n\t"
+        "v_min3_f32 %1, %1, %2, %18\n\t"
+        "v_min3_f32 %0, %0, %1, %19"
+        : "=&v"(r0), "=&v"(r1), "=&v"(r2)
+        : "v"(acc[0]), "v"(acc[1]), "v"(acc[2]), "v"(acc[3]), "v"(acc[4]), "v"(acc[5]), "v"(acc[6]), "v"(acc[7]), "v"(acc[8]),
+          "v"(acc[9]), "v"(acc[10]), "v"(acc[11]), "v"(acc[12]), "v"(acc[13]), "v"(acc[14]), "v"(last), "v"(inf));
+    return r0;
+}
+__device__ __forceinline__ float fmed3i(float a, float b, float c) {
+    float r;
+    asm("v_med3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
+
 // One WAVE of queries against the WHOLE target, screened on the matrix cores (described in grid_chamfer_kernel); lanes with `done`
 // take part in the matrix instructions and write nothing.
 template <bool WANT_IDX>
@@ -564,55 +602,132 @@ __device__ __forceinline__ void chamfer_scan_wave(const ChGridGroup &G, const Gr
         if (lane == 0) atomicAdd(stats + grp * 8 + 5, 1ull);
         if (!done) atomicAdd(stats + grp * 8 + 6, 1ull);
     }
-    float bq[2][2];
-#pragma unroll
-    for (int tl = 0; tl < 2; ++tl) {
-        const int src = j32 + 32 * tl;
-        const float x = __shfl(qp.x, src, 64), y = __shfl(qp.y, src, 64), z = __shfl(qp.z, src, 64);
-        bq[tl][0] = hh ? y : x;
-        bq[tl][1] = hh ? 1.f : z;
-    }
     // per half of the wave's queries: the two smallest tile minima with their tiles, and the smallest of all the others
     float tb[2] = {INFINITY, INFINITY}, ts[2] = {INFINITY, INFINITY}, th[2] = {INFINITY, INFINITY};
     int tt[2] = {0, 0}, tu[2] = {0, 0};
-    // (four tiles per trip, the next four requested before these are used: one exposed round trip per scan instead of one per tile -
-    // in the retry kernel few waves scan at a time and nothing else covers a load per tile)
-    constexpr int TB = 4;
-    float4 nx[TB];
-#pragma unroll
-    for (int u = 0; u < TB; ++u) {
-        const int pi = 32 * u + j32;
-        nx[u] = g.pts[pi < P ? pi : P - 1];
-    }
-    for (int s00 = 0; s00 < P; s00 += 32 * TB) {
-        float4 cur[TB];
+    const float finf = INFINITY;
+    // one 32 x 32 unit's minimum m (never NaN, see acc_min16) against the running three: tb <= ts <= th are the three smallest
+    // seen, the new three are min, median, median; the tiles of the first two follow by selects
+    auto keep = [&](int tl, float m, int s0) {
+        const bool lt1 = m < tb[tl], lt2 = m < ts[tl];
+        int tun = lt2 ? s0 : tu[tl];
+        asm volatile("" : "+v"(tun));   // (a select, not a branch around one)
+        tu[tl] = lt1 ? tt[tl] : tun;
+        tt[tl] = lt1 ? s0 : tt[tl];
+        th[tl] = fmed3i(ts[tl], th[tl], m);
+        ts[tl] = fmed3i(tb[tl], ts[tl], m);
+        tb[tl] = fmin2i(tb[tl], m);
+    };
+    // (two tiles per half trip, the next two requested before these are used: one exposed round trip per scan instead of one per
+    // tile - in the retry kernel few waves scan at a time and nothing else covers a load per tile.  Two buffers taken in turn: as
+    // one buffer copied forward the loop carried a register copy per coordinate and trip.  Two buffers of FOUR tiles cost 14
+    // registers more than the kernel had, and with them the third resident workgroup of a CU.)
+    constexpr int TB = 2;
+    auto fetch = [&](float4 (&buf)[TB], int s00) {   // tiles s00 .. s00 + 32 TB, clamped to the last point (the tile's offset is a constant)
 #pragma unroll
         for (int u = 0; u < TB; ++u) {
-            cur[u] = nx[u];
-            const int pi = s00 + 32 * (TB + u) + j32;
-            nx[u] = g.pts[pi < P ? pi : P - 1];
+            const int pi = s00 + j32, last = P - 1 - 32 * u;
+            buf[u] = g.pts[(pi < last ? pi : last) + 32 * u];
         }
+    };
+    // (a tile wholly past the end is skipped, wave-uniformly.  Rows past the end in the last tile hold the clamped load, the last
+    // point once more: its duplicates in its own tile leave the tile's minimum what it is.)
+    auto sweep = [&](auto &&unit) {
+        float4 pa[TB], pb[TB];
+        fetch(pa, 0);
+        for (int s00 = 0; s00 < P; s00 += 64 * TB) {
+            fetch(pb, s00 + 32 * TB);
 #pragma unroll
-        for (int u = 0; u < TB; ++u) {
-            const int s0 = s00 + 32 * u, pi = s0 + j32;
-            const float4 pc = cur[u];
-            const float pn = pi < P ? pc.w : INFINITY;   // (rows past the end: +inf, never the minimum)
-            const float a0 = hh ? -2.f * pc.y : -2.f * pc.x, a1 = hh ? pn : -2.f * pc.z;
+            for (int u = 0; u < TB; ++u) {
+                if (s00 + 32 * u >= P) break;
+                unit(pa[u], s00 + 32 * u);
+            }
+            fetch(pa, s00 + 64 * TB);
+#pragma unroll
+            for (int u = 0; u < TB; ++u) {
+                if (s00 + 32 * (TB + u) >= P) break;
+                unit(pb[u], s00 + 32 * (TB + u));
+            }
+        }
+    };
+    // The screen on ONE v_mfma_f32_32x32x16_f16 per unit (32 cycles, and vector instructions issue beside it; the two fp32
+    // instructions take 128 and nothing issues beside them).  Coordinates and norms are scaled by powers of two, exactly:
+    // P = s p, Q = s q with s^2 R^2 in [2^24, 2^26), R^2 = max(scale2, the wave's largest |q|^2) - so |P|, |Q| < 2^13.  Each
+    // scaled value is split in two fp16 pieces, v = h + m (split2x2), X = -2 P and N = 2^-12 |P|^2 on the target side, Q and the
+    // constant 2^12 on the query side.  The sixteen k-slots: lanes 0..31 hold [Xh.xyz, Nh, Xm.xyz, Nm] against
+    // [Qh.xyz, 2^12, Qh.xyz, 2^12], lanes 32..63 hold [0 x 4, Xh.xyz, Nh] against [0 x 4, Qm.xyz, 0]: the sum is
+    // N + Xh.Qh + Xm.Qh + Xh.Qm = s^2 (|p|^2 - 2 p.q) less the errors below - the quantity the fp32 form screens on, times s^2.
+    //
+    // Error of a unit's entry against s^2 (|p|^2 - 2 p.q) in real numbers, in units of u = 2^-23 S, S = s^2 (scale2 + |q|^2)
+    // (|P|^2 <= s^2 scale2; |P| |Q| <= S / 2):
+    //   * the pieces: |v - h| <= 2^-11 |v|, |v - h - m| <= max(2^-22 |v|, 2^-25) (an m below 2^-14 is an fp16 subnormal).  Per
+    //     coordinate X Q - (Xh Qh + Xm Qh + Xh Qm) = Xm Qm + (X - Xh - Xm) Q + (Xh + Xm)(Q - Qh - Qm), at most 3 2^-22 |X| |Q|
+    //     + 2^-25 (|X| + |Q|); over the three coordinates 6 2^-22 |P| |Q| <= 6 u, and less than 2^-9 absolute;
+    //   * the norm in two pieces: 2^12 max(2^-22 N, 2^-25) <= 2 u, or 2^-13 absolute; pc.w itself is |p|^2 rounded three
+    //     times: 1.5 u;
+    //   * the accumulation: products of fp16 pieces are exact in fp32; twelve additions (eleven terms and C = 0), each rounded or
+    //     truncated to fp32, every partial sum at most sum |term| <= N + 2 (1 + 2^-10) |P| |Q| <= 2 S: 24 u;
+    //   * should the matrix cores flush fp16 subnormal inputs (pieces below 2^-14), each such piece costs its partner's size,
+    //     2^-14 (|X|_1 + |Q|_1 + 2^12) < 3 absolute, in place of the 2^-25 terms.
+    // Together E <= 34 u + 4.  Certification needs every other tile's points farther than the best IN THE DIFFERENCE FORM, whose
+    // own rounding is 3 2^-24 d^2 <= 3 u per distance: sother - sbest > 2 E + 6 u = 74 u + 8.  The test below is
+    // sother - sbest > 2 (margin s^2 + 4) = 128 u + 8: the fp32 form's margin, 64 ulp, covers the f16 screen as it stands.
+    // A wave with a non-finite scale (an infinite or overflowing coordinate in the target or among its queries) keeps the fp32
+    // form; NaN coordinates stay in their own row or column of either form and are passed over by the minimum.
+    float q2m = sumsq3(qp.x, qp.y, qp.z);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) q2m = fmaxf(q2m, __shfl_xor(q2m, o, 64));
+    const int r2bits = __builtin_amdgcn_readfirstlane(__float_as_int(fmaxf(g.scale2, q2m)));   // (>= 1e-30: a normal number, or +inf)
+    const bool f16 = r2bits < 0x7f800000;   // (wave-uniform)
+    const int ks = (25 - ((r2bits >> 23) - 127)) >> 1;              // s = 2^ks
+    const float sc2 = f16 ? __int_as_float((2 * ks + 127) << 23) : 1.f;   // s^2: what the screen's values are scaled by
+    if (f16) {
+        const float sq = __int_as_float((ks + 127) << 23), sx = -2.f * sq, sn = __int_as_float((2 * ks - 12 + 127) << 23);
+        f16x8_g bq[2];
+#pragma unroll
+        for (int tl = 0; tl < 2; ++tl) {
+            const int src = j32 + 32 * tl;
+            const float x = __shfl(qp.x, src, 64), y = __shfl(qp.y, src, 64), z = __shfl(qp.z, src, 64);
+            unsigned h01, m01, h23, m23;
+            split2x2(sq * x, sq * y, h01, m01);
+            split2x2(sq * z, 4096.f, h23, m23);   // (h23 = [Qh.z, 2^12], m23 = [Qm.z, 0])
+            bq[tl] = __builtin_bit_cast(f16x8_g, u32x4_g{hh ? 0u : h01, hh ? 0u : h23, hh ? m01 : h01, hh ? m23 : h23});
+        }
+        sweep([&](const float4 &pc, int s0) {
+            unsigned h01, m01, h23, m23;
+            split2x2(sx * pc.x, sx * pc.y, h01, m01);
+            split2x2(sx * pc.z, sn * pc.w, h23, m23);
+            // (every register of the operand comes out of a select: an instruction of the compiler's own between the asm
+            // statements of the split and the matrix instruction, which keeps its operand hazards the compiler's business)
+            const f16x8_g a = __builtin_bit_cast(f16x8_g, u32x4_g{hh ? 0u : h01, hh ? 0u : h23, hh ? h01 : m01, hh ? h23 : m23});
+            // (both halves' instructions first: the first half's minimum and bookkeeping issue while the second runs)
+            const f32x16_g zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            const f32x16_g acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, bq[0], zero, 0, 0, 0);
+            const f32x16_g acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, bq[1], zero, 0, 0, 0);
+            keep(0, acc_min16(acc0, finf), s0);
+            keep(1, acc_min16(acc1, finf), s0);
+        });
+    } else {
+        // the fp32 form: rows [px, py, pz, |p|^2] against columns [-2 qx, -2 qy, -2 qz, 1] (the factor -2 rides on the query
+        // side, once per scan: p (-2 q) and (-2 p) q are the same product), two v_mfma_f32_32x32x2_f32 per unit
+        float bq[2][2];
+#pragma unroll
+        for (int tl = 0; tl < 2; ++tl) {
+            const int src = j32 + 32 * tl;
+            const float x = __shfl(qp.x, src, 64), y = __shfl(qp.y, src, 64), z = __shfl(qp.z, src, 64);
+            bq[tl][0] = hh ? -2.f * y : -2.f * x;
+            bq[tl][1] = hh ? 1.f : -2.f * z;
+        }
+        sweep([&](const float4 &pc, int s0) {
+            const float a0 = hh ? pc.y : pc.x, a1 = hh ? pc.w : pc.z;
 #pragma unroll
             for (int tl = 0; tl < 2; ++tl) {
                 f32x16_g acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
                 acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, bq[tl][0], acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, bq[tl][1], acc, 0, 0, 0);
-                float m = fminf(fminf(fminf(acc[0], acc[1]), fminf(acc[2], acc[3])), fminf(fminf(acc[4], acc[5]), fminf(acc[6], acc[7])));
-                m = fminf(m, fminf(fminf(fminf(acc[8], acc[9]), fminf(acc[10], acc[11])), fminf(fminf(acc[12], acc[13]), fminf(acc[14], acc[15]))));
-                const bool lt1 = m < tb[tl], lt2 = m < ts[tl];   // (tiles past the end are all +inf: never smaller)
-                th[tl] = lt2 ? ts[tl] : fminf(th[tl], m);
-                tu[tl] = lt1 ? tt[tl] : (lt2 ? s0 : tu[tl]);
-                ts[tl] = lt1 ? tb[tl] : (lt2 ? m : ts[tl]);
-                tt[tl] = lt1 ? s0 : tt[tl];
-                tb[tl] = lt1 ? m : tb[tl];
+                keep(tl, acc_min16(acc, finf), s0);
             }
-        }
+        });
     }
     // a query's 32 points per tile sit in two lanes (its own and lane ^ 32): merge the halves at the query's own lane
     // (each lane saw HALF of every tile's points: a tile's minimum is the smaller of the two lanes' values for it.  Of the four
@@ -636,7 +751,7 @@ __device__ __forceinline__ void chamfer_scan_wave(const ChGridGroup &G, const Gr
     if (!done) {
         chamfer_exact_scan<WANT_IDX>(g, met, stile, stile + 32 < P ? stile + 32 : P, best, bs);
         if (ssec < INFINITY) chamfer_exact_scan<WANT_IDX>(g, met, stile2, stile2 + 32 < P ? stile2 + 32 : P, best, bs);
-        cert = sother - sbest > 2.f * margin;
+        cert = sother - sbest > 2.f * (f16 ? margin * sc2 + 4.f : margin);   // (the f16 form's values carry s^2: derivation above)
     }
     if (__ballot(!done && !cert) != 0) {   // (rare: a near-tie between tiles, within the screening's error)
         if (!done && !cert) {
@@ -809,15 +924,19 @@ __global__ __launch_bounds__(THREADS) void grid_chamfer_kernel(const ChGridArgs 
     if (nfall == 0) return;
     // When many lanes of the wave are in that position — a query cloud far from, or much larger than, the target: a COLLAPSED
     // correspondence image (flat soft-max rows at small alpha) makes every query of the other cloud such a one — the wave goes
-    // through the WHOLE target instead of walking cells.  Round 3: that scan is screened on the matrix cores.  Per 32 target
-    // points, two v_mfma_f32_32x32x2_f32 per half of the wave's queries give |p|^2 - 2 p.q — the squared distance less the
-    // query's own |q|^2, which does not move a query's minimum — for 32 x 32 pairs (rows [-2 px, -2 py, -2 pz, |p|^2] against
-    // columns [qx, qy, qz, 1]); a lane keeps, per query, the smallest value
-    // it has seen, the tile it came from and the smallest value of any OTHER tile.  At the end the best tile's 32 points are
-    // evaluated with the reference's difference form (ties by original index), and the result stands if every other tile's
-    // minimum lies more than twice the screening's error bound above the best — otherwise that query is scanned exactly.
+    // through the WHOLE target instead of walking cells.  That scan is screened on the matrix cores (chamfer_scan_wave).  Per 32
+    // target points and half of the wave's queries - a 32 x 32 unit - one v_mfma_f32_32x32x16_f16 on exact fp16 pieces of
+    // power-of-two scaled operands (or, where a scale is not finite, two v_mfma_f32_32x32x2_f32, rows [px, py, pz, |p|^2] against
+    // columns [-2 qx, -2 qy, -2 qz, 1]) gives |p|^2 - 2 p.q - the squared distance less the query's own |q|^2, which does not
+    // move a query's minimum.  A lane takes the unit's minimum over its sixteen accumulator registers with eight three-input
+    // minima and keeps, per query, the two smallest tile minima with their tiles and the smallest of all the others, by a
+    // minimum, two medians and three selects: no branch.  At the end the best two tiles' points are evaluated with the
+    // reference's difference form (ties by original index), and the result stands if every other tile's minimum lies more than
+    // twice the screening's error bound above the best - otherwise that query is scanned exactly.
     // (The vector form of this scan was 12 instructions per pair and the whole of the kernel's time in the bench's regime:
-    // 2.57 ms per launch of 4 x 512 clouds.)
+    // 2.57 ms per launch of 4 x 512 clouds.  The first matrix-core form spent 45 vector instructions per unit beside its two
+    // fp32 instructions - canonicalising v_max in front of every fminf, exec-mask branches around the bookkeeping; this one 26
+    // beside one f16 instruction, profiles/notes_chamfer_scan.md.)
     bool scan = nfall >= args.scan_min;   // (wave-uniform)
     if (!scan) {
         // few open lanes: they walk on from the radius-1 cube (seeded with its best) — but only two more shells: a lane still
