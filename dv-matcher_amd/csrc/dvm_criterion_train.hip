@@ -333,7 +333,7 @@ struct CritWs {
     // backward scratch
     float *dwarped, *dv12, *dR, *dT, *ddef9, *dh[3], *dz, *colpart, *g2t_c, *dval_n, *dgpT, *dgp, *wexp, *dvalw, *dpool, *dpoolT, *gval, *df1, *df2;
     double *sumpart;
-    int32_t *offsA, *curA, *edgesA, *offsB, *curB, *edgesB, *offsC, *curC, *edgesC;
+    RevLists revA, revB, revC;   // of pidx_n over M, of knn_s over N, of knn_t over M (not swapped)
     void *sbws, *wgws;
     size_t sb_bytes, wg_bytes;
     // dist term (nA > 0; swapped form only)
@@ -369,10 +369,9 @@ void carve(Arena &ar, const Dims &d, CritWs &w) {
     w.wexp = ar.take<float>(PX * k), w.dvalw = ar.take<float>(PX * k), w.dpool = ar.take<float>(PN * CT_C), w.gval = ar.take<float>(PN * topk);
     w.dpoolT = d.swapped ? nullptr : ar.take<float>(PM * CT_C);
     w.df1 = ar.take<float>(PN * CT_C), w.df2 = ar.take<float>(PM * CT_C);
-    w.offsA = ar.take<int32_t>((size_t)P * (M + 1)), w.curA = ar.take<int32_t>(PM), w.edgesA = ar.take<int32_t>(R * topk);
-    w.offsB = ar.take<int32_t>((size_t)P * (N + 1)), w.curB = ar.take<int32_t>(PN), w.edgesB = ar.take<int32_t>(PN * k);
-    w.offsC = w.curC = w.edgesC = nullptr;
-    if (!d.swapped) w.offsC = ar.take<int32_t>((size_t)P * (M + 1)), w.curC = ar.take<int32_t>(PM), w.edgesC = ar.take<int32_t>(PM * k);
+    w.revA.take(ar, P, M, Nn * topk), w.revB.take(ar, P, N, (size_t)N * k);
+    w.revC = RevLists();
+    if (!d.swapped) w.revC.take(ar, P, M, (size_t)M * k);
     w.sb_bytes = dvm_softcorr_bwd_workspace_bytes(P, N, M, CT_C), w.sbws = ar.take<char>(w.sb_bytes);
     w.wg_bytes = dvm_linear_wgrad_workspace_bytes((long)R, 512, CT_Z), w.wgws = ar.take<char>(w.wg_bytes);
     if (d.nA > 0) {
@@ -562,9 +561,9 @@ int crit_bwd(const char *who, const Dims &d, Sides io, const DistIn &di, const f
     }
     // z rows back to their sources
     hipLaunchKernelGGL(z_bwd_split_kernel, node_grid, dim3(256), 0, s, w.dz, io.nodes, N, Nn, w.dv12, w.g2t_c);
-    launch_rev_csr(w.pidx_n, P, (long)Nn * topk, M, w.offsA, w.curA, w.edgesA, s);
+    launch_rev_csr(w.pidx_n, P, (long)Nn * topk, M, w.revA, s);
     launch_apply_bwd_dval(w.pval_n, w.pidx_n, w.gpT, w.g2t_c, P, Nn, M, topk, CT_C, w.dval_n, s);
-    launch_apply_bwd_gather(w.pval_n, w.g2t_c, w.offsA, w.edgesA, P, Nn, M, topk, CT_C, w.dgpT, s);
+    launch_apply_bwd_gather(w.pval_n, w.g2t_c, w.revA.offs, w.revA.edges, P, Nn, M, topk, CT_C, w.dgpT, s);
     if (d.swapped) {   // d gp[q] = d gpT[(q + B) mod P] (+ the node rows of dz)
         const void *src[1] = {w.dgpT};
         void *dst[1] = {w.dgp};
@@ -575,24 +574,24 @@ int crit_bwd(const char *who, const Dims &d, Sides io, const DistIn &di, const f
     }
     hipLaunchKernelGGL(z_bwd_pool_kernel, node_grid, dim3(256), 0, s, w.dz, io.nodes, N, Nn, w.dgp);
     // the pooling conv backward through the reversed xyz-kNN lists (also the map term's left-hand side)
-    launch_rev_csr(io.knn_s, P, (long)N * k, N, w.offsB, w.curB, w.edgesB, s);
+    launch_rev_csr(io.knn_s, P, (long)N * k, N, w.revB, s);
     hipLaunchKernelGGL(expand_w_kernel, dim3(blocks_for(PN * k)), dim3(256), 0, s, params[PW_CONV_W], k, PN * k, w.wexp);
     launch_apply_bwd_dval(w.wexp, io.knn_s, io.feat_s, w.dgp, P, N, N, k, CT_C, w.dvalw, s);
-    launch_apply_bwd_gather(w.wexp, w.dgp, w.offsB, w.edgesB, P, N, N, k, CT_C, w.dpool, s);
+    launch_apply_bwd_gather(w.wexp, w.dgp, w.revB.offs, w.revB.edges, P, N, N, k, CT_C, w.dpool, s);
     colsum_add(w.dvalw, PN, k, grads[PW_CONV_W], w, s);
     hipLaunchKernelGGL(sum_all_partial_kernel, dim3(SUM_BLOCKS), dim3(256), 0, s, (const f32x4 *)w.dgp, PN * CT_C / 4, w.sumpart);
     hipLaunchKernelGGL(sum_all_final_kernel, dim3(1), dim3(256), 0, s, w.sumpart, SUM_BLOCKS, grads[PW_CONV_B]);
     if (!d.swapped) {   // ... and of the targets' own pooling (the swapped form pooled them as the other half's sources)
-        launch_rev_csr(io.knn_t, P, (long)M * k, M, w.offsC, w.curC, w.edgesC, s);
+        launch_rev_csr(io.knn_t, P, (long)M * k, M, w.revC, s);
         hipLaunchKernelGGL(expand_w_kernel, dim3(blocks_for(PM * k)), dim3(256), 0, s, params[PW_CONV_W], k, PM * k, w.wexp);
         launch_apply_bwd_dval(w.wexp, io.knn_t, io.feat_t, w.dgpT, P, M, M, k, CT_C, w.dvalw, s);
-        launch_apply_bwd_gather(w.wexp, w.dgpT, w.offsC, w.edgesC, P, M, M, k, CT_C, w.dpoolT, s);
+        launch_apply_bwd_gather(w.wexp, w.dgpT, w.revC.offs, w.revC.edges, P, M, M, k, CT_C, w.dpoolT, s);
         colsum_add(w.dvalw, PM, k, grads[PW_CONV_W], w, s);
         hipLaunchKernelGGL(sum_all_partial_kernel, dim3(SUM_BLOCKS), dim3(256), 0, s, (const f32x4 *)w.dgpT, PM * CT_C / 4, w.sumpart);
         hipLaunchKernelGGL(sum_all_final_kernel, dim3(1), dim3(256), 0, s, w.sumpart, SUM_BLOCKS, grads[PW_CONV_B]);
     }
     if (with_map)
-        hipLaunchKernelGGL(map_bwd_gather_kernel, dim3((N + 255) / 256, P), dim3(256), 0, s, w.resid, w.offsB, w.edgesB, g_terms, N, k, w.dv12);
+        hipLaunchKernelGGL(map_bwd_gather_kernel, dim3((N + 255) / 256, P), dim3(256), 0, s, w.resid, w.revB.offs, w.revB.edges, g_terms, N, k, w.dv12);
     // everything that reaches the correspondence values, then the soft correspondence itself
     hipLaunchKernelGGL(gval_total_kernel, dim3((unsigned)(((long)N * topk + 255) / 256), P), dim3(256), 0, s, w.dv12, io.verts_t, io.knn_t, w.pidx,
                        with_map ? w.resid : (const float *)nullptr, g_terms, N, M, k, topk, w.gval);

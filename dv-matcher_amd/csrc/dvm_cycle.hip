@@ -14,25 +14,24 @@
 //   3. gradient (GRAD): thread (t, s) reads C[c] back: the sample smp[b][i][t][s] (what the column kernel needs from this row) and
 //      the term R[i,c] val21[j,s]; thread t < k12 adds its k21 terms in slot order in float64 -> g12[i,t], unscaled.
 // cycle_col_kernel, one wave per column j of P12 = row j of P21, lanes = 4 list entries x 16 slots s: the list of j from
-// launch_rev_csr (dvm_geom.hip) is walked twice for the order-free sum of dvm_common.h (the list's order is that of integer
-// atomics): the largest |term| per slot s, then the 64-bit integer sum -> g21[j,s], unscaled; 0 for a column nobody picks.
-// launch_frob_finish (dvm_rank.hip): loss = sqrt(F^2), g12 and g21 *= 1 / F, 0 where F == 0 (torch.norm's gradient at zero).
-// The loss-only call runs steps 1 and 2 and the finish: no lists, no samples.  No float atomics anywhere; arrays: the lists
-// (B (2 M + 1 + N k12) int32), B N doubles, B floats, the samples (B N k12 k21 floats).
-#include "dvm_common.h"
+// launch_rev_csr (dvm_geom.hip) is walked twice for the order-free sum that dvm_frob.h explains: the largest |term| per slot s,
+// then the 64-bit integer sum -> g21[j,s], unscaled; 0 for a column nobody picks.
+// frob_finish (dvm_frob.hip): loss = sqrt(F^2), g12 and g21 *= 1 / F, 0 where F == 0.
+// The loss-only call runs steps 1 and 2 and the finish: no lists, no samples.  Arrays: the lists (B (2 M + 1 + N k12) int32),
+// B N doubles, B floats, the samples (B N k12 k21 floats).
+#include "dvm_frob.h"
 
 namespace dvm {
 
-constexpr int CYCLE_MAX_N = 8192;    // the row of C takes N fp32 words of LDS (32 KB at the limit), as the rank term's row
-constexpr int CYCLE_THREADS = 256;   // block_tree_sum's width; 16 x 16 (t, s) pairs
+static_assert(FROB_THREADS == 16 * 16, "cycle_row_kernel: one thread per (t, s) pair");
 
 template <bool GRAD>
-__global__ __launch_bounds__(CYCLE_THREADS) void cycle_row_kernel(const float *__restrict__ val12, const int32_t *__restrict__ idx12,
+__global__ __launch_bounds__(FROB_THREADS) void cycle_row_kernel(const float *__restrict__ val12, const int32_t *__restrict__ idx12,
                                                                   const float *__restrict__ val21, const int32_t *__restrict__ idx21, int N,
                                                                   int M, int k12, int k21, double *__restrict__ partial,
                                                                   float *__restrict__ g12, float *__restrict__ smp) {
     extern __shared__ float cycle_lds[];   // C [N]
-    __shared__ double gterm[CYCLE_THREADS];
+    __shared__ double gterm[FROB_THREADS];
     float *C = cycle_lds;
     const int tid = threadIdx.x, i = blockIdx.x, b = blockIdx.y;
     const int t = tid >> 4, s = tid & 15;
@@ -50,19 +49,14 @@ __global__ __launch_bounds__(CYCLE_THREADS) void cycle_row_kernel(const float *_
             if (cc >= 0 && cc < N) c = cc;
         }
     }
-    for (int r = tid; r < N; r += CYCLE_THREADS) C[r] = 0.f;
+    for (int r = tid; r < N; r += FROB_THREADS) C[r] = 0.f;
     __syncthreads();
     for (int u = 0; u < k12; ++u) {
         // a value of 0 adds nothing; skipping it also keeps the repeated (0, 0) slots of a row with fewer columns than topk off one word
         if (t == u && c >= 0 && v != 0.f && w != 0.f) C[c] = fmaf(v, w, C[c]);
         __syncthreads();
     }
-    double acc = 0.0;
-    for (int r = tid; r < N; r += CYCLE_THREADS) {
-        const double x = (double)C[r] - (r == i ? 1.0 : 0.0);
-        acc += x * x;
-    }
-    acc = block_tree_sum(acc);
+    const double acc = frob_row_sq_sum(C, N, i);
     if (tid == 0) partial[(size_t)b * N + i] = acc;
     if (!GRAD) return;
     const float cs = c >= 0 ? C[c] : 0.f;
@@ -77,12 +71,12 @@ __global__ __launch_bounds__(CYCLE_THREADS) void cycle_row_kernel(const float *_
 }
 
 // g21[j,s] = sum over the list of column j (entries e = i * k12 + t with idx12[e] == j) of val12[e] (smp[e][s] - delta(i, idx21[j,s])), unscaled
-__global__ __launch_bounds__(CYCLE_THREADS) void cycle_col_kernel(const float *__restrict__ val12, const int32_t *__restrict__ idx21,
+__global__ __launch_bounds__(FROB_THREADS) void cycle_col_kernel(const float *__restrict__ val12, const int32_t *__restrict__ idx21,
                                                                   const int32_t *__restrict__ offs, const int32_t *__restrict__ edges,
                                                                   const float *__restrict__ smp, int N, int M, int k12, int k21,
                                                                   float *__restrict__ g21) {
     const int lane = threadIdx.x & (WAVE - 1), b = blockIdx.y;
-    const long jl = (long)blockIdx.x * (CYCLE_THREADS / WAVE) + threadIdx.x / WAVE;
+    const long jl = (long)blockIdx.x * (FROB_THREADS / WAVE) + threadIdx.x / WAVE;
     if (jl >= M) return;   // whole waves leave; the kernel has no barrier
     const int j = (int)jl, s = lane & 15, sub = lane >> 4;
     const size_t E12 = (size_t)N * k12, row21 = ((size_t)b * M + j) * k21;
@@ -120,55 +114,50 @@ __global__ __launch_bounds__(CYCLE_THREADS) void cycle_col_kernel(const float *_
 using namespace dvm;
 
 struct CycleWs {
-    int32_t *offs, *cursor, *edges;   // the reversed lists of idx12 over the M columns (launch_rev_csr)
-    double *partial;                  // [B][N]: one per row
-    float *f2;                        // [B]
-    float *smp;                       // [B][N][k12][k21]: C[i, idx21[idx12[i,t], s]]
+    RevLists rev;    // the reversed lists of idx12 over the M columns
+    FrobSums sums;
+    float *smp;      // [B][N][k12][k21]: C[i, idx21[idx12[i,t], s]]
 };
 static size_t carve_cycle(Arena &ar, int B, int N, int M, int k12, int k21, CycleWs &w) {
-    w.offs = ar.take<int32_t>((size_t)B * (M + 1));
-    w.cursor = ar.take<int32_t>((size_t)B * M);
-    w.edges = ar.take<int32_t>((size_t)B * N * k12);
-    w.partial = ar.take<double>((size_t)B * N);
-    w.f2 = ar.take<float>((size_t)B);
+    w.rev.take(ar, B, M, (size_t)N * k12);
+    w.sums.take(ar, B, N);
     w.smp = ar.take<float>((size_t)B * N * k12 * k21);
     return ar.off;
 }
-static bool cycle_shape_ok(int B, int N, int M, int k12, int k21) {
-    return B >= 1 && B <= 65535 && N >= 1 && N <= CYCLE_MAX_N && M >= 1 && k12 >= 1 && k12 <= 16 && k21 >= 1 && k21 <= 16;
+// the row of C takes N fp32 words of LDS (32 KB at the limit), as the rank term's row
+static const char *cycle_limits(int B, int N, int M, int k12, int k21) {
+    const char *who = "dvm_cycle_term_f32";
+    FROB_BATCH_LIMITS(who, B, N, M);
+    FROB_TOPK_LIMIT(who, k12);
+    FROB_TOPK_LIMIT(who, k21);
+    FROB_LIMIT(N <= FROB_MAX_N, "%s: N=%d unsupported (a row of P12 P21 must fit LDS: N <= %d)", who, N, FROB_MAX_N);
+    return nullptr;
 }
 
-DVM_EXPORT int dvm_cycle_term_max_n(void) { return CYCLE_MAX_N; }
+DVM_EXPORT int dvm_cycle_term_max_n(void) { return FROB_MAX_N; }
 
 DVM_EXPORT size_t dvm_cycle_term_workspace_bytes(int B, int N, int M, int k12, int k21) {
-    return cycle_shape_ok(B, N, M, k12, k21) ? null_carve<CycleWs>(carve_cycle, B, N, M, k12, k21) : 0;
+    return cycle_limits(B, N, M, k12, k21) ? 0 : null_carve<CycleWs>(carve_cycle, B, N, M, k12, k21);
 }
 
 DVM_EXPORT int dvm_cycle_term_f32(const float *val12, const int32_t *idx12, const float *val21, const int32_t *idx21, int B, int N, int M,
                                   int k12, int k21, float *loss, float *g12, float *g21, void *ws, size_t ws_bytes, void *stream) {
     DVM_REQUIRE(val12 && idx12 && val21 && idx21 && loss, "dvm_cycle_term_f32: null pointer");
-    DVM_REQUIRE(B >= 1 && N >= 1 && M >= 1, "dvm_cycle_term_f32: empty input (B=%d N=%d M=%d)", B, N, M);
-    DVM_REQUIRE(B <= 65535, "dvm_cycle_term_f32: B=%d unsupported (<= 65535)", B);
-    DVM_REQUIRE(k12 >= 1 && k12 <= 16, "dvm_cycle_term_f32: k12=%d unsupported (1..16)", k12);
-    DVM_REQUIRE(k21 >= 1 && k21 <= 16, "dvm_cycle_term_f32: k21=%d unsupported (1..16)", k21);
-    DVM_REQUIRE(N <= CYCLE_MAX_N, "dvm_cycle_term_f32: N=%d unsupported (a row of P12 P21 must fit LDS: N <= %d)", N, CYCLE_MAX_N);
+    const char *why = cycle_limits(B, N, M, k12, k21);
+    DVM_REQUIRE(!why, "%s", why);
     DVM_REQUIRE((g12 == nullptr) == (g21 == nullptr), "dvm_cycle_term_f32: g12 and g21 must both be NULL or both be given");
     CycleWs w;
     if (!carve_ws(ws, ws_bytes, "dvm_cycle_term_f32", w, carve_cycle, B, N, M, k12, k21)) return DVM_ENOSPACE;
     hipStream_t s = (hipStream_t)stream;
     const size_t lds = (size_t)N * sizeof(float);
-    const dim3 grid(N, B), block(CYCLE_THREADS);
+    const dim3 grid(N, B), block(FROB_THREADS);
     if (!g12) {
-        hipLaunchKernelGGL(cycle_row_kernel<false>, grid, block, lds, s, val12, idx12, val21, idx21, N, M, k12, k21, w.partial, g12, w.smp);
+        hipLaunchKernelGGL(cycle_row_kernel<false>, grid, block, lds, s, val12, idx12, val21, idx21, N, M, k12, k21, w.sums.partial, g12, w.smp);
     } else {
-        launch_rev_csr(idx12, B, (long)N * k12, M, w.offs, w.cursor, w.edges, s);
-        hipLaunchKernelGGL(cycle_row_kernel<true>, grid, block, lds, s, val12, idx12, val21, idx21, N, M, k12, k21, w.partial, g12, w.smp);
-        const dim3 cgrid((unsigned)(((long)M + CYCLE_THREADS / WAVE - 1) / (CYCLE_THREADS / WAVE)), B);
-        hipLaunchKernelGGL(cycle_col_kernel, cgrid, block, 0, s, val12, idx21, w.offs, w.edges, w.smp, N, M, k12, k21, g21);
+        launch_rev_csr(idx12, B, (long)N * k12, M, w.rev, s);
+        hipLaunchKernelGGL(cycle_row_kernel<true>, grid, block, lds, s, val12, idx12, val21, idx21, N, M, k12, k21, w.sums.partial, g12, w.smp);
+        const dim3 cgrid((unsigned)(((long)M + FROB_THREADS / WAVE - 1) / (FROB_THREADS / WAVE)), B);
+        hipLaunchKernelGGL(cycle_col_kernel, cgrid, block, 0, s, val12, idx21, w.rev.offs, w.rev.edges, w.smp, N, M, k12, k21, g21);
     }
-    launch_reduce_partials(w.partial, B, N, 1.f, w.f2, 1, 0, s);
-    launch_frob_finish(w.f2, B, (size_t)N * k12, 1.0, loss, g12, s);
-    if (g21) launch_frob_finish(w.f2, B, (size_t)M * k21, 1.0, loss, g21, s);
-    DVM_CHECK_LAUNCH("cycle_term");
-    return DVM_OK;
+    return frob_finish(w.sums, B, N, 1.0, loss, {{g12, (size_t)N * k12}, {g21, (size_t)M * k21}}, "cycle_term", s);
 }

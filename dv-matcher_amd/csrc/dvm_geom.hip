@@ -915,18 +915,12 @@ void launch_apply_bwd_gather(const float *pi_val, const float *g_out, const int3
 }
 }  // namespace dvm
 
-// the reversed lists of launch_rev_csr
-struct RevCsrWs {
-    int32_t *offs, *cursor, *edges;
-};
-static size_t carve_rev_csr(Arena &ar, int B, int N, int M, int topk, RevCsrWs &w) {
-    w.offs = ar.take<int32_t>((size_t)B * (M + 1));
-    w.cursor = ar.take<int32_t>((size_t)B * M);
-    w.edges = ar.take<int32_t>((size_t)B * N * topk);
+static size_t carve_rev_csr(Arena &ar, int B, int N, int M, int topk, RevLists &w) {
+    w.take(ar, B, M, (size_t)N * topk);
     return ar.off;
 }
 
-DVM_EXPORT size_t dvm_softcorr_apply_bwd_workspace_bytes(int B, int N, int M, int topk) { return null_carve<RevCsrWs>(carve_rev_csr, B, N, M, topk); }
+DVM_EXPORT size_t dvm_softcorr_apply_bwd_workspace_bytes(int B, int N, int M, int topk) { return null_carve<RevLists>(carve_rev_csr, B, N, M, topk); }
 
 DVM_EXPORT int dvm_softcorr_apply_bwd_f32(const float *pi_val, const int32_t *pi_idx, const float *V, const float *g_out, int B,
                                           int N, int M, int topk, int C, float *d_val, float *d_V, void *ws, size_t ws_bytes,
@@ -941,9 +935,9 @@ DVM_EXPORT int dvm_softcorr_apply_bwd_f32(const float *pi_val, const int32_t *pi
     long threads = (long)N * gp2;
     dim3 grid((unsigned)((threads + 255) / 256), B), block(256);
     if (ws != nullptr) {  // reversed lists + gather: no float atomics
-        RevCsrWs w;
+        RevLists w;
         if (!carve_ws(ws, ws_bytes, "dvm_softcorr_apply_bwd_f32", w, carve_rev_csr, B, N, M, topk)) return DVM_ENOSPACE;
-        launch_rev_csr(pi_idx, B, (long)N * topk, M, w.offs, w.cursor, w.edges, s);
+        launch_rev_csr(pi_idx, B, (long)N * topk, M, w, s);
         launch_apply_bwd_dval(pi_val, pi_idx, V, g_out, B, N, M, topk, C, d_val, s);
         launch_apply_bwd_gather(pi_val, g_out, w.offs, w.edges, B, N, M, topk, C, d_V, s);
         DVM_CHECK_LAUNCH("softcorr_apply_bwd(gather)");

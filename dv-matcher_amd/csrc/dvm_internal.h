@@ -2,7 +2,7 @@
 // ONCE, grouped by the file that defines it (with the workspace struct or constants its callers need); default arguments appear
 // here and nowhere else.  Included at the end of
 // dvm_common.h: no .hip file declares a function it does not define.  (The K1 sweep's launchers, whose signatures need its
-// argument structs, are in dvm_softcorr_f16.h; set_error / prof_* / options and their kin, defined in dvm_api.cpp, in dvm_common.h.)
+// argument structs, are in dvm_softcorr_f16.h; the Frobenius-norm terms' frob_finish in dvm_frob.h; set_error / prof_* / options and their kin, defined in dvm_api.cpp, in dvm_common.h.)
 #pragma once
 
 namespace dvm {
@@ -58,6 +58,18 @@ int launch_map_term(const float *verts12, const float *verts2, const int32_t *id
                     int B, int N, int M, int k, int topk, double *partial, hipStream_t s, float *resid = nullptr);
 // idx [B][E] (entries with a target in [0, M)) -> offs [B][M+1], edges [B][E] (entry numbers grouped by target); cursor [B][M] scratch
 void launch_rev_csr(const int32_t *idx, int B, long E, int M, int32_t *offs, int32_t *cursor, int32_t *edges, hipStream_t s);
+// those three arrays as a workspace piece: B batches, M targets, E entries per batch
+struct RevLists {
+    int32_t *offs = nullptr, *cursor = nullptr, *edges = nullptr;
+    void take(Arena &ar, size_t B, size_t M, size_t E) {
+        offs = ar.take<int32_t>(B * (M + 1));
+        cursor = ar.take<int32_t>(B * M);
+        edges = ar.take<int32_t>(B * E);
+    }
+};
+static inline void launch_rev_csr(const int32_t *idx, int B, long E, int M, const RevLists &r, hipStream_t s) {
+    launch_rev_csr(idx, B, E, M, r.offs, r.cursor, r.edges, s);
+}
 void launch_apply_bwd_dval(const float *pi_val, const int32_t *pi_idx, const float *V, const float *g_out, int B, int N, int M, int topk, int C, float
                            *d_val, hipStream_t s);
 void launch_apply_bwd_gather(const float *pi_val, const float *g_out, const int32_t *offs, const int32_t *edges, int B, int N, int M, int topk, int C,
@@ -128,10 +140,6 @@ int *launch_mlp_planes_f16(const void *zp, int rows, const float *W0, const floa
                            *b2, const float *W3, const float *b3, void *scratch, float *out, hipStream_t s);
 size_t mlp_zplane_bytes(int rows);   // bytes of the plane form of `rows` z rows (padded to whole 64-row blocks)
 size_t mlp_zplane_row_bytes();   // MH_SZ
-
-// ---- dvm_rank.hip
-// f2 [B] = F^2 -> loss [B] = F and (g_val != NULL) g_val [B][E] *= num / F, 0 where F == 0: the last step of a Frobenius-norm term
-void launch_frob_finish(const float *f2, int B, size_t E, double num, float *loss, float *g_val, hipStream_t s);
 
 // ---- the SA attention core (dvm_sa.hip, dvm_sa_bwd.hip): channels of p and of v, padded p row of the staged tiles (floats)
 constexpr int SA_P = 16, SA_C = 64, SA_LDP = 20;

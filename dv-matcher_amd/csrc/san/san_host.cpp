@@ -158,6 +158,54 @@ int main() {
         EXPECT(strstr(dvm_last_error(), "workspace") != nullptr);
         EXPECT(dvm_rank_term_f32(dummy, idummy, 2, 300, 170, 10, dummy, nullptr, nullptr, 0, nullptr) == DVM_ENOSPACE);
     }
+    // the cycle term: the same frame; its sizes hold the samples (B N k12 k21 floats) and no N x N / N x M array, both gradients or none
+    {
+        float *const F = dummy;
+        int32_t *const I = idummy;
+        const int nmax = dvm_cycle_term_max_n();
+        const size_t cb = dvm_cycle_term_workspace_bytes(2, 300, 170, 10, 10);
+        std::vector<char> cws(cb);
+        EXPECT(nmax >= 8192 && cb >= (size_t)4 * 2 * (2 * 170 + 1 + 300 * 10 + 300 * 100) + 8 * 2 * 300 && cb < (size_t)2 * 300 * 170 * 4);
+        EXPECT(dvm_cycle_term_workspace_bytes(1, nmax, 1 << 20, 16, 16) > 0 && dvm_cycle_term_workspace_bytes(1, nmax + 1, 64, 1, 1) == 0);
+        EXPECT(dvm_cycle_term_workspace_bytes(0, 8, 8, 4, 4) == 0 && dvm_cycle_term_workspace_bytes(1, 8, 8, 17, 4) == 0 &&
+               dvm_cycle_term_workspace_bytes(1, 8, 8, 4, 17) == 0 && dvm_cycle_term_workspace_bytes(65536, 8, 8, 4, 4) == 0);
+#define CYC(v12, B, N, M, k12, k21, g12, g21, ws, nb) dvm_cycle_term_f32(v12, I, F, I, B, N, M, k12, k21, F, g12, g21, ws, nb, nullptr)
+        EXPECT(CYC(nullptr, 2, 300, 170, 10, 10, nullptr, nullptr, cws.data(), cb) == DVM_EINVAL && strstr(dvm_last_error(), "null pointer"));
+        EXPECT(CYC(F, 2, 300, 0, 10, 10, F, F, cws.data(), cb) == DVM_EINVAL && strstr(dvm_last_error(), "empty input"));
+        EXPECT(CYC(F, 65536, 300, 170, 10, 10, F, F, cws.data(), cb) == DVM_EINVAL && strstr(dvm_last_error(), "B=65536"));
+        EXPECT(CYC(F, 2, 300, 170, 17, 10, F, F, cws.data(), cb) == DVM_EINVAL && strstr(dvm_last_error(), "k12=17"));
+        EXPECT(CYC(F, 2, 300, 170, 10, 0, F, F, cws.data(), cb) == DVM_EINVAL && strstr(dvm_last_error(), "k21=0"));
+        EXPECT(CYC(F, 1, nmax + 1, 64, 1, 1, nullptr, nullptr, cws.data(), cb) == DVM_EINVAL && strstr(dvm_last_error(), "N="));
+        EXPECT(CYC(F, 2, 300, 170, 10, 10, F, nullptr, cws.data(), cb) == DVM_EINVAL && strstr(dvm_last_error(), "both"));
+        EXPECT(CYC(F, 2, 300, 170, 10, 10, nullptr, F, cws.data(), cb) == DVM_EINVAL && strstr(dvm_last_error(), "both"));
+        EXPECT(CYC(F, 2, 300, 170, 10, 10, F, F, cws.data(), cb - 1) == DVM_ENOSPACE && strstr(dvm_last_error(), "workspace"));
+        EXPECT(CYC(F, 2, 300, 170, 10, 10, nullptr, nullptr, nullptr, 0) == DVM_ENOSPACE);
+#undef CYC
+    }
+    // the distortion term: B N doubles and B floats whatever M and topk; N and M each have the limit
+    {
+        float *const F = dummy;
+        int32_t *const I = idummy;
+        const int nmax = dvm_distortion_term_max_n();
+        const size_t db = dvm_distortion_term_workspace_bytes(2, 300, 170, 10);
+        std::vector<char> dws(db);
+        EXPECT(nmax >= 8192 && db >= (size_t)8 * 2 * 300 + 4 * 2 && db < (size_t)16 * 1024);
+        EXPECT(dvm_distortion_term_workspace_bytes(1, nmax, nmax, 16) > 0 && dvm_distortion_term_workspace_bytes(1, nmax + 1, 64, 1) == 0 &&
+               dvm_distortion_term_workspace_bytes(1, 64, nmax + 1, 1) == 0);
+        EXPECT(dvm_distortion_term_workspace_bytes(0, 8, 8, 4) == 0 && dvm_distortion_term_workspace_bytes(1, 8, 8, 17) == 0 &&
+               dvm_distortion_term_workspace_bytes(65536, 8, 8, 4) == 0);
+#define DST(d1, B, N, M, k, g, ws, nb) dvm_distortion_term_f32(F, I, d1, F, B, N, M, k, F, g, ws, nb, nullptr)
+        EXPECT(DST(nullptr, 2, 300, 170, 10, nullptr, dws.data(), db) == DVM_EINVAL && strstr(dvm_last_error(), "null pointer"));
+        EXPECT(DST(F, 2, 0, 170, 10, F, dws.data(), db) == DVM_EINVAL && strstr(dvm_last_error(), "empty input"));
+        EXPECT(DST(F, 65536, 300, 170, 10, F, dws.data(), db) == DVM_EINVAL && strstr(dvm_last_error(), "B=65536"));
+        EXPECT(DST(F, 2, 300, 170, 17, F, dws.data(), db) == DVM_EINVAL && strstr(dvm_last_error(), "topk=17"));
+        EXPECT(DST(F, 1, nmax + 1, 64, 1, nullptr, dws.data(), db) == DVM_EINVAL && strstr(dvm_last_error(), "N="));
+        EXPECT(DST(F, 1, 64, nmax + 1, 1, nullptr, dws.data(), db) == DVM_EINVAL && strstr(dvm_last_error(), "M="));
+        EXPECT(DST(F, 1, nmax + 1, nmax + 1, 1, nullptr, dws.data(), db) == DVM_EINVAL && strstr(dvm_last_error(), "N="));   // N is reported first
+        EXPECT(DST(F, 2, 300, 170, 10, F, dws.data(), db - 1) == DVM_ENOSPACE && strstr(dvm_last_error(), "workspace"));
+        EXPECT(DST(F, 2, 300, 170, 10, nullptr, nullptr, 0) == DVM_ENOSPACE);
+#undef DST
+    }
     EXPECT(dvm_linear_f32(nullptr, dummy, 1, 4, 4, 4, 0, nullptr, nullptr, nullptr, nullptr, 1.f, dummy, nullptr) == DVM_EINVAL);
     EXPECT(dvm_linear_f32(dummy, dummy, 1, 4, 4, 4, 0, nullptr, nullptr, dummy, nullptr, 1.f, dummy, nullptr) == DVM_EINVAL);               // alpha without beta
     EXPECT(dvm_linear_f32(dummy, dummy, 1, 4, 100000, 4, 0, nullptr, nullptr, nullptr, nullptr, 1.f, dummy, nullptr) == DVM_EINVAL);        // K too large
@@ -231,6 +279,8 @@ int main() {
         SHORT(dvm_dist_loss_workspace_bytes(B, N, d, 16, k), dvm_dist_loss_fwd_f32(F, F, I, B, N, d, 16, k, F, I, ws, q - 1, nullptr));
         SHORT(dvm_map_term_workspace_bytes(B, N), dvm_map_term_f32(F, F, I, I, F, I, B, N, M, 16, 10, F, ws, q - 1, nullptr));
         SHORT(dvm_rank_term_workspace_bytes(B, N, M, 10), dvm_rank_term_f32(F, I, B, N, M, 10, F, F, ws, q - 1, nullptr));
+        SHORT(dvm_cycle_term_workspace_bytes(B, N, M, 10, 10), dvm_cycle_term_f32(F, I, F, I, B, N, M, 10, 10, F, F, F, ws, q - 1, nullptr));
+        SHORT(dvm_distortion_term_workspace_bytes(B, N, M, 10), dvm_distortion_term_f32(F, I, F, F, B, N, M, 10, F, F, ws, q - 1, nullptr));
         SHORT(dvm_pair_direction_workspace_bytes(B, N, M),
               dvm_pair_direction_fwd_f32(F, F, F, F, B, N, M, -1.f, I, F, F, F, F, F, F, F, F, F, F, 1, F, F, I, F, ws, q - 1, nullptr));
         SHORT(dvm_pair_workspace_bytes(B, N, M),

@@ -577,20 +577,24 @@ class _SparseApply(torch.autograd.Function):
         return dval, None, dV
 
 
-class _RankTerm(torch.autograd.Function):
-    """||P P^T - I||_F per batch element of the sparse top-k P on the HIP kernel (dvm_rank_term_f32): the forward call returns the
-    gradient as well (the residual row is in LDS then), and the backward only scales it."""
+class _FrobTerm(torch.autograd.Function):
+    """A sparse Frobenius-norm term per batch element on its HIP kernel (dvm_rank_term_f32, dvm_cycle_term_f32,
+    dvm_distortion_term_f32): the forward call op(*args, grad=True) returns the gradients as well (the residual row is in LDS then), one
+    per positional input named in `diff`, and the backward only scales them.  Every other input is a constant."""
 
     @staticmethod
-    def forward(ctx, val, idx, M):
-        loss, g_val = ops.rank_term(val, idx, M, grad=True)
-        ctx.save_for_backward(g_val)
+    def forward(ctx, op, diff, *args):
+        loss, *grads = op(*args, grad=True)
+        ctx.save_for_backward(*grads)
+        ctx.diff, ctx.nargs = diff, len(args)
         return loss
 
     @staticmethod
     def backward(ctx, gout):
-        g_val, = ctx.saved_tensors
-        return g_val * gout[:, None, None], None, None
+        out = [None] * (2 + ctx.nargs)
+        for pos, g in zip(ctx.diff, ctx.saved_tensors):
+            out[2 + pos] = g * gout[:, None, None]
+        return tuple(out)
 
 
 def rank_term(val, idx, M):
@@ -598,23 +602,7 @@ def rank_term(val, idx, M):
     the term is 0).  Without grad it is ops.rank_term: no gradient is formed."""
     if not (torch.is_grad_enabled() and val.requires_grad):
         return ops.rank_term(val, idx, M)
-    return _RankTerm.apply(val, idx, M)
-
-
-class _CycleTerm(torch.autograd.Function):
-    """||P12 P21 - I||_F per batch element of a pair's two sparse correspondences on the HIP kernel (dvm_cycle_term_f32): the forward
-    call returns both gradients as well (the residual row is in LDS then), and the backward only scales them."""
-
-    @staticmethod
-    def forward(ctx, val12, idx12, val21, idx21):
-        loss, g12, g21 = ops.cycle_term(val12, idx12, val21, idx21, grad=True)
-        ctx.save_for_backward(g12, g21)
-        return loss
-
-    @staticmethod
-    def backward(ctx, gout):
-        g12, g21 = ctx.saved_tensors
-        return g12 * gout[:, None, None], None, g21 * gout[:, None, None], None
+    return _FrobTerm.apply(ops.rank_term, (0,), val, idx, M)
 
 
 def cycle_term(val12, idx12, val21, idx21):
@@ -622,24 +610,7 @@ def cycle_term(val12, idx12, val21, idx21):
     w.r.t. val12 and val21 (0 where the term is 0).  Without grad it is ops.cycle_term: no gradient is formed."""
     if not (torch.is_grad_enabled() and (val12.requires_grad or val21.requires_grad)):
         return ops.cycle_term(val12, idx12, val21, idx21)
-    return _CycleTerm.apply(val12, idx12, val21, idx21)
-
-
-class _DistortionTerm(torch.autograd.Function):
-    """||P D2 P^T - D1||_F per batch element of the sparse top-k P on the HIP kernel (dvm_distortion_term_f32): the forward call
-    returns the gradient in val as well (the residual row is in LDS then), and the backward only scales it.  The distance matrices
-    are constants."""
-
-    @staticmethod
-    def forward(ctx, val, idx, dist_src, dist_tgt):
-        loss, g_val = ops.distortion_term(val, idx, dist_src, dist_tgt, grad=True)
-        ctx.save_for_backward(g_val)
-        return loss
-
-    @staticmethod
-    def backward(ctx, gout):
-        g_val, = ctx.saved_tensors
-        return g_val * gout[:, None, None], None, None, None
+    return _FrobTerm.apply(ops.cycle_term, (0, 2), val12, idx12, val21, idx21)
 
 
 def distortion_term(val, idx, dist_src, dist_tgt):
@@ -648,7 +619,7 @@ def distortion_term(val, idx, dist_src, dist_tgt):
     ops.distortion_term: no gradient is formed."""
     if not (torch.is_grad_enabled() and val.requires_grad):
         return ops.distortion_term(val, idx, dist_src, dist_tgt)
-    return _DistortionTerm.apply(val, idx, dist_src, dist_tgt)
+    return _FrobTerm.apply(ops.distortion_term, (0,), val, idx, dist_src, dist_tgt)
 
 
 class _DistLoss(torch.autograd.Function):

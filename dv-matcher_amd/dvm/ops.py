@@ -697,9 +697,23 @@ def map_term(verts12, verts2, idx11, idx22, pi_val, pi_idx):
     return out
 
 
+def _frob_max_n(name):
+    return int(getattr(_lib.load(), "dvm_%s_term_max_n" % name)())
+
+
+def _frob_term(name, ptrs, dims, grad_of, grad):
+    """The call of dvm_<name>_term_f32(*ptrs, *dims, loss, *gradients): loss (dims[0],) and, under grad, one gradient like each tensor
+    of grad_of (NULL otherwise); `dims` are also the sizes of its workspace query -> loss, or (loss, *gradients) under grad."""
+    dev = grad_of[0].device
+    loss = _new(dev, dims[0])
+    gs = [torch.empty_like(t) if grad else None for t in grad_of]
+    _call_ws("dvm_%s_term_f32" % name, (*ptrs, *dims, _p(loss), *[_p(g) for g in gs]), dev, name, "dvm_%s_term_workspace_bytes" % name, *dims)
+    return (loss, *gs) if grad else loss
+
+
 def rank_term_max_n():
     """The largest N dvm_rank_term_f32 takes (a row of P P^T must fit LDS); models.loss.rank_term falls back to torch beyond it."""
-    return int(_lib.load().dvm_rank_term_max_n())
+    return _frob_max_n("rank")
 
 
 def rank_term(pi_val, pi_idx, M, grad=False):
@@ -712,17 +726,12 @@ def rank_term(pi_val, pi_idx, M, grad=False):
     B, N, topk = pi_val.shape
     if tuple(pi_idx.shape) != (B, N, topk):
         raise ValueError("rank_term: pi_idx must have pi_val's shape %s, got %s" % ((B, N, topk), tuple(pi_idx.shape)))
-    dev = pi_val.device
-    loss = _new(dev, B)
-    g_val = torch.empty_like(pi_val) if grad else None
-    _call_ws("dvm_rank_term_f32", (_p(pi_val), _p(pi_idx), B, N, int(M), topk, _p(loss), _p(g_val)),
-             dev, "rank", "dvm_rank_term_workspace_bytes", B, N, int(M), topk)
-    return (loss, g_val) if grad else loss
+    return _frob_term("rank", (_p(pi_val), _p(pi_idx)), (B, N, int(M), topk), (pi_val,), grad)
 
 
 def cycle_term_max_n():
     """The largest N dvm_cycle_term_f32 takes (a row of P12 P21 must fit LDS); models.loss.cycle_term falls back to torch beyond it."""
-    return int(_lib.load().dvm_cycle_term_max_n())
+    return _frob_max_n("cycle")
 
 
 def cycle_term(val12, idx12, val21, idx21, grad=False):
@@ -739,19 +748,13 @@ def cycle_term(val12, idx12, val21, idx21, grad=False):
                          % (tuple(val12.shape), tuple(val21.shape), tuple(idx12.shape), tuple(idx21.shape)))
     B, N, k12 = val12.shape
     M, k21 = val21.shape[1], val21.shape[2]
-    dev = val12.device
-    loss = _new(dev, B)
-    g12 = torch.empty_like(val12) if grad else None
-    g21 = torch.empty_like(val21) if grad else None
-    _call_ws("dvm_cycle_term_f32", (_p(val12), _p(idx12), _p(val21), _p(idx21), B, N, M, k12, k21, _p(loss), _p(g12), _p(g21)),
-             dev, "cycle", "dvm_cycle_term_workspace_bytes", B, N, M, k12, k21)
-    return (loss, g12, g21) if grad else loss
+    return _frob_term("cycle", (_p(val12), _p(idx12), _p(val21), _p(idx21)), (B, N, M, k12, k21), (val12, val21), grad)
 
 
 def distortion_term_max_n():
     """The largest N and M dvm_distortion_term_f32 takes (the rows it keeps must fit LDS); models.loss.distortion_term falls back to
     torch beyond it."""
-    return int(_lib.load().dvm_distortion_term_max_n())
+    return _frob_max_n("distortion")
 
 
 def distortion_term(val, idx, dist_src, dist_tgt, grad=False):
@@ -769,12 +772,7 @@ def distortion_term(val, idx, dist_src, dist_tgt, grad=False):
     if dist_tgt.dim() != 3 or dist_tgt.shape[0] != B or dist_tgt.shape[1] != dist_tgt.shape[2]:
         raise ValueError("distortion_term: dist_tgt must be (%d,M,M), got %s" % (B, tuple(dist_tgt.shape)))
     M = dist_tgt.shape[1]
-    dev = val.device
-    loss = _new(dev, B)
-    g_val = torch.empty_like(val) if grad else None
-    _call_ws("dvm_distortion_term_f32", (_p(val), _p(idx), _p(dist_src), _p(dist_tgt), B, N, M, topk, _p(loss), _p(g_val)),
-             dev, "distortion", "dvm_distortion_term_workspace_bytes", B, N, M, topk)
-    return (loss, g_val) if grad else loss
+    return _frob_term("distortion", (_p(val), _p(idx), _p(dist_src), _p(dist_tgt)), (B, N, M, topk), (val,), grad)
 
 
 def _pair_out(B, n, dev):

@@ -150,6 +150,19 @@ class _SafeSqrt(torch.autograd.Function):
         return torch.where(r > 0, g / (2 * r).clamp_min(torch.finfo(r.dtype).tiny), torch.zeros_like(g))
 
 
+def _frob_norm(R):
+    """||R||_F per batch element of float64 residuals (B, ...) in fp32; the gradient where it is 0 is 0, as the kernels'."""
+    return _SafeSqrt.apply(R.square().flatten(1).sum(1)).float()
+
+
+def _frob_kernel_takes(max_n, pvals, others=(), rows_of=None):
+    """What the sparse Frobenius-norm kernels take: CUDA float32 3-D tensors with a batch, 1 <= k <= 16 for every pval, and
+    1 <= rows <= max_n() for every tensor of rows_of (default: the first pval).  max_n is asked last: it loads the library."""
+    ts = (*pvals, *others)
+    return (all(t.is_cuda and t.dtype == torch.float32 and t.dim() == 3 for t in ts) and ts[0].shape[0] >= 1
+            and all(1 <= p.shape[2] <= 16 for p in pvals) and all(1 <= t.shape[1] <= max_n() for t in (rows_of or pvals[:1])))
+
+
 def _rank_term_torch(pval, pidx, M):
     """rank_term with plain torch ops, for what the kernel does not take (CPU tensors, other dtypes, N over its limit):
         ||P P^T - I||_F^2 = ||P^T P||_F^2 - sum_i d_i^2 + sum_i (d_i - 1)^2,   d_i = sum_t val[i,t]^2 = (P P^T)_ii,
@@ -172,8 +185,7 @@ def rank_term(pval, pidx, M):
     where the term is 0 (an exact permutation) is 0.  CUDA float32 input within the kernel's limits (N <= ops.rank_term_max_n(),
     k <= 16) runs on dvm_rank_term_f32 (nn_ops.rank_term: row by row, no dense array, no float atomics); anything else on the
     torch formula of _rank_term_torch, which forms an M x M float64 matrix."""
-    if (pval.is_cuda and pval.dtype == torch.float32 and pval.dim() == 3 and pval.shape[0] >= 1 and 1 <= pval.shape[1] <= ops.rank_term_max_n()
-            and 1 <= pval.shape[2] <= 16 and M >= 1):
+    if _frob_kernel_takes(ops.rank_term_max_n, (pval,)) and M >= 1:
         return nn_ops.rank_term(pval, pidx, M)
     return _rank_term_torch(pval, pidx, M)
 
@@ -188,7 +200,7 @@ def _cycle_term_torch(pval12, pidx12, pval21, pidx21):
     P21 = torch.zeros(B, M, N, dtype=torch.float64, device=pval21.device).scatter_add(-1, pidx21.long(), pval21.double())
     R = torch.bmm(P12, P21)
     R.diagonal(dim1=1, dim2=2).sub_(1.0)
-    return _SafeSqrt.apply(R.square().flatten(1).sum(1)).float()
+    return _frob_norm(R)
 
 
 def cycle_term(pval12, pidx12, pval21, pidx21):
@@ -197,8 +209,7 @@ def cycle_term(pval12, pidx12, pval21, pidx21):
     Differentiable w.r.t. both pval; the gradient where the term is 0 is 0.  CUDA float32 input within the kernel's limits
     (N <= ops.cycle_term_max_n(), k <= 16) runs on dvm_cycle_term_f32 (nn_ops.cycle_term: row by row, no dense array, no float
     atomics); anything else on the torch formula of _cycle_term_torch, which forms dense float64 arrays."""
-    if (all(p.is_cuda and p.dtype == torch.float32 and p.dim() == 3 and 1 <= p.shape[2] <= 16 for p in (pval12, pval21))
-            and pval12.shape[0] >= 1 and 1 <= pval12.shape[1] <= ops.cycle_term_max_n() and pval21.shape[1] >= 1):
+    if _frob_kernel_takes(ops.cycle_term_max_n, (pval12, pval21)) and pval21.shape[1] >= 1:
         return nn_ops.cycle_term(pval12, pidx12, pval21, pidx21)
     return _cycle_term_torch(pval12, pidx12, pval21, pidx21)
 
@@ -216,7 +227,7 @@ def _distortion_term_torch(pval, pidx, dist_src, dist_tgt):
     M = dist_tgt.shape[1]
     P = torch.zeros(B, N, M, dtype=torch.float64, device=pval.device).scatter_add(-1, pidx.long(), pval.double())
     R = torch.bmm(torch.bmm(P, dist_tgt.detach().double()), P.transpose(1, 2)) - dist_src.detach().double()
-    return _SafeSqrt.apply(R.square().flatten(1).sum(1)).float()
+    return _frob_norm(R)
 
 
 def distortion_term(pval, pidx, dist_src, dist_tgt, symmetric=False):
@@ -230,8 +241,7 @@ def distortion_term(pval, pidx, dist_src, dist_tgt, symmetric=False):
     formula of _distortion_term_torch, which forms dense float64 arrays."""
     if not symmetric:
         dist_src, dist_tgt = _symmetrised(dist_src), _symmetrised(dist_tgt)
-    if (all(t.is_cuda and t.dtype == torch.float32 and t.dim() == 3 for t in (pval, dist_src, dist_tgt)) and pval.shape[0] >= 1
-            and 1 <= pval.shape[2] <= 16 and all(1 <= n <= ops.distortion_term_max_n() for n in (pval.shape[1], dist_tgt.shape[1]))):
+    if _frob_kernel_takes(ops.distortion_term_max_n, (pval,), (dist_src, dist_tgt), rows_of=(pval, dist_tgt)):
         return nn_ops.distortion_term(pval, pidx, dist_src, dist_tgt)
     return _distortion_term_torch(pval, pidx, dist_src, dist_tgt)
 
@@ -621,22 +631,25 @@ class GraphDeformLoss_Neural(nn.Module):
             if self.w_rank > 0:
                 if N != M:   # the reference compares the M x M product of the reverse direction with an N x N identity
                     raise ValueError("w_rank > 0 needs N == M (got %d, %d), as in the reference" % (N, M))
-                self.rank_loss = (rank_term(ex12["pval"], ex12["pidx"], M).mean() +
-                                  rank_term(ex21["pval"], ex21["pidx"], N).mean()) * self.w_rank / 2
+                self.rank_loss = self._pair_mean_term(self.w_rank, rank_term(ex12["pval"], ex12["pidx"], M), rank_term(ex21["pval"], ex21["pidx"], N))
                 loss = loss + self.rank_loss
-                self._mean_part = self._mean_part + self.rank_loss
             if self.w_cycle > 0:
-                self.cycle_loss = (cycle_term(ex12["pval"], ex12["pidx"], ex21["pval"], ex21["pidx"]).mean() +
-                                   cycle_term(ex21["pval"], ex21["pidx"], ex12["pval"], ex12["pidx"]).mean()) * self.w_cycle / 2
+                self.cycle_loss = self._pair_mean_term(self.w_cycle, cycle_term(ex12["pval"], ex12["pidx"], ex21["pval"], ex21["pidx"]),
+                                                       cycle_term(ex21["pval"], ex21["pidx"], ex12["pval"], ex12["pidx"]))
                 loss = loss + self.cycle_loss
-                self._mean_part = self._mean_part + self.cycle_loss
             if self.w_distortion > 0:
                 sym1, sym2 = _symmetrised(dist1), _symmetrised(dist2)   # once per call, for both directions
-                self.distortion_loss = (distortion_term(ex12["pval"], ex12["pidx"], sym1, sym2, symmetric=True).mean() +
-                                        distortion_term(ex21["pval"], ex21["pidx"], sym2, sym1, symmetric=True).mean()) * self.w_distortion / 2
+                self.distortion_loss = self._pair_mean_term(self.w_distortion, distortion_term(ex12["pval"], ex12["pidx"], sym1, sym2, symmetric=True),
+                                                            distortion_term(ex21["pval"], ex21["pidx"], sym2, sym1, symmetric=True))
                 loss = loss + self.distortion_loss
-                self._mean_part = self._mean_part + self.distortion_loss
         return loss, self.dist_loss, self.deform_loss, self.map_loss, self.self_rec_loss
+
+    def _pair_mean_term(self, w, t12, t21):
+        """A per-pair term of both directions (each (B,)) as the criterion counts it: the two batch means, weighted and halved; a
+        mean-type term for data_parallel_loss."""
+        term = (t12.mean() + t21.mean()) * w / 2
+        self._mean_part = self._mean_part + term
+        return term
 
     def data_parallel_loss(self, fraction):
         """The loss to back-propagate on ONE SHARD of a data-parallel batch (call after forward): the reference's

@@ -13,9 +13,10 @@ covers the summation order, the last term the fp32 output.  A12 / A21 are the gr
 what an entry-wise relative error of C can move.  At F = 0 loss and gradients are exactly 0."""
 import torch
 
+import frob_term_common as T
 import rank_term_ref as R
 
-U = R.U
+U = T.U
 
 
 def plant_pair(kind12, kind21, gen, B, N, M, k12, k21):
@@ -35,16 +36,14 @@ def _inverse_idx(B, N, M, k):
 
 def plant_near_inverse(B, N, M, k):
     """val = (1 - 1e-3, 1e-3 / (k - 1), ...) on both sides: at N == M, F ~ 0.026 and the diagonal residual dominates"""
-    row = torch.full((k,), 1e-3 / (k - 1), dtype=torch.float32)
-    row[0] = 1.0 - 1e-3
+    row = T.near_row(k)
     idx12, idx21 = _inverse_idx(B, N, M, k)
     return row.expand(B, N, k).contiguous(), idx12, row.expand(B, M, k).contiguous(), idx21
 
 
 def plant_exact_inverse(B, N, M, k):
     """the same indices, val = (1, 0, ...): P12 P21 = I exactly (N <= M)"""
-    row = torch.zeros(k, dtype=torch.float32)
-    row[0] = 1.0
+    row = T.exact_row(k)
     idx12, idx21 = _inverse_idx(B, N, M, k)
     return row.expand(B, N, k).contiguous(), idx12, row.expand(B, M, k).contiguous(), idx21
 
@@ -75,12 +74,9 @@ def dense_reference(val12, idx12, val21, idx21, grad=True):
 
 
 def loss_bound(ref, k):
-    return 4 * (k + 2) * U * ref["C_fro"] + 2 * U * ref["F"]
+    return T.loss_bound(ref, k + 2, ref["C_fro"])
 
 
 def grad_bound(ref, k, side):
     """side = "12" or "21"; k = k12 for both"""
-    F = ref["F"][:, None, None]
-    g = ref["g" + side].abs()
-    ratio = torch.where(F > 0, ref["C_fro"][:, None, None] / F.clamp_min(1e-300), torch.zeros_like(F))
-    return 4 * (k + 2) * U * (ref["A" + side] + g * ratio) + 2 * U * g
+    return T.grad_bound(ref, k + 2, ref["C_fro"], ref["g" + side], ref["A" + side])

@@ -24,9 +24,10 @@ An fp32 emulation of the two chains on the CPU (torch fp32 multiply-adds in slot
 bars at most on the plantings used here (k = 1 the largest, 0.1 - 0.6 % at k >= 10): a kernel near a bar has a bug."""
 import torch
 
+import frob_term_common as T
 import rank_term_ref as R
 
-U = R.U
+U = T.U
 
 
 def distances(gen, B, n):
@@ -56,16 +57,12 @@ def _isometry(gen, B, N, k, row):
 
 def plant_exact_isometry(gen, B, N, k):
     """val = (1, 0, ...): S[i,j] = D2[pi(i), pi(j)] = D1[i,j] with no rounding anywhere, F is exactly 0 in fp32"""
-    row = torch.zeros(k, dtype=torch.float32)
-    row[0] = 1.0
-    return _isometry(gen, B, N, k, row)
+    return _isometry(gen, B, N, k, T.exact_row(k))
 
 
 def plant_near_isometry(gen, B, N, k):
     """val = (1 - 1e-3, 1e-3 / (k - 1), ...): F is a thousandth of ||S||_F, the cancellation case"""
-    row = torch.full((k,), 1e-3 / (k - 1), dtype=torch.float32)
-    row[0] = 1.0 - 1e-3
-    return _isometry(gen, B, N, k, row)
+    return _isometry(gen, B, N, k, T.near_row(k))
 
 
 def dense_reference(val, idx, D1, D2, grad=True):
@@ -89,11 +86,8 @@ def dense_reference(val, idx, D1, D2, grad=True):
 
 
 def loss_bound(ref, k):
-    return 4 * (2 * k + 2) * U * ref["S_fro"] + 2 * U * ref["F"]
+    return T.loss_bound(ref, 2 * k + 2, ref["S_fro"])
 
 
 def grad_bound(ref, k):
-    F = ref["F"][:, None, None]
-    g = ref["g"].abs()
-    ratio = torch.where(F > 0, (ref["S_fro"] + ref["D1_fro"])[:, None, None] / F.clamp_min(1e-300), torch.zeros_like(F))
-    return 4 * (2 * k + 2) * U * (ref["A"] + g * ratio) + 2 * U * g
+    return T.grad_bound(ref, 2 * k + 2, ref["S_fro"] + ref["D1_fro"], ref["g"], ref["A"])

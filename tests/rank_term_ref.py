@@ -12,7 +12,9 @@ Reference: pi_val.double() scattered into a dense P (N x M), S = P P^T, F = ||S 
 last term the fp32 output.  At F = 0 loss and gradient are exactly 0."""
 import torch
 
-U = 2.0 ** -24
+import frob_term_common as T
+
+U = T.U
 
 
 def random_sets(gen, B, N, M, k):
@@ -38,16 +40,12 @@ def _shift_idx(B, N, M, k):
 
 def plant_near_perm(B, N, M, k):
     """idx[i,t] = (i + t) mod M, val = (1 - 1e-3, 1e-3 / (k - 1), ...): F ~ 0.026, the diagonal residual dominates"""
-    row = torch.full((k,), 1e-3 / (k - 1), dtype=torch.float32)
-    row[0] = 1.0 - 1e-3
-    return row.expand(B, N, k).contiguous(), _shift_idx(B, N, M, k)
+    return T.near_row(k).expand(B, N, k).contiguous(), _shift_idx(B, N, M, k)
 
 
 def plant_exact_perm(B, N, M, k):
     """the same indices, val = (1, 0, ...): P P^T = I exactly"""
-    row = torch.zeros(k, dtype=torch.float32)
-    row[0] = 1.0
-    return row.expand(B, N, k).contiguous(), _shift_idx(B, N, M, k)
+    return T.exact_row(k).expand(B, N, k).contiguous(), _shift_idx(B, N, M, k)
 
 
 def dense_reference(val, idx, M, grad=True):
@@ -74,10 +72,8 @@ def dense_reference(val, idx, M, grad=True):
 
 
 def loss_bound(ref, k):
-    return 4 * (k + 2) * U * ref["S_fro"] + 2 * U * ref["F"]
+    return T.loss_bound(ref, k + 2, ref["S_fro"])
 
 
 def grad_bound(ref, k):
-    F = ref["F"][:, None, None]
-    ratio = torch.where(F > 0, ref["S_fro"][:, None, None] / F.clamp_min(1e-300), torch.zeros_like(F))
-    return 4 * (k + 2) * U * (ref["A"] + ref["g"].abs() * ratio) + 2 * U * ref["g"].abs()
+    return T.grad_bound(ref, k + 2, ref["S_fro"], ref["g"], ref["A"])

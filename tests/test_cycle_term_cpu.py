@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import cycle_term_ref as C
+import frob_term_common as T
 
 ONE = ctypes.c_void_p(16)   # a pointer that must never be dereferenced
 K = 10
@@ -33,14 +34,10 @@ def test_cpu_fallback_matches_dense_float64(name, N, M):
     v12, v21 = val12.clone().requires_grad_(True), val21.clone().requires_grad_(True)
     loss = ml.cycle_term(v12, idx12, v21, idx21)
     assert loss.dtype == torch.float32 and tuple(loss.shape) == (1,)
-    err = (loss.detach().double() - ref["F"]).abs()
-    print(name, (N, M), "F", ref["F"].tolist(), "err", err.tolist(), "bound", (2 * C.U * ref["F"]).tolist())
-    assert bool((err <= 2 * C.U * ref["F"]).all())
+    T.check_fallback("%s %s" % (name, (N, M)), loss, ref)
     loss.sum().backward()
     for side, v in (("12", v12), ("21", v21)):
-        assert bool(torch.isfinite(v.grad).all())
-        gerr, gbar = (v.grad.double() - ref["g" + side]).abs(), C.grad_bound(ref, K, side)
-        assert bool((gerr <= gbar).all()), (side, float((gerr / gbar.clamp_min(1e-300)).max()))
+        T.check_fallback_grad(v.grad, ref["g" + side], C.grad_bound(ref, K, side))
     if name == "exact_inverse":
         assert bool((loss == 0).all()) and bool((v12.grad == 0).all()) and bool((v21.grad == 0).all())
     elif name == "near_inverse":
@@ -50,12 +47,7 @@ def test_cpu_fallback_matches_dense_float64(name, N, M):
 
 
 def test_entries_exported_sized_and_limited():
-    from dvm import _lib
-    lib = _lib.load()
-    raw = ctypes.CDLL(_lib.SO_PATH)
-    for name in ("dvm_cycle_term_max_n", "dvm_cycle_term_workspace_bytes", "dvm_cycle_term_f32"):
-        assert hasattr(raw, name) and name in _lib.SIGNATURES, name
-    nmax = lib.dvm_cycle_term_max_n()
+    lib, nmax = T.check_entries_exported("cycle")
     assert nmax >= 8192
     B, N, M, k12, k21 = 2, 300, 170, 10, 10
     # the reversed lists of idx12, one double per row, one float per element, the k12 x k21 samples of every row
@@ -92,13 +84,7 @@ def test_argument_validation_without_gpu():
 
 
 def test_wrappers_have_no_cpu_path():
-    from dvm import nn_ops, ops
-    from dvm._lib import DvmError
-    val12, idx12, val21, idx21 = C.plant_near_inverse(1, 8, 8, 3)
-    with pytest.raises(DvmError):
-        ops.cycle_term(val12, idx12, val21, idx21)
-    with pytest.raises(DvmError):
-        nn_ops.cycle_term(val12.clone().requires_grad_(True), idx12, val21, idx21)
+    T.check_no_cpu_path("cycle", C.plant_near_inverse(1, 8, 8, 3))
 
 
 def test_wrapper_shape_checks(monkeypatch):

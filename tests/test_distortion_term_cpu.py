@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import distortion_term_ref as D
+import frob_term_common as T
 
 ONE = ctypes.c_void_p(16)   # a pointer that must never be dereferenced
 K = 10
@@ -31,13 +32,9 @@ def test_cpu_fallback_matches_dense_float64(name, N, M):
     v = val.clone().requires_grad_(True)
     loss = ml.distortion_term(v, idx, D1, D2, symmetric=True)
     assert loss.dtype == torch.float32 and tuple(loss.shape) == (1,)
-    err = (loss.detach().double() - ref["F"]).abs()
-    print(name, (N, M), "F", ref["F"].tolist(), "err", err.tolist(), "bound", (2 * D.U * ref["F"]).tolist())
-    assert bool((err <= 2 * D.U * ref["F"]).all())
+    T.check_fallback("%s %s" % (name, (N, M)), loss, ref)
     loss.sum().backward()
-    assert bool(torch.isfinite(v.grad).all())
-    gerr, gbar = (v.grad.double() - ref["g"]).abs(), D.grad_bound(ref, K)
-    assert bool((gerr <= gbar).all()), float((gerr / gbar.clamp_min(1e-300)).max())
+    T.check_fallback_grad(v.grad, ref["g"], D.grad_bound(ref, K))
     if name == "exact_isometry":
         assert bool((loss == 0).all()) and bool((v.grad == 0).all())
     elif name == "near_isometry":
@@ -75,12 +72,7 @@ def test_fallback_symmetrises():
 
 
 def test_entries_exported_sized_and_limited():
-    from dvm import _lib
-    lib = _lib.load()
-    raw = ctypes.CDLL(_lib.SO_PATH)
-    for name in ("dvm_distortion_term_max_n", "dvm_distortion_term_workspace_bytes", "dvm_distortion_term_f32"):
-        assert hasattr(raw, name) and name in _lib.SIGNATURES, name
-    nmax = lib.dvm_distortion_term_max_n()
+    lib, nmax = T.check_entries_exported("distortion")
     assert nmax == 8192
     B, N, M, k = 2, 300, 170, 10
     got = lib.dvm_distortion_term_workspace_bytes(B, N, M, k)
@@ -118,13 +110,7 @@ def test_argument_validation_without_gpu():
 
 
 def test_wrappers_have_no_cpu_path():
-    from dvm import nn_ops, ops
-    from dvm._lib import DvmError
-    val, idx, D1, D2 = D.plant_near_isometry(torch.Generator().manual_seed(1), 1, 8, 3)
-    with pytest.raises(DvmError):
-        ops.distortion_term(val, idx, D1, D2)
-    with pytest.raises(DvmError):
-        nn_ops.distortion_term(val.clone().requires_grad_(True), idx, D1, D2)
+    T.check_no_cpu_path("distortion", D.plant_near_isometry(torch.Generator().manual_seed(1), 1, 8, 3))
 
 
 def test_wrapper_shape_checks(monkeypatch):

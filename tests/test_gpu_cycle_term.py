@@ -12,32 +12,19 @@ import pytest
 import torch
 
 import cycle_term_ref as C
+import frob_term_common as T
 
 pytestmark = pytest.mark.gpu
+_gen, _bits = T.gen, T.bits
 
 
 @pytest.fixture(scope="module")
 def ops():
-    from dvm import ops as _ops
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return _ops
-
-
-def _gen(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-def _bits(t):
-    return t.detach().cpu().contiguous().view(torch.int32)
+    return T.load_ops()
 
 
 def _run(ops, pair):
-    dev = [t.cuda() for t in pair]
-    loss, g12, g21 = ops.cycle_term(*dev, grad=True)
-    loss_only = ops.cycle_term(*dev)
-    torch.cuda.synchronize()
-    assert torch.equal(_bits(loss), _bits(loss_only)), "the loss-only call gives other bits than the one that also forms the gradients"
-    return loss.cpu(), g12.cpu(), g21.cpu()
+    return T.run_both(ops.cycle_term, pair)
 
 
 def _check(ops, name, pair):
@@ -49,7 +36,7 @@ def _check(ops, name, pair):
     worst = {}
     for side, g in (("12", g12), ("21", g21)):
         gerr, gbar = (g.double() - ref["g" + side]).abs(), C.grad_bound(ref, k, side)
-        worst[side] = float((gerr / gbar.clamp_min(1e-300)).max())
+        worst[side] = T.worst_ratio(gerr, gbar)
     print("%s: F %s loss err %s bar %s ratio %.4f; worst gradient err / bar: g12 %.4f g21 %.4f" %
           (name, ref["F"].tolist(), lerr.tolist(), lbar.tolist(), float((lerr / lbar).max()), worst["12"], worst["21"]))
     assert bool((lerr <= lbar).all()), (name, lerr.tolist(), lbar.tolist())
@@ -100,61 +87,19 @@ def _batch_160():
 
 def test_batch_independence(ops):
     """A batch of the random, hub and near-inverse plantings: every element gets the bits it gets alone."""
-    pair = _batch_160()
-    out = _run(ops, pair)
-    for b in range(pair[0].shape[0]):
-        alone = _run(ops, tuple(t[b:b + 1].contiguous() for t in pair))
-        for whole, one in zip(out, alone):
-            assert torch.equal(_bits(whole[b:b + 1]), _bits(one)), b
+    T.check_batch_independence(lambda pair: _run(ops, pair), _batch_160())
 
 
 def test_scratch_hygiene(ops, monkeypatch):
     """The same call on a workspace that held 0xFF bytes (int32 -1, a NaN in every float format) and fp32 NaNs: the same bits."""
-    pair = _batch_160()
-    clean = _run(ops, pair)
-    again = _run(ops, pair)
-    assert all(torch.equal(_bits(a), _bits(b)) for a, b in zip(clean, again))   # run to run
-    kept = []
-
-    def filled(fill):
-        def workspace(nbytes, device, tag="ws"):
-            n = (int(nbytes) + 3) // 4 * 4
-            buf = torch.full((n,), 0xFF, dtype=torch.uint8, device=device)
-            if fill == "nan":
-                buf.view(torch.float32).fill_(float("nan"))
-            kept.append(buf)
-            return buf
-        return workspace
-
-    for fill in ("ff", "nan"):
-        monkeypatch.setattr(ops, "workspace", filled(fill))
-        out = _run(ops, pair)
-        assert all(torch.equal(_bits(a), _bits(b)) for a, b in zip(clean, out)), fill
-    assert len(kept) == 4
+    T.check_scratch_hygiene(ops, monkeypatch, lambda pair: _run(ops, pair), _batch_160())
 
 
 def test_route_and_autograd(ops):
     """models.loss.cycle_term on CUDA float32 is the kernel: ops.cycle_term's bits, and backward() gives g12 / g21 times the incoming
     gradient."""
     import models.loss as ml
-    dev = [t.cuda() for t in _batch_160()]
-    val12, idx12, val21, idx21 = dev
-    loss_k, g12_k, g21_k = ops.cycle_term(*dev, grad=True)
-    with torch.no_grad():
-        assert torch.equal(_bits(ml.cycle_term(*dev)), _bits(loss_k))
-    v12, v21 = val12.clone().requires_grad_(True), val21.clone().requires_grad_(True)
-    loss = ml.cycle_term(v12, idx12, v21, idx21)
-    assert loss.dtype == torch.float32 and loss.requires_grad
-    assert torch.equal(_bits(loss), _bits(loss_k))
-    loss.sum().backward()
-    assert torch.equal(_bits(v12.grad), _bits(g12_k)) and torch.equal(_bits(v21.grad), _bits(g21_k))
-    w = torch.tensor([0.5, -2.0, 3.0], device="cuda")
-    u12, u21 = val12.clone().requires_grad_(True), val21.clone().requires_grad_(True)
-    (ml.cycle_term(u12, idx12, u21, idx21) * w).sum().backward()
-    assert torch.equal(_bits(u12.grad), _bits(g12_k * w[:, None, None]))
-    assert torch.equal(_bits(u21.grad), _bits(g21_k * w[:, None, None]))
-    with torch.no_grad():   # the criterion's own index dtype may be int64: same route, same bits
-        assert torch.equal(_bits(ml.cycle_term(val12, idx12.long(), val21, idx21.long())), _bits(loss_k))
+    T.check_route_and_autograd(ops.cycle_term, ml.cycle_term, _batch_160(), (0, 2))
 
 
 def test_limit(ops):
@@ -172,20 +117,11 @@ def test_limit(ops):
     assert lib.dvm_cycle_term_workspace_bytes(1, N, M, k, k) == 0
     assert lib.dvm_cycle_term_workspace_bytes(1, N - 1, M, k, k) > 0
     dev = [t.cuda() for t in (val12, idx12, val21, idx21)]
-    out = torch.full((1,), -7.0, device="cuda")
-    ws = torch.empty(lib.dvm_cycle_term_workspace_bytes(1, N - 1, M, k, k) * 2, dtype=torch.uint8, device="cuda")
-    rc = lib.dvm_cycle_term_f32(dev[0].data_ptr(), dev[1].data_ptr(), dev[2].data_ptr(), dev[3].data_ptr(), 1, N, M, k, k, out.data_ptr(),
-                                None, None, ws.data_ptr(), ws.numel(), None)
-    torch.cuda.synchronize()
-    assert rc == -1 and b"N=%d" % N in lib.dvm_last_error()
-    assert float(out) == -7.0   # nothing ran
+    T.refused_before_launch(lib, "dvm_cycle_term_f32", (*dev, 1, N, M, k, k), 2, lib.dvm_cycle_term_workspace_bytes(1, N - 1, M, k, k) * 2,
+                            b"N=%d" % N)
     with pytest.raises(_lib.DvmError):
         ops.cycle_term(*dev)
-    ref = C.dense_reference(val12, idx12, val21, idx21, grad=False)
-    loss = ml.cycle_term(*dev).cpu()
-    err = (loss.double() - ref["F"]).abs()
-    print("limit: N %d F %s err %s bar %s" % (N, ref["F"].tolist(), err.tolist(), (2 * C.U * ref["F"]).tolist()))
-    assert bool((err <= 2 * C.U * ref["F"]).all())
+    T.check_fallback("limit: N %d" % N, ml.cycle_term(*dev), C.dense_reference(val12, idx12, val21, idx21, grad=False))
 
 
 def test_memory(ops):
@@ -194,43 +130,15 @@ def test_memory(ops):
     import models.loss as ml
     B, N, M, k = 4, 8192, 8192, 10
     gen = torch.Generator(device="cuda").manual_seed(5)
-
-    def side():
-        # k distinct buckets of 64 columns per row, one random column in each: random sets without an N x M draw
-        bucket = torch.rand(B, N, 128, generator=gen, device="cuda").argsort(-1)[..., :k]
-        idx = (bucket * 64 + torch.randint(0, 64, (B, N, k), generator=gen, device="cuda")).to(torch.int32).contiguous()
-        val = torch.softmax(3.0 * torch.randn(B, N, k, generator=gen, device="cuda"), -1).contiguous().requires_grad_(True)
-        return val, idx
-
-    val12, idx12 = side()
-    val21, idx21 = side()
+    val12, idx12 = T.bucketed_sets(gen, B, N, k, 64)
+    val21, idx21 = T.bucketed_sets(gen, B, N, k, 64)
     assert int(min(idx12.min(), idx21.min())) >= 0 and int(max(idx12.max(), idx21.max())) < M
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-    torch.cuda.reset_peak_memory_stats()
-    base = torch.cuda.memory_allocated()
-    ml.cycle_term(val12, idx12, val21, idx21).sum().backward()
-    torch.cuda.synchronize()
-    rise = torch.cuda.max_memory_allocated() - base
+    rise, _ = T.peak_rise(lambda: ml.cycle_term(val12, idx12, val21, idx21).sum().backward())
     bound = 8 * B * N * k * k + 64 * B * (N + M) * k
     print("memory: peak rise %d bytes, bound %d" % (rise, bound))
     assert rise <= bound
     for v in (val12, val21):
         assert bool(torch.isfinite(v.grad).all()) and float(v.grad.abs().max()) > 0
-
-
-def _criterion_inputs(B, N, M, seed):
-    gen = _gen(seed)
-    f1 = (0.3 * torch.relu(torch.randn(B, N, 128, generator=gen))).cuda().requires_grad_(True)
-    f2 = (0.3 * torch.relu(torch.randn(B, M, 128, generator=gen))).cuda().requires_grad_(True)
-    v1, v2 = torch.rand(B, N, 3, generator=gen).cuda(), torch.rand(B, M, 3, generator=gen).cuda()
-    return f1, f2, v1, v2
-
-
-def _criterion(ml, partial, w_rank=0):
-    cls = ml.GraphDeformLoss_Neural_Partial if partial else ml.GraphDeformLoss_Neural
-    return cls(save_name="t", k_deform=10, w_dist=0.02, w_map=0 if partial else 0.005, k_dist=30, N_dist=60, partial=partial, w_deform=0.5,
-               w_img=0, w_rank=w_rank, w_self_rec=0.5, w_cd=0.1, w_arap=0.01)
 
 
 @pytest.mark.parametrize("N,M", [(256, 256), (256, 192)])
@@ -251,9 +159,9 @@ def test_criterion_step(ops, monkeypatch, N, M):
     monkeypatch.setattr(ml, "cycle_term", spy)
     torch.manual_seed(3)
     B, w_cycle = 2, 0.3
-    f1, f2, v1, v2 = _criterion_inputs(B, N, M, 21)
+    f1, f2, v1, v2 = T.criterion_inputs(B, N, M, 21)
     d = mm.Deformer(10).cuda().train()
-    crit = _criterion(ml, partial=N != M)
+    crit = T.make_criterion(ml, partial=N != M)
     assert crit.w_cycle == 0 and crit.cycle_loss == 0
     crit.w_cycle = w_cycle
     out = crit(f1, f2, torch.cdist(v1, v1), torch.cdist(v2, v2), v1, v2, np.float64(100.0), d)
@@ -261,43 +169,11 @@ def test_criterion_step(ops, monkeypatch, N, M):
     assert len(seen) == 2 and all(s[4] for s in seen)   # both directions, on the route the kernel takes
     assert tuple(seen[0][0].shape) == (B, N, 10) and tuple(seen[0][2].shape) == (B, M, 10)
     assert tuple(seen[1][0].shape) == (B, M, 10) and tuple(seen[1][2].shape) == (B, N, 10)
-    want, bar = 0.0, 0.0
-    for pair in seen:
-        ref = C.dense_reference(*pair[:4], grad=False)
-        want += float(ref["F"].mean()) * w_cycle / 2
-        bar += float(C.loss_bound(ref, pair[0].shape[-1]).mean()) * w_cycle / 2
-    got = float(crit.cycle_loss.detach())
-    bar += 4 * C.U * abs(want)
-    print("criterion (%d,%d): cycle_loss %.9g reference %.9g err %.3e bar %.3e" % (N, M, got, want, abs(got - want), bar))
-    assert abs(got - want) <= bar
-    out[0].backward()
-    assert bool(torch.isfinite(f1.grad).all()) and bool(torch.isfinite(f2.grad).all())
-    assert float(f1.grad.abs().max()) > 0 and float(f2.grad.abs().max()) > 0
+    refs = [C.dense_reference(*pair[:4], grad=False) for pair in seen]
+    T.check_criterion_term("criterion (%d,%d): cycle_loss" % (N, M), crit.cycle_loss,
+                           [(ref, C.loss_bound(ref, pair[0].shape[-1])) for ref, pair in zip(refs, seen)], w_cycle, out, (f1, f2), (f1, f2))
 
 
 def test_criterion_default_is_untouched(ops, monkeypatch):
     """w_cycle left at 0: the term is never computed and the native node (nn_ops.criterion_train) is still the route taken."""
-    import models.loss as ml
-    import models.model as mm
-    from dvm import nn_ops
-    calls = {"cycle": 0, "native": 0}
-    real_term, real_native = ml.cycle_term, nn_ops.criterion_train
-
-    def spy_term(*a):
-        calls["cycle"] += 1
-        return real_term(*a)
-
-    def spy_native(*a, **kw):
-        calls["native"] += 1
-        return real_native(*a, **kw)
-
-    monkeypatch.setattr(ml, "cycle_term", spy_term)
-    monkeypatch.setattr(nn_ops, "criterion_train", spy_native)
-    torch.manual_seed(3)
-    B, N = 2, 256
-    f1, f2, v1, v2 = _criterion_inputs(B, N, N, 21)
-    d = mm.Deformer(10).cuda().train()
-    crit = _criterion(ml, partial=False)
-    out = crit(f1, f2, torch.cdist(v1, v1), torch.cdist(v2, v2), v1, v2, np.float64(100.0), d)
-    assert calls == {"cycle": 0, "native": 1}
-    assert crit.cycle_loss == 0 and bool(torch.isfinite(out[0]))
+    T.check_criterion_default_untouched(monkeypatch, "cycle")

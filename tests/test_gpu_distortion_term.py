@@ -12,32 +12,19 @@ import pytest
 import torch
 
 import distortion_term_ref as D
+import frob_term_common as T
 
 pytestmark = pytest.mark.gpu
+_gen, _bits = T.gen, T.bits
 
 
 @pytest.fixture(scope="module")
 def ops():
-    from dvm import ops as _ops
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return _ops
-
-
-def _gen(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-def _bits(t):
-    return t.detach().cpu().contiguous().view(torch.int32)
+    return T.load_ops()
 
 
 def _run(ops, case):
-    dev = [t.cuda() for t in case]
-    loss, g = ops.distortion_term(*dev, grad=True)
-    loss_only = ops.distortion_term(*dev)
-    torch.cuda.synchronize()
-    assert torch.equal(_bits(loss), _bits(loss_only)), "the loss-only call gives other bits than the one that also forms the gradient"
-    return loss.cpu(), g.cpu()
+    return T.run_both(ops.distortion_term, case)
 
 
 def _check(ops, name, case):
@@ -47,7 +34,7 @@ def _check(ops, name, case):
     assert bool(torch.isfinite(loss).all()) and bool(torch.isfinite(g).all())
     lerr, lbar = (loss.double() - ref["F"]).abs(), D.loss_bound(ref, k)
     gerr, gbar = (g.double() - ref["g"]).abs(), D.grad_bound(ref, k)
-    worst = float((gerr / gbar.clamp_min(1e-300)).max())
+    worst = T.worst_ratio(gerr, gbar)
     print("%s: F %s ||S|| %s loss err %s bar %s err / bar %.4f; worst gradient err / bar %.4f" %
           (name, ref["F"].tolist(), ref["S_fro"].tolist(), lerr.tolist(), lbar.tolist(), float((lerr / lbar).max()), worst))
     assert bool((lerr <= lbar).all()), (name, lerr.tolist(), lbar.tolist())
@@ -93,7 +80,7 @@ def test_asymmetric_matrices(ops):
     loss.sum().backward()
     lerr, lbar = (loss.detach().cpu().double() - ref["F"]).abs(), D.loss_bound(ref, 10)
     gerr, gbar = (v.grad.cpu().double() - ref["g"]).abs(), D.grad_bound(ref, 10)
-    worst = float((gerr / gbar.clamp_min(1e-300)).max())
+    worst = T.worst_ratio(gerr, gbar)
     print("asymmetric: F %s loss err / bar %.4f worst gradient err / bar %.4f" % (ref["F"].tolist(), float((lerr / lbar).max()), worst))
     assert bool((lerr <= lbar).all()) and worst <= 1.0
 
@@ -107,60 +94,27 @@ def _batch_160():
 
 def test_batch_independence(ops):
     """A batch of the random, hub and near-isometry plantings: every element gets the bits it gets alone."""
-    case = _batch_160()
-    out = _run(ops, case)
-    for b in range(case[0].shape[0]):
-        alone = _run(ops, tuple(t[b:b + 1].contiguous() for t in case))
-        for whole, one in zip(out, alone):
-            assert torch.equal(_bits(whole[b:b + 1]), _bits(one)), b
+    T.check_batch_independence(lambda case: _run(ops, case), _batch_160())
 
 
 def test_scratch_hygiene(ops, monkeypatch):
     """The same call on a workspace that held 0xFF bytes (int32 -1, a NaN in every float format) and fp32 NaNs: the same bits."""
-    case = _batch_160()
-    clean = _run(ops, case)
-    again = _run(ops, case)
-    assert all(torch.equal(_bits(a), _bits(b)) for a, b in zip(clean, again))   # run to run
-    kept = []
-
-    def filled(fill):
-        def workspace(nbytes, device, tag="ws"):
-            n = (int(nbytes) + 3) // 4 * 4
-            buf = torch.full((n,), 0xFF, dtype=torch.uint8, device=device)
-            if fill == "nan":
-                buf.view(torch.float32).fill_(float("nan"))
-            kept.append(buf)
-            return buf
-        return workspace
-
-    for fill in ("ff", "nan"):
-        monkeypatch.setattr(ops, "workspace", filled(fill))
-        out = _run(ops, case)
-        assert all(torch.equal(_bits(a), _bits(b)) for a, b in zip(clean, out)), fill
-    assert len(kept) == 4
+    T.check_scratch_hygiene(ops, monkeypatch, lambda case: _run(ops, case), _batch_160())
 
 
 def test_route_and_autograd(ops):
     """models.loss.distortion_term on CUDA float32 is the kernel: ops.distortion_term's bits, and backward() gives g times the
     incoming gradient, to val only."""
     import models.loss as ml
-    val, idx, D1, D2 = [t.cuda() for t in _batch_160()]
-    loss_k, g_k = ops.distortion_term(val, idx, D1, D2, grad=True)
+    case = _batch_160()
+    T.check_route_and_autograd(ops.distortion_term, lambda *a: ml.distortion_term(*a, symmetric=True), case, (0,))
+    val, idx, D1, D2 = T.to_cuda(case)
+    loss_k = ops.distortion_term(val, idx, D1, D2)
     with torch.no_grad():
-        assert torch.equal(_bits(ml.distortion_term(val, idx, D1, D2, symmetric=True)), _bits(loss_k))
         assert torch.equal(_bits(ml.distortion_term(val, idx, D1, D2)), _bits(loss_k))   # symmetric already: the same matrices
-    v, d1 = val.clone().requires_grad_(True), D1.clone().requires_grad_(True)
-    loss = ml.distortion_term(v, idx, d1, D2, symmetric=True)
-    assert loss.dtype == torch.float32 and loss.requires_grad
-    assert torch.equal(_bits(loss), _bits(loss_k))
-    loss.sum().backward()
-    assert torch.equal(_bits(v.grad), _bits(g_k)) and d1.grad is None
-    w = torch.tensor([0.5, -2.0, 3.0], device="cuda")
-    u = val.clone().requires_grad_(True)
-    (ml.distortion_term(u, idx, D1, D2, symmetric=True) * w).sum().backward()
-    assert torch.equal(_bits(u.grad), _bits(g_k * w[:, None, None]))
-    with torch.no_grad():   # the criterion's own index dtype may be int64: same route, same bits
-        assert torch.equal(_bits(ml.distortion_term(val, idx.long(), D1, D2, symmetric=True)), _bits(loss_k))
+    d1 = D1.clone().requires_grad_(True)
+    ml.distortion_term(val.clone().requires_grad_(True), idx, d1, D2, symmetric=True).sum().backward()
+    assert d1.grad is None
 
 
 def test_out_of_range_and_zero_slots(ops):
@@ -199,20 +153,10 @@ def test_limit(ops, which):
     assert lib.dvm_distortion_term_workspace_bytes(1, N, M, k) == 0
     assert lib.dvm_distortion_term_workspace_bytes(1, min(N, big - 1), min(M, big - 1), k) > 0
     dev = [t.cuda() for t in (val, idx, D1, D2)]
-    out = torch.full((1,), -7.0, device="cuda")
-    ws = torch.empty(1 << 20, dtype=torch.uint8, device="cuda")
-    rc = lib.dvm_distortion_term_f32(dev[0].data_ptr(), dev[1].data_ptr(), dev[2].data_ptr(), dev[3].data_ptr(), 1, N, M, k, out.data_ptr(),
-                                     None, ws.data_ptr(), ws.numel(), None)
-    torch.cuda.synchronize()
-    assert rc == -1 and b"%s=%d" % (which.encode(), big) in lib.dvm_last_error()
-    assert float(out) == -7.0   # nothing ran
+    T.refused_before_launch(lib, "dvm_distortion_term_f32", (*dev, 1, N, M, k), 1, 1 << 20, b"%s=%d" % (which.encode(), big))
     with pytest.raises(_lib.DvmError):
         ops.distortion_term(*dev)
-    ref = D.dense_reference(val, idx, D1, D2, grad=False)
-    loss = ml.distortion_term(*dev, symmetric=True).cpu()
-    err = (loss.double() - ref["F"]).abs()
-    print("limit: N %d M %d F %s err %s bar %s" % (N, M, ref["F"].tolist(), err.tolist(), (2 * D.U * ref["F"]).tolist()))
-    assert bool((err <= 2 * D.U * ref["F"]).all())
+    T.check_fallback("limit: N %d M %d" % (N, M), ml.distortion_term(*dev, symmetric=True), D.dense_reference(val, idx, D1, D2, grad=False))
 
 
 def test_memory(ops):
@@ -230,21 +174,16 @@ def test_memory(ops):
         d.diagonal(dim1=1, dim2=2).zero_()
         return d.contiguous()
 
-    # k distinct buckets of 32 columns per row, one random column in each: random sets without an N x M draw
-    bucket = torch.rand(B, N, 128, generator=gen, device="cuda").argsort(-1)[..., :k]
-    idx = (bucket * 32 + torch.randint(0, 32, (B, N, k), generator=gen, device="cuda")).to(torch.int32).contiguous()
-    val = torch.softmax(3.0 * torch.randn(B, N, k, generator=gen, device="cuda"), -1).contiguous().requires_grad_(True)
+    val, idx = T.bucketed_sets(gen, B, N, k, 32)
     D1, D2 = dist(N), dist(M)
-    del bucket
     assert int(idx.min()) >= 0 and int(idx.max()) < M
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-    torch.cuda.reset_peak_memory_stats()
-    base = torch.cuda.memory_allocated()
-    loss = ml.distortion_term(val, idx, D1, D2, symmetric=True)
-    loss.sum().backward()
-    torch.cuda.synchronize()
-    rise = torch.cuda.max_memory_allocated() - base
+
+    def step():
+        loss = ml.distortion_term(val, idx, D1, D2, symmetric=True)
+        loss.sum().backward()
+        return loss
+
+    rise, loss = T.peak_rise(step)
     bound = 64 * B * (N + M) * k
     print("memory: peak rise %d bytes, bound %d; loss %s" % (rise, bound, loss.tolist()))
     assert rise <= bound
@@ -253,20 +192,6 @@ def test_memory(ops):
     # the same rows through the loss-only kernel (4 M bytes of LDS): the same bits
     with torch.no_grad():
         assert torch.equal(_bits(ml.distortion_term(val, idx, D1, D2, symmetric=True)), _bits(loss))
-
-
-def _criterion_inputs(B, N, M, seed):
-    gen = _gen(seed)
-    f1 = (0.3 * torch.relu(torch.randn(B, N, 128, generator=gen))).cuda().requires_grad_(True)
-    f2 = (0.3 * torch.relu(torch.randn(B, M, 128, generator=gen))).cuda().requires_grad_(True)
-    v1, v2 = torch.rand(B, N, 3, generator=gen).cuda(), torch.rand(B, M, 3, generator=gen).cuda()
-    return f1, f2, v1, v2
-
-
-def _criterion(ml, partial):
-    cls = ml.GraphDeformLoss_Neural_Partial if partial else ml.GraphDeformLoss_Neural
-    return cls(save_name="t", k_deform=10, w_dist=0.02, w_map=0 if partial else 0.005, k_dist=30, N_dist=60, partial=partial, w_deform=0.5,
-               w_img=0, w_rank=0, w_self_rec=0.5, w_cd=0.1, w_arap=0.01)
 
 
 @pytest.mark.parametrize("N,M", [(256, 256), (256, 192)])
@@ -288,9 +213,9 @@ def test_criterion_step(ops, monkeypatch, N, M):
     monkeypatch.setattr(ml, "distortion_term", spy)
     torch.manual_seed(3)
     B, w = 2, 0.3
-    f1, f2, v1, v2 = _criterion_inputs(B, N, M, 21)
+    f1, f2, v1, v2 = T.criterion_inputs(B, N, M, 21)
     d = mm.Deformer(10).cuda().train()
-    crit = _criterion(ml, partial=N != M)
+    crit = T.make_criterion(ml, partial=N != M)
     assert crit.w_distortion == 0 and crit.distortion_loss == 0
     crit.w_distortion = w
     # matmul-form distances: symmetric only to rounding, as the criterion's real input
@@ -305,43 +230,11 @@ def test_criterion_step(ops, monkeypatch, N, M):
     for s in seen:
         assert torch.equal(s[2], s[2].transpose(1, 2)) and torch.equal(s[3], s[3].transpose(1, 2))
     assert torch.equal(seen[0][2], (0.5 * (dist1 + dist1.transpose(1, 2))).cpu()) and torch.equal(seen[0][3], seen[1][2])
-    want, bar = 0.0, 0.0
-    for s in seen:
-        ref = D.dense_reference(*s[:4], grad=False)
-        want += float(ref["F"].mean()) * w / 2
-        bar += float(D.loss_bound(ref, s[0].shape[-1]).mean()) * w / 2
-    got = float(crit.distortion_loss.detach())
-    bar += 4 * D.U * abs(want)
-    print("criterion (%d,%d): distortion_loss %.9g reference %.9g err %.3e bar %.3e" % (N, M, got, want, abs(got - want), bar))
-    assert abs(got - want) <= bar
-    out[0].backward()
-    assert bool(torch.isfinite(f1.grad).all()) and bool(torch.isfinite(f2.grad).all())
-    assert float(f1.grad.abs().max()) > 0 and float(f2.grad.abs().max()) > 0
+    refs = [D.dense_reference(*s[:4], grad=False) for s in seen]
+    T.check_criterion_term("criterion (%d,%d): distortion_loss" % (N, M), crit.distortion_loss,
+                           [(ref, D.loss_bound(ref, s[0].shape[-1])) for ref, s in zip(refs, seen)], w, out, (f1, f2), (f1, f2))
 
 
 def test_criterion_default_is_untouched(ops, monkeypatch):
     """w_distortion left at 0: the term is never computed and the native node (nn_ops.criterion_train) is still the route taken."""
-    import models.loss as ml
-    import models.model as mm
-    from dvm import nn_ops
-    calls = {"distortion": 0, "native": 0}
-    real_term, real_native = ml.distortion_term, nn_ops.criterion_train
-
-    def spy_term(*a, **kw):
-        calls["distortion"] += 1
-        return real_term(*a, **kw)
-
-    def spy_native(*a, **kw):
-        calls["native"] += 1
-        return real_native(*a, **kw)
-
-    monkeypatch.setattr(ml, "distortion_term", spy_term)
-    monkeypatch.setattr(nn_ops, "criterion_train", spy_native)
-    torch.manual_seed(3)
-    B, N = 2, 256
-    f1, f2, v1, v2 = _criterion_inputs(B, N, N, 21)
-    d = mm.Deformer(10).cuda().train()
-    crit = _criterion(ml, partial=False)
-    out = crit(f1, f2, torch.cdist(v1, v1), torch.cdist(v2, v2), v1, v2, np.float64(100.0), d)
-    assert calls == {"distortion": 0, "native": 1}
-    assert crit.distortion_loss == 0 and bool(torch.isfinite(out[0]))
+    T.check_criterion_default_untouched(monkeypatch, "distortion")

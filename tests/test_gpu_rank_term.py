@@ -10,32 +10,20 @@ import numpy as np
 import pytest
 import torch
 
+import frob_term_common as T
 import rank_term_ref as R
 
 pytestmark = pytest.mark.gpu
+_gen, _bits = T.gen, T.bits
 
 
 @pytest.fixture(scope="module")
 def ops():
-    from dvm import ops as _ops
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return _ops
-
-
-def _gen(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-def _bits(t):
-    return t.detach().cpu().contiguous().view(torch.int32)
+    return T.load_ops()
 
 
 def _run(ops, val, idx, M):
-    loss, g = ops.rank_term(val.cuda(), idx.cuda(), M, grad=True)
-    loss_only = ops.rank_term(val.cuda(), idx.cuda(), M)
-    torch.cuda.synchronize()
-    assert torch.equal(_bits(loss), _bits(loss_only)), "the forward-only kernel gives other bits than the one that also forms the gradient"
-    return loss.cpu(), g.cpu()
+    return T.run_both(ops.rank_term, (val, idx, M))
 
 
 def _check(ops, name, val, idx, M):
@@ -45,7 +33,7 @@ def _check(ops, name, val, idx, M):
     assert bool(torch.isfinite(loss).all()) and bool(torch.isfinite(g).all())
     lerr, lbar = (loss.double() - ref["F"]).abs(), R.loss_bound(ref, k)
     gerr, gbar = (g.double() - ref["g"]).abs(), R.grad_bound(ref, k)
-    worst = float((gerr / gbar.clamp_min(1e-300)).max())
+    worst = T.worst_ratio(gerr, gbar)
     print("%s: F %s loss err %s bar %s; gradient: worst err / bar %.4f, max |g| %.3e" %
           (name, ref["F"].tolist(), lerr.tolist(), lbar.tolist(), worst, float(ref["g"].abs().max())))
     assert bool((lerr <= lbar).all()), (name, lerr.tolist(), lbar.tolist())
@@ -91,60 +79,18 @@ def _batch_160():
 
 def test_batch_independence(ops):
     """A batch of the random, hub and near-permutation plantings: every element gets the bits it gets alone."""
-    val, idx, M = _batch_160()
-    loss, g = _run(ops, val, idx, M)
-    for b in range(val.shape[0]):
-        l1, g1 = _run(ops, val[b:b + 1].contiguous(), idx[b:b + 1].contiguous(), M)
-        assert torch.equal(_bits(loss[b:b + 1]), _bits(l1)), b
-        assert torch.equal(_bits(g[b:b + 1]), _bits(g1)), b
+    T.check_batch_independence(lambda case: _run(ops, *case), _batch_160())
 
 
 def test_scratch_hygiene(ops, monkeypatch):
     """The same call on a workspace that held 0xFF bytes (int32 -1, a NaN in every float format) and fp32 NaNs: the same bits."""
-    val, idx, M = _batch_160()
-    clean_loss, clean_g = _run(ops, val, idx, M)
-    again_loss, again_g = _run(ops, val, idx, M)
-    assert torch.equal(_bits(clean_loss), _bits(again_loss)) and torch.equal(_bits(clean_g), _bits(again_g))   # run to run
-    kept = []
-
-    def filled(fill):
-        def workspace(nbytes, device, tag="ws"):
-            n = (int(nbytes) + 3) // 4 * 4
-            buf = torch.full((n,), 0xFF, dtype=torch.uint8, device=device)
-            if fill == "nan":
-                buf.view(torch.float32).fill_(float("nan"))
-            kept.append(buf)
-            return buf
-        return workspace
-
-    for fill in ("ff", "nan"):
-        monkeypatch.setattr(ops, "workspace", filled(fill))
-        loss, g = _run(ops, val, idx, M)
-        assert torch.equal(_bits(loss), _bits(clean_loss)), fill
-        assert torch.equal(_bits(g), _bits(clean_g)), fill
-    assert len(kept) == 4
+    T.check_scratch_hygiene(ops, monkeypatch, lambda case: _run(ops, *case), _batch_160())
 
 
 def test_route_and_autograd(ops):
     """models.loss.rank_term on CUDA float32 is the kernel: ops.rank_term's bits, and backward() gives g_val times the incoming gradient."""
     import models.loss as ml
-    val, idx, M = _batch_160()
-    loss_k, g_k = ops.rank_term(val.cuda(), idx.cuda(), M, grad=True)
-    with torch.no_grad():
-        assert torch.equal(_bits(ml.rank_term(val.cuda(), idx.cuda(), M)), _bits(loss_k))
-    v = val.cuda().requires_grad_(True)
-    loss = ml.rank_term(v, idx.cuda(), M)
-    assert loss.dtype == torch.float32 and loss.requires_grad
-    assert torch.equal(_bits(loss), _bits(loss_k))
-    loss.sum().backward()
-    assert torch.equal(_bits(v.grad), _bits(g_k))
-    w = torch.tensor([0.5, -2.0, 3.0], device="cuda")
-    v2 = val.cuda().requires_grad_(True)
-    (ml.rank_term(v2, idx.cuda(), M) * w).sum().backward()
-    assert torch.equal(_bits(v2.grad), _bits(g_k * w[:, None, None]))
-    idx64 = idx.cuda().long()   # the criterion's own index dtype may be int64: same route, same bits
-    with torch.no_grad():
-        assert torch.equal(_bits(ml.rank_term(val.cuda(), idx64, M)), _bits(loss_k))
+    T.check_route_and_autograd(ops.rank_term, ml.rank_term, _batch_160(), (0,))
 
 
 def test_limit(ops):
@@ -160,19 +106,10 @@ def test_limit(ops):
     assert lib.dvm_rank_term_workspace_bytes(1, N, M, k) == 0
     assert lib.dvm_rank_term_workspace_bytes(1, N - 1, M, k) > 0
     vd, idd = val.cuda(), idx.cuda()
-    out = torch.full((1,), -7.0, device="cuda")
-    ws = torch.empty(lib.dvm_rank_term_workspace_bytes(1, N - 1, M, k) * 2, dtype=torch.uint8, device="cuda")
-    rc = lib.dvm_rank_term_f32(vd.data_ptr(), idd.data_ptr(), 1, N, M, k, out.data_ptr(), None, ws.data_ptr(), ws.numel(), None)
-    torch.cuda.synchronize()
-    assert rc == -1 and b"N=%d" % N in lib.dvm_last_error()
-    assert float(out) == -7.0   # nothing ran
+    T.refused_before_launch(lib, "dvm_rank_term_f32", (vd, idd, 1, N, M, k), 1, lib.dvm_rank_term_workspace_bytes(1, N - 1, M, k) * 2, b"N=%d" % N)
     with pytest.raises(_lib.DvmError):
         ops.rank_term(vd, idd, M)
-    ref = R.dense_reference(val, idx, M, grad=False)
-    loss = ml.rank_term(vd, idd, M).cpu()
-    err = (loss.double() - ref["F"]).abs()
-    print("limit: N %d F %s err %s bar %s" % (N, ref["F"].tolist(), err.tolist(), (2 * R.U * ref["F"]).tolist()))
-    assert bool((err <= 2 * R.U * ref["F"]).all())
+    T.check_fallback("limit: N %d" % N, ml.rank_term(vd, idd, M), R.dense_reference(val, idx, M, grad=False))
 
 
 def test_memory(ops):
@@ -180,20 +117,9 @@ def test_memory(ops):
     condition, not a measurement (the kernel's arrays are about 16 B N k bytes; a dense B x M x M float64 array is 2.1 GB)."""
     import models.loss as ml
     B, N, M, k = 4, 8192, 8192, 10
-    gen = torch.Generator(device="cuda").manual_seed(5)
-    # k distinct buckets of 64 columns per row, one random column in each: random sets without an N x M draw
-    bucket = torch.rand(B, N, 128, generator=gen, device="cuda").argsort(-1)[..., :k]
-    idx = (bucket * 64 + torch.randint(0, 64, (B, N, k), generator=gen, device="cuda")).to(torch.int32).contiguous()
-    val = torch.softmax(3.0 * torch.randn(B, N, k, generator=gen, device="cuda"), -1).contiguous().requires_grad_(True)
-    del bucket
+    val, idx = T.bucketed_sets(torch.Generator(device="cuda").manual_seed(5), B, N, k, 64)
     assert int(idx.min()) >= 0 and int(idx.max()) < M
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-    torch.cuda.reset_peak_memory_stats()
-    base = torch.cuda.memory_allocated()
-    ml.rank_term(val, idx, M).sum().backward()
-    torch.cuda.synchronize()
-    rise = torch.cuda.max_memory_allocated() - base
+    rise, _ = T.peak_rise(lambda: ml.rank_term(val, idx, M).sum().backward())
     print("memory: peak rise %d bytes, bound %d" % (rise, 64 * B * N * k))
     assert rise <= 64 * B * N * k
     assert bool(torch.isfinite(val.grad).all()) and float(val.grad.abs().max()) > 0
@@ -215,25 +141,12 @@ def test_criterion_step(ops, monkeypatch):
     monkeypatch.setattr(ml, "rank_term", spy)
     torch.manual_seed(3)
     B, N, w_rank = 2, 256, 0.3
-    gen = _gen(21)
-    f1 = (0.3 * torch.relu(torch.randn(B, N, 128, generator=gen))).cuda().requires_grad_(True)
-    f2 = (0.3 * torch.relu(torch.randn(B, N, 128, generator=gen))).cuda().requires_grad_(True)
-    v1, v2 = torch.rand(B, N, 3, generator=gen).cuda(), torch.rand(B, N, 3, generator=gen).cuda()
+    f1, f2, v1, v2 = T.criterion_inputs(B, N, N, 21)
     d = mm.Deformer(10).cuda().train()
-    crit = ml.GraphDeformLoss_Neural(save_name="t", k_deform=10, w_dist=0.02, w_map=0.005, k_dist=30, N_dist=60, partial=False, w_deform=0.5,
-                                     w_img=0, w_rank=w_rank, w_self_rec=0.5, w_cd=0.1, w_arap=0.01)
+    crit = T.make_criterion(ml, partial=False, w_rank=w_rank)
     out = crit(f1, f2, torch.cdist(v1, v1), torch.cdist(v2, v2), v1, v2, np.float64(100.0), d)
     assert len(seen) == 2 and all(s[3] for s in seen)   # both directions, on the route the kernel takes
-    want, bar = 0.0, 0.0
-    for pval, pidx, M, _ in seen:
-        assert M == N
-        ref = R.dense_reference(pval, pidx, M, grad=False)
-        want += float(ref["F"].mean()) * w_rank / 2
-        bar += float(R.loss_bound(ref, pval.shape[-1]).mean()) * w_rank / 2
-    got = float(crit.rank_loss.detach())
-    bar += 4 * R.U * abs(want)
-    print("criterion: rank_loss %.9g reference %.9g err %.3e bar %.3e" % (got, want, abs(got - want), bar))
-    assert abs(got - want) <= bar
-    out[0].backward()
-    assert bool(torch.isfinite(f1.grad).all()) and bool(torch.isfinite(f2.grad).all())
-    assert float(f1.grad.abs().max()) > 0
+    assert all(M == N for _, _, M, _ in seen)
+    refs = [R.dense_reference(pval, pidx, M, grad=False) for pval, pidx, M, _ in seen]
+    T.check_criterion_term("criterion: rank_loss", crit.rank_loss, [(ref, R.loss_bound(ref, s[0].shape[-1])) for ref, s in zip(refs, seen)], w_rank,
+                           out, (f1, f2), (f1,))

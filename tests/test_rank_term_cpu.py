@@ -6,6 +6,7 @@ import ctypes
 import pytest
 import torch
 
+import frob_term_common as T
 import rank_term_ref as R
 
 ONE = ctypes.c_void_p(16)   # a pointer that must never be dereferenced
@@ -29,13 +30,9 @@ def test_cpu_fallback_matches_dense_float64(name):
     v = val.clone().requires_grad_(True)
     loss = ml.rank_term(v, idx, M)
     assert loss.dtype == torch.float32 and tuple(loss.shape) == (SHAPE[0],)
-    err = (loss.detach().double() - ref["F"]).abs()
-    print(name, "F", ref["F"].tolist(), "err", err.tolist(), "bound", (2 * R.U * ref["F"]).tolist())
-    assert bool((err <= 2 * R.U * ref["F"]).all())
+    T.check_fallback(name, loss, ref)
     loss.sum().backward()
-    assert bool(torch.isfinite(v.grad).all())
-    gerr = (v.grad.double() - ref["g"]).abs()
-    assert bool((gerr <= R.grad_bound(ref, k)).all()), float((gerr / R.grad_bound(ref, k).clamp_min(1e-300)).max())
+    T.check_fallback_grad(v.grad, ref["g"], R.grad_bound(ref, k))
 
 
 def test_cpu_gradient_at_exact_permutation_is_zero():
@@ -50,12 +47,7 @@ def test_cpu_gradient_at_exact_permutation_is_zero():
 
 
 def test_entries_exported_sized_and_limited():
-    from dvm import _lib
-    lib = _lib.load()
-    raw = ctypes.CDLL(_lib.SO_PATH)
-    for name in ("dvm_rank_term_max_n", "dvm_rank_term_workspace_bytes", "dvm_rank_term_f32"):
-        assert hasattr(raw, name) and name in _lib.SIGNATURES, name
-    nmax = lib.dvm_rank_term_max_n()
+    lib, nmax = T.check_entries_exported("rank")
     assert nmax >= 8192   # the criterion's own gate
     B, N, M, k = 2, 300, 170, 10
     need = 4 * B * (2 * M + 1 + N * k) + 8 * B * N + 4 * B   # the reversed lists, one double per row, one float per element
@@ -85,10 +77,4 @@ def test_argument_validation_without_gpu():
 
 
 def test_wrappers_have_no_cpu_path():
-    from dvm import nn_ops, ops
-    from dvm._lib import DvmError
-    val, idx = R.plant_near_perm(1, 8, 8, 3)
-    with pytest.raises(DvmError):
-        ops.rank_term(val, idx, 8)
-    with pytest.raises(DvmError):
-        nn_ops.rank_term(val.clone().requires_grad_(True), idx, 8)
+    T.check_no_cpu_path("rank", (*R.plant_near_perm(1, 8, 8, 3), 8))

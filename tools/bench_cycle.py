@@ -8,42 +8,12 @@ seconds of work each; the peak memory of one step of each is read from torch's a
     python tools/bench_cycle.py [--shapes 8x2048x2048,2x4995x2200] [--alphas 10,100] [--rounds 5] [--out FILE]
 """
 import argparse
-import json
-import os
-import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "dv-matcher_amd"))
-sys.path.insert(0, ROOT)
-import torch  # noqa: E402
+import term_bench as tb
+import torch
 
-import models.loss as ml  # noqa: E402
+import models.loss as ml  # noqa: E402  (term_bench puts the package on sys.path)
 from dvm import ops  # noqa: E402
-
-MIN_S = 0.3
-
-
-def window(fn, reps):
-    """Seconds per call over `reps` back-to-back calls, by device events."""
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) * 1e-3 / reps
-
-
-def peak_of(fn):
-    """Bytes by which one call raises the allocator's peak."""
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-    torch.cuda.reset_peak_memory_stats()
-    base = torch.cuda.memory_allocated()
-    fn()
-    torch.cuda.synchronize()
-    return torch.cuda.max_memory_allocated() - base
 
 
 def dense_term(val12, idx12, val21, idx21):
@@ -71,44 +41,25 @@ def main(argv=None):
         for alpha in [float(x) for x in args.alphas.split(",")]:
             val12, idx12, _, _ = ops.softcorr(f1, f2, alpha)
             val21, idx21, _, _ = ops.softcorr(f2, f1, alpha)
-            col_counts = torch.zeros(B, M, dtype=torch.int64, device=dev).scatter_add_(1, idx12.long().flatten(1), torch.ones(B, N * 10, dtype=torch.int64, device=dev))
+            col_counts = tb.column_counts(idx12, M)
             v12, v21 = val12.clone().requires_grad_(True), val21.clone().requires_grad_(True)
 
             def step(term):
                 v12.grad = v21.grad = None
                 term(v12, idx12, v21, idx21).sum().backward()
 
-            fns = {"kernel": lambda: step(ml.cycle_term), "dense": lambda: step(dense_term)}
             res = {}
             for k, term in (("kernel", ml.cycle_term), ("dense", dense_term)):
                 step(term)
                 res[k] = (v12.grad.clone(), v21.grad.clone(), term(v12.detach(), idx12, v21.detach(), idx21))
-            reps, peak = {}, {}
-            for k, fn in fns.items():   # warm-up, and the repetition count that fills MIN_S
-                fn()
-                torch.cuda.synchronize()
-                reps[k] = max(3, int(MIN_S / window(fn, 3)) + 1)
-                peak[k] = peak_of(fn)
-            rounds = {k: [] for k in fns}
-            for _ in range(args.rounds):   # alternate the candidates; report every round
-                for k, fn in fns.items():
-                    rounds[k].append(window(fn, reps[k]))
-            med = {k: statistics.median(x) for k, x in rounds.items()}
-            line = dict(B=B, N=N, M=M, k=10, alpha=alpha, t_kernel_ms=med["kernel"] * 1e3, t_dense_ms=med["dense"] * 1e3,
-                        speedup=med["dense"] / med["kernel"],
-                        spread_ms={k: (max(x) - min(x)) * 1e3 for k, x in rounds.items()},
-                        rounds_ms={k: [round(t * 1e3, 4) for t in x] for k, x in rounds.items()}, reps=reps,
-                        peak_bytes=peak, largest_column=int(col_counts.max()),
+            line = dict(B=B, N=N, M=M, k=10, alpha=alpha,
+                        **tb.compare({"kernel": lambda: step(ml.cycle_term), "dense": lambda: step(dense_term)}, args.rounds),
+                        largest_column=int(col_counts.max()),
                         loss_kernel=res["kernel"][2].tolist(), loss_dense=res["dense"][2].tolist(),
                         g12_max_abs_diff=float((res["kernel"][0] - res["dense"][0]).abs().max()), g12_max_abs=float(res["dense"][0].abs().max()),
                         g21_max_abs_diff=float((res["kernel"][1] - res["dense"][1]).abs().max()), g21_max_abs=float(res["dense"][1].abs().max()))
-            print(json.dumps(line))
-            lines.append(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            for line in lines:
-                f.write(json.dumps(line) + "\n")
+            tb.emit(line, lines)
+    tb.write_lines(args.out, lines)
 
 
 if __name__ == "__main__":

@@ -8,42 +8,12 @@ JSON line per shape (and keeps them in --out; profiles/notes_distortion.md).
     python tools/bench_distortion.py [--shapes 2x2048x2048,1x4995x2200] [--alpha 100] [--rounds 5] [--out FILE]
 """
 import argparse
-import json
-import os
-import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "dv-matcher_amd"))
-sys.path.insert(0, ROOT)
-import torch  # noqa: E402
+import term_bench as tb
+import torch
 
-import models.loss as ml  # noqa: E402
+import models.loss as ml  # noqa: E402  (term_bench puts the package on sys.path)
 from dvm import ops  # noqa: E402
-
-MIN_S = 0.3
-
-
-def window(fn, reps):
-    """Seconds per call over `reps` back-to-back calls, by device events."""
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) * 1e-3 / reps
-
-
-def peak_of(fn):
-    """Bytes by which one call raises the allocator's peak."""
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-    torch.cuda.reset_peak_memory_stats()
-    base = torch.cuda.memory_allocated()
-    fn()
-    torch.cuda.synchronize()
-    return torch.cuda.max_memory_allocated() - base
 
 
 def inputs(B, N, M, alpha, dev):
@@ -62,22 +32,6 @@ def inputs(B, N, M, alpha, dev):
     return val, idx, mats[0], mats[1]
 
 
-def compare(fns, rounds):
-    """fns: name -> callable.  -> (median seconds, spread, the rounds, repetitions, peak bytes) per name; the candidates alternate."""
-    reps, peak = {}, {}
-    for k, fn in fns.items():   # warm-up, and the repetition count that fills MIN_S
-        fn()
-        torch.cuda.synchronize()
-        reps[k] = max(3, int(MIN_S / window(fn, 3)) + 1)
-        peak[k] = peak_of(fn)
-    times = {k: [] for k in fns}
-    for _ in range(rounds):
-        for k, fn in fns.items():
-            times[k].append(window(fn, reps[k]))
-    med = {k: statistics.median(x) for k, x in times.items()}
-    return med, {k: max(x) - min(x) for k, x in times.items()}, times, reps, peak
-
-
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="2x2048x2048,1x4995x2200", help="BxNxM[,BxNxM...]")
@@ -91,7 +45,7 @@ def main(argv=None):
     for shape in args.shapes.split(","):
         B, N, M = (int(x) for x in shape.split("x"))
         val, idx, D1, D2 = inputs(B, N, M, args.alpha, dev)
-        counts = torch.zeros(B, M, dtype=torch.int64, device=dev).scatter_add_(1, idx.long().flatten(1), torch.ones(B, N * idx.shape[-1], dtype=torch.int64, device=dev))
+        counts = tb.column_counts(idx, M)
         v = val.clone().requires_grad_(True)
 
         def dense():
@@ -105,19 +59,11 @@ def main(argv=None):
 
         lk, gk = kernel()
         ld, gd = dense()
-        med, spread, times, reps, peak = compare({"kernel": kernel, "dense": dense}, args.rounds)
-        line = dict(B=B, N=N, M=M, k=int(idx.shape[-1]), alpha=args.alpha, t_kernel_ms=med["kernel"] * 1e3, t_dense_ms=med["dense"] * 1e3,
-                    speedup=med["dense"] / med["kernel"], spread_ms={k: x * 1e3 for k, x in spread.items()},
-                    rounds_ms={k: [round(t * 1e3, 4) for t in x] for k, x in times.items()}, reps=reps, peak_bytes=peak,
+        line = dict(B=B, N=N, M=M, k=int(idx.shape[-1]), alpha=args.alpha, **tb.compare({"kernel": kernel, "dense": dense}, args.rounds),
                     largest_column=int(counts.max()), loss_kernel=lk.tolist(), loss_dense=ld.tolist(),
                     g_max_abs_diff=float((gk - gd).abs().max()), g_max_abs=float(gd.abs().max()))
-        print(json.dumps(line))
-        lines.append(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            for line in lines:
-                f.write(json.dumps(line) + "\n")
+        tb.emit(line, lines)
+    tb.write_lines(args.out, lines)
 
 
 if __name__ == "__main__":

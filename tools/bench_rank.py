@@ -7,42 +7,12 @@ allocator.  Prints one JSON line per (shape, alpha) (and keeps them in --out; pr
     python tools/bench_rank.py [--shapes 8x2048,2x4995] [--alphas 10,100] [--rounds 5] [--out FILE]
 """
 import argparse
-import json
-import os
-import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "dv-matcher_amd"))
-sys.path.insert(0, ROOT)
-import torch  # noqa: E402
+import term_bench as tb
+import torch
 
-import models.loss as ml  # noqa: E402
+import models.loss as ml  # noqa: E402  (term_bench puts the package on sys.path)
 from dvm import ops  # noqa: E402
-
-MIN_S = 0.3
-
-
-def window(fn, reps):
-    """Seconds per call over `reps` back-to-back calls, by device events."""
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) * 1e-3 / reps
-
-
-def peak_of(fn):
-    """Bytes by which one call raises the allocator's peak."""
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-    torch.cuda.reset_peak_memory_stats()
-    base = torch.cuda.memory_allocated()
-    fn()
-    torch.cuda.synchronize()
-    return torch.cuda.max_memory_allocated() - base
 
 
 def main(argv=None):
@@ -62,43 +32,24 @@ def main(argv=None):
         f2 = torch.randn(B, N, 128, generator=g).to(dev)
         for alpha in [float(x) for x in args.alphas.split(",")]:
             val, idx, _, _ = ops.softcorr(f1, f2, alpha)
-            col_counts = torch.zeros(B, N, dtype=torch.int64, device=dev).scatter_add_(1, idx.long().flatten(1), torch.ones(B, N * 10, dtype=torch.int64, device=dev))
+            col_counts = tb.column_counts(idx, N)
             v = val.clone().requires_grad_(True)
 
             def step(term):
                 v.grad = None
                 term(v, idx, N).sum().backward()
 
-            fns = {"kernel": lambda: step(ml.rank_term), "torch": lambda: step(ml._rank_term_torch)}
             step(ml.rank_term)
             gk, lk = v.grad.clone(), ml.rank_term(v.detach(), idx, N)
             step(ml._rank_term_torch)
             gt, lt = v.grad.clone(), ml._rank_term_torch(v.detach(), idx, N)
-            reps, peak = {}, {}
-            for k, fn in fns.items():   # warm-up, and the repetition count that fills MIN_S
-                fn()
-                torch.cuda.synchronize()
-                reps[k] = max(3, int(MIN_S / window(fn, 3)) + 1)
-                peak[k] = peak_of(fn)
-            rounds = {k: [] for k in fns}
-            for _ in range(args.rounds):   # alternate the candidates; report every round
-                for k, fn in fns.items():
-                    rounds[k].append(window(fn, reps[k]))
-            med = {k: statistics.median(x) for k, x in rounds.items()}
-            line = dict(B=B, N=N, M=N, k=10, alpha=alpha, t_kernel_ms=med["kernel"] * 1e3, t_torch_ms=med["torch"] * 1e3,
-                        speedup=med["torch"] / med["kernel"],
-                        spread_ms={k: (max(x) - min(x)) * 1e3 for k, x in rounds.items()},
-                        rounds_ms={k: [round(t * 1e3, 4) for t in x] for k, x in rounds.items()}, reps=reps,
-                        peak_bytes=peak, largest_column=int(col_counts.max()), sum_cj2=int((col_counts * col_counts).sum()),
+            line = dict(B=B, N=N, M=N, k=10, alpha=alpha,
+                        **tb.compare({"kernel": lambda: step(ml.rank_term), "torch": lambda: step(ml._rank_term_torch)}, args.rounds),
+                        largest_column=int(col_counts.max()), sum_cj2=int((col_counts * col_counts).sum()),
                         loss_kernel=lk.tolist(), loss_torch=lt.tolist(),
                         grad_max_abs_diff=float((gk - gt).abs().max()), grad_max_abs=float(gt.abs().max()))
-            print(json.dumps(line))
-            lines.append(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            for line in lines:
-                f.write(json.dumps(line) + "\n")
+            tb.emit(line, lines)
+    tb.write_lines(args.out, lines)
 
 
 if __name__ == "__main__":

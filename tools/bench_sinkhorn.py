@@ -25,20 +25,10 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 from dvm import ops  # noqa: E402
+from term_bench import window  # noqa: E402
 
 FP32_MATRIX_TFLOPS = 157.3
 MIN_S = 0.5
-
-
-def window(fn, reps):
-    """Seconds per call over `reps` back-to-back calls, by device events."""
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) * 1e-3 / reps
 
 
 def main(argv=None):
