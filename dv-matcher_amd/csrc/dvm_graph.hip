@@ -14,7 +14,7 @@ namespace dvm {
 // ---------------------------------------------------------------- farthest point sampling
 // One workgroup per shape; thread t owns points t, t+T, t+2T, ... (PPT of them) with their
 // running min-distance in registers; the cloud is also kept in LDS for the centroid broadcast.
-// threads per cloud: 256 / 512 / 1024 (launch_fps), points per thread matched to N
+// threads per cloud: 256 / 512 (launch_fps), points per thread matched to N
 
 struct ArgMax {
     float v;
@@ -255,20 +255,23 @@ static void launch_fps_t(const float *xyz, int B, int N, int npoint, const int32
 // two), the cross-wave part grows with the wave count.
 int launch_fps(const float *xyz, int B, int N, int npoint, const int32_t *start, int32_t *out, hipStream_t s) {
     // measured (us/step at 256 / 512 / 1024 threads): N = 2048: 0.65 / 0.71 / 1.18; 4995: 0.93 / 0.89 / 1.31; 12000: 1.63 / 1.22 / 1.63
-    int T = N <= 4096 ? 256 : 512;
-    if (N > 48 * T) T = N > 48 * 512 ? 1024 : 512;
+    // (1024 threads lost at each of these sizes and are not instantiated; at DVM_MAX_POINTS 512 threads hold 24 points each)
+    if (N > DVM_MAX_POINTS) {
+        set_error("fps: N=%d exceeds %d", N, DVM_MAX_POINTS);
+        return DVM_EINVAL;
+    }
+    const int T = N <= 4096 ? 256 : 512;
     const int ppt = (N + T - 1) / T;
 #define DVM_FPS_CASE(P)                                                                          \
     if (ppt <= P) {                                                                              \
         if (T == 256) launch_fps_t<P, 256>(xyz, B, N, npoint, start, out, s);                    \
-        else if (T == 512) launch_fps_t<P, 512>(xyz, B, N, npoint, start, out, s);               \
-        else launch_fps_t<P, 1024>(xyz, B, N, npoint, start, out, s);                            \
+        else launch_fps_t<P, 512>(xyz, B, N, npoint, start, out, s);                             \
         return DVM_OK;                                                                           \
     }
     DVM_FPS_CASE(2) DVM_FPS_CASE(4) DVM_FPS_CASE(6) DVM_FPS_CASE(8) DVM_FPS_CASE(10) DVM_FPS_CASE(12) DVM_FPS_CASE(16)
-    DVM_FPS_CASE(20) DVM_FPS_CASE(24) DVM_FPS_CASE(32) DVM_FPS_CASE(48)
+    DVM_FPS_CASE(20) DVM_FPS_CASE(24)
 #undef DVM_FPS_CASE
-    return DVM_EINVAL;
+    return DVM_EINVAL;   // (not reached: ppt <= 24 under the limit)
 }
 
 // graph build on uniform grids (dvm_grid.hip): gverts = grid over all vertices (built here, reusable by
@@ -279,7 +282,8 @@ int launch_dg_build(const float *xyz, int B, int N, const int32_t *start, int32_
     // gverts_ready: the vertex grid is built by another stream (which records this event behind it); waited for in front of the
     // influence search, the first kernel here that reads it
     const int Nn = N / 2;
-    launch_fps(xyz, B, N, Nn, start, nodes_idx, s);
+    const int rc = launch_fps(xyz, B, N, Nn, start, nodes_idx, s);
+    if (rc != DVM_OK) return rc;   // nothing behind a refused FPS: every later kernel gathers through nodes_idx
     if (build_gverts) launch_grid_build(xyz, B, N, nullptr, gverts, s);
     launch_grid_build(xyz, B, N, nodes_idx, gnodes, s);
     launch_grid_ring(gnodes, B, ring, s);
@@ -419,13 +423,12 @@ bool launch_dg_warp_pair(const float *xyz1, const float *xyz2, int B, int N, int
 
 using namespace dvm;
 
-constexpr int DVM_MAX_POINTS = 48 * 256;  // fps_kernel<48>; LDS: 12288*12 B = 144 KiB
-
 DVM_EXPORT int dvm_fps_f32(const float *xyz, int B, int N, int npoint, const int32_t *start, int32_t *out, void *stream) {
     DVM_REQUIRE(xyz && start && out, "dvm_fps_f32: null pointer");
     DVM_REQUIRE(B >= 1 && N >= 1 && npoint >= 1 && npoint <= N, "dvm_fps_f32: bad sizes (B=%d N=%d npoint=%d)", B, N, npoint);
     DVM_REQUIRE(N <= DVM_MAX_POINTS, "dvm_fps_f32: N=%d exceeds %d", N, DVM_MAX_POINTS);
-    launch_fps(xyz, B, N, npoint, start, out, (hipStream_t)stream);
+    const int rc = launch_fps(xyz, B, N, npoint, start, out, (hipStream_t)stream);
+    if (rc != DVM_OK) return rc;
     DVM_CHECK_LAUNCH("fps");
     return DVM_OK;
 }
@@ -450,7 +453,8 @@ DVM_EXPORT int dvm_dg_build_f32(const float *xyz, int B, int N, const int32_t *s
     DVM_REQUIRE(N <= DVM_MAX_POINTS, "dvm_dg_build_f32: N=%d exceeds %d", N, DVM_MAX_POINTS);
     DgBuildWs w;
     if (!carve_ws(ws, ws_bytes, "dvm_dg_build_f32", w, carve_dg_build, B, N)) return DVM_ENOSPACE;
-    launch_dg_build(xyz, B, N, start, nodes_idx, ring, infl_idx, dists, weights, sigma, w.nnd, w.gv, w.gn, true, (hipStream_t)stream);
+    const int rc = launch_dg_build(xyz, B, N, start, nodes_idx, ring, infl_idx, dists, weights, sigma, w.nnd, w.gv, w.gn, true, (hipStream_t)stream);
+    if (rc != DVM_OK) return rc;
     DVM_CHECK_LAUNCH("dg_build");
     return DVM_OK;
 }

@@ -90,6 +90,10 @@ bool launch_apply3_pair(const float *val12, const int32_t *idx12, const float *v
                         *idx21, const float *verts1, float *verts21, int32_t *T21, int B, int N, int M, hipStream_t s);
 
 // ---- dvm_graph.hip
+// The largest cloud a deformation graph is built on: fps_kernel keeps the cloud in LDS (12288 * 12 B = 144 KiB) and 24 points
+// per thread at 512 threads.  dvm_fps_f32, dvm_dg_build_f32 and the pair entries refuse a larger one before they launch anything.
+constexpr int DVM_MAX_POINTS = 12288;
+// launch_dg_build: DVM_EINVAL with nothing launched for N > DVM_MAX_POINTS (every later kernel gathers through nodes_idx)
 int launch_dg_warp(const float *xyz, int B, int N, const int32_t *nodes_idx, const int32_t *ring, const int32_t *infl_idx, const float *weights, const
                    float *def9, float *R, float *T, float *warped, float *arap, int arap_stride, float *sr, hipStream_t s);
 int launch_dg_build(const float *xyz, int B, int N, const int32_t *start, int32_t *nodes_idx, int32_t *ring, int32_t *infl_idx, float *dists, float

@@ -78,6 +78,7 @@ DVM_EXPORT int dvm_pair_direction_fwd_f32(const float *feat1, const float *feat2
     DVM_REQUIRE(conv_w && conv_b && W0 && b0 && W1 && b1 && W2 && b2 && W3 && b3,
                 "dvm_pair_direction_fwd_f32: null weight pointer");
     DVM_REQUIRE(B >= 1 && N >= 20 && M >= 10, "dvm_pair_direction_fwd_f32: bad sizes (B=%d N=%d M=%d)", B, N, M);
+    DVM_REQUIRE(N <= DVM_MAX_POINTS, "dvm_pair_direction_fwd_f32: N=%d exceeds %d (the cloud whose graph is built)", N, DVM_MAX_POINTS);
     DVM_REQUIRE(neg_alpha < 0.f, "dvm_pair_direction_fwd_f32: neg_alpha must be negative");
     PairWs w;
     if (!carve_ws(ws, ws_bytes, "dvm_pair_direction_fwd_f32", w, carve_pair, B, N, M)) return DVM_ENOSPACE;
@@ -85,7 +86,8 @@ DVM_EXPORT int dvm_pair_direction_fwd_f32(const float *feat1, const float *feat2
     const int Nn = N / 2, k = 10, topk = 10;
     int rc;
     // graph of the source cloud (nodes, ring, skinning weights)
-    launch_dg_build(verts1, B, N, fps_start, w.nodes, w.ring, w.infl, w.dists, w.weights, nullptr, w.nnd, w.gv1, w.gn1, true, s);
+    rc = launch_dg_build(verts1, B, N, fps_start, w.nodes, w.ring, w.infl, w.dists, w.weights, nullptr, w.nnd, w.gv1, w.gn1, true, s);
+    if (rc != DVM_OK) return rc;
     // soft correspondence Pi_12 (top-10) and the arg-max map
     rc = dvm_softcorr_fwd_f32(feat1, feat2, B, N, M, 128, neg_alpha, topk, w.pval, w.pidx, nullptr, nullptr, 0, w.sc_ws,
                               w.sc_bytes, s);
@@ -225,9 +227,12 @@ DVM_EXPORT int dvm_pair_set_overlap(int on) {
 // returns).  `pool` (feature pointers given): the Deformer's pooled features are made right behind the xyz kNN on that stream.
 // Reference: lib/deformation_graph_point.py:18-33, 177-201; models/loss.py:1325-1337 (graphs), :97-101 (xyz kNN).
 namespace dvm {
-static bool pair_geometry(PairCtx *cx, hipStream_t s, const Pair2Ws &w, const float *verts1, const float *verts2, int B, int N, int M,
-                          const int32_t *start1, const int32_t *start2, bool both, bool gather_nbr, const float *pool_feat1,
-                          const float *pool_feat2, const float *conv_w, const float *conv_b) {
+// -> launch_dg_build's status (on a refusal the helper stream is still joined into `s`; the workspace then holds no geometry);
+// *pooled: the pooled features were made here
+static int pair_geometry(PairCtx *cx, hipStream_t s, const Pair2Ws &w, const float *verts1, const float *verts2, int B, int N, int M,
+                         const int32_t *start1, const int32_t *start2, bool both, bool gather_nbr, const float *pool_feat1,
+                         const float *pool_feat2, const float *conv_w, const float *conv_b, bool *pooled_out) {
+    int rc = DVM_OK;
     const int P[2] = {N, M};
     const float *verts[2] = {verts1, verts2};
     const int32_t *start[2] = {start1, start2};
@@ -252,13 +257,13 @@ static bool pair_geometry(PairCtx *cx, hipStream_t s, const Pair2Ws &w, const fl
                 pooled = true;
             }
             (void)hipEventRecord(cx->ev_join2, cx->side2);
-            launch_dg_build(w.vcat, 2 * B, N, w.startcat, w.nodes[0], w.ring[0], w.infl[0], w.dists[0], w.weights[0], nullptr,
-                            w.nnd[0], w.gvcat, w.gncat, false, s, cx->ev_aux);
+            rc = launch_dg_build(w.vcat, 2 * B, N, w.startcat, w.nodes[0], w.ring[0], w.infl[0], w.dists[0], w.weights[0], nullptr,
+                                 w.nnd[0], w.gvcat, w.gncat, false, s, cx->ev_aux);
             (void)hipStreamWaitEvent(s, cx->ev_join2, 0);
         } else {
-            launch_dg_build(w.vcat, 2 * B, N, w.startcat, w.nodes[0], w.ring[0], w.infl[0], w.dists[0], w.weights[0], nullptr,
-                            w.nnd[0], w.gvcat, w.gncat, true, s);
-            launch_grid_knn_self(w.gvcat, 2 * B, 10, w.idxk[0], s);
+            rc = launch_dg_build(w.vcat, 2 * B, N, w.startcat, w.nodes[0], w.ring[0], w.infl[0], w.dists[0], w.weights[0], nullptr,
+                                 w.nnd[0], w.gvcat, w.gncat, true, s);
+            if (rc == DVM_OK) launch_grid_knn_self(w.gvcat, 2 * B, 10, w.idxk[0], s);
         }
     } else {
         // N != M (or sizes that do not tile the arena): one chain per cloud set.  FPS is a one-workgroup-per-cloud
@@ -269,8 +274,9 @@ static bool pair_geometry(PairCtx *cx, hipStream_t s, const Pair2Ws &w, const fl
         }
         for (int sd = 0; sd < 2; ++sd) {
             const hipStream_t cs = (cx && sd == 1) ? cx->side2 : s;
-            launch_dg_build(verts[sd], B, P[sd], start[sd], w.nodes[sd], w.ring[sd], w.infl[sd], w.dists[sd], w.weights[sd],
-                            nullptr, w.nnd[sd], w.gv[sd], w.gn[sd], true, cs);
+            rc = launch_dg_build(verts[sd], B, P[sd], start[sd], w.nodes[sd], w.ring[sd], w.infl[sd], w.dists[sd], w.weights[sd],
+                                 nullptr, w.nnd[sd], w.gv[sd], w.gn[sd], true, cs);
+            if (rc != DVM_OK) break;
             launch_grid_knn_self(w.gv[sd], B, 10, w.idxk[sd], cs);
         }
         if (cx) {
@@ -278,11 +284,13 @@ static bool pair_geometry(PairCtx *cx, hipStream_t s, const Pair2Ws &w, const fl
             (void)hipStreamWaitEvent(s, cx->ev_join2, 0);
         }
     }
+    *pooled_out = pooled;
+    if (rc != DVM_OK) return rc;
     if (gather_nbr) {
         launch_gather_nbr_xyz(verts2, w.idxk[1], B, M, 10, w.nbrxyz[1], s);
         launch_gather_nbr_xyz(verts1, w.idxk[0], B, N, 10, w.nbrxyz[0], s);
     }
-    return pooled;
+    return DVM_OK;
 }
 }  // namespace dvm
 
@@ -301,6 +309,7 @@ static int pair_fwd_impl(const float *feat1, const float *feat2, const float *ve
                 "dvm_pair_fwd_f32: null output pointer");
     DVM_REQUIRE(conv_w && conv_b && W0 && b0 && W1 && b1 && W2 && b2 && W3 && b3, "dvm_pair_fwd_f32: null weight pointer");
     DVM_REQUIRE(B >= 1 && N >= 20 && M >= 20, "dvm_pair_fwd_f32: bad sizes (B=%d N=%d M=%d)", B, N, M);
+    DVM_REQUIRE(N <= DVM_MAX_POINTS && M <= DVM_MAX_POINTS, "dvm_pair_fwd_f32: N=%d or M=%d exceeds %d", N, M, DVM_MAX_POINTS);
     DVM_REQUIRE(neg_alpha < 0.f, "dvm_pair_fwd_f32: neg_alpha must be negative");
     Pair2Ws w;
     if (!carve_ws(ws, ws_bytes, "dvm_pair_fwd_f32", w, carve_pair2, B, N, M)) return DVM_ENOSPACE;
@@ -323,8 +332,16 @@ static int pair_fwd_impl(const float *feat1, const float *feat2, const float *ve
     }
     const bool map_lds = map_term_lds_applies(N, M, 10) && map_term_lds_applies(M, N, 10);   // (the target side in LDS: no neighbour tables)
     bool pooled = false;   // the pooled features were made on the second helper stream
-    if (!reuse_geometry)
-        pooled = pair_geometry(cx, s, w, verts1, verts2, B, N, M, start1, start2, both, with_map && !map_lds, feat1, feat2, conv_w, conv_b);
+    if (!reuse_geometry) {
+        rc = pair_geometry(cx, s, w, verts1, verts2, B, N, M, start1, start2, both, with_map && !map_lds, feat1, feat2, conv_w, conv_b, &pooled);
+        if (rc != DVM_OK) {   // join the helper stream before the caller may reuse the workspace
+            if (overlap) {
+                (void)hipEventRecord(cx->ev_join, cx->side);
+                (void)hipStreamWaitEvent(caller, cx->ev_join, 0);
+            }
+            return rc;
+        }
+    }
     // still on the geometry side: what depends on the xyz kNN and the input features only — the Deformer's pooled features
     // (once per cloud, points in grid-cell order) — so that the L2-bound gathers run next to the ALU-bound sweep instead of after it
     if (!pooled) {
@@ -468,13 +485,17 @@ DVM_EXPORT int dvm_pair_geometry_f32(const float *verts1, const float *verts2, i
                                      const int32_t *start2, int with_map, void *ws, size_t ws_bytes, void *stream) {
     DVM_REQUIRE(verts1 && verts2 && start1 && start2, "dvm_pair_geometry_f32: null input pointer");
     DVM_REQUIRE(B >= 1 && N >= 20 && M >= 20, "dvm_pair_geometry_f32: bad sizes (B=%d N=%d M=%d)", B, N, M);
+    DVM_REQUIRE(N <= DVM_MAX_POINTS && M <= DVM_MAX_POINTS, "dvm_pair_geometry_f32: N=%d or M=%d exceeds %d", N, M, DVM_MAX_POINTS);
     Pair2Ws w;
     if (!carve_ws(ws, ws_bytes, "dvm_pair_geometry_f32", w, carve_pair2, B, N, M)) return DVM_ENOSPACE;
     hipStream_t s = (hipStream_t)stream;
     PairCtx *cx = g_pair_overlap != 0 ? pair_ctx_find(s) : nullptr;
     const bool both = (N == M) && contiguous_sides(B, N);
     const bool map_lds = map_term_lds_applies(N, M, 10) && map_term_lds_applies(M, N, 10);
-    pair_geometry(cx, s, w, verts1, verts2, B, N, M, start1, start2, both, with_map && !map_lds, nullptr, nullptr, nullptr, nullptr);
+    bool pooled;
+    const int rc = pair_geometry(cx, s, w, verts1, verts2, B, N, M, start1, start2, both, with_map && !map_lds, nullptr, nullptr, nullptr, nullptr,
+                                 &pooled);
+    if (rc != DVM_OK) return rc;
     DVM_CHECK_LAUNCH("pair_geometry");
     return DVM_OK;
 }

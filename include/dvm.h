@@ -412,13 +412,16 @@ int dvm_distortion_term_f32(const float *pi_val, const int32_t *pi_idx, const fl
                             float *g_val /* [B,N,topk], may be NULL */, void *ws, size_t ws_bytes, void *stream);
 
 /* farthest_point_sample — lib/deformation_graph_point.py:18-33 with the random
- * start index made an input.  xyz [B,N,3], start [B] -> out [B,npoint]. */
+ * start index made an input.  xyz [B,N,3], start [B] -> out [B,npoint].
+ * Limit: N <= 12288 (the cloud is held in LDS); a larger N is DVM_EINVAL before anything is launched — as at every entry
+ * below that builds a deformation graph. */
 int dvm_fps_f32(const float *xyz, int B, int N, int npoint, const int32_t *start, int32_t *out, void *stream);
 
 /* DeformationGraph_geod.construct_graph_euclidean via deformation_graph_node —
  * lib/deformation_graph_point.py:177-201, models/loss.py:1325-1337.
  * xyz [B,N,3], start [B] -> nodes_idx [B,Nn] (Nn = N/2), ring [B,Nn,9] (node-local),
- * infl_idx [B,N,3] (node-local), dists [B,N,3], weights [B,N,3], sigma [B] (double). */
+ * infl_idx [B,N,3] (node-local), dists [B,N,3], weights [B,N,3], sigma [B] (double).
+ * Limit: N <= 12288 (dvm_fps_f32's). */
 size_t dvm_dg_build_workspace_bytes(int B, int N);
 int dvm_dg_build_f32(const float *xyz, int B, int N, const int32_t *start, int32_t *nodes_idx, int32_t *ring,
                      int32_t *infl_idx, float *dists, float *weights, double *sigma, void *ws, size_t ws_bytes,
@@ -656,7 +659,8 @@ int dvm_map_term_f32(const float *verts12, const float *verts2, const int32_t *i
  * Outputs: warped [B,N,3], verts12 [B,N,3], T12 [B,N] (argmax of Pi),
  *          losses [B,6] = {mean d(warped->verts2), mean d(verts2->warped), arap,
  *                          mean d(verts12->verts2), mean d(verts2->verts12), map_sum}
- *          (squared NN distances; chamfer_loss = [0]+[1], the partial variant keeps one side). */
+ *          (squared NN distances; chamfer_loss = [0]+[1], the partial variant keeps one side).
+ * Limit: N <= 12288, the cloud whose graph is built (dvm_fps_f32's limit; DVM_EINVAL before anything is launched). */
 size_t dvm_pair_direction_workspace_bytes(int B, int N, int M);
 int dvm_pair_direction_fwd_f32(const float *feat1, const float *feat2, const float *verts1, const float *verts2,
                                int B, int N, int M, float neg_alpha, const int32_t *fps_start, const float *conv_w,
@@ -669,7 +673,9 @@ int dvm_pair_direction_fwd_f32(const float *feat1, const float *feat2, const flo
  * models/loss.py:1401-1411 (graphs of both clouds, Pi_12 and Pi_21, deform() twice) with the work
  * shared between the directions (xyz kNN, pooled features, one soft-correspondence launch, one MLP
  * launch, one grouped Chamfer launch).  Outputs as in dvm_pair_direction_fwd_f32, once per direction
- * (`12`: cloud 1 deformed towards cloud 2; `21`: the reverse). */
+ * (`12`: cloud 1 deformed towards cloud 2; `21`: the reverse).
+ * Limit: N, M <= 12288 (a graph is built on both clouds: dvm_fps_f32's limit; DVM_EINVAL before anything is launched) — here,
+ * at dvm_pair_fwd_cached_f32 and at dvm_pair_geometry_f32. */
 size_t dvm_pair_workspace_bytes(int B, int N, int M);
 int dvm_pair_fwd_f32(const float *feat1, const float *feat2, const float *verts1, const float *verts2, int B, int N,
                      int M, float neg_alpha, const int32_t *start1, const int32_t *start2, const float *conv_w,
