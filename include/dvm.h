@@ -559,7 +559,10 @@ int dvm_graph_geodesics_f64(const int32_t *nbr, const double *w, int N, int K, d
  * axis-permuted views) -> img [B,3,224,224]: every point adds its depth (3rd coordinate) to the 5x5 pixels around its
  * cell, sigmoid, ImageNet-normalise, min-max rescale per image, 'PiYG' colour table, pixels whose depth sum is exactly 0
  * -> -1.  Also returns what I2P needs: pc_min [B,2], grid_size [B], offsets [B,2] (float-valued integers).  The depth
- * sums are accumulated in 64-bit fixed point, so the image is bit-reproducible from run to run. */
+ * sums are accumulated in 64-bit fixed point, so the image is bit-reproducible from run to run.
+ * Resolution: a depth enters the sum as round(z * 2^e), e = min(40, 60 - floor(log2(25 N max|z|))) (40 while
+ * 25 N max|z| < 2^21), so a term below 2^-(e+1) is dropped: a point alone in a pixel with |z| < 2^-(e+1) renders as background
+ * where the reference colours it.  An image whose depths are all 0 is -1 everywhere. */
 size_t dvm_proj2img_workspace_bytes(int B);
 int dvm_proj2img_f32(const float *pts, int B, int N, float *img, float *pc_min, float *grid_size, float *offsets, void *ws,
                      size_t ws_bytes, void *stream);

@@ -181,7 +181,7 @@ def proj2img(pc):
     out = torch.empty(B, 3, _IMG, _IMG)
     for b in range(B):
         d = (v[b] - v[b].min()) / (v[b].max() - v[b].min())
-        k = torch.clamp((d * 256).long(), max=255)
+        k = torch.clamp(torch.nan_to_num(d * 256).long(), max=255)                      # NaN (flat image, e.g. every depth 0) -> "bad" colour below
         col = lut[k]                                                                    # (224,224,3)
         col[torch.isnan(d)] = 0
         out[b] = col.permute(2, 0, 1)

@@ -1,6 +1,9 @@
 """-m gpu: the image backbone of the visual-feature injection path (BASELINE configs[4]) — a random-init
 DINOv2 ViT-S/14 + FeatUp JBU stack (parity unpinned for the network: its packages and weights are not in the reference
-tree; see models/image_backbone.py) — and `Uni3FC.forward(x, None, upsampler)` end to end."""
+tree; see models/image_backbone.py) — and `Uni3FC.forward(x, None, upsampler)` end to end.
+The kernels of the JBU stage (adaptive convolution, bicubic resize + pad, range x spatial kernel) are checked here over whole tensors;
+per element, at their partial tiles, both temperature clamps and underflowing sigmas, in tests/test_gpu_visual_elements.py (references
+and bars: tests/visual_ref.py, CPU half: tests/test_visual_ref_cpu.py)."""
 import numpy as np
 import pytest
 import torch

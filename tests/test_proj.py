@@ -1,6 +1,9 @@
 """Visual-feature injection: depth rendering (proj2img) and back-projection (I2P).
 CPU: the oracle restatement against vectors recorded from the reference (tests/golden/make_fixtures_proj.py).
-GPU: the HIP kernels against the same vectors and against the oracle at the real sizes."""
+GPU: the HIP kernels against the same vectors and against the oracle at the real sizes.
+These are whole-image / whole-tensor checks on benign clouds; the per-pixel and per-element checks on planted inputs (border shift,
+collisions, cancellation, lattice quotients, every tap class of the back-projection, the out= / col form) live in
+tests/test_gpu_visual_elements.py, with tests/visual_ref.py and tests/test_visual_ref_cpu.py."""
 import numpy as np
 import pytest
 import torch
