@@ -33,6 +33,7 @@ import zlib
 import pytest
 import torch
 
+from attention_ref import n2p_ref64
 from oracle import torch_ref as TR
 
 pytestmark = pytest.mark.gpu
@@ -377,15 +378,8 @@ def n2p_check(ops, qkv, idx, gout, H=4):
     torch.cuda.synchronize()
     for e in range(B):
         x = qkv[e:e + 1].double().cuda().requires_grad_(True)
-        gi = i_[e:e + 1].long().reshape(1, N * Kn, 1).expand(-1, -1, C)
-        q, kp, vp = x[..., :C], x[..., C:2 * C], x[..., 2 * C:]
-        kj = torch.gather(kp, 1, gi).view(1, N, Kn, C)
-        vj = torch.gather(vp, 1, gi).view(1, N, Kn, C)
-        kd = (kj - kp[:, :, None]).view(1, N, Kn, H, Dh)
-        vd = (vj - vp[:, :, None]).view(1, N, Kn, H, Dh)
-        qh = q.view(1, N, 1, H, Dh)
-        a = torch.softmax((qh * kd).sum(-1) / Dh ** 0.5, dim=2)
-        ref = (a.unsqueeze(-1) * vd).sum(2).reshape(1, N, C)
+        r = n2p_ref64(x, i_[e:e + 1], H)                                     # the float64 block shared with tests/attention_ref.py
+        gi, kp, vp, kj, vj, qh, a, ref = r["gi"], r["kp"], r["vp"], r["kj"], r["vj"], r["qh"], r["a"], r["out"]
         gd = g_[e:e + 1].double()
         (ref * gd).sum().backward()
         with torch.no_grad():
