@@ -254,6 +254,100 @@ def bn_act_train_bwd_pm(dy, y, x, res, gamma, mean, invstd, slope, grads=None):
     return dx, dgamma, dbeta
 
 
+def _bn_pm_rows(x, groups):
+    """-> (C, rows per group) of a merged batch of `groups` blocks; a group count the library refuses is passed on for it to refuse."""
+    C = x.shape[-1]
+    rows = x.numel() // C
+    if groups >= 1 and rows % groups:
+        raise DvmError("bn_act_train_*_pm_groups: %d rows do not split into %d groups" % (rows, groups))
+    return C, rows // max(int(groups), 1)
+
+
+def bn_act_train_fwd_pm_sync(x, res, gamma, beta, eps, slope, momentum, groups, coll, sync_buf, want_var=False, running_mean=None,
+                             running_var=None, y=None):
+    """bn_act_train_fwd_pm_groups with the statistics taken over all ranks (dvm_bn_act_train_fwd_pm_sync_f32): coll is the address
+    of a dvm_collective (None: the plain call), sync_buf a device tensor of dvm_bn_pm_sync_bytes(C, groups) bytes that the
+    collective's all-reduce is handed."""
+    _need_gpu(x, res, gamma, beta, sync_buf)
+    x = _f(x)
+    C, R = _bn_pm_rows(x, groups)
+    res = None if res is None else _f(res)
+    y = torch.empty_like(x) if y is None else y
+    mean = _new(x.device, max(int(groups), 1), C)
+    invstd = torch.empty_like(mean)
+    var = torch.empty_like(mean) if want_var else None
+    lib = _lib.load()
+    nb = lib.dvm_bn_pm_groups_workspace_bytes(R, C, int(groups))
+    ws = workspace(nb, x.device, "bn_pm")
+    if coll is not None and sync_buf.numel() * sync_buf.element_size() < lib.dvm_bn_pm_sync_bytes(C, int(groups)):
+        raise DvmError("bn_act_train_fwd_pm_sync: sync_buf is smaller than dvm_bn_pm_sync_bytes")
+    _call("dvm_bn_act_train_fwd_pm_sync_f32", _p(x), _p(res), _p(gamma), _p(beta), R, C, int(groups), float(eps), float(slope),
+          float(momentum), _p(y), _p(mean), _p(invstd), _p(var), _p(running_mean), _p(running_var), _p(ws), nb, coll, _p(sync_buf))
+    return (y, mean, invstd, var) if want_var else (y, mean, invstd)
+
+
+def bn_act_train_fwd_pm_groups(x, res, gamma, beta, eps, slope, momentum, groups, want_var=False, running_mean=None, running_var=None,
+                               y=None):
+    """bn_act_train_fwd_pm on `groups` consecutive row blocks of x, each normalised with its own statistics
+    (dvm_bn_act_train_fwd_pm_var_f32): -> (y, mean [groups][C], invstd [groups][C]) and, with want_var, the unbiased batch variance
+    [groups][C]; the running statistics take the groups' updates one after the other.  `y`: an output tensor to fill."""
+    _need_gpu(x, res, gamma, beta)
+    x = _f(x)
+    C, R = _bn_pm_rows(x, groups)
+    res = None if res is None else _f(res)
+    y = torch.empty_like(x) if y is None else y
+    mean = _new(x.device, max(int(groups), 1), C)
+    invstd = torch.empty_like(mean)
+    var = torch.empty_like(mean) if want_var else None
+    nb = _lib.load().dvm_bn_pm_groups_workspace_bytes(R, C, int(groups))
+    ws = workspace(nb, x.device, "bn_pm")
+    _call("dvm_bn_act_train_fwd_pm_var_f32", _p(x), _p(res), _p(gamma), _p(beta), R, C, int(groups), float(eps), float(slope),
+          float(momentum), _p(y), _p(mean), _p(invstd), _p(var), _p(running_mean), _p(running_var), _p(ws), nb)
+    return (y, mean, invstd, var) if want_var else (y, mean, invstd)
+
+
+def _bn_pm_grads(grads, C, dev):
+    if grads is None:
+        return _new(dev, C), _new(dev, C)
+    for t in grads:
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != C:
+            raise ValueError("bn_act_train_bwd_pm: grads must be contiguous float32 tensors of %d elements" % C)
+    return grads
+
+
+def bn_act_train_bwd_pm_groups(dy, y, x, res, gamma, mean, invstd, slope, groups, grads=None, dx=None):
+    """bn_act_train_bwd_pm for a merged batch (dvm_bn_act_train_bwd_pm_groups_f32): mean / invstd [groups][C]; dgamma / dbeta are
+    the groups' sums added in group order, ADDED to grads = (dgamma, dbeta) when given."""
+    _need_gpu(dy, y, x)
+    dy, x = _f(dy), _f(x)
+    C, R = _bn_pm_rows(x, groups)
+    dx = torch.empty_like(x) if dx is None else dx
+    dgamma, dbeta = _bn_pm_grads(grads, C, x.device)
+    nb = _lib.load().dvm_bn_pm_groups_workspace_bytes(R, C, int(groups))
+    ws = workspace(nb, x.device, "bn_pm")
+    _call("dvm_bn_act_train_bwd_pm_groups_f32", _p(dy), _p(y), _p(x), _p(res), _p(gamma), _p(mean), _p(invstd), R, C, int(groups),
+          float(slope), _p(dx), _p(dgamma), _p(dbeta), int(grads is not None), _p(ws), nb)
+    return dx, dgamma, dbeta
+
+
+def bn_act_train_bwd_pm_sync(dy, y, x, res, gamma, mean, invstd, slope, groups, coll, sync_buf, grads=None):
+    """bn_act_train_bwd_pm_groups with the means of dz and dz xhat taken over all ranks (dvm_bn_act_train_bwd_pm_sync_f32; coll and
+    sync_buf as in bn_act_train_fwd_pm_sync); dgamma / dbeta stay this rank's own sums."""
+    _need_gpu(dy, y, x, sync_buf)
+    dy, x = _f(dy), _f(x)
+    C, R = _bn_pm_rows(x, groups)
+    dx = torch.empty_like(x)
+    dgamma, dbeta = _bn_pm_grads(grads, C, x.device)
+    lib = _lib.load()
+    nb = lib.dvm_bn_pm_groups_workspace_bytes(R, C, int(groups))
+    ws = workspace(nb, x.device, "bn_pm")
+    if coll is not None and sync_buf.numel() * sync_buf.element_size() < lib.dvm_bn_pm_sync_bytes(C, int(groups)):
+        raise DvmError("bn_act_train_bwd_pm_sync: sync_buf is smaller than dvm_bn_pm_sync_bytes")
+    _call("dvm_bn_act_train_bwd_pm_sync_f32", _p(dy), _p(y), _p(x), _p(res), _p(gamma), _p(mean), _p(invstd), R, C, int(groups),
+          float(slope), _p(dx), _p(dgamma), _p(dbeta), int(grads is not None), _p(ws), nb, coll, _p(sync_buf))
+    return dx, dgamma, dbeta
+
+
 def softcorr(f1, f2, alpha, topk=10, variant=0, stats=True):
     """f1 (B,N,d), f2 (B,M,d) -> pi_val (B,N,topk), pi_idx (B,N,topk) int32, row_smax (B,N), row_sum (B,N)."""
     _need_gpu(f1, f2)
