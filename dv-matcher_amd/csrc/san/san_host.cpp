@@ -316,6 +316,21 @@ int main() {
         EXPECT(strstr(dvm_last_error(), "workspace too small") != nullptr);
     }
     EXPECT(dvm_graph_geodesics_f64(nullptr, nullptr, 10, 4, nullptr, nullptr) == DVM_EINVAL);
+    {
+        // dvm_mesh_geodesics_f64: every refusal that comes before a launch
+        double *Dd = (double *)0x1000;
+        int32_t *Ii = (int32_t *)0x1000;
+        const int vmax = dvm_mesh_geodesics_max_v();
+        const size_t mb = dvm_mesh_geodesics_workspace_bytes(100, 162);
+        EXPECT(mb >= 3 * 162 * 48 && dvm_mesh_geodesics_workspace_bytes(vmax, 4) > 0);
+        EXPECT(dvm_mesh_geodesics_workspace_bytes(0, 4) == 0 && dvm_mesh_geodesics_workspace_bytes(8, -1) == 0 &&
+               dvm_mesh_geodesics_workspace_bytes(vmax + 1, 4) == 0);
+        EXPECT(dvm_mesh_geodesics_f64(nullptr, Ii, 100, 162, nullptr, 0, Dd, Dd, mb, nullptr) == DVM_EINVAL);
+        EXPECT(dvm_mesh_geodesics_f64(Dd, Ii, vmax + 1, 162, nullptr, 0, Dd, Dd, (size_t)1 << 40, nullptr) == DVM_EINVAL);
+        EXPECT(dvm_mesh_geodesics_f64(Dd, Ii, 100, 162, Ii, 0, Dd, Dd, mb, nullptr) == DVM_EINVAL);
+        EXPECT(dvm_mesh_geodesics_f64(Dd, Ii, 100, 162, nullptr, 0, Dd, Dd, mb - 1, nullptr) == DVM_ENOSPACE);
+        EXPECT(dvm_mesh_geodesics_f64(Dd, Ii, 100, 162, nullptr, 0, Dd, nullptr, 0, nullptr) == DVM_ENOSPACE);
+    }
     EXPECT(dvm_profile_read(nullptr, nullptr) == DVM_EINVAL);
     EXPECT(dvm_profile_enable(0) == DVM_EINVAL);
     // context registry: destroying with nothing registered, twice, is fine; set_overlap returns the previous value

@@ -983,6 +983,33 @@ def graph_geodesics(nbr, w):
     return D
 
 
+def mesh_geodesics_max_v():
+    """The largest vertex count dvm_mesh_geodesics_f64 takes (a source's V distances stay in LDS)."""
+    return int(_lib.load().dvm_mesh_geodesics_max_v())
+
+
+def mesh_geodesics(verts, faces, sources=None):
+    """Geodesic distances on a triangle mesh by the triangle-front (fast-marching) update, dvm_mesh_geodesics_f64: verts (V,3),
+    faces (F,3) on the device, sources (S,) vertex ids or None = every vertex -> (S or V, V) float64, row r = distances from
+    source r (+inf between components).  Asymmetric at the 0.5 % level; never above the edge-path distance.  The call waits for
+    its own result (the entry reports bad indices as its return value)."""
+    _need_gpu(verts, faces, sources)
+    verts, faces = verts.detach().contiguous().double(), _i(faces)
+    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError("mesh_geodesics: verts must be (V,3) and faces (F,3), got %s and %s" % (tuple(verts.shape), tuple(faces.shape)))
+    V, F = verts.shape[0], faces.shape[0]
+    S = 0
+    if sources is not None:
+        sources = _i(sources).reshape(-1)
+        S = sources.numel()
+        if S < 1:
+            raise ValueError("mesh_geodesics: an empty list of sources (pass None for every vertex)")
+    D = _new(verts.device, S if sources is not None else V, V, dtype=torch.float64)
+    _call_ws("dvm_mesh_geodesics_f64", (_p(verts), _p(faces), V, F, _p(sources), S, _p(D)), verts.device, "mesh_geo",
+             "dvm_mesh_geodesics_workspace_bytes", V, F)
+    return D
+
+
 def proj2img(pts):
     """One view's point cloud (B,N,3) -> (img (B,3,224,224), pc_min (B,2), grid_size (B,), offsets (B,2))."""
     _need_gpu(pts)

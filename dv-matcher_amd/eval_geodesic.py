@@ -19,13 +19,23 @@ def mesh_area(verts, faces):
     return float(np.sqrt((v ** 2).sum(1)).sum() / 2)
 
 
-def geodesic_distmat(verts, faces, normalize=True):
+def geodesic_distmat(verts, faces, normalize=True, method="edges"):
     """eval/geo_mat.py:15-41: shortest paths over the mesh edges weighted by their Euclidean lengths; with
-    `normalize` divided by sqrt(surface area) (the M matrices the MATLAB evaluation loads)."""
+    `normalize` divided by sqrt(surface area) (the M matrices the MATLAB evaluation loads).
+    method="mesh" instead takes the symmetrised triangle-front distances (models.dataset.cal_geo's "mesh": dvm.ops.mesh_geodesics,
+    needs a HIP device), which cut across triangles; the default stays the reference's Dijkstra."""
     from scipy.sparse import coo_matrix
     from scipy.sparse.csgraph import shortest_path
+    if method not in ("edges", "mesh"):
+        raise ValueError("geodesic_distmat: method must be 'edges' or 'mesh', got %r" % (method,))
     verts = np.asarray(verts, np.float64)
     faces = np.asarray(faces, np.int64)
+    if method == "mesh":
+        from models.dataset import _mesh_geodesics_gpu
+        geo = _mesh_geodesics_gpu(verts.reshape(-1, 3), faces)
+        if np.isinf(geo).any():
+            raise ValueError("mesh graph is not connected")
+        return geo / np.sqrt(mesh_area(verts, faces)) if normalize else geo
     e = np.concatenate([faces[:, [0, 1]], faces[:, [1, 2]], faces[:, [2, 0]]], 0)
     e = np.unique(np.sort(e, 1), axis=0)
     w = np.linalg.norm(verts[e[:, 0]] - verts[e[:, 1]], axis=1)

@@ -248,6 +248,9 @@ def main(argv=None):
     ap.add_argument("--step-breakdown", action="store_true", help="timing mode: host seconds per phase of the step on stderr")
     ap.add_argument("--data-root", default=None, help="dataset directory (shapes_train/, shapes_test/, feat/, cache_*.pt); default: synthetic")
     ap.add_argument("--data-name", default=None)
+    ap.add_argument("--geodesics", choices=("graph", "mesh"), default="graph", help="with --data-root: the geodesic matrices of the dataset, "
+                    "'graph' = edge paths (the default, reference-compatible cache names), 'mesh' = the triangle-front solver "
+                    "(dvm_mesh_geodesics_f64; triangle meshes only, caches named *_meshgeo.pt)")
     ap.add_argument("--random-feat", action="store_true", help="with --data-root: random visual features instead of feat/*.mat")
     ap.add_argument("--upsampler-weights", default=None, help="state_dict of the FeatUp / DINOv2 image backbone (hub layout) for "
                     "configurations with with_dino = False, whose visual features are rendered and back-projected on the fly "
@@ -320,7 +323,8 @@ def main(argv=None):
         from models import dataset as ds
         name = args.data_name or ("scape_partial" if partial else "scape_r")
         cls = ds.PartialDataset if partial else ds.Dataset
-        kw = dict(with_dino=bool(cfg.get("with_dino", True)) and not args.random_feat, feat_mat=bool(cfg.get("feat_mat", True)))
+        kw = dict(with_dino=bool(cfg.get("with_dino", True)) and not args.random_feat, feat_mat=bool(cfg.get("feat_mat", True)),
+                  geodesics=args.geodesics)
         train_set = DatasetPairs(cls(args.data_root, name=name, train=True, **kw), N, M, dev, args.random_feat, seed_data)
         try:
             val_set = DatasetPairs(cls(args.data_root, name=name, train=False, **kw), N, M, dev, args.random_feat, seed_data + 1)

@@ -555,6 +555,31 @@ int dvm_bn_act_train_bwd_f32(const float *dy, const float *y, const float *x, co
  * nbr [N,K] (-1 ends a list), w [N,K] fp64 edge lengths -> D [N,N] fp64 (+inf between components).  N <= 19200. */
 int dvm_graph_geodesics_f64(const int32_t *nbr, const double *w, int N, int K, double *D, void *stream);
 
+/* cal_geo(method="mesh") — geodesic distances on a triangle mesh by the first-order upwind ("fast-marching") update on triangles,
+ * relaxed to its fixed point (the scheme is stated in tests/mesh_geodesic_ref.py): unlike the edge paths above, which cannot cut
+ * across a triangle and overestimate by 5 - 8 % at any resolution, a discretisation of the surface metric (error 1 - 2 % on the test
+ * meshes, falling with refinement; never above the edge-path distance).  Not the reference's heat method either: its values stay
+ * unpinned.  verts [V,3] fp64, faces [F,3] int32 (degenerate, repeated and duplicate faces are allowed; vertices in no face stay at
+ * +inf), sources [S] int32 vertex ids (repeats allowed) or NULL = all V vertices in order, D [S or V, V] fp64: D[r, v] = distance
+ * from source r to vertex v, +inf between components.  The result is asymmetric at the 0.5 % level (as the heat method's).
+ * Updates are made in place, in the order the hardware runs the threads: two calls agree to the acceptance margin's effect
+ * (relative differences of some 1e-12), not bit for bit.
+ * One workgroup per source with its V distances in LDS: V <= dvm_mesh_geodesics_max_v() (16384).  A prologue writes the corner
+ * table (48 bytes per corner, CSR by vertex) into the workspace: dvm_mesh_geodesics_workspace_bytes(V, F), 0 for sizes the entry
+ * refuses.
+ * Errors.  Before any launch: null pointers, V < 1, F < 0, V over the limit, S < 1 with a list (DVM_EINVAL), a short workspace
+ * (DVM_ENOSPACE).  On the device: a face or source index outside [0, V) (checked before it is used: such a face is left out, such
+ * a source's row is not written; DVM_EINVAL) and a source that has not settled after 4 V sweeps (DVM_ELAUNCH) set a flag word in
+ * the workspace.  THIS ENTRY SYNCHRONISES: after its last launch it copies that one word back and waits for `stream`, so that
+ * the error is this call's return value — the exception to the conventions above (it is once-per-shape preprocessing; do not
+ * call it under stream capture).
+ * Diagnostics: after the call the workspace holds, at byte 256, int32 sweeps[min(S or V, V)], the sweeps each of the first sources
+ * took. */
+int dvm_mesh_geodesics_max_v(void);
+size_t dvm_mesh_geodesics_workspace_bytes(int V, int F);
+int dvm_mesh_geodesics_f64(const double *verts, const int32_t *faces, int V, int F, const int32_t *sources, int S, double *D, void *ws,
+                           size_t ws_bytes, void *stream);
+
 /* Uni3FC.proj2img — models/model.py:584-650 (+ get_colored_depth_maps 563-581).  pts [B,N,3] (one of the three
  * axis-permuted views) -> img [B,3,224,224]: every point adds its depth (3rd coordinate) to the 5x5 pixels around its
  * cell, sigmoid, ImageNet-normalise, min-max rescale per image, 'PiYG' colour table, pixels whose depth sum is exactly 0
