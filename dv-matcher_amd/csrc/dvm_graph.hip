@@ -459,6 +459,40 @@ DVM_EXPORT int dvm_dg_build_f32(const float *xyz, int B, int N, const int32_t *s
     return DVM_OK;
 }
 
+// dvm_dg_build_f32 whole (nodes, Euclidean ring, sigma: its bits), then the skinning — and under ring_metric 1 the ring — again
+// from the caller's matrix (dvm_dg_geod.hip), behind it on the stream
+struct DgBuildGeodWs {
+    DgBuildWs build;
+    double *sigma;   // where the caller wants none
+};
+static size_t carve_dg_build_geod(Arena &ar, int B, int N, DgBuildGeodWs &w) {
+    carve_dg_build(ar, B, N, w.build);
+    w.sigma = ar.take<double>((size_t)B);
+    return ar.off;
+}
+
+DVM_EXPORT size_t dvm_dg_build_geod_workspace_bytes(int B, int N) { return null_carve<DgBuildGeodWs>(carve_dg_build_geod, B, N); }
+
+DVM_EXPORT int dvm_dg_build_geod_f32(const float *xyz, const float *dist, int B, int N, const int32_t *start, int ring_metric, int32_t *nodes_idx,
+                                     int32_t *ring, int32_t *infl_idx, float *dists, float *weights, double *sigma, void *ws, size_t ws_bytes,
+                                     void *stream) {
+    DVM_REQUIRE(xyz && dist && start && nodes_idx && ring && infl_idx && dists && weights, "dvm_dg_build_geod_f32: null pointer");
+    DVM_REQUIRE(B >= 1 && B <= 65535 && N >= 6, "dvm_dg_build_geod_f32: bad sizes (B=%d N=%d; need N >= 6, B <= 65535)", B, N);
+    DVM_REQUIRE(N <= DVM_MAX_POINTS, "dvm_dg_build_geod_f32: N=%d exceeds %d", N, DVM_MAX_POINTS);
+    DVM_REQUIRE(ring_metric == 0 || ring_metric == 1, "dvm_dg_build_geod_f32: bad ring_metric %d (0 = Euclidean, 1 = geodesic)", ring_metric);
+    DVM_REQUIRE(ring_metric == 0 || N / 2 >= 9, "dvm_dg_build_geod_f32: a geodesic ring of 9 needs N >= 18 (N=%d)", N);
+    DgBuildGeodWs w;
+    if (!carve_ws(ws, ws_bytes, "dvm_dg_build_geod_f32", w, carve_dg_build_geod, B, N)) return DVM_ENOSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    double *sg = sigma ? sigma : w.sigma;
+    const int rc = launch_dg_build(xyz, B, N, start, nodes_idx, ring, infl_idx, dists, weights, sg, w.build.nnd, w.build.gv, w.build.gn, true, s);
+    if (rc != DVM_OK) return rc;
+    launch_dg_skin_geod(dist, nodes_idx, B, N, N / 2, ring_metric ? 9 : 0, infl_idx, dists, ring, s);
+    launch_dg_skin_weights(dists, sg, B, N, weights, s);
+    DVM_CHECK_LAUNCH("dg_build_geod");
+    return DVM_OK;
+}
+
 DVM_EXPORT int dvm_rot6d_f32(const float *d6, int rows, float *R, void *stream) {
     DVM_REQUIRE(d6 && R && rows >= 1, "dvm_rot6d_f32: bad arguments");
     hipLaunchKernelGGL(rot6d_plain_kernel, dim3((rows + 255) / 256), dim3(256), 0, (hipStream_t)stream, d6, rows, R);

@@ -103,6 +103,15 @@ bool launch_dg_warp_pair(const float *xyz1, const float *xyz2, int B, int N, int
                          int32_t *const infl[2], const float *const weights[2], const float *def9_12, const float *def9_21, float *R12, float *R21,
                          float *T12, float *T21, float *warped12, float *warped21, float *arap12, float *arap21, int arap_stride, hipStream_t s);
 
+// ---- dvm_dg_geod.hip: skinning and rings by a caller-supplied distance matrix
+// vertices per workgroup (one lane each); most waves that share a tile's node range; longest ring; the wave count below which
+// the node range is split, and the fewest node rows a wave is left with
+constexpr int DG_GEOD_TILE = 64, DG_GEOD_MAX_SLICES = 8, DG_GEOD_MAX_RING = 16, DG_GEOD_TARGET_WAVES = 4096, DG_GEOD_MIN_SLICE = 16;
+// dvm_dg_skin_geod_f32 without its checks; slices: waves per tile, 0 = dg_skin_geod_slices(B, N, Nn)
+void launch_dg_skin_geod(const float *dist, const int32_t *nodes_idx, int B, int N, int Nn, int ring_k, int32_t *infl_idx, float *dists, int32_t *ring,
+                         hipStream_t s, int slices = 0);
+void launch_dg_skin_weights(const float *dists, const double *sigma, int B, int N, float *weights, hipStream_t s);
+
 // ---- dvm_grid.hip: uniform-grid neighbour search over GridBuf (dvm_common.h)
 size_t grid_bytes(int B, int P);
 GridBuf grid_carve(Arena &ar, int B, int P);

@@ -253,6 +253,16 @@ int main() {
         SHORT(dvm_softcorr_dense_workspace_bytes(B, N, M, d), dvm_softcorr_dense_f32(F, F, B, N, M, d, -1.f, F, ws, q - 1, nullptr));
         SHORT(dvm_softcorr_apply_bwd_workspace_bytes(B, N, M, 10), dvm_softcorr_apply_bwd_f32(F, I, F, F, B, N, M, 10, 3, F, F, ws, q - 1, nullptr));
         SHORT(dvm_dg_build_workspace_bytes(B, N), dvm_dg_build_f32(F, B, N, I, I, I, I, F, F, dd, ws, q - 1, nullptr));
+        SHORT(dvm_dg_build_geod_workspace_bytes(B, N), dvm_dg_build_geod_f32(F, F, B, N, I, 1, I, I, I, F, F, dd, ws, q - 1, nullptr));
+        // ... and the refusals of the geodesic skinning, which has no workspace: too few nodes, a ring longer than the node list or
+        // than 16, a cloud above the FPS limit, a bad ring metric
+        EXPECT(dvm_dg_skin_geod_f32(F, I, B, N, 2, 0, I, F, nullptr, nullptr) == DVM_EINVAL);
+        EXPECT(dvm_dg_skin_geod_f32(F, I, B, N, 8, 9, I, F, I, nullptr) == DVM_EINVAL);
+        EXPECT(dvm_dg_skin_geod_f32(F, I, B, N, N / 2, 17, I, F, I, nullptr) == DVM_EINVAL);
+        EXPECT(dvm_dg_skin_geod_slices_f32(F, I, B, N, N / 2, 9, 9, I, F, I, nullptr) == DVM_EINVAL);
+        EXPECT(dvm_dg_skin_weights_f32(F, nullptr, B, N, F, nullptr) == DVM_EINVAL);
+        EXPECT(dvm_dg_build_geod_f32(F, F, B, 12289, I, 0, I, I, I, F, F, dd, ws, q, nullptr) == DVM_EINVAL);
+        EXPECT(dvm_dg_build_geod_f32(F, F, B, N, I, 2, I, I, I, F, F, dd, ws, q, nullptr) == DVM_EINVAL);
         SHORT(dvm_chamfer_workspace_bytes(B, 8192, 8192), dvm_chamfer_fwd_f32(F, F, B, 8192, 8192, F, F, I, I, ws, q - 1, nullptr));   // (large enough for the grid form)
         SHORT(dvm_deformer_workspace_bytes(B, N, M, N / 2),
               dvm_deformer_fwd_f32(F, F, F, F, I, I, F, I, I, B, N, M, N / 2, k, 10, F, F, F, F, F, F, F, F, F, F, F, 0, ws, q - 1, nullptr));

@@ -671,6 +671,76 @@ def dg_build(xyz, start):
     return out
 
 
+_RING_METRICS = {"euclidean": 0, "geodesic": 1}
+
+
+def dg_skin_geod_plan(B, N, Nn, ring_k=0):
+    """How dg_skin_geod launches at these sizes -> (vertices per workgroup, waves that share a tile's node range, length of the
+    per-lane list).  No device is needed."""
+    t, s, ln = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    check(_lib.load().dvm_dg_skin_geod_plan(B, N, Nn, ring_k, ctypes.byref(t), ctypes.byref(s), ctypes.byref(ln)), "dvm_dg_skin_geod_plan")
+    return t.value, s.value, ln.value
+
+
+def dg_skin_geod(dist, nodes_idx, ring_k=0, slices=None):
+    """Skinning by a distance matrix: dist (B,N,N), nodes_idx (B,Nn) -> (infl_idx (B,N,3) int32, dists (B,N,3), ring (B,Nn,ring_k)
+    int32 or None).  Vertex v meets node position j at dist[b, nodes_idx[b,j], v]; the order is (d, j) with NaN as +inf, -0 == +0
+    and ties to the lower j (include/dvm.h).  slices: the waves per vertex tile, None = the library's choice."""
+    _need_gpu(dist, nodes_idx)
+    dist, nodes_idx = _f(dist), _i(nodes_idx)
+    B, N, N2 = dist.shape
+    if N2 != N or nodes_idx.dim() != 2 or nodes_idx.shape[0] != B:
+        raise DvmError("dg_skin_geod: dist must be (B,N,N) and nodes_idx (B,Nn) (got %s, %s)" % (tuple(dist.shape), tuple(nodes_idx.shape)))
+    Nn = nodes_idx.shape[1]
+    dev = dist.device
+    ring_k = int(ring_k)
+    infl, dists = _new(dev, B, N, 3, dtype=torch.int32), _new(dev, B, N, 3)
+    ring = _new(dev, B, Nn, ring_k, dtype=torch.int32) if ring_k > 0 else None
+    if slices is None:
+        _call("dvm_dg_skin_geod_f32", _p(dist), _p(nodes_idx), B, N, Nn, ring_k, _p(infl), _p(dists), _p(ring))
+    else:
+        _call("dvm_dg_skin_geod_slices_f32", _p(dist), _p(nodes_idx), B, N, Nn, ring_k, int(slices), _p(infl), _p(dists), _p(ring))
+    return infl, dists, ring
+
+
+def dg_skin_weights(dists, sigma):
+    """dists (B,N,3), sigma (B,) -> weights (B,N,3) = exp(-d^2 / float(2 sigma^2)) row-normalised; an infinite d weighs 0 and a row
+    without weight becomes (1,0,0)."""
+    _need_gpu(dists)
+    dists = _f(dists)
+    B, N, _ = dists.shape
+    sigma = torch.as_tensor(sigma, dtype=torch.float64).reshape(-1).to(dists.device).contiguous()
+    if sigma.numel() != B:
+        raise DvmError("dg_skin_weights: sigma must hold one value per batch element (got %d for B=%d)" % (sigma.numel(), B))
+    out = torch.empty_like(dists)
+    _call("dvm_dg_skin_weights_f32", _p(dists), _p(sigma), B, N, _p(out))
+    return out
+
+
+def dg_build_geod(xyz, dist, start, ring_metric="euclidean"):
+    """dg_build with the skinning taken from dist (B,N,N) -> the same dict.  nodes_idx, sigma and (ring_metric "euclidean") one_ring
+    are dg_build's; infl_idx, dists, weights — and under ring_metric "geodesic" one_ring — follow dist (dg_skin_geod's rules)."""
+    if ring_metric not in _RING_METRICS:
+        raise ValueError("ring_metric must be 'euclidean' or 'geodesic' (got %r)" % (ring_metric,))
+    _need_gpu(xyz, dist, start)
+    xyz, dist, start = _f(xyz), _f(dist), _i(start)
+    B, N, _ = xyz.shape
+    if tuple(dist.shape) != (B, N, N):
+        raise DvmError("dg_build_geod: dist must be (B,N,N) = %s (got %s)" % ((B, N, N), tuple(dist.shape)))
+    Nn = N // 2
+    dev = xyz.device
+    out = dict(nodes_idx=_new(dev, B, Nn, dtype=torch.int32),
+               one_ring=_new(dev, B, Nn, 9, dtype=torch.int32),
+               infl_idx=_new(dev, B, N, 3, dtype=torch.int32),
+               dists=_new(dev, B, N, 3),
+               weights=_new(dev, B, N, 3),
+               sigma=_new(dev, B, dtype=torch.float64))
+    _call_ws("dvm_dg_build_geod_f32", (_p(xyz), _p(dist), B, N, _p(start), _RING_METRICS[ring_metric], _p(out["nodes_idx"]),
+                                       _p(out["one_ring"]), _p(out["infl_idx"]), _p(out["dists"]), _p(out["weights"]), _p(out["sigma"])),
+             dev, "dg_build", "dvm_dg_build_geod_workspace_bytes", B, N)
+    return out
+
+
 def rot6d(d6):
     """rotation_6d_to_matrix: d6 (...,6) -> (...,3,3)."""
     _need_gpu(d6)

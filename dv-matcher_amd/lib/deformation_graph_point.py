@@ -70,10 +70,13 @@ class DeformationGraph_geod(nn.Module):
         self.sigma = g["sigma"][0]
         self.pre_idx = self.influence_nodes_idx[:, :1]
 
-    def construct_graph_euclidean(self, vertices=None, geod=None, device=None, start=None):
-        """vertices (N,3) tensor.  `geod` (the N x N cdist the reference passes in as a host array) is
+    def construct_graph_euclidean(self, vertices=None, geod=None, device=None, start=None, use_geod=False, ring_metric="euclidean"):
+        """vertices (N,3) tensor.  By default `geod` (the N x N cdist the reference passes in as a host array) is
         not needed: the kernels recompute the same matmul-form distances on the device.  `device`
-        selects the HIP device when `vertices` is a CPU tensor (as in the reference's call)."""
+        selects the HIP device when `vertices` is a CPU tensor (as in the reference's call).
+        use_geod=True honours `geod` (host array or device tensor, (N,N)) as the reference does: every vertex is skinned to the
+        3 nodes with the smallest geod[nodes_idx[j], v] (ops.dg_build_geod); ring_metric="geodesic" takes the node rings from
+        it as well.  The nodes stay the Euclidean FPS and sigma the Euclidean spacing, as in the reference under any geod."""
         if self.sampling_strategy != 'qslim':
             raise NotImplementedError("only the 'qslim' (FPS) sampling of the reference is implemented")
         v = torch.as_tensor(vertices, dtype=torch.float32)
@@ -83,7 +86,17 @@ class DeformationGraph_geod(nn.Module):
         if start is None:  # same RNG draw as the reference's FPS (shape (1,), CPU generator)
             start = torch.randint(0, N, (1,), dtype=torch.long)
         start = torch.as_tensor(start).reshape(1).to(v.device)
-        self._g = ops.dg_build(v[None], start)
+        if use_geod:
+            if geod is None:
+                raise ValueError("use_geod=True needs the (N,N) distance matrix `geod`")
+            d = torch.as_tensor(geod)
+            if tuple(d.shape) != (N, N):
+                raise ValueError("geod must be (N,N) = (%d,%d), got %s" % (N, N, tuple(d.shape)))
+            self._g = ops.dg_build_geod(v[None], d.to(v.device, torch.float32)[None], start, ring_metric)
+        else:
+            if ring_metric != "euclidean":
+                raise ValueError("ring_metric=%r needs use_geod=True" % (ring_metric,))
+            self._g = ops.dg_build(v[None], start)
         self._publish(v)
 
     def construct_graph(self, vertices=None, faces=None, geod=None, device=None):
@@ -92,7 +105,8 @@ class DeformationGraph_geod(nn.Module):
         decimated mesh (padded to max_neigh_num = 18 with the node itself), every vertex is skinned to its 3 geodesically
         nearest nodes (`geod`: the (V,V) geodesic matrix the caller supplies) with Gaussian weights of width
         20 x the decimated mesh's mean edge length.  The build is host code, as in the reference (lib/mesh_sampling.py);
-        the graph then lives on the device and forward() runs on the HIP kernels."""
+        the graph then lives on the device and forward() runs on the HIP kernels.  A `geod` that is a device tensor stays
+        there: its top-3 and the weights run on ops.dg_skin_geod / ops.dg_skin_weights (ties to the lower node position)."""
         if self.sampling_strategy != 'qslim':
             raise NotImplementedError("only the 'qslim' sampling of the reference is implemented")
         from lib.mesh_sampling import Mesh, generate_transform_matrices
@@ -111,14 +125,27 @@ class DeformationGraph_geod(nn.Module):
                 raise ValueError("node %d has %d neighbours (max_neigh_num = %d)" % (i, len(nb), self.max_neigh_num))
             ring.append(nb + [i] * (self.max_neigh_num - len(nb)))
         self.one_ring_neigh = torch.tensor(ring)
-        geod_mat = torch.from_numpy(-np.asarray(geod)[self.nodes_idx]).transpose(1, 0)
-        dists, infl = geod_mat.topk(self.k, dim=-1)
-        self.dists = -dists
-        self.pre_idx = geod_mat.topk(1, dim=-1)[1]
         gv, gf = torch.tensor(self.graph.v), torch.tensor(self.graph.f.astype(np.int64))
         self.sigma = 20 * torch.mean(compute_edge_lengths(gv, gf))
-        w = torch.exp(-(self.dists ** 2) / (2 * self.sigma * self.sigma))
-        self.weights = (w / w.sum(1).reshape(-1, 1)).float()
+        if torch.is_tensor(geod) and geod.is_cuda:
+            # a device matrix stays there: the top-k and the weights on the skinning kernels (dvm_dg_geod.hip), k = 3
+            if self.k != 3:
+                raise NotImplementedError("a device `geod` is skinned by the HIP kernels, which pick k = 3 nodes")
+            nodes_dev = torch.from_numpy(np.asarray(self.nodes_idx)).int().to(geod.device)[None]
+            infl, dists, _ = ops.dg_skin_geod(geod[None], nodes_dev)
+            self.dists = dists[0]
+            self.weights = ops.dg_skin_weights(dists, self.sigma.double().reshape(1))[0]
+            infl = infl[0].long()
+            self.pre_idx = infl[:, :1]
+            if device is None:
+                device = geod.device
+        else:
+            geod_mat = torch.from_numpy(-np.asarray(geod)[self.nodes_idx]).transpose(1, 0)
+            dists, infl = geod_mat.topk(self.k, dim=-1)
+            self.dists = -dists
+            self.pre_idx = geod_mat.topk(1, dim=-1)[1]
+            w = torch.exp(-(self.dists ** 2) / (2 * self.sigma * self.sigma))
+            self.weights = (w / w.sum(1).reshape(-1, 1)).float()
         dev = torch.device(device) if device is not None else (vertices.device if torch.is_tensor(vertices) and vertices.is_cuda
                                                                  else torch.device("cuda"))
         self.influence_nodes_idx = infl.to(dev)

@@ -253,7 +253,8 @@ class GraphDeformLoss_Neural(nn.Module):
                  w_rank=1, w_self_rec=1, w_cd=1, w_arap=1, save_name=None, dump=False, graph_cache=None):
         super().__init__()
         # opt-in per-shape graph cache: a dict filled by geometry(..., shape_ids=...); the reference rebuilds
-        # every graph on every call (models/loss.py:1325-1337).  Entries are keyed by (shape id, FPS start, point count)
+        # every graph on every call (models/loss.py:1325-1337).  Entries are keyed by (shape id, FPS start, point count,
+        # graph_metric, graph_ring_metric)
         self.graph_cache = graph_cache
         self.graph_cache_max = 4096     # entries kept when graph_cache is an OrderedDict (~60 KB each at N = 2048)
         self.device = 'cuda:0'
@@ -285,6 +286,21 @@ class GraphDeformLoss_Neural(nn.Module):
         # exactly the paths above; > 0 takes the paths w_cycle > 0 takes
         self.w_distortion = 0
         self.distortion_loss = 0
+        # opt-in: "geodesic" skins every vertex to the 3 nodes nearest by the distance matrices the criterion is handed (dist1 /
+        # dist2; ops.dg_build_geod — what the reference's construct_graph_euclidean does with a `geod` that is not cdist);
+        # graph_ring_metric = "geodesic" takes the ARAP rings from them as well.  Nodes (Euclidean FPS) and sigma stay.
+        # "euclidean" = the graphs of ops.dg_build, on exactly the paths above; everything behind geometry() is the same either way
+        self.graph_metric = "euclidean"
+        self.graph_ring_metric = "euclidean"
+
+    def _graph_kind(self):
+        """(graph_metric, graph_ring_metric), checked: part of every graph-cache key."""
+        if self.graph_metric not in ("euclidean", "geodesic") or self.graph_ring_metric not in ("euclidean", "geodesic"):
+            raise ValueError("graph_metric / graph_ring_metric must be 'euclidean' or 'geodesic' (got %r, %r)"
+                             % (self.graph_metric, self.graph_ring_metric))
+        if self.graph_metric == "euclidean" and self.graph_ring_metric != "euclidean":
+            raise ValueError("graph_ring_metric = 'geodesic' needs graph_metric = 'geodesic'")
+        return self.graph_metric, self.graph_ring_metric
 
     def _identity6(self, device):
         """[1,0,0,0,1,0]: the identity rotation in the 6D parametrisation (models/loss.py:1258-1262), made once per device."""
@@ -307,12 +323,21 @@ class GraphDeformLoss_Neural(nn.Module):
         v, i = torch.topk(A, 10, dim=-1)
         return torch.zeros_like(A).scatter_(-1, i, v)
 
-    def deformation_graph_node(self, verts1, starts=None):
+    def _build_graphs(self, verts, starts, dist=None):
+        """ops.dg_build, or under graph_metric = "geodesic" ops.dg_build_geod on the shapes' distance matrices dist (B,N,N)."""
+        metric, ring_metric = self._graph_kind()
+        if metric == "euclidean":
+            return ops.dg_build(verts, starts)
+        if dist is None:
+            raise ValueError("graph_metric = 'geodesic' needs the shapes' distance matrices")
+        return ops.dg_build_geod(verts, dist, starts, ring_metric)
+
+    def deformation_graph_node(self, verts1, starts=None, dist=None):
         """-> (nodes_idx (B,Nn) float like the reference, [graph objects], batched graph dict)."""
         B, N, _ = verts1.shape
         if starts is None:  # one torch.randint(0,N,(1,)) per batch element, in order, like the reference
             starts = torch.cat([torch.randint(0, N, (1,), dtype=torch.long) for _ in range(B)])
-        g = ops.dg_build(verts1, _host_draw_to_device(starts, verts1.device))
+        g = self._build_graphs(verts1, _host_draw_to_device(starts, verts1.device), dist)
         dg_list = [DeformationGraph_geod.from_batch(g, b, verts1[b]) for b in range(B)] if self.dump else []
         return g["nodes_idx"].float(), dg_list, g
 
@@ -432,17 +457,19 @@ class GraphDeformLoss_Neural(nn.Module):
             save_off_file(path + '/' + name + n + '.off', t.detach().cpu().numpy())
 
     # ---- forward ------------------------------------------------------------------------------
-    def _cached_side(self, verts, starts, ids):
+    def _cached_side(self, verts, starts, ids, dist=None):
         """Graph + xyz kNN of a batch of shapes assembled from per-shape cache entries; shapes not yet seen are built in ONE
-        batched call and stored.  Bit-identical to building the batch (every kernel of the build works per shape)."""
+        batched call and stored.  Bit-identical to building the batch (every kernel of the build works per shape).  The keys
+        carry (graph_metric, graph_ring_metric): graphs of different kinds never mix."""
         B, N, _ = verts.shape
-        keys = [(ids[b], int(starts[b]), N) for b in range(B)]
+        kind = self._graph_kind()
+        keys = [(ids[b], int(starts[b]), N) + kind for b in range(B)]
         miss = [b for b in range(B) if keys[b] not in self.graph_cache]
         if miss:
             sel = torch.as_tensor(miss, device=verts.device)
             sub = verts.index_select(0, sel).contiguous()
             st = torch.as_tensor([int(starts[b]) for b in miss], dtype=torch.int32)
-            g = ops.dg_build(sub, _host_draw_to_device(st, verts.device))
+            g = self._build_graphs(sub, _host_draw_to_device(st, verts.device), dist.index_select(0, sel) if dist is not None else None)
             idx = ops.knn_cdist(sub, sub, self.k_deform)
             for j, b in enumerate(miss):
                 ent = {name: t[j].clone() for name, t in g.items()}
@@ -457,14 +484,20 @@ class GraphDeformLoss_Neural(nn.Module):
         g = {name: torch.stack([e[name] for e in ents]) for name in ents[0] if name != "_idx"}
         return g, torch.stack([e["_idx"] for e in ents])
 
-    def geometry(self, verts1, verts2, fps_starts=None, shape_ids=None):
+    def geometry(self, verts1, verts2, fps_starts=None, shape_ids=None, dists=None):
         """The part of the criterion that depends on the COORDINATES only — both shapes' deformation graphs (FPS nodes, node
         rings, skinning) and their xyz kNN — as (g1, g2, idx11, idx22).  forward() calls it itself; a driver may call it
         earlier, on another stream, while the network is still computing the features (FPS is a chain of N/2 dependent
         steps on one workgroup per shape: 0.65 ms during which nothing else of the criterion can start), and hand the
-        result to forward(geometry=...).  The FPS start indices are drawn here, in the reference's order."""
+        result to forward(geometry=...).  The FPS start indices are drawn here, in the reference's order.
+        dists = (dist1 (B,N,N), dist2 (B,M,M)): the matrices that skin the graphs under graph_metric = "geodesic" (unused
+        otherwise)."""
         B, N, _ = verts1.shape
         M = verts2.shape[1]
+        geod = self._graph_kind()[0] == "geodesic"
+        if geod and (dists is None or dists[0] is None or dists[1] is None):
+            raise ValueError("graph_metric = 'geodesic' needs both distance matrices (dists=(dist1, dist2))")
+        d1, d2 = dists if geod else (None, None)
         s1, s2 = fps_starts if fps_starts is not None else (None, None)
         k = self.k_deform
         if self.graph_cache is not None and shape_ids is not None and not self.dump:
@@ -474,8 +507,8 @@ class GraphDeformLoss_Neural(nn.Module):
             if s2 is None:
                 s2 = torch.cat([torch.randint(0, M, (1,), dtype=torch.long) for _ in range(B)])
             if not any(torch.is_tensor(t) and t.is_cuda for t in (s1, s2)):
-                g1, idx11 = self._cached_side(verts1, list(torch.as_tensor(s1).reshape(-1).tolist()), list(shape_ids[0]))
-                g2, idx22 = self._cached_side(verts2, list(torch.as_tensor(s2).reshape(-1).tolist()), list(shape_ids[1]))
+                g1, idx11 = self._cached_side(verts1, list(torch.as_tensor(s1).reshape(-1).tolist()), list(shape_ids[0]), d1)
+                g2, idx22 = self._cached_side(verts2, list(torch.as_tensor(s2).reshape(-1).tolist()), list(shape_ids[1]), d2)
                 return g1, g2, idx11, idx22
         if verts1.shape == verts2.shape and not self.dump:
             # both shapes' graphs and xyz-kNN in ONE batched call each (FPS is a sequential 1-workgroup-per-shape
@@ -485,14 +518,18 @@ class GraphDeformLoss_Neural(nn.Module):
             if s2 is None:
                 s2 = torch.cat([torch.randint(0, M, (1,), dtype=torch.long) for _ in range(B)])
             both = torch.cat([verts1, verts2], dim=0)
-            _, _, g = self.deformation_graph_node(both, torch.cat([torch.as_tensor(s1).reshape(-1), torch.as_tensor(s2).reshape(-1)]))
-            g1 = {key: (v[:B] if torch.is_tensor(v) and v.dim() > 0 and v.shape[0] == 2 * B else v) for key, v in g.items()}
-            g2 = {key: (v[B:] if torch.is_tensor(v) and v.dim() > 0 and v.shape[0] == 2 * B else v) for key, v in g.items()}
+            if geod:   # one call per side: joining the two (B,N,N) matrices would copy them (every kernel of the build works per shape)
+                _, _, g1 = self.deformation_graph_node(verts1, s1, d1)
+                _, _, g2 = self.deformation_graph_node(verts2, s2, d2)
+            else:
+                _, _, g = self.deformation_graph_node(both, torch.cat([torch.as_tensor(s1).reshape(-1), torch.as_tensor(s2).reshape(-1)]))
+                g1 = {key: (v[:B] if torch.is_tensor(v) and v.dim() > 0 and v.shape[0] == 2 * B else v) for key, v in g.items()}
+                g2 = {key: (v[B:] if torch.is_tensor(v) and v.dim() > 0 and v.shape[0] == 2 * B else v) for key, v in g.items()}
             idx = ops.knn_cdist(both, both, k)
             idx11, idx22 = idx[:B], idx[B:]
         else:
-            _, _, g1 = self.deformation_graph_node(verts1, s1)
-            _, _, g2 = self.deformation_graph_node(verts2, s2)
+            _, _, g1 = self.deformation_graph_node(verts1, s1, d1)
+            _, _, g2 = self.deformation_graph_node(verts2, s2, d2)
             idx11, idx22 = ops.knn_cdist(verts1, verts1, k), ops.knn_cdist(verts2, verts2, k)
         return g1, g2, idx11, idx22
 
@@ -509,6 +546,8 @@ class GraphDeformLoss_Neural(nn.Module):
         M = verts2.shape[1]
         if self.w_distortion > 0 and (dist1 is None or dist2 is None):
             raise ValueError("w_distortion > 0 needs both distance matrices (dist1, dist2)")
+        if self._graph_kind()[0] == "geodesic" and (dist1 is None or dist2 is None):
+            raise ValueError("graph_metric = 'geodesic' needs both distance matrices (dist1, dist2)")
         train = torch.is_grad_enabled() and (feat1.requires_grad or feat2.requires_grad or
                                              any(p.requires_grad for p in deformer.parameters()))
         dist_term = self._dist_term_train if train else self._dist_term
@@ -543,7 +582,7 @@ class GraphDeformLoss_Neural(nn.Module):
             a1, a2 = _host_draw_to_device(anchors[0], feat1.device), _host_draw_to_device(anchors[1], feat2.device)
         native_dist = False
         if self.w_deform > 0 or not self.partial_variant:
-            g1, g2, idx11, idx22 = geometry if geometry is not None else self.geometry(verts1, verts2, fps_starts, shape_ids)
+            g1, g2, idx11, idx22 = geometry if geometry is not None else self.geometry(verts1, verts2, fps_starts, shape_ids, (dist1, dist2))
             merged = (train and N == M and not self.dump and not self.partial_variant and self.w_rank <= 0 and self.w_cycle <= 0
                       and self.w_distortion <= 0 and all(torch.is_tensor(g1[k]) for k in g1))
             native = (merged and self.native_train and self.sinkhorn_iters <= 0 and feat1.is_cuda and feat1.dtype == torch.float32 and feat1.shape[-1] == 128 and N % 4 == 0

@@ -111,6 +111,7 @@ def save_ckpt(net, dfm, ckpt_dir, expname, tag):
 
 class SyntheticPairs:
     """`pairs` fixed random pairs per split, N source / M target points, seeded per rank; dist = Euclidean cdist."""
+    carries_dist = True   # every batch has its (B,N,N) / (B,M,M) distance matrices (--graph-metric geodesic needs them)
 
     def __init__(self, pairs, N, M, seed, dev):
         g = torch.Generator().manual_seed(seed)
@@ -127,6 +128,7 @@ class SyntheticPairs:
 
 class DatasetPairs:
     """Pairs of a dataset directory (models/dataset.py), truncated to the first `N` / `M` points of each shape."""
+    carries_dist = True
 
     def __init__(self, data, N, M, dev, random_feat, seed):
         self.data, self.N, self.M, self.dev, self.random_feat = data, N, M, dev, random_feat
@@ -234,6 +236,12 @@ def main(argv=None):
                     help="weight of the geodesic distortion term ||Pi D_target Pi^T - D_source||_F of both directions (criterion.w_distortion = W, "
                          "models.loss.distortion_term on the symmetrised distance matrices; not in the reference; the criterion leaves its "
                          "native nodes for the per-op path).  0: off")
+    ap.add_argument("--graph-metric", choices=("euclidean", "geodesic"), default="euclidean",
+                    help="what skins the deformation graphs (criterion.graph_metric): 'geodesic' ties every vertex to the 3 nodes nearest by "
+                         "the batch's distance matrices (ops.dg_build_geod), as the reference does with a geod that is not cdist; "
+                         "'euclidean': the graphs of ops.dg_build")
+    ap.add_argument("--graph-ring-metric", choices=("euclidean", "geodesic"), default="euclidean",
+                    help="with --graph-metric geodesic: take the ARAP node rings from the distance matrices as well (criterion.graph_ring_metric)")
     ap.add_argument("--graph", action="store_true", help="timing mode, one rank: capture the whole step (forward, criterion, backward, "
                     "Adam) into ONE HIP graph and replay it — ~2000 kernel launches per step become one graph launch")
     ap.add_argument("--sync-stats", action="store_true", help="DDP: BatchNorm statistics and the positional encoding's min/max "
@@ -345,6 +353,11 @@ def main(argv=None):
     if args.w_distortion < 0:
         ap.error("--w-distortion must not be negative")
     crit.w_distortion = args.w_distortion
+    if args.graph_ring_metric == "geodesic" and args.graph_metric != "geodesic":
+        ap.error("--graph-ring-metric geodesic needs --graph-metric geodesic")
+    if args.graph_metric == "geodesic" and not (getattr(train_set, "carries_dist", False) and getattr(val_set, "carries_dist", False)):
+        ap.error("--graph-metric geodesic needs pair sets that carry distance matrices")
+    crit.graph_metric, crit.graph_ring_metric = args.graph_metric, args.graph_ring_metric
     if args.graph_cache:
         import collections
         crit.graph_cache = collections.OrderedDict()   # least-recently-used shapes are dropped beyond crit.graph_cache_max
@@ -396,12 +409,12 @@ def main(argv=None):
         s2 = torch.tensor([zlib.crc32(("s:" + nm).encode()) % n2 for nm in names[1]], dtype=torch.long)
         return (s1, s2), (list(names[0]), list(names[1]))
 
-    def prefetch_geometry(v1, v2, starts=None, shape_ids=None):
+    def prefetch_geometry(v1, v2, starts=None, shape_ids=None, dists=None):
         if geo_stream is None:
             return None
         geo_stream.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(geo_stream), torch.no_grad():
-            return crit.geometry(v1, v2, starts, shape_ids)
+            return crit.geometry(v1, v2, starts, shape_ids, dists)
 
     def join_geometry(geo):
         if geo is None:
@@ -419,7 +432,7 @@ def main(argv=None):
         fit_criterion(crit, cfg, min(v1.shape[1], v2.shape[1]))
         t = time.perf_counter()
         starts, shape_ids = cached_keys(pair_ids, v1.shape[1], v2.shape[1]) if (args.graph_cache and pair_ids is not None) else (None, None)   # pair_ids: the batch's shape names
-        geo = prefetch_geometry(v1, v2, starts, shape_ids)
+        geo = prefetch_geometry(v1, v2, starts, shape_ids, (dist1, dist2))
         f1, f2 = forward_pair(v1, d1, v2, d2)
         t = mark(0, t)
         out = crit(f1, f2, dist1, dist2, v1, v2, alpha, dfm, fps_starts=starts, geometry=join_geometry(geo), shape_ids=shape_ids)
@@ -476,7 +489,7 @@ def main(argv=None):
 
             def graph_step():
                 v1, v2, d1, d2, dist1, dist2 = batch
-                geo = prefetch_geometry(v1, v2, starts)
+                geo = prefetch_geometry(v1, v2, starts, None, (dist1, dist2))
                 f1, f2 = forward_pair(v1, d1, v2, d2)
                 out = crit(f1, f2, dist1, dist2, v1, v2, alpha, dfm, fps_starts=starts, anchors=anchors, geometry=join_geometry(geo))
                 out[0].backward()
@@ -534,7 +547,7 @@ def main(argv=None):
                                            "note": "algorithmic matrix flops of the whole step per GPU over the step time; the step is "
                                                    "~900 small launches, bound by the latency of its kernel chain (network forward -> criterion -> backward), not by the matrix pipe"},
                               "points": N, "points_target": M, "criterion": type(crit).__name__, "alpha": float(alpha),
-                              "sinkhorn_iters": crit.sinkhorn_iters, "sinkhorn_tau": crit.sinkhorn_tau, "w_cycle": crit.w_cycle, "w_distortion": crit.w_distortion, "hip_graph": use_graph, "graph_cache": bool(args.graph_cache),
+                              "sinkhorn_iters": crit.sinkhorn_iters, "sinkhorn_tau": crit.sinkhorn_tau, "w_cycle": crit.w_cycle, "w_distortion": crit.w_distortion, "graph_metric": crit.graph_metric, "graph_ring_metric": crit.graph_ring_metric, "hip_graph": use_graph, "graph_cache": bool(args.graph_cache),
                               "sync_stats": (None if not (args.sync_stats and dist_on) else
                                              {"native_node": getattr(net, "sync_stats", None) is not None,
                                               "native_calls": net.__dict__.get("native_train_calls", 0),
@@ -591,7 +604,7 @@ def main(argv=None):
                 save_ckpt(net, dfm, args.ckpt_dir, cfg["expname"], "val_best")
     if rank == 0:
         print(json.dumps({"epochs": epochs, "history": history, "best_val": best_val, "criterion": type(crit).__name__,
-                          "sinkhorn_iters": crit.sinkhorn_iters, "sinkhorn_tau": crit.sinkhorn_tau, "w_cycle": crit.w_cycle, "w_distortion": crit.w_distortion,
+                          "sinkhorn_iters": crit.sinkhorn_iters, "sinkhorn_tau": crit.sinkhorn_tau, "w_cycle": crit.w_cycle, "w_distortion": crit.w_distortion, "graph_metric": crit.graph_metric, "graph_ring_metric": crit.graph_ring_metric,
                           "ckpt": list(ckpt_paths(args.ckpt_dir, cfg["expname"], "val_best"))}))
     if dist_on:
         dist.destroy_process_group()

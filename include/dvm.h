@@ -427,6 +427,41 @@ int dvm_dg_build_f32(const float *xyz, int B, int N, const int32_t *start, int32
                      int32_t *infl_idx, float *dists, float *weights, double *sigma, void *ws, size_t ws_bytes,
                      void *stream);
 
+/* Skinning (and node rings) by a caller-supplied distance matrix — what the reference's construct_graph_euclidean /
+ * construct_graph do with their `geod` argument (lib/deformation_graph_point.py:186-198, 219-224: top-k of geod[nodes_idx].T).
+ * dist [B,N,N] fp32 row-major, nodes_idx [B,Nn] with entries in [0,N) (an entry outside is read as the nearest end), any
+ * 3 <= Nn <= N.
+ * Orientation: vertex v and node position j meet at d(v,j) = dist[b, nodes_idx[b,j], v] — node ROWS, read along v; it matters
+ * for a matrix that is not symmetric.
+ * Order: candidates are sorted by the key (d, j): d compares as fp32 with NaN ranked as +inf and -0 == +0; among equal d the
+ * lower j comes first.  infl_idx [B,N,3] (node-local, as dvm_dg_build_f32's) and dists [B,N,3] (the selected matrix entries,
+ * copied unchanged: a NaN stays a NaN) are the first three entries of that order; ring [B,Nn,ring_k] (node-local; ring_k = 0:
+ * none, ring may be NULL) holds for node i the first ring_k entries of the same order for the vertex nodes_idx[b,i] — the node
+ * itself comes first only because dist[i,i] = 0, as in a KDTree's answer.
+ * Limits: 0 <= ring_k <= 16, ring_k <= Nn, B <= 65535; outside them DVM_EINVAL before anything is launched.
+ * One lane per vertex, 64 vertices per workgroup; the node range is split over up to 8 waves whose lists are merged in LDS by
+ * the same key (a total order: the split cannot reach the result).  Asynchronous on `stream`, no workspace, no atomics,
+ * capturable.  dvm_dg_skin_geod_slices_f32 is the same call with the waves per workgroup (1..8) chosen by the caller
+ * (measurements, tests); dvm_dg_skin_geod_plan reports, without a device, the vertex tile, the waves per workgroup the plain
+ * call takes and the length of the per-lane list (3, 9 or 16). */
+int dvm_dg_skin_geod_f32(const float *dist, const int32_t *nodes_idx, int B, int N, int Nn, int ring_k /* 0 = none */,
+                         int32_t *infl_idx, float *dists, int32_t *ring, void *stream);
+int dvm_dg_skin_geod_slices_f32(const float *dist, const int32_t *nodes_idx, int B, int N, int Nn, int ring_k, int slices,
+                                int32_t *infl_idx, float *dists, int32_t *ring, void *stream);
+int dvm_dg_skin_geod_plan(int B, int N, int Nn, int ring_k, int *tile, int *slices, int *list);
+/* Skinning weights of such distances: dists [B,N,3], sigma [B] (double, device) -> weights [B,N,3] =
+ * exp(-d^2 / float(2 sigma^2)) row-normalised, the expressions of dvm_dg_build_f32 in its order.  Non-finite rule: an infinite
+ * (or NaN) d weighs 0; a row whose sum is 0 or not finite becomes (1,0,0); no NaN is written. */
+int dvm_dg_skin_weights_f32(const float *dists, const double *sigma, int B, int N, float *weights, void *stream);
+/* dvm_dg_build_f32 with the skinning taken from dist [B,N,N] (the rules of dvm_dg_skin_geod_f32, Nn = N/2): nodes_idx (the
+ * Euclidean FPS of xyz), sigma (20 x the mean Euclidean nearest-neighbour spacing, as the reference keeps it under any geod)
+ * and, for ring_metric 0, ring are dvm_dg_build_f32's bit for bit; infl_idx, dists, weights — and for ring_metric 1 the ring
+ * [B,Nn,9] — come from dist.  Limits: 6 <= N <= 12288 (dvm_fps_f32's), N >= 18 for ring_metric 1, B <= 65535. */
+size_t dvm_dg_build_geod_workspace_bytes(int B, int N);
+int dvm_dg_build_geod_f32(const float *xyz, const float *dist, int B, int N, const int32_t *start,
+                          int ring_metric /* 0 Euclidean, 1 geodesic */, int32_t *nodes_idx, int32_t *ring, int32_t *infl_idx,
+                          float *dists, float *weights, double *sigma, void *ws, size_t ws_bytes, void *stream);
+
 /* rotation_6d_to_matrix — models/loss.py:39-45.  d6 [rows,6] -> R [rows,9] (rows b1,b2,b1xb2). */
 int dvm_rot6d_f32(const float *d6, int rows, float *R, void *stream);
 /* Backward of dvm_rot6d_f32: g_R [rows,9] -> g_d6 [rows,6] (Gram-Schmidt differentiated). */
