@@ -813,7 +813,8 @@ DVM_EXPORT int dvm_argmin_exact_f32(const float *f1, const float *f2, int B, int
     DVM_REQUIRE(B >= 1 && N >= 1 && M >= 1, "dvm_argmin_exact_f32: empty input (B=%d N=%d M=%d)", B, N, M);
     DVM_REQUIRE(d >= 4 && d % 4 == 0 && d <= 512, "dvm_argmin_exact_f32: d=%d unsupported (need d%%4==0, 4<=d<=512)", d);
     if (ws != nullptr && d == 128) {
-        int rc = launch_argmin_f16(f1, f2, B, N, M, T, dmin, nullptr, nullptr, ws, ws_bytes, (hipStream_t)stream);
+        const K1HardOut out{T, dmin};
+        int rc = launch_argmin_f16(K1Sides{{f1, f2}, {nullptr, nullptr}, B, {N, M}, false}, &out, ws, ws_bytes, (hipStream_t)stream);
         if (rc != DVM_OK) return rc;
         DVM_CHECK_LAUNCH("argmin_exact(sweep)");
         return DVM_OK;
@@ -827,7 +828,8 @@ DVM_EXPORT int dvm_argmin_pair_f32(const float *f1, const float *f2, int B, int 
     DVM_REQUIRE(B >= 1 && N >= 1 && M >= 1, "dvm_argmin_pair_f32: empty input (B=%d N=%d M=%d)", B, N, M);
     DVM_REQUIRE(d >= 4 && d % 4 == 0 && d <= 512, "dvm_argmin_pair_f32: d=%d unsupported (need d%%4==0, 4<=d<=512)", d);
     if (ws != nullptr && d == 128) {
-        int rc = launch_argmin_f16(f1, f2, B, N, M, T12, dmin12, T21, dmin21, ws, ws_bytes, (hipStream_t)stream);
+        const K1HardOut out[2] = {{T12, dmin12}, {T21, dmin21}};
+        int rc = launch_argmin_f16(K1Sides{{f1, f2}, {nullptr, nullptr}, B, {N, M}, true}, out, ws, ws_bytes, (hipStream_t)stream);
         if (rc != DVM_OK) return rc;
         DVM_CHECK_LAUNCH("argmin_pair(sweep)");
         return DVM_OK;

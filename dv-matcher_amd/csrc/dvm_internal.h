@@ -1,8 +1,8 @@
 // dvm_internal.h — every dvm:: function that one translation unit of libdvm_hip.so defines and another one calls, declared
 // ONCE, grouped by the file that defines it (with the workspace struct or constants its callers need); default arguments appear
 // here and nowhere else.  Included at the end of
-// dvm_common.h: no .hip file declares a function it does not define.  (The K1 sweep's launchers, whose signatures need its
-// argument structs, are in dvm_softcorr_f16.h; the Frobenius-norm terms' frob_finish in dvm_frob.h; set_error / prof_* / options and their kin, defined in dvm_api.cpp, in dvm_common.h.)
+// dvm_common.h: no .hip file declares a function it does not define.  (What the K1 sweep's own files call of each other, whose
+// signatures need its argument structs, is in dvm_softcorr_f16.h; the Frobenius-norm terms' frob_finish in dvm_frob.h; set_error / prof_* / options and their kin, defined in dvm_api.cpp, in dvm_common.h.)
 #pragma once
 
 namespace dvm {
@@ -166,22 +166,47 @@ void launch_sa_apply_f16(const _Float16 *pp, const _Float16 *vp, const float *st
 
 // ---- dvm_softcorr.hip
 void launch_rownorm2(const float *x, int rows, int K, float *out, hipStream_t s);
-size_t softcorr_pair_ws_bytes(int B, int N, int M);
-int launch_softcorr_pair(const float *f1, const float *f2, float *n1, float *n2, int B, int N, int M, float neg_alpha, float *val12, int32_t *idx12,
-                         float *val21, int32_t *idx21, void *ws, size_t ws_bytes, hipStream_t s);
 // K == 128 only: also maxes the bit pattern of max |x| into the 256 slots of `absmax_slots` (zero them first);
 // launch_absmax_finalize folds nt x 256 slots into nt values
 void launch_rownorm2_absmax(const float *x, int rows, float *out, int *absmax_slots, hipStream_t s);
 void launch_absmax_finalize(const int *slots, int nt, int *out, hipStream_t s);
 
-// ---- dvm_softcorr_f16.hip
-size_t argmin_f16_ws_bytes(int B, int N, int M, bool both);
-int launch_argmin_f16(const float *f1, const float *f2, int B, int N, int M, int32_t *T12, float *dmin12, int32_t *T21, float *dmin21, void *ws,
-                      size_t ws_bytes, hipStream_t s);
+// ---- dvm_softcorr_k1.hip: the fp16-split sweep (K1), d = 128
+// The two sides of a call: features f[0] [B][rows[0]][128], f[1] [B][rows[1]][128] and their squared row norms n[sd] [B][rows[sd]]
+// — buffers the call's preparation WRITES (launch_argmin_f16 takes them from its own workspace and ignores these).  Direction d =
+// rows of side d against side d ^ 1: direction 0 always, direction 1 with `both`.
+struct K1Sides {
+    const float *f[2];
+    float *n[2];
+    int B, rows[2];
+    bool both;
+    long total(int sd) const { return (long)B * rows[sd]; }
+    int dirs() const { return both ? 2 : 1; }
+};
+// one direction's outputs: top-`topk` values / columns and the optional row statistics; the hard map and its optional distances
+struct K1SoftOut {
+    float *val;
+    int32_t *idx;
+    float *smax, *sum;
+};
+struct K1HardOut {
+    int32_t *T;
+    float *dmin;
+};
+// how norms, scale and planes are made: norms + absmax, then the split (two passes over the features), or the pair path's one pass
+enum K1Prep { K1_PREP_TWO_PASS, K1_PREP_FUSED };
+// out[d] = direction d's outputs (out[1] is read only with c.both); topk <= 10
+int launch_softcorr_f16(const K1Sides &c, const K1SoftOut *out, float neg_alpha, int topk, K1Prep prep, void *ws, size_t ws_bytes, hipStream_t s);
 size_t softcorr_f16_ws_bytes(int B, int N, int M, bool both);
-int launch_softcorr_f16(const float *f1, const float *f2, const float *n1, const float *n2, int B, int N, int M, float neg_alpha, int topk, float
-                        *val12, int32_t *idx12, float *smax12, float *sum12, float *val21, int32_t *idx21, float *smax21, float *sum21, const int
-                        *amax, void *ws, size_t ws_bytes, hipStream_t s, int *fuse_slots = nullptr);
+// the norms of both sides and, with k1, the K1 workspace behind them: ONE layout for dvm_softcorr_fwd_f32 and the hard map
+struct K1NormsWs {
+    float *n1, *n2;
+    char *k1ws;
+    size_t k1_bytes;
+};
+size_t carve_k1_norms(Arena &ar, int B, int N, int M, bool both, bool k1, K1NormsWs &w);
+int launch_argmin_f16(const K1Sides &c, const K1HardOut *out, void *ws, size_t ws_bytes, hipStream_t s);
+size_t argmin_f16_ws_bytes(int B, int N, int M, bool both);
 
 // ---- the fp32 soft-correspondence family's entry points (dvm_softcorr.hip, dvm_softcorr_bwd.hip, dvm_sinkhorn.hip,
 // dvm_sinkhorn_bwd.hip): the checks of the arguments they share, in the order every entry tests them; `who` names the entry.

@@ -179,7 +179,7 @@ static size_t carve_pair2(Arena &ar, int B, int N, int M, Pair2Ws &w) {
     w.T = ar.take<float>(rows * 3);
     w.wp = ar.take<float>(mlp_pack_floats());
     for (int sd = 0; sd < 2; ++sd) w.nbrxyz[sd] = ar.take<float>((size_t)B * P[sd] * 30);
-    w.k1ws_bytes = softcorr_pair_ws_bytes(B, N, M);
+    w.k1ws_bytes = softcorr_f16_ws_bytes(B, N, M, true);
     w.k1ws = ar.take<char>(w.k1ws_bytes);
     const int cdn[8] = {N, M, N, M, M, N, M, N};
     for (int q = 0; q < 8; ++q) w.cd[q] = ar.take<float>((size_t)B * cdn[q]);
@@ -359,8 +359,9 @@ static int pair_fwd_impl(const float *feat1, const float *feat2, const float *ve
         return code;
     };
     // ---- soft correspondence, both directions in one launch
-    rc = launch_softcorr_pair(feat1, feat2, w.nrm[0], w.nrm[1], B, N, M, neg_alpha, w.pval[0], w.pidx[0], w.pval[1], w.pidx[1], w.k1ws,
-                              w.k1ws_bytes, s);
+    // (row norms, absmax and the fp16 planes come out of ONE pass over the features: the fused preparation)
+    const K1SoftOut pi[2] = {{w.pval[0], w.pidx[0], nullptr, nullptr}, {w.pval[1], w.pidx[1], nullptr, nullptr}};
+    rc = launch_softcorr_f16(K1Sides{{feat1, feat2}, {w.nrm[0], w.nrm[1]}, B, {N, M}, true}, pi, neg_alpha, 10, K1_PREP_FUSED, w.k1ws, w.k1ws_bytes, s);
     if (rc != DVM_OK) return fail(rc);
     if (!launch_apply3_pair(w.pval[0], w.pidx[0], verts2, verts12, T12, w.pval[1], w.pidx[1], verts1, verts21, T21, B, N, M, s)) {
         hipLaunchKernelGGL(take_col0_kernel, dim3((B * N + 255) / 256), dim3(256), 0, s, w.pidx[0], B * N, 10, T12);

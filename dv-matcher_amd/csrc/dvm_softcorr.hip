@@ -72,7 +72,7 @@ __global__ __launch_bounds__(256) void rownorm2_k128_kernel(const float *__restr
         const long row0 = half * RN_ROWS + q;
         if (l32 == 7 && row0 < rows) out[row0] = u;
     }
-    if (absmax) {  // optional: bit pattern of max |x| of the tensor (the fp16 split's scale, dvm_softcorr_f16.hip)
+    if (absmax) {  // optional: bit pattern of max |x| of the tensor (the fp16 split's scale, dvm_softcorr_prep.hip)
         int m = __float_as_int(am);   // non-negative floats order like their bit patterns
         m = max(m, __builtin_amdgcn_update_dpp(0, m, 0x111, 0xf, 0xf, false));  // row_shr:1
         m = max(m, __builtin_amdgcn_update_dpp(0, m, 0x112, 0xf, 0xf, false));  // row_shr:2
@@ -423,47 +423,9 @@ void launch_absmax_finalize(const int *slots, int nt, int *out, hipStream_t s) {
     hipLaunchKernelGGL(absmax_finalize_kernel, dim3(nt), dim3(64), 0, s, slots, out);
 }
 
-// norms of both sides + soft correspondence in both directions for the fused pair path (d = 128, top-10)
-// the 2 x 256 absmax slots + the two absmax values, with the K1 workspace (dvm_softcorr_f16.hip) RIGHT behind them: there
-// launch_softcorr_f16 clears the slots and its own zero-initialised head with one fill
-struct K1CallWs {
-    int *slots;
-    char *k1ws;
-    size_t k1_bytes;
-};
-static size_t carve_k1_call(Arena &ar, int B, int N, int M, bool both, K1CallWs &w) {
-    w.slots = ar.take<int>(2 * 256 + 2);
-    w.k1_bytes = softcorr_f16_ws_bytes(B, N, M, both);
-    w.k1ws = ar.take<char>(w.k1_bytes);
-    return ar.off;
-}
-size_t softcorr_pair_ws_bytes(int B, int N, int M) { return null_carve<K1CallWs>(carve_k1_call, B, N, M, true); }
-int launch_softcorr_pair(const float *f1, const float *f2, float *n1, float *n2, int B, int N, int M, float neg_alpha, float *val12,
-                         int32_t *idx12, float *val21, int32_t *idx21, void *ws, size_t ws_bytes, hipStream_t s) {
-    K1CallWs w;
-    if (!carve_ws(ws, ws_bytes, "softcorr (pair)", w, carve_k1_call, B, N, M, true)) return DVM_ENOSPACE;
-    // (row norms, absmax and the fp16 planes come out of ONE pass over the features inside launch_softcorr_f16: `slots`)
-    return launch_softcorr_f16(f1, f2, n1, n2, B, N, M, neg_alpha, 10, val12, idx12, nullptr, nullptr, val21, idx21, nullptr, nullptr,
-                                w.slots + 512, w.k1ws, w.k1_bytes, s, w.slots);
-}
-
-// dvm_softcorr_fwd_f32's workspace: the norms of both sides and, for the fp16-split sweep (k1), what carve_k1_call lays out
-struct SoftcorrWs {
-    float *n1, *n2;
-    K1CallWs k;
-};
-static size_t carve_softcorr(Arena &ar, int B, int N, int M, bool k1, SoftcorrWs &w) {
-    w.n1 = ar.take<float>((size_t)B * N);
-    w.n2 = ar.take<float>((size_t)B * M);
-    w.k = K1CallWs{nullptr, nullptr, 0};
-    if (k1) carve_k1_call(ar, B, N, M, false, w.k);
-    return ar.off;
-}
-
 void launch_rownorm2(const float *x, int rows, int K, float *out, hipStream_t s) {
     if (K == 128)
-        hipLaunchKernelGGL(rownorm2_k128_kernel, dim3((unsigned)((((long)rows + RN_ROWS - 1) / RN_ROWS * 32 + 255) / 256)), dim3(256), 0, s, x, rows, out,
-                           (int *)nullptr);
+        launch_rownorm2_absmax(x, rows, out, nullptr, s);
     else
         hipLaunchKernelGGL(rownorm2_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, x, rows, K, out);
 }
@@ -481,7 +443,7 @@ DVM_EXPORT int dvm_rownorm2_f32(const float *x, int rows, int K, float *out, voi
 }
 
 DVM_EXPORT size_t dvm_softcorr_workspace_bytes(int B, int N, int M, int d) {
-    return null_carve<SoftcorrWs>(carve_softcorr, B, N, M, d == D);   // (d == 128: sized for the fp16-split sweep, whichever variant is asked for)
+    return null_carve<K1NormsWs>(carve_k1_norms, B, N, M, false, d == D);   // (d == 128: sized for the fp16-split sweep, whichever variant is asked for)
 }
 
 DVM_EXPORT int dvm_softcorr_fwd_f32(const float *f1, const float *f2, int B, int N, int M, int d, float neg_alpha,
@@ -492,18 +454,13 @@ DVM_EXPORT int dvm_softcorr_fwd_f32(const float *f1, const float *f2, int B, int
     DVM_REQUIRE(variant < 2 || d == D, "dvm_softcorr_fwd_f32: the matrix-core variants need d == 128");
     DVM_REQUIRE(variant != 3 || topk <= 10, "dvm_softcorr_fwd_f32: the bf16 variant keeps 12 candidates (topk <= 10)");
     if (variant == 0 && d == D && topk <= 10) variant = 3;   // auto: the fp16-split sweep (variants 1 / 2: the `variant` argument)
-    SoftcorrWs w;
-    if (!carve_ws(ws, ws_bytes, "dvm_softcorr_fwd_f32", w, carve_softcorr, B, N, M, variant == 3)) return DVM_ENOSPACE;
+    K1NormsWs w;   // the norms of both sides and, for the fp16-split sweep, its workspace
+    if (!carve_ws(ws, ws_bytes, "dvm_softcorr_fwd_f32", w, carve_k1_norms, B, N, M, false, variant == 3)) return DVM_ENOSPACE;
     float *const n1 = w.n1, *const n2 = w.n2;
     hipStream_t s = (hipStream_t)stream;
     if (variant == 3) {
-        int *const slots = w.k.slots, *const amax = slots + 512;
-        (void)hipMemsetAsync(slots, 0, 512 * sizeof(int), s);
-        launch_rownorm2_absmax(f1, B * N, n1, slots, s);
-        launch_rownorm2_absmax(f2, B * M, n2, slots + 256, s);
-        launch_absmax_finalize(slots, 2, amax, s);
-        int rc = launch_softcorr_f16(f1, f2, n1, n2, B, N, M, neg_alpha, topk, pi_val, pi_idx, row_smax, row_sum, nullptr, nullptr,
-                                      nullptr, nullptr, amax, w.k.k1ws, w.k.k1_bytes, s);
+        const K1SoftOut out{pi_val, pi_idx, row_smax, row_sum};
+        int rc = launch_softcorr_f16(K1Sides{{f1, f2}, {n1, n2}, B, {N, M}, false}, &out, neg_alpha, topk, K1_PREP_TWO_PASS, w.k1ws, w.k1_bytes, s);
         if (rc != DVM_OK) return rc;
         DVM_CHECK_LAUNCH("softcorr (fp16)");
         return DVM_OK;
@@ -543,13 +500,13 @@ DVM_EXPORT int dvm_softcorr_fwd_f32(const float *f1, const float *f2, int B, int
 
 // dvm_softcorr_fwd_f32's workspace in front (its norms are read again here), then the row statistics and the top-1 outputs
 struct SoftcorrDenseWs {
-    SoftcorrWs sc;
+    K1NormsWs sc;
     size_t sc_bytes;
     float *smax, *ssum, *v1;
     int32_t *i1;
 };
 static size_t carve_softcorr_dense(Arena &ar, int B, int N, int M, int d, SoftcorrDenseWs &w) {
-    w.sc_bytes = carve_softcorr(ar, B, N, M, d == D, w.sc);   // (first in the arena: its end offset is its size)
+    w.sc_bytes = carve_k1_norms(ar, B, N, M, false, d == D, w.sc);   // (first in the arena: its end offset is its size)
     w.smax = ar.take<float>((size_t)B * N), w.ssum = ar.take<float>((size_t)B * N);
     w.v1 = ar.take<float>((size_t)B * N);
     w.i1 = ar.take<int32_t>((size_t)B * N);
@@ -568,7 +525,7 @@ DVM_EXPORT int dvm_softcorr_dense_f32(const float *f1, const float *f2, int B, i
     SoftcorrDenseWs w;
     if (!carve_ws(ws, ws_bytes, "dvm_softcorr_dense_f32", w, carve_softcorr_dense, B, N, M, d)) return DVM_ENOSPACE;
     float *const smax = w.smax, *const ssum = w.ssum;
-    // (the soft-correspondence call carves the head of `ws` as carve_softcorr did here: its norms are w.sc.n1 / n2)
+    // (the soft-correspondence call carves the head of `ws` as carve_k1_norms did here: its norms are w.sc.n1 / n2)
     int rc = dvm_softcorr_fwd_f32(f1, f2, B, N, M, d, neg_alpha, 1, w.v1, w.i1, smax, ssum, 0, ws, w.sc_bytes, stream);
     if (rc != DVM_OK) return rc;
     const float *n1 = w.sc.n1, *n2 = w.sc.n2;

@@ -36,7 +36,6 @@
 //    larger of the two 8th) are dropped — each half-lane is complete only up to its own 12th, taken again after the re-done
 //    sub-tiles have pushed entries out —, so the largest entry written IS the completeness bound pass B certifies against.
 #include <stdlib.h>
-#include <type_traits>
 
 #include "dvm_softcorr_f16.h"
 
@@ -131,15 +130,6 @@ __device__ __forceinline__ Top3 top3_of_16(const unsigned (&v)[16]) {
                     merge3(merge3(sort3(v[6], v[7], v[8]), sort3(v[9], v[10], v[11])), sort3(v[12], v[13], v[14])));
     const unsigned x = v[15];
     return Top3{min(t.s0, x), umed3(t.s0, t.s1, x), umed3(t.s1, t.s2, x)};
-}
-
-// compile-time loop: f(std::integral_constant<int, I>) for I in [B, E)
-template <int B, int E, class F>
-__device__ __forceinline__ void static_for(F &&f) {
-    if constexpr (B < E) {
-        f(std::integral_constant<int, B>{});
-        static_for<B + 1, E>(f);
-    }
 }
 
 // sorted list of K unsigned entries; insertion = one three-input median per slot
@@ -601,6 +591,7 @@ bool coarse_supports(int N, int M) { return M <= HC_MAX_M && N <= HC_MAX_M; }
 // pad_norms x 2, norm_frags x 2 — at a strong-scaling rank's batch the prologue of the sweep is a chain of ~20 launches of a few
 // microseconds each): per side the maximum per batch element (atomic: positive floats order like their bit patterns), the norms padded
 // to whole key tiles with +inf, the coarse screen's norm fragments; block (0, 0, 0) also zeroes the flagged-row counters.
+// (here, not with the other preparation kernels: outside this file's -fno-honor-nans its fmaxf reduction compiles to other instructions)
 __global__ __launch_bounds__(256) void norm_prep_kernel(const NormPrep a) {
     const int sd = blockIdx.z, b = blockIdx.y;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;

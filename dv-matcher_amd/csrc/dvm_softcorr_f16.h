@@ -1,6 +1,10 @@
-// dvm_softcorr_f16.h — what the two translation units of the fp16-split soft-correspondence sweep share
-// (dvm_softcorr_f16.hip: splitting, first form of pass A, pass B, launchers; dvm_softcorr_coarse.hip: the one-plane screen).
+// dvm_softcorr_f16.h — what the translation units of the fp16-split soft-correspondence sweep (K1) share: constants, the pass-A
+// argument structs, the workspace layout, and one launcher declaration per step.  dvm_softcorr_prep.hip: norms, scale, planes;
+// dvm_softcorr_f16.hip: first form of pass A; dvm_softcorr_coarse.hip: the one-plane screen; dvm_softcorr_passb.hip: probe, pass B,
+// gate, exact rows; dvm_softcorr_hardmap.hip: the hard map's kernels; dvm_softcorr_k1.hip: workspace, plan and the two launchers.
 #pragma once
+#include <type_traits>
+
 #include "dvm_mfma_tile.h"
 
 namespace dvm {
@@ -20,7 +24,14 @@ constexpr int HB_KC = 12;               // candidates kept per row (top-10 + 2 o
 constexpr size_t HB_LDS_BYTES = (size_t)2 * HB_KT * HB_ROWB + 2 * HB_KT * sizeof(float) + (size_t)HB_WAVES * HB_STAGE * sizeof(float);
 constexpr float HB_ERR = 2.5e-5f;  // |d2_passA - d2_chain| <= HB_ERR (|q|^2 + |k|^2): gamma_128 of both fp32 accumulations
                                    // (2 x 7.7e-6) + the dropped split terms (1.4e-6), with room to spare
-
+// compile-time loop: f(std::integral_constant<int, I>) for I in [B, E) (DPP controls must be constants)
+template <int B, int E, class F>
+__device__ __forceinline__ void static_for(F &&f) {
+    if constexpr (B < E) {
+        f(std::integral_constant<int, B>{});
+        static_for<B + 1, E>(f);
+    }
+}
 
 // power of two s with max|x| * s in [2^11, 2^12): well inside fp16's range, the m-plane of every element within 2^-8 of
 // the largest stays a normal fp16 number (smaller ones keep an absolute error of 2^-25 in scaled units: far below the
@@ -109,8 +120,6 @@ constexpr float HC_ERR = 1.12e-3f;
 bool coarse_supports(int N, int M);
 void launch_coarse(const HBArgs &a, const char *knf0, const char *knf1, const int *amaxc, int blocks, hipStream_t s);
 
-
-// key-side norm fragments of the coarse screen [B][Mpad][32 B] (dvm_softcorr_coarse.hip)
 // one launch for the norms of both sides (dvm_softcorr_coarse.hip::norm_prep_kernel): side sd has rows[sd] norms per batch element,
 // padded to pad[sd]; nmax [B] (zeroed by the caller) always; npad [B][pad] / nfrag [B][pad][32 B] where not NULL; zero[]: counters to clear
 struct NormPrep {
@@ -122,6 +131,45 @@ struct NormPrep {
     int32_t *zero[2];
 };
 void launch_norm_prep(const NormPrep &a, int B, hipStream_t s);
+
+// ---------------------------------------------------------------- one call's workspace, plan and steps
+// The K1 workspace for (B, N, M): planes of both sides, candidates of both directions (one without `both`), flags.  ONE layout for
+// launch_softcorr_f16 and launch_argmin_f16 (which uses neither spec, route2 nor pfrac) and for the size queries (carve_k1).
+struct K1Ws {
+    // the zero-initialised head, back to back, `zero_bytes` in all: every call clears it with one fill (launch_prep)
+    int *slots;       // 2 x 256 absmax slots of the norm kernels, then the absmax of either side
+    float *nmax[2];   // [B] maxima of the norms
+    int *amax;        // [2] the common absmax (ONE scale for both sides), twice
+    int *spec;        // fused preparation: [0] absmax of the sampled rows (provisional scale), [1] planes must be re-made
+    size_t zero_bytes;
+    char *p[2];       // fp16 planes [B][rows][HB_ROWB]
+    float *npad[2];   // norms padded to whole key tiles
+    char *nfrag[2];   // norm fragments of the coarse screen
+    int *route, *route2;   // [2B] routes of the first pass and of the gate's second pass
+    float *pfrac;          // [2B] the probe's fractions
+    int32_t *cidx[2], *flag[2];   // per direction: candidate columns; flag [0] = counter, [1..] = rows
+    float *cd2[2], *lsum[2];
+    int pad[2];       // rows of either side padded to whole key tiles
+};
+// What a soft-correspondence launch does, decided once (k1_plan): the probe routes every direction (`fixed` < 0), or all of them
+// take `fixed` (K1_ROUTE_*); coarse: the coarse screen runs, and behind it the gate and its second pass.
+struct K1Plan {
+    bool routed, coarse;
+    int fixed;
+    const int *route(const K1Ws &w) const { return routed ? w.route : nullptr; }   // what the first pass's kernels read
+};
+// dvm_softcorr_prep.hip: the zero fill, then norms into c.n, the common scale at w.amax and the planes
+void launch_prep(const K1Sides &c, const K1Ws &w, K1Prep form, hipStream_t s);
+// dvm_softcorr_f16.hip: the first form over `blocks` workgroups; form: K1_ROUTE_FULL / K1_ROUTE_LEAN, or
+constexpr int K1_SWEEP_ROUTED = -1, K1_SWEEP_GATED = -2;   // per a.route; the lean form where the gate's routes (a.route) say so
+void launch_sweep_f16(const HBArgs &a, int blocks, int form, hipStream_t s);
+// dvm_softcorr_passb.hip.  launch_refine, first pass: pass B, and behind the coarse screen the gate; second: the gate's pass (lean lists, w.route2)
+void launch_probe(const K1Sides &c, const K1Ws &w, float neg_alpha, bool have_coarse, hipStream_t s);
+void launch_refine(const K1Sides &c, const K1SoftOut *out, const K1Ws &w, const K1Plan &p, float neg_alpha, int topk, bool second, hipStream_t s);
+void launch_exact_rows(const K1Sides &c, const K1SoftOut *out, const K1Ws &w, float neg_alpha, int topk, hipStream_t s);
+// dvm_softcorr_hardmap.hip.  pass 0: the coarse screen's lists, then the gate; 1: the first form's (gated when the screen ran),
+// then the full scan of the rows still flagged
+void launch_argmin_refine(const K1Sides &c, const K1HardOut *out, const K1Ws &w, int pass, bool have_coarse, hipStream_t s);
 
 }  // namespace k1
 }  // namespace dvm

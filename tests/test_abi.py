@@ -122,6 +122,29 @@ def test_loads_and_reports_without_gpu():
     assert lib.dvm_pair_direction_workspace_bytes(1, 256, 256) > 0
 
 
+# (B, N, M) at d = 128 -> bytes: soft correspondence, pair, hard map one direction / both
+K1_WORKSPACE_BYTES = {
+    (1, 1, 1): (11264, 3116800, 8960 + 2304, 9984 + 2304),
+    (2, 257, 64): (435968, 4868352, 433664 + 2304, 451840 + 2304),
+    (3, 1021, 777): (3417088, 17952512, 3414784 + 2304, 3741440 + 2304),
+    (2, 2048, 2048): (5099776, 25541376, 5097472 + 2304, 5671168 + 2304),
+    (1, 8193, 300): (5843456, 26486272, 5841152 + 2304, 5883392 + 2304),
+}
+
+
+def test_k1_workspace_sizes_are_pinned():
+    """The K1 workspace is one layout for the soft correspondence, the pair path and the hard map: sizes as recorded (the hard
+    map's: its earlier size plus the 2304-byte block of absmax slots it now shares), and the hard map's one-direction workspace
+    IS the soft correspondence's — the norms of both sides in front of the same K1 layout."""
+    from dvm import _lib
+    lib = _lib.load()
+    for (B, N, M), (soft, pair, hard1, hard2) in K1_WORKSPACE_BYTES.items():
+        got = (lib.dvm_softcorr_workspace_bytes(B, N, M, 128), lib.dvm_pair_workspace_bytes(B, N, M),
+               lib.dvm_argmin_workspace_bytes(B, N, M, 128, 0), lib.dvm_argmin_workspace_bytes(B, N, M, 128, 1))
+        assert got == (soft, pair, hard1, hard2), (B, N, M, got)
+        assert got[2] == got[0], (B, N, M, got)
+
+
 def test_no_cpu_fallback():
     import torch
     from dvm import ops

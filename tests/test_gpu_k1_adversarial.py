@@ -513,6 +513,37 @@ def test_planted_hard_map(ops, family, shape):
         np.testing.assert_array_equal(T21[b][cols], oT21)
 
 
+@pytest.mark.parametrize("where", ["f1_last", "f2_last", "f1_first", "f2_first"])
+@pytest.mark.parametrize("shape", [(300, 170), (150, 5), (65, 33)], ids=shape_id)
+def test_hard_map_absmax_at_the_edge_rows(ops, shape, where):
+    """The hard map's scale comes from the absmax slots of the row-norm kernel (8 rows per half-wave, 64 per workgroup).  One
+    element of 300.0 in the last channel of the last row of the last batch entry (or of row 0 of entry 0), in either tensor, among
+    unit normal features: with that maximum missed the scale would take it past fp16's range (300 x 2^9).  Every row of both
+    maps, and the distances, bit for bit against the oracle and against screen=False."""
+    N, M = shape
+    B = 2
+    rng = np.random.default_rng(zlib.crc32(("edge %d %d %s" % (N, M, where)).encode()))
+    f1 = rng.standard_normal((B, N, D)).astype(np.float32)
+    f2 = rng.standard_normal((B, M, D)).astype(np.float32)
+    t = f1 if where.startswith("f1") else f2
+    if where.endswith("last"):
+        t[B - 1, -1, D - 1] = 300.0
+    else:
+        t[0, 0, D - 1] = 300.0
+    T, dm = ops.argmin_exact(dev(f1), dev(f2), want_dist=True)
+    Tf, dmf = ops.argmin_exact(dev(f1), dev(f2), want_dist=True, screen=False)
+    T12, T21 = ops.argmin_pair(dev(f1), dev(f2))
+    T, dm, Tf, dmf, T12, T21 = (host(x) for x in (T, dm, Tf, dmf, T12, T21))
+    for b in range(B):
+        oT, odm = O.argmin_exact(f1[b], f2[b])
+        np.testing.assert_array_equal(T[b], oT)
+        np.testing.assert_array_equal(dm[b], odm)
+        np.testing.assert_array_equal(Tf[b], oT)
+        np.testing.assert_array_equal(dmf[b], odm)
+        np.testing.assert_array_equal(T12[b], oT)
+        np.testing.assert_array_equal(T21[b], O.argmin_exact(f2[b], f1[b])[0])
+
+
 def test_coarse_limit_8193_takes_another_form(ops):
     """M or N = 8193 is beyond the coarse screen's 8-bit sub-tile field: even with route 3 forced the launch must be served by
     another form, say so in dvm_k1_last_routes, and still give the oracle's results."""

@@ -1,4 +1,4 @@
-"""-m gpu: pass A of the soft-correspondence kernel is chosen per launch by a probe (csrc/dvm_softcorr_f16.hip::k1_probe_kernel:
+"""-m gpu: pass A of the soft-correspondence kernel is chosen per launch by a probe (csrc/dvm_softcorr_passb.hip::k1_probe_kernel:
 coarse one-plane screen / lean first form / full first form); the results must not depend on the choice.  The policy is read once
 per process, so each forced route runs the K1 slice of the parity suite in a child process:
   DVM_K1_ROUTE=3   the coarse screen for every launch at alpha >= 32 (csrc/dvm_softcorr_coarse.hip), whatever the probe says — on

@@ -99,7 +99,7 @@ def test_softcorr_writes_every_output_slot(ops):
 
 @pytest.mark.parametrize("alpha", [33.0, 100.0, 150.0])
 def test_softcorr_routed_sweeps_vs_oracle(ops, alpha):
-    """Pass A is chosen per launch by the probe (dvm_softcorr_f16.hip::k1_probe_kernel): on the "trained-like" feature set
+    """Pass A is chosen per launch by the probe (dvm_softcorr_passb.hip::k1_probe_kernel): on the "trained-like" feature set
     (0.3 relu(N(0,1)): tight distance spread) the alphas below take the full and the lean first form; random features at alpha
     100 take the coarse screen (test_pair_forward_full_size_vs_oracle, the bench).  Whatever the route, the result is the
     oracle's: columns exact, values to 5e-5.
@@ -140,7 +140,7 @@ def test_softcorr_probe_routes():
 @pytest.mark.parametrize("mode", ["sq", "spike", "ragged", "zero"])
 def test_pair_forward_fused_preparation_equals_two_pass(ops, golden, mode):
     """The pair path makes the row norms, the absmax and the fp16 planes of the features in ONE pass (rownorm_split_kernel,
-    dvm_softcorr_f16.hip) with a provisional scale from a 1/64 sample of the rows, and re-makes the planes only when the true
+    dvm_softcorr_prep.hip) with a provisional scale from a 1/64 sample of the rows, and re-makes the planes only when the true
     absmax has another exponent.  The one-direction entry prepares in two passes (norms + absmax, then the planes): every output of
     the fused call must be that path's, bit for bit — on random features (the sample is right), with one large value in a row the
     sample does not see (the planes are re-made), at a shape whose row counts are no multiples of anything, and for all-zero
