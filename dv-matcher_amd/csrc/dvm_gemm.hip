@@ -467,8 +467,15 @@ __global__ __launch_bounds__(256, 2) void linear_mfma_kernel(const LinArgs a) {
         }
 }
 
+// what the most recent launch_linear_impl of this host thread launched (host memory only), read back by dvm_linear_last_launch
+struct LinearLastLaunch {
+    int info[8];   // channel_major, table index launched, LDS-DMA staging, nkb, kvec, yvec, tiles_i, tiles_j
+    bool set;
+};
+static thread_local LinearLastLaunch g_linear_last = {{0, 0, 0, 0, 0, 0, 0, 0}, false};
+
 template <bool CM, int WM, int WN, int TM, int TN, bool DMA = false>
-static void launch_cfg(LinArgs &a, int B, hipStream_t s) {
+static void launch_cfg(LinArgs &a, int B, hipStream_t s, int cfg) {
     constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
     a.tiles_i = (a.I + BM - 1) / BM;
     a.tiles_j = (a.J + BN - 1) / BN;
@@ -478,6 +485,7 @@ static void launch_cfg(LinArgs &a, int B, hipStream_t s) {
     constexpr int QSZ = CM ? GK * BN : BN * GLD;
     constexpr size_t lds = DMA ? (size_t)2 * (BM + BN) * GK * sizeof(float) : (size_t)2 * (BM * GLD + QSZ) * sizeof(float);
     ensure_dyn_lds((const void *)linear_mfma_kernel<CM, WM, WN, TM, TN, DMA>, (int)lds);
+    g_linear_last = LinearLastLaunch{{CM ? 1 : 0, cfg, DMA ? 1 : 0, a.nkb, a.kvec, a.yvec, a.tiles_i, a.tiles_j}, true};
     hipLaunchKernelGGL((linear_mfma_kernel<CM, WM, WN, TM, TN, DMA>), dim3((unsigned)(a.tiles_i * a.tiles_j), (unsigned)B), dim3(256), lds, s, a);
 }
 
@@ -497,7 +505,7 @@ struct TileCfg {
 // staging registers and their ds_write instructions (102 -> 61 VGPRs at 64x64), and the K-block totals' round trips through the
 // output buffer (they live in a second accumulator set).  Default: DMA 64x64, DMA 64x128 from K = 768 on.
 static int pick_cfg(int n, long rows_out_narrow, int K = 0) {
-    const int c = options().linear_cfg;   // DVM_LINEAR_CFG: every configuration gives the same bits (tests/test_gpu_linear.py runs them all)
+    const int c = options().linear_cfg;   // DVM_LINEAR_CFG: every configuration gives the same bits (tests/test_gpu_linear_cfgs.py runs them all)
     if (c >= 0 && c < n) return c;
     if (rows_out_narrow <= 32) return 0;
     return n > 4 ? (K >= 768 ? 6 : 4) : 1;
@@ -515,6 +523,10 @@ static void launch_linear_impl(const float *x, const float *w, int B, int N, int
     a.kvec = 1;
     for (int i = 0; i <= a.nkb; ++i)
         if (a.kb[i] % 4) a.kvec = 0;
+    // the 16-byte loads of the K-contiguous operands (and of the row prefix) need 16-byte-aligned bases as well as block edges:
+    // an operand that starts off that grid (a view into a larger buffer) takes the 4-byte loads
+    const uintptr_t kbits = channel_major ? (uintptr_t)w : ((uintptr_t)x | (uintptr_t)w | (uintptr_t)a.G);
+    if (kbits % 16) a.kvec = 0;
     if (!channel_major) {
         a.P = x, a.Q = w, a.I = B * N, a.J = Co, a.q_bs = 0, a.y_bs = 0, a.ldy = Co, a.qvec = 1;
         bool dma_ok = a.kvec && !a.G && ((uintptr_t)x | (uintptr_t)w) % 16 == 0;
@@ -525,22 +537,23 @@ static void launch_linear_impl(const float *x, const float *w, int B, int N, int
             cfg = twin[cfg - 4];
         }
         switch (cfg) {   // {4,1,1,1} 128x32, {2,2,1,1} 64x64, {2,2,1,2} 64x128, {2,2,2,2} 128x128; 4..7: LDS-DMA staging, 64x64 / 128x64 / 64x128 / 128x128
-            case 0: launch_cfg<false, 4, 1, 1, 1>(a, 1, s); break;
-            case 1: launch_cfg<false, 2, 2, 1, 1>(a, 1, s); break;
-            case 2: launch_cfg<false, 2, 2, 1, 2>(a, 1, s); break;
-            case 3: launch_cfg<false, 2, 2, 2, 2>(a, 1, s); break;
-            case 4: launch_cfg<false, 2, 2, 1, 1, true>(a, 1, s); break;
-            case 5: launch_cfg<false, 2, 2, 2, 1, true>(a, 1, s); break;
-            case 6: launch_cfg<false, 2, 2, 1, 2, true>(a, 1, s); break;
-            default: launch_cfg<false, 2, 2, 2, 2, true>(a, 1, s); break;
+            case 0: launch_cfg<false, 4, 1, 1, 1>(a, 1, s, 0); break;
+            case 1: launch_cfg<false, 2, 2, 1, 1>(a, 1, s, 1); break;
+            case 2: launch_cfg<false, 2, 2, 1, 2>(a, 1, s, 2); break;
+            case 3: launch_cfg<false, 2, 2, 2, 2>(a, 1, s, 3); break;
+            case 4: launch_cfg<false, 2, 2, 1, 1, true>(a, 1, s, 4); break;
+            case 5: launch_cfg<false, 2, 2, 2, 1, true>(a, 1, s, 5); break;
+            case 6: launch_cfg<false, 2, 2, 1, 2, true>(a, 1, s, 6); break;
+            default: launch_cfg<false, 2, 2, 2, 2, true>(a, 1, s, 7); break;
         }
     } else {
-        a.P = w, a.Q = x, a.I = Co, a.J = N, a.q_bs = (long)K * N, a.y_bs = (long)Co * N, a.ldy = N, a.qvec = (N % 4 == 0);
+        a.P = w, a.Q = x, a.I = Co, a.J = N, a.q_bs = (long)K * N, a.y_bs = (long)Co * N, a.ldy = N;
+        a.qvec = (N % 4 == 0 && (uintptr_t)x % 16 == 0);
         switch (pick_cfg(4, Co)) {   // {1,4,1,1} 32x128, {2,2,1,1} 64x64, {2,2,2,1} 128x64, {2,2,2,2} 128x128
-            case 0: launch_cfg<true, 1, 4, 1, 1>(a, B, s); break;
-            case 1: launch_cfg<true, 2, 2, 1, 1>(a, B, s); break;
-            case 2: launch_cfg<true, 2, 2, 2, 1>(a, B, s); break;
-            default: launch_cfg<true, 2, 2, 2, 2>(a, B, s); break;
+            case 0: launch_cfg<true, 1, 4, 1, 1>(a, B, s, 0); break;
+            case 1: launch_cfg<true, 2, 2, 1, 1>(a, B, s, 1); break;
+            case 2: launch_cfg<true, 2, 2, 2, 1>(a, B, s, 2); break;
+            default: launch_cfg<true, 2, 2, 2, 2>(a, B, s, 3); break;
         }
     }
 }
@@ -668,6 +681,18 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float *__restri
 }  // namespace dvm
 
 using namespace dvm;
+
+// Diagnostic, host only (no device work, no synchronisation): what the most recent forward GEMM launch of this host thread was.
+// info[0] channel_major, [1] the table index launched (after the twin substitution), [2] 1 = LDS-DMA staging, [3] nkb, [4] kvec,
+// [5] yvec, [6] tiles_i, [7] tiles_j.
+DVM_EXPORT int dvm_linear_last_launch(int *info) {
+    DVM_REQUIRE(info, "dvm_linear_last_launch: null pointer");
+    const dvm::LinearLastLaunch &L = dvm::g_linear_last;
+    for (int i = 0; i < 8; ++i) info[i] = 0;
+    DVM_REQUIRE(L.set, "dvm_linear_last_launch: no forward GEMM launch on this thread yet");
+    for (int i = 0; i < 8; ++i) info[i] = L.info[i];
+    return DVM_OK;
+}
 
 DVM_EXPORT int dvm_linear_prefix_f32(const float *xg, int Cg, const float *x, const float *w, int B, int N, int K, int Co,
                                      const float *bias, const float *res, const float *bn_alpha, const float *bn_beta, float slope,

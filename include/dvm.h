@@ -63,7 +63,8 @@ typedef struct dvm_collective {
  *                              3 coarse screen; default: a probe picks per launch and direction, and a device-side gate sends a
  *                              direction the coarse screen serves badly through the lean form (results never depend on the route)
  *   DVM_K1_ROUTE_P="pc,pl"     the probe's thresholds (fractions of a row within the softmax cut; default 0.0014,0.02)
- *   DVM_LINEAR_CFG=0..7        tile configuration of dvm_linear_f32 (default: chosen per shape; all give the same bits)
+ *   DVM_LINEAR_CFG=0..7        tile configuration of dvm_linear_f32 (default: chosen per shape; all give the same bits:
+ *                              tests/test_gpu_linear_cfgs.py)
  *   DVM_PAIR_OVERLAP=0         initial value of dvm_pair_set_overlap (helper-stream overlap of the pair forward)
  *   DVM_DEBUG=<bits>           synchronous diagnostics on stderr: 1 K1 routes per launch, 2 rows sent to the exact-rows kernel,
  *                              4 grid-Chamfer query statistics, 8 K1 coarse-screen cycle stamps, 16 Deformer-MLP cycle stamps
@@ -131,6 +132,15 @@ int dvm_linear_prefix_f32(const float *xg, int Cg, const float *x, const float *
  * (two roundings, as the torch expression). */
 int dvm_linear_scaled_residual_f32(const float *x, const float *w, int B, int N, int K, int Co, int channel_major, const float *bias,
                                    float scale, const float *res, float *y, void *stream);
+
+/* Diagnostic, host only: what the most recent forward GEMM launch (the three entry points above, or a layer of a fused entry
+ * point) of the calling host thread was.  No counterpart in the reference.  No device work, no synchronisation; DVM_EINVAL
+ * before the first such launch on the thread.  info[0] channel_major, [1] the index launched in the tile-configuration table
+ * (point-major 0..7, channel-major 0..3; for DVM_LINEAR_CFG=4..7 the register-staged twin 1, 1, 2, 3 where LDS-DMA staging does
+ * not apply: K-blocks that are no multiples of 32, a row prefix, operands off the 16-byte grid), [2] 1 = LDS-DMA staging,
+ * [3] number of K-blocks, [4] 1 = 16-byte operand loads along K, [5] 1 = 16-byte accesses in the epilogue, [6] row tiles,
+ * [7] column tiles.  tests/test_gpu_linear_cfgs.py reads it to prove which instantiation a forced configuration ran. */
+int dvm_linear_last_launch(int *info);
 
 /* Weight gradient of the point-major layer above (what autograd computes for nn.Conv1d.weight in `loss.backward()`,
  * train.py:110):  dW[co][k] += sum_r gy[r][co] * x[r][k]  over the R = B*N rows; gy [R, Co], x [R, K], dW [Co, K] must be

@@ -156,6 +156,28 @@ def test_no_cpu_fallback():
         ops.knn_cdist(torch.rand(1, 8, 3), torch.rand(1, 8, 3), 3)
 
 
+def test_linear_last_launch_before_any_launch():
+    """dvm_linear_last_launch is host-only: on a thread that has launched no forward GEMM (a fresh one: the record is per thread) it
+    is an argument error that names the reason and zeroes the caller's eight ints; a null pointer is refused."""
+    import threading
+    from ctypes import c_int, c_void_p
+    from dvm import _lib
+    lib = _lib.load()
+    assert _lib.SIGNATURES["dvm_linear_last_launch"] == (c_int, [c_void_p])
+    got = {}
+
+    def ask():
+        info = (c_int * 8)(*range(1, 9))
+        got["rc"], got["msg"], got["info"] = lib.dvm_linear_last_launch(info), lib.dvm_last_error(), list(info)
+        got["null"] = (lib.dvm_linear_last_launch(None), lib.dvm_last_error())
+
+    t = threading.Thread(target=ask)
+    t.start()
+    t.join()
+    assert got["rc"] == -1 and b"no forward GEMM launch on this thread yet" in got["msg"] and got["info"] == [0] * 8, got
+    assert got["null"][0] == -1 and b"null pointer" in got["null"][1], got
+
+
 def test_argument_validation_without_gpu():
     """Shape/argument errors are reported before anything touches a device."""
     from dvm import _lib
