@@ -218,7 +218,9 @@ def test_criterion_backward_matches_reference(golden, name, cls, kw):
                                       (300, 64, 40, 25)])
 def test_dist_loss_vs_torch(ops, N, C, nA, k):
     """C = 128, k <= 512: the half-wave-per-row kernel (odd / even / multi-chunk k); other widths: the
-    lane-per-row kernel (k itself is capped at 512 by the kNN selection)."""
+    lane-per-row kernel (k itself is capped at 512 by the kNN selection).  A batch sum on random data at rtol 1e-5, and cdist is
+    symmetric: the pin of the selection, of every neighbour slot, of the workgroup slots and of the dist[v, a] read is
+    tests/test_gpu_dist_term_anchors.py (per anchor, bit for bit)."""
     g = torch.Generator().manual_seed(21 + k)
     B = 2
     feat = torch.randn(B, N, C, generator=g).cuda()

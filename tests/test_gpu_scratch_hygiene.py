@@ -678,8 +678,9 @@ def test_apply_bwd_poisoned_scratch(ops, monkeypatch, deterministic, C):
 @pytest.mark.parametrize("N,nA,k", [(300, 40, 25), (1100, 50, 500)])
 def test_dist_loss_poisoned_scratch(ops, monkeypatch, deterministic, N, nA, k):
     """Forward against the reference's formulation (models/loss.py:1351-1396, as tests/test_gpu_backward.py evaluates it in fp64)
-    on the kernel's own neighbour sets (their selection is pinned by tests/test_gpu_backbone.py::test_dist_loss_vs_torch, which the
-    child run below repeats on poisoned scratch); the backward weights poisoned == clean."""
+    on the kernel's own neighbour sets (their selection and every neighbour slot are pinned per anchor, bit for bit, by
+    tests/test_gpu_dist_term_anchors.py; tests/test_gpu_backbone.py::test_dist_loss_vs_torch, which the child run below repeats on
+    poisoned scratch, checks the batch sum on random data); the backward weights poisoned == clean."""
     B, C = 2, 128
     g = torch.Generator().manual_seed(N + k)
     feat = torch.randn(B, N, C, generator=g)
