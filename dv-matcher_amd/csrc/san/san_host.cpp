@@ -263,6 +263,29 @@ int main() {
         EXPECT(dvm_dg_skin_weights_f32(F, nullptr, B, N, F, nullptr) == DVM_EINVAL);
         EXPECT(dvm_dg_build_geod_f32(F, F, B, 12289, I, 0, I, I, I, F, F, dd, ws, q, nullptr) == DVM_EINVAL);
         EXPECT(dvm_dg_build_geod_f32(F, F, B, N, I, 2, I, I, I, F, F, dd, ws, q, nullptr) == DVM_EINVAL);
+        // the precise map: a short workspace, then its refusals — a null required pointer, sizes below 1, a d that is no multiple
+        // of 4 or above 512, M above the cap (the size query answers 0 there), a plan query without its outputs
+        SHORT(dvm_precise_map_workspace_bytes(B, N, M, d, 32), dvm_precise_map_f32(F, F, I, B, N, M, d, 32, I, F, I, F, nullptr, ws, q - 1, nullptr));
+        {
+            int64_t st[2];
+            int pr = 0, pt = 0, pc = 0, pm = 0;
+            const int cap = dvm_precise_map_max_m();
+            EXPECT(dvm_precise_map_f32(nullptr, F, I, B, N, M, d, 32, I, F, I, F, st, ws, q, nullptr) == DVM_EINVAL);
+            EXPECT(dvm_precise_map_f32(F, F, nullptr, B, N, M, d, 32, I, F, I, F, st, ws, q, nullptr) == DVM_EINVAL);
+            EXPECT(dvm_precise_map_f32(F, F, I, B, N, M, d, 32, I, nullptr, I, F, st, ws, q, nullptr) == DVM_EINVAL);
+            EXPECT(dvm_precise_map_f32(F, F, I, 0, N, M, d, 32, I, F, I, F, st, ws, q, nullptr) == DVM_EINVAL);
+            EXPECT(dvm_precise_map_f32(F, F, I, B, 0, M, d, 32, I, F, I, F, st, ws, q, nullptr) == DVM_EINVAL);
+            EXPECT(dvm_precise_map_f32(F, F, I, B, N, 0, d, 32, I, F, I, F, st, ws, q, nullptr) == DVM_EINVAL);
+            EXPECT(dvm_precise_map_f32(F, F, I, B, N, M, d, 0, I, F, I, F, st, ws, q, nullptr) == DVM_EINVAL);
+            EXPECT(dvm_precise_map_f32(F, F, I, B, N, M, 130, 32, I, F, I, F, st, ws, q, nullptr) == DVM_EINVAL);
+            EXPECT(dvm_precise_map_f32(F, F, I, B, N, M, 516, 32, I, F, I, F, st, ws, q, nullptr) == DVM_EINVAL);
+            EXPECT(dvm_precise_map_f32(F, F, I, B, N, cap + 1, d, 32, I, F, I, F, st, ws, q, nullptr) == DVM_EINVAL);
+            EXPECT(strstr(dvm_last_error(), "dvm_precise_map_max_m"));
+            EXPECT(dvm_precise_map_workspace_bytes(B, N, cap + 1, d, 32) == 0 && dvm_precise_map_workspace_bytes(B, N, cap, d, 32) == q);
+            EXPECT(dvm_precise_map_plan(B, N, M, d, 32, &pr, &pt, &pc, nullptr) == DVM_EINVAL);
+            EXPECT(dvm_precise_map_plan(B, N, cap + 1, d, 32, &pr, &pt, &pc, &pm) == DVM_EINVAL);
+            EXPECT(dvm_precise_map_plan(B, N, M, d, 32, &pr, &pt, &pc, &pm) == DVM_OK && pr >= 1 && pt % 64 == 0 && pc >= 1 && pm == cap);
+        }
         SHORT(dvm_chamfer_workspace_bytes(B, 8192, 8192), dvm_chamfer_fwd_f32(F, F, B, 8192, 8192, F, F, I, I, ws, q - 1, nullptr));   // (large enough for the grid form)
         SHORT(dvm_deformer_workspace_bytes(B, N, M, N / 2),
               dvm_deformer_fwd_f32(F, F, F, F, I, I, F, I, I, B, N, M, N / 2, k, 10, F, F, F, F, F, F, F, F, F, F, F, 0, ws, q - 1, nullptr));

@@ -594,6 +594,48 @@ def argmin_exact(f1, f2, want_dist=False, screen=True):
     return (T, dm) if want_dist else T
 
 
+def precise_map_max_m():
+    """The largest M precise_map takes (a row's products with every target vertex are held in LDS).  No device is needed."""
+    return int(_lib.load().dvm_precise_map_max_m())
+
+
+def precise_map_plan(B, N, M, d, F):
+    """How precise_map launches at these sizes -> (source rows per workgroup, threads per workgroup, target rows per step of the
+    LDS fill, the cap on M).  No device is needed."""
+    r, t, c, m = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    check(_lib.load().dvm_precise_map_plan(B, N, M, d, F, ctypes.byref(r), ctypes.byref(t), ctypes.byref(c), ctypes.byref(m)),
+          "dvm_precise_map_plan")
+    return r.value, t.value, c.value, m.value
+
+
+def precise_map(f1, f2, faces, want_dist=True, check=True, want_stats=False):
+    """The precise (vertex-to-point) map: for every f1[b,i] the closest point of the triangle mesh (f2[b], faces) in feature space
+    -> (face (B,N) int32, bary (B,N,3), pi_idx (B,N,3) int32 = faces[face], dist (B,N) or None).  (bary, pi_idx) is a sparse row
+    of three entries: ops.apply and the loss terms take it as (pi_val, pi_idx).  faces (F,3), one connectivity for the B entries;
+    a face with an index outside [0,M) is left out: check=True reads the count back (one synchronisation) and raises DvmError if
+    there is one, check=False never synchronises.  want_stats appends the device tensor stats (2,) int64: faces left out, exact
+    evaluations made.  Definition, ties and limits: include/dvm.h."""
+    read_back = check   # (the parameter, named by the interface, hides the module's check() in this body: use this name here)
+    _need_gpu(f1, f2, faces)
+    f1, f2, faces = _f(f1), _f(f2), _i(faces)
+    if f1.dim() != 3 or f2.dim() != 3 or f2.shape[0] != f1.shape[0] or f2.shape[2] != f1.shape[2] or faces.dim() != 2 or faces.shape[1] != 3:
+        raise DvmError("precise_map: f1 must be (B,N,d), f2 (B,M,d) and faces (F,3) (got %s, %s, %s)"
+                       % (tuple(f1.shape), tuple(f2.shape), tuple(faces.shape)))
+    B, N, d = f1.shape
+    M, F = f2.shape[1], faces.shape[0]
+    dev = f1.device
+    face, bary, pi_idx = _new(dev, B, N, dtype=torch.int32), _new(dev, B, N, 3), _new(dev, B, N, 3, dtype=torch.int32)
+    dist = _new(dev, B, N) if want_dist else None
+    stats = _new(dev, 2, dtype=torch.int64)
+    _call_ws("dvm_precise_map_f32", (_p(f1), _p(f2), _p(faces), B, N, M, d, F, _p(face), _p(bary), _p(pi_idx), _p(dist), _p(stats)), dev,
+             "precise_map", "dvm_precise_map_workspace_bytes", B, N, M, d, F)
+    if read_back:
+        bad = int(stats[0].item())
+        if bad:
+            raise DvmError("precise_map: %d of the %d faces hold an index outside [0, %d) and were left out" % (bad, F, M))
+    return (face, bary, pi_idx, dist, stats) if want_stats else (face, bary, pi_idx, dist)
+
+
 def argmin_pair(f1, f2):
     """Both hard maps of a pair from one sweep: (T12 (B,N) into f2, T21 (B,M) into f1)."""
     _need_gpu(f1, f2)

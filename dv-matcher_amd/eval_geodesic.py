@@ -68,5 +68,32 @@ def geodesic_errors(T, vts_src, vts_tgt, M_tgt):
     return np.asarray(M_tgt)[T[np.asarray(vts_src)], np.asarray(vts_tgt)]
 
 
-def mean_geodesic_error(phi_src, phi_tgt, vts_src, vts_tgt, M_tgt):
+def match_precise(phi_src, phi_tgt, faces_tgt):
+    """The precise map of the source features onto the target mesh in feature space (ops.precise_map) ->
+    (face (N,) int64, bary (N,3) float64): source point i lands in the target triangle faces_tgt[face[i]] with those weights."""
+    import torch
+    from dvm import ops
+    a = torch.as_tensor(np.ascontiguousarray(phi_src), dtype=torch.float32).cuda()[None]
+    b = torch.as_tensor(np.ascontiguousarray(phi_tgt), dtype=torch.float32).cuda()[None]
+    f = torch.as_tensor(np.ascontiguousarray(np.asarray(faces_tgt).reshape(-1, 3)), dtype=torch.int32).cuda()
+    face, bary, _, _ = ops.precise_map(a, b, f, want_dist=False)
+    return face[0].cpu().numpy().astype(np.int64), bary[0].cpu().numpy().astype(np.float64)
+
+
+def geodesic_errors_precise(face, bary, faces_tgt, vts_src, vts_tgt, M_tgt):
+    """geodesic_errors for a precise map: the landmark's image is a point of a target triangle, and its distance to the true
+    partner is interpolated from the triangle's corners,
+    error_l = sum_k bary[vts_src[l], k] * M_tgt[faces_tgt[face[vts_src[l]], k], vts_tgt[l]].
+    A map with one-hot weights gives geodesic_errors of the vertex it names."""
+    face, bary = np.asarray(face).reshape(-1), np.asarray(bary, dtype=np.float64).reshape(-1, 3)
+    vts_src, vts_tgt = np.asarray(vts_src), np.asarray(vts_tgt)
+    corners = np.asarray(faces_tgt).reshape(-1, 3)[face[vts_src]]                      # (L,3)
+    return (bary[vts_src] * np.asarray(M_tgt)[corners, vts_tgt[:, None]]).sum(axis=1)
+
+
+def mean_geodesic_error(phi_src, phi_tgt, vts_src, vts_tgt, M_tgt, faces_tgt=None):
+    """The vertex map's mean error; with faces_tgt the precise map's (match_precise, geodesic_errors_precise)."""
+    if faces_tgt is not None:
+        face, bary = match_precise(phi_src, phi_tgt, faces_tgt)
+        return float(geodesic_errors_precise(face, bary, faces_tgt, vts_src, vts_tgt, M_tgt).mean())
     return float(geodesic_errors(match(phi_src, phi_tgt), vts_src, vts_tgt, M_tgt).mean())

@@ -248,7 +248,7 @@ class _ShapeCollection(_TorchDataset):
         self.feat_list = []
         if with_sym:
             raise NotImplementedError("with_sym needs corres/*.sym.vts files, which the reference does not load either")
-        split = "train" if train else "test"
+        split = self._split = "train" if train else "test"
         wks_suf = "" if with_wks is None else "wks_"
         geo_suf = "_meshgeo" if geodesics == "mesh" and self._with_dist else ""
         cache = os.path.join(self.cache_dir, "cache_%s_%s%s%s%s.pt" % (name, wks_suf, split, self._cache_suffix, geo_suf))
@@ -264,6 +264,8 @@ class _ShapeCollection(_TorchDataset):
         shapes_dir = Path(root_dir) / ("shapes_" + split)
         self.used_shapes = sorted(x.stem for x in shapes_dir.iterdir() if "DS_" not in x.stem)
         self.verts_list, self.fps_list, self.dist_list = [], [], []
+        if not _is_point_cloud_set(name):
+            self._faces_list = []
         for shape in self.used_shapes:
             path = str(shapes_dir / (shape + ".off"))
             if _is_point_cloud_set(name):
@@ -272,6 +274,8 @@ class _ShapeCollection(_TorchDataset):
                 verts, faces = read_mesh(path)
             if self._with_dist:
                 self.dist_list.append(cal_geo(verts, faces, method=geodesics))
+            if faces is not None:
+                self._faces_list.append(faces)
             verts = torch.from_numpy(np.ascontiguousarray(verts)).float()
             fps = farthest_point_sample(verts, verts.shape[0])
             self.verts_list.append(verts)
@@ -280,6 +284,20 @@ class _ShapeCollection(_TorchDataset):
         if use_cache:
             blob = (self.verts_list, self.used_shapes, self.fps_list) + ((self.dist_list,) if self._with_dist else ())
             torch.save(blob, cache)
+
+    _faces_list = None   # not read yet (a set loaded from its cache, which holds no faces)
+
+    @property
+    def faces_list(self):
+        """The triangles of every shape, (F,3) int64 arrays in the order of verts_list (vertex ids of the whole mesh, not of an
+        FPS selection); None for a set of bare point clouds.  The caches hold no faces: a set loaded from one parses its OFF
+        files when this is first asked for."""
+        if _is_point_cloud_set(self.name):
+            return None
+        if self._faces_list is None:
+            shapes_dir = Path(self.root_dir) / ("shapes_" + self._split)
+            self._faces_list = [read_mesh(str(shapes_dir / (shape + ".off")))[1] for shape in self.used_shapes]
+        return self._faces_list
 
     def _enumerate(self):
         return _pairs(self.name, self.used_shapes)

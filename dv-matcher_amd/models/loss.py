@@ -112,6 +112,17 @@ class SparsePi:
         return ops.apply(self.val, self.idx, V)
 
 
+def precise_map(x, y, faces):
+    """The precise (vertex-to-point) map of x (B,N,d) onto the triangle mesh (y (B,M,d), faces (F,3)) in feature space as a
+    SparsePi of three entries per row (val = the barycentric weights, idx = the face's vertices; not in the reference): matmul(V)
+    gives the mapped coordinates on the target surface, and the rank / cycle / distortion terms take it as any other SparsePi.
+    It also carries .face (B,N) and .dist (B,N).  No gradient flows through it (ops.precise_map)."""
+    face, bary, pi_idx, dist = ops.precise_map(x, y, faces)
+    pi = SparsePi(bary, pi_idx, y.shape[1])
+    pi.face, pi.dist = face, dist
+    return pi
+
+
 def _relaxed(tau):
     """Whether a sinkhorn_tau setting leaves the balanced operator: None and (1, 1) do not."""
     return tau is not None and tuple(ops.tau_pair(tau)) != (1.0, 1.0)

@@ -300,6 +300,36 @@ int dvm_argmin_exact_f32(const float *f1, const float *f2, int B, int N, int M, 
 int dvm_argmin_pair_f32(const float *f1, const float *f2, int B, int N, int M, int d, int32_t *T12, int32_t *T21,
                         float *dmin12, float *dmin21, void *ws, size_t ws_bytes, void *stream);
 
+/* The precise (vertex-to-point) map beside the vertex map above: the closest point of the target's triangle mesh embedded
+ * in feature space.  Not in the reference, which stops at knnsearch_t.
+ * f1 [B,N,d], f2 [B,M,d] fp32 (rows 16-byte aligned), faces [F,3] int32, one connectivity shared by the B entries.  For every
+ * (b,i), p = f1[b,i]: over all faces (a,b,c) whose three indices lie in [0,M), q = the point of the triangle f2[b,a], f2[b,b],
+ * f2[b,c] in R^d closest to p; the face with the smallest distance wins, ties in the compared fp32 value go to the lowest face
+ * index.  The compared value is the exact-difference form: per face the closest point of each edge as a segment and, where the
+ * face's Gram determinant exceeds its own rounding (det > 2^-21 e11 e22), the interior projection if all its weights are >= 0;
+ * for each the residual (f2[a] - p) + s (f2[b] - f2[a]) + t (f2[c] - f2[a]) is formed and its squared norm summed by a k-ordered
+ * fmaf chain.  A face with a repeated index or collinear features is the union of its edges: a valid candidate, never a NaN.  A
+ * face whose value is NaN never wins (NaN counts as +inf, as in dvm_dg_skin_geod_f32).  A face with an index outside [0,M) is
+ * left out and counted.
+ * Outputs: face [B,N] int32; bary [B,N,3] (each >= 0, summing to 1 within 4 ulp, in the vertex order of the face);
+ * pi_idx [B,N,3] = faces[face] — (bary, pi_idx) is the (pi_val, pi_idx) layout of dvm_sparse_apply_f32 and the loss terms;
+ * dist [B,N] = |p - q| (may be NULL); stats [2] int64 on the device (may be NULL): faces left out, exact evaluations made.  A
+ * row with no admissible face gets face = -1, bary = 0, pi_idx = 0, dist = +inf; a row whose best value is +inf (a non-finite
+ * row, or non-finite corners everywhere) gets the lowest admissible face with bary = (1,0,0) and dist = +inf.
+ * Limits: d % 4 == 0, 4 <= d <= 512, M <= dvm_precise_map_max_m() (8192: the row's products with every target vertex are held
+ * in LDS), B <= 65535, all sizes >= 1; outside them, or with a null required pointer, DVM_EINVAL and a size query of 0; a short
+ * workspace DVM_ENOSPACE; both before anything is launched.
+ * The faces are screened by the Gram form and every face within a proved error band of the row's minimum is evaluated in the
+ * exact form (csrc/dvm_precise_map.hip derives the band): the result is the exact form's arg-min over all faces.  Asynchronous
+ * on `stream`, no host synchronisation, no float atomics, the same bits from run to run, capturable.
+ * dvm_precise_map_plan reports, without a device, the source rows and threads per workgroup, the target rows per step of the
+ * LDS fill and the cap on M. */
+int dvm_precise_map_max_m(void);
+int dvm_precise_map_plan(int B, int N, int M, int d, int F, int *rows, int *threads, int *chunk, int *max_m);
+size_t dvm_precise_map_workspace_bytes(int B, int N, int M, int d, int F);
+int dvm_precise_map_f32(const float *f1, const float *f2, const int32_t *faces, int B, int N, int M, int d, int F, int32_t *face,
+                        float *bary, int32_t *pi_idx, float *dist, int64_t *stats, void *ws, size_t ws_bytes, void *stream);
+
 /* knn_grad — models/loss.py:97-101: the k smallest of cdist(x,y) (matmul form)
  * per row, ascending.  x [B,N,C], y [B,M,C] -> idx [B,N,k]; C <= 16, k <= 16.  A 3-D cloud against
  * itself (x == y) is searched exactly on a uniform grid; otherwise brute force (ws may be NULL). */
