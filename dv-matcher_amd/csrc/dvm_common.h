@@ -466,6 +466,56 @@ __device__ __forceinline__ double block_tree_sum(double s) {
     return red[0];
 }
 
+// The workgroup exclusive scan, defined once: the exclusive prefix of one int per thread of a THREADS-thread workgroup, in
+// thread order; total = the sum of all of them, in every thread.  A wave scan on __shfl_up, then the per-wave sums through
+// smem [THREADS / 64].  EVERY lane of the workgroup must reach the call: __shfl_up reads lanes that have to be active, and
+// the barriers are the workgroup's.  The leading barrier makes back-to-back calls on the same smem safe.
+template <int THREADS>
+__device__ __forceinline__ int block_exclusive_scan(int v, int *smem /* [THREADS / 64] */, int &total) {
+    static_assert(THREADS % 64 == 0 && THREADS >= 64 && THREADS <= 1024, "whole waves, one workgroup");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        int t = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += t;
+    }
+    __syncthreads();
+    if (lane == 63) smem[wave] = inc;
+    __syncthreads();
+    int base = 0, sum = 0;
+#pragma unroll
+    for (int w = 0; w < THREADS / 64; ++w) {
+        const int sw = smem[w];
+        base += w < wave ? sw : 0;
+        sum += sw;
+    }
+    total = sum;
+    return base + inc - v;
+}
+
+// Counters -> offsets, for n counters owned in contiguous chunks: thread tid owns [min(n, tid per), min(n, tid per + per)),
+// per = ceil(n / THREADS).  It sums its chunk, the sums are scanned, and the chunk is walked again: write_offset(i, offset)
+// hands counter i its exclusive offset, after read_count(i) has been read (so the write may go in place).  Returns the total.
+// The counters may live in LDS or in global memory; every lane of the workgroup must reach the call (block_exclusive_scan),
+// and the caller's barrier stands between the last count and this call.
+template <int THREADS, class Read, class Write>
+__device__ __forceinline__ int block_scan_counts(int n, Read read_count, Write write_offset) {
+    __shared__ int wave_sums[THREADS / 64];
+    const int per = (n + THREADS - 1) / THREADS;
+    const int lo = min(n, (int)threadIdx.x * per), hi = min(n, lo + per);
+    int s = 0;
+    for (int i = lo; i < hi; ++i) s += read_count(i);
+    int total;
+    int run = block_exclusive_scan<THREADS>(s, wave_sums, total);
+    for (int i = lo; i < hi; ++i) {
+        const int v = read_count(i);
+        write_offset(i, run);
+        run += v;
+    }
+    return total;
+}
+
 }  // namespace dvm
 
 #include "dvm_internal.h"   // the launchers one .hip file defines and another calls

@@ -14,7 +14,7 @@
 //   3. gradient (GRAD): thread (t, s) reads C[c] back: the sample smp[b][i][t][s] (what the column kernel needs from this row) and
 //      the term R[i,c] val21[j,s]; thread t < k12 adds its k21 terms in slot order in float64 -> g12[i,t], unscaled.
 // cycle_col_kernel, one wave per column j of P12 = row j of P21, lanes = 4 list entries x 16 slots s: the list of j from
-// launch_rev_csr (dvm_geom.hip) is walked twice for the order-free sum that dvm_frob.h explains: the largest |term| per slot s,
+// launch_rev_csr (dvm_revlist.hip) is walked twice for the order-free sum that dvm_frob.h explains: the largest |term| per slot s,
 // then the 64-bit integer sum -> g21[j,s], unscaled; 0 for a column nobody picks.
 // frob_finish (dvm_frob.hip): loss = sqrt(F^2), g12 and g21 *= 1 / F, 0 where F == 0.
 // The loss-only call runs steps 1 and 2 and the finish: no lists, no samples.  Arrays: the lists (B (2 M + 1 + N k12) int32),

@@ -312,54 +312,8 @@ __global__ __launch_bounds__(256) void apply_bwd_kernel(const float *__restrict_
     }
 }
 
-// d_V without float atomics: the (row, slot) -> target lists are reversed by a counting sort (one int atomic per
-// entry), then one wave per target row sums its in-edges, lanes over channels.
-__global__ void rev_count_kernel(const int32_t *__restrict__ idx, long E, int M, int32_t *__restrict__ cnt) {
-    const int b = blockIdx.y;
-    const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= E) return;
-    const int j = idx[(size_t)b * E + e];
-    if (j >= 0 && j < M) atomicAdd(cnt + (size_t)b * (M + 1) + j, 1);
-}
-
-// exclusive scan of cnt[b][0..M) in place (cnt[b][M] = total); cursor = copy of the offsets
-__global__ __launch_bounds__(1024) void rev_scan_kernel(int32_t *__restrict__ cnt, int M, int32_t *__restrict__ cursor) {
-    __shared__ int part[1024];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    int32_t *c = cnt + (size_t)b * (M + 1);
-    const int per = (M + 1023) / 1024;
-    const int lo = min(M, tid * per), hi = min(M, lo + per);
-    int s = 0;
-    for (int i = lo; i < hi; ++i) s += c[i];
-    part[tid] = s;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        int v = tid >= o ? part[tid - o] : 0;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    int run = part[tid] - s;
-    for (int i = lo; i < hi; ++i) {
-        const int v = c[i];
-        c[i] = run;
-        cursor[(size_t)b * M + i] = run;
-        run += v;
-    }
-    if (tid == 1023) c[M] = part[1023];
-}
-
-__global__ void rev_fill_kernel(const int32_t *__restrict__ idx, long E, int M, int32_t *__restrict__ cursor,
-                                int32_t *__restrict__ edges) {
-    const int b = blockIdx.y;
-    const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= E) return;
-    const int j = idx[(size_t)b * E + e];
-    if (j < 0 || j >= M) return;
-    const int pos = atomicAdd(cursor + (size_t)b * M + j, 1);
-    edges[(size_t)b * E + pos] = (int32_t)e;  // e = row * topk + slot
-}
-
+// d_V without float atomics: the (row, slot) -> target lists are reversed by a counting sort (launch_rev_csr, dvm_revlist.hip:
+// one int atomic per entry), then one wave per target row sums its in-edges, lanes over channels.
 // sum of val[e] * gout[row(e)] over the in-edges ed[beg..end) of one target, lanes over channels
 __device__ __forceinline__ void gather_edges(const int32_t *__restrict__ ed, int beg, int end, const float *__restrict__ vb,
                                              const float *__restrict__ gb, int topk, int C, int lane, float (&acc)[4]) {
@@ -895,15 +849,7 @@ DVM_EXPORT int dvm_softcorr_apply_f32(const float *pi_val, const int32_t *pi_idx
 }
 
 namespace dvm {
-// The pieces of dvm_softcorr_apply_bwd_f32's gather form, for callers that keep the reversed lists (dvm_criterion_train.hip):
-// idx [B][E] (entries with a target in [0, M)) -> offs [B][M+1], edges [B][E] (entry numbers grouped by target); cursor [B][M] scratch
-void launch_rev_csr(const int32_t *idx, int B, long E, int M, int32_t *offs, int32_t *cursor, int32_t *edges, hipStream_t s) {
-    dim3 egrid((unsigned)((E + 255) / 256), B);
-    (void)hipMemsetAsync(offs, 0, (size_t)B * (M + 1) * sizeof(int32_t), s);
-    hipLaunchKernelGGL(rev_count_kernel, egrid, dim3(256), 0, s, idx, E, M, offs);
-    hipLaunchKernelGGL(rev_scan_kernel, dim3(B), dim3(1024), 0, s, offs, M, cursor);
-    hipLaunchKernelGGL(rev_fill_kernel, egrid, dim3(256), 0, s, idx, E, M, cursor, edges);
-}
+// The pieces of dvm_softcorr_apply_bwd_f32's gather form, for callers that keep the reversed lists (dvm_criterion_train.hip)
 void launch_apply_bwd_dval(const float *pi_val, const int32_t *pi_idx, const float *V, const float *g_out, int B, int N, int M, int topk, int C,
                            float *d_val, hipStream_t s) {
     int gp2 = 1;

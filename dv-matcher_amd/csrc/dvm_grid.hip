@@ -64,7 +64,6 @@ __device__ __forceinline__ void grid_build_body(const float *__restrict__ xyz, i
     extern __shared__ int lds[];  // [G^3 + 1] counts/starts, then cursors [G^3]
     __shared__ float red[6][GRID_T / 64];
     __shared__ float par[8];
-    __shared__ int wsum[GRID_T / 64];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int P = gb.P, G = gb.G, G3 = G * G * G;
     const float *p = xyz + (size_t)b * Nsrc * 3;
@@ -141,28 +140,9 @@ __device__ __forceinline__ void grid_build_body(const float *__restrict__ xyz, i
     };
     each_point([&](int, float x, float y, float z) { atomicAdd(&lds[cell_of(x, y, z)], 1); });
     __syncthreads();
-    // exclusive scan of G3 counts (each thread owns a contiguous chunk)
-    const int chunk = (G3 + GRID_T - 1) / GRID_T;
-    int local = 0;
-    for (int c = tid * chunk; c < (tid + 1) * chunk && c < G3; ++c) local += lds[c];
-    int inc = local;
-    for (int o = 1; o < 64; o <<= 1) {
-        int t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-    }
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    int base = inc - local;
-    for (int w2 = 0; w2 < wave; ++w2) base += wsum[w2];
-    __syncthreads();
+    // exclusive scan of the G3 counts, in place, and a copy as the cursors
     int *cursor = lds + G3 + 1;
-    int run = base;
-    for (int c = tid * chunk; c < (tid + 1) * chunk && c < G3; ++c) {
-        int cnt = lds[c];
-        lds[c] = run;
-        cursor[c] = run;
-        run += cnt;
-    }
+    block_scan_counts<GRID_T>(G3, [&](int c) { return lds[c]; }, [&](int c, int run) { lds[c] = cursor[c] = run; });
     if (tid == 0) lds[G3] = P;
     __syncthreads();
     int32_t *st = gb.start + (size_t)b * (G3 + 1);

@@ -56,20 +56,6 @@ int launch_mean_grouped(const float *const *in, const int *n, float *const *out,
 int map_term_blocks(int N, int k);
 int launch_map_term(const float *verts12, const float *verts2, const int32_t *idx11, const int32_t *idx22, const float *pi_val, const int32_t *pi_idx,
                     int B, int N, int M, int k, int topk, double *partial, hipStream_t s, float *resid = nullptr);
-// idx [B][E] (entries with a target in [0, M)) -> offs [B][M+1], edges [B][E] (entry numbers grouped by target); cursor [B][M] scratch
-void launch_rev_csr(const int32_t *idx, int B, long E, int M, int32_t *offs, int32_t *cursor, int32_t *edges, hipStream_t s);
-// those three arrays as a workspace piece: B batches, M targets, E entries per batch
-struct RevLists {
-    int32_t *offs = nullptr, *cursor = nullptr, *edges = nullptr;
-    void take(Arena &ar, size_t B, size_t M, size_t E) {
-        offs = ar.take<int32_t>(B * (M + 1));
-        cursor = ar.take<int32_t>(B * M);
-        edges = ar.take<int32_t>(B * E);
-    }
-};
-static inline void launch_rev_csr(const int32_t *idx, int B, long E, int M, const RevLists &r, hipStream_t s) {
-    launch_rev_csr(idx, B, E, M, r.offs, r.cursor, r.edges, s);
-}
 void launch_apply_bwd_dval(const float *pi_val, const int32_t *pi_idx, const float *V, const float *g_out, int B, int N, int M, int topk, int C, float
                            *d_val, hipStream_t s);
 void launch_apply_bwd_gather(const float *pi_val, const float *g_out, const int32_t *offs, const int32_t *edges, int B, int N, int M, int topk, int C,
@@ -88,6 +74,36 @@ bool launch_map_term_lds_pair(const float *verts12, const float *verts21, const 
 // -> false if a target cloud does not fit LDS (the caller then uses apply_kernel + take_col0)
 bool launch_apply3_pair(const float *val12, const int32_t *idx12, const float *verts2, float *verts12, int32_t *T12, const float *val21, const int32_t
                         *idx21, const float *verts1, float *verts21, int32_t *T21, int B, int N, int M, hipStream_t s);
+
+// ---- dvm_revlist.hip: reversed index lists by a counting sort (count, exclusive scan, fill)
+// idx [B][E] (an entry with a target outside [0, M) is left out) -> offs [B][M+1], edges [B][E] (entries grouped by target).
+// The entry record: int32_t = the entry number e; int2 = (e, e / K), the entry and its source row.
+// The arrays as a workspace piece, B batches, M targets, E entries per batch: cursor [B][M] is scratch of the global route,
+// hist [B][REV_DET_CHUNKS][M] (taken last, on request) that of the ordered one.
+constexpr int REV_DET_CHUNKS = 64;
+template <class Edge>
+struct RevListsT {
+    int32_t *offs = nullptr, *cursor = nullptr;
+    Edge *edges = nullptr;
+    int32_t *hist = nullptr;
+    void take(Arena &ar, size_t B, size_t M, size_t E, bool ordered = false) {
+        offs = ar.take<int32_t>(B * (M + 1));
+        cursor = ar.take<int32_t>(B * M);
+        edges = ar.take<Edge>(B * E);
+        if (ordered) hist = ar.take<int32_t>(B * REV_DET_CHUNKS * M);
+    }
+};
+typedef RevListsT<int32_t> RevLists;
+// global: count, scan and fill as three launches of global atomics; LDS: one workgroup per batch element (needs (2 M + 1) ints
+// of LDS and E < 2^31); ordered: REV_DET_CHUNKS histograms, every list in ascending entry order, no atomics between threads
+// (needs M ints of LDS and r.hist)
+enum RevRoute { REV_GLOBAL, REV_LDS, REV_ORDERED };
+RevRoute rev_route(int B, long E, int M);   // the N2P backward's rule
+template <class Edge>
+void launch_rev_lists(const int32_t *idx, int B, long E, int M, int K, const RevListsT<Edge> &r, RevRoute route, hipStream_t s);
+static inline void launch_rev_csr(const int32_t *idx, int B, long E, int M, const RevLists &r, hipStream_t s, RevRoute route = REV_GLOBAL) {
+    launch_rev_lists(idx, B, E, M, 1, r, route, s);
+}
 
 // ---- dvm_graph.hip
 // The largest cloud a deformation graph is built on: fps_kernel keeps the cloud in LDS (12288 * 12 B = 144 KiB) and 24 points

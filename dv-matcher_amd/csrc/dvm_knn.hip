@@ -192,30 +192,12 @@ __device__ __forceinline__ unsigned desc_key(float f) {
     return ~u;
 }
 
-__device__ __forceinline__ int block_exclusive_scan(int v, int *smem /* [8] */, int &total) {
-    // 256 threads; returns exclusive prefix of v in thread order
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        int t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-    }
-    __syncthreads();
-    if (lane == 63) smem[wave] = inc;
-    __syncthreads();
-    int base = 0;
-    for (int w = 0; w < wave; ++w) base += smem[w];
-    total = smem[0] + smem[1] + smem[2] + smem[3];
-    return base + inc - v;
-}
-
 // One workgroup per row: exact k-th key by 4 radix passes, compaction in index order (ties ->
 // lowest index), bitonic sort of the k winners by (key, index).
 template <int EPT>
 __global__ __launch_bounds__(256) void topk_select_kernel(const float *__restrict__ S, int M, int k, int32_t *__restrict__ idx) {
     __shared__ int hist[256];
-    __shared__ int sc[8];
+    __shared__ int sc[4];
     __shared__ int bc[4];
     __shared__ unsigned long long sel[512];
     const size_t row = blockIdx.x;
@@ -241,7 +223,7 @@ __global__ __launch_bounds__(256) void topk_select_kernel(const float *__restric
         __syncthreads();
         int total;
         int mine = hist[tid];
-        int excl = block_exclusive_scan(mine, sc, total);
+        int excl = block_exclusive_scan<256>(mine, sc, total);
         if (excl < remaining && excl + mine >= remaining) {  // exactly one bin
             bc[0] = tid;
             bc[1] = excl;
@@ -263,8 +245,8 @@ __global__ __launch_bounds__(256) void topk_select_kernel(const float *__restric
         }
     }
     int tot_lt, tot_eq;
-    int plt = block_exclusive_scan(nlt, sc, tot_lt);
-    int peq = block_exclusive_scan(neq, sc, tot_eq);
+    int plt = block_exclusive_scan<256>(nlt, sc, tot_lt);
+    int peq = block_exclusive_scan<256>(neq, sc, tot_eq);
     int kp2 = 1;
     while (kp2 < k) kp2 <<= 1;
     for (int e = tid; e < kp2; e += 256) sel[e] = ~0ull;

@@ -61,27 +61,8 @@ __global__ __launch_bounds__(MG_THREADS) void mesh_corner_count_kernel(const int
 // offs [V + 1] = exclusive scan of count [V] (one workgroup), cursor [V] = offs [V]
 __global__ __launch_bounds__(MG_SCAN_THREADS) void mesh_corner_scan_kernel(const int32_t *__restrict__ count, int V, int32_t *__restrict__ offs,
                                                                           int32_t *__restrict__ cursor) {
-    __shared__ int32_t part[MG_SCAN_THREADS];
-    const int tid = threadIdx.x;
-    const int per = (V + MG_SCAN_THREADS - 1) / MG_SCAN_THREADS;
-    const int lo = min(tid * per, V), hi = min(lo + per, V);
-    int32_t sum = 0;
-    for (int v = lo; v < hi; ++v) sum += count[v];
-    part[tid] = sum;
-    __syncthreads();
-    for (int o = 1; o < MG_SCAN_THREADS; o <<= 1) {   // inclusive scan of the threads' sums
-        const int32_t add = tid >= o ? part[tid - o] : 0;
-        __syncthreads();
-        part[tid] += add;
-        __syncthreads();
-    }
-    int32_t run = part[tid] - sum;
-    for (int v = lo; v < hi; ++v) {
-        offs[v] = run;
-        cursor[v] = run;
-        run += count[v];
-    }
-    if (tid == MG_SCAN_THREADS - 1) offs[V] = part[tid];
+    const int total = block_scan_counts<MG_SCAN_THREADS>(V, [&](int v) { return count[v]; }, [&](int v, int run) { offs[v] = cursor[v] = run; });
+    if (threadIdx.x == 0) offs[V] = total;
 }
 
 __device__ __forceinline__ void corner_fill(const double *__restrict__ verts, int v, int a, int b, int32_t *__restrict__ cursor,

@@ -103,7 +103,7 @@ __global__ __launch_bounds__(256) void n2p_core_fwd_kernel(const float *__restri
 
 // ---- backward.  Point pass: de (scaled by 1/sqrt(D)) for every (point, neighbour, head) and dq by gathering
 // kp rows.  The scatter side (dkp_j += de q_i, dvp_j += a g_i) is turned into a gather as well: a counting
-// sort of idx gives every target row its list of (point, slot) references (CSR), and one wave per target row
+// sort of idx gives every target row its list of (point, slot) references (CSR; dvm_revlist.hip), and one wave per target row
 // sums its in-edges in registers — 40 int atomics per point instead of 80 x C float atomics.
 template <int C>
 __global__ __launch_bounds__(256) void n2p_bwd_point_kernel(const float *__restrict__ qkv, const int32_t *__restrict__ idx,
@@ -155,179 +155,10 @@ __global__ __launch_bounds__(256) void n2p_bwd_point_kernel(const float *__restr
     if (valid && sub == 0) *(f32x4 *)(dqkv + (base + pt) * L::LD + 4 * l) = dq;
 }
 
-__global__ void csr_count_kernel(const int32_t *__restrict__ idx, int N, int K, int32_t *__restrict__ cnt) {
-    const int b = blockIdx.y;
-    const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= (long)N * K) return;
-    atomicAdd(cnt + (size_t)b * (N + 1) + idx[(size_t)b * N * K + e], 1);
-}
-
-// exclusive scan of cnt[b][0..N) in place -> offs (cnt[b][N] = total); cursor = copy of the offsets
-__global__ __launch_bounds__(1024) void csr_scan_kernel(int32_t *__restrict__ cnt, int N, int32_t *__restrict__ cursor) {
-    __shared__ int part[1024];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    int32_t *c = cnt + (size_t)b * (N + 1);
-    const int per = (N + 1023) / 1024;
-    const int lo = min(N, tid * per), hi = min(N, lo + per);
-    int s = 0;
-    for (int i = lo; i < hi; ++i) s += c[i];
-    part[tid] = s;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        int v = tid >= o ? part[tid - o] : 0;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    int run = part[tid] - s;  // exclusive prefix of this thread's chunk
-    for (int i = lo; i < hi; ++i) {
-        const int v = c[i];
-        c[i] = run;
-        cursor[(size_t)b * N + i] = run;
-        run += v;
-    }
-    if (tid == 1023) c[N] = part[1023];
-}
-
-// edges[pos] = (e, source point) with e = point * K + slot (the point is stored, not derived: an integer division by the
-// run-time K per edge was a fifth of the gather kernel's instructions)
-__global__ void csr_fill_kernel(const int32_t *__restrict__ idx, int N, int K, int32_t *__restrict__ cursor,
-                                int2 *__restrict__ edges) {
-    const int b = blockIdx.y;
-    const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= (long)N * K) return;
-    const int pos = atomicAdd(cursor + (size_t)b * N + idx[(size_t)b * N * K + e], 1);
-    edges[(size_t)b * N * K + pos] = make_int2((int)e, (int)(e / K));
-}
-
 // dkp_r = sum over the in-edges (i -> r) of de_i,slot * q_i (per head), dvp_r = sum a_i,slot * g_i - g_r.
 // One wave per target point; a lane owns 4 consecutive channels (16-byte loads), so a row takes C/4 lanes and the wave
 // walks 64 / (C/4) in-edges per instruction (4 at C = 64, 2 at C = 128), two such groups in flight; the partial sums of
 // the edge slots are combined at the end.  (One float per lane and one edge per instruction before: 213 / 192 us.)
-// The three kernels above in one, for clouds whose counters fit in LDS (2 (N + 1) ints): ONE workgroup per cloud counts,
-// scans and fills with LDS atomics — 8 workgroups instead of 3 launches of global atomics (35 + 5 + 46 us per layer at
-// 8 x 2048 x 40); it runs beside the other stream's kernels, and the order inside a list carries no contract (the gather
-// sums fp32 either way).
-__global__ __launch_bounds__(1024) void csr_build_lds_kernel(const int32_t *__restrict__ idx, int N, int K, int32_t *__restrict__ offs,
-                                                             int2 *__restrict__ edges) {
-    extern __shared__ int csr_lds[];          // cnt[N + 1] | cursor[N]
-    __shared__ int part[1024];
-    int *cnt = csr_lds, *cursor = csr_lds + N + 1;
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const int32_t *ib = idx + (size_t)b * N * K;
-    const int E = N * K;
-    for (int i = tid; i <= N; i += 1024) cnt[i] = 0;
-    __syncthreads();
-    // (8 index loads in flight per thread: one workgroup per cloud has only its own 16 waves to cover the load latency)
-    for (int e0 = tid; e0 < E; e0 += 8 * 1024) {
-        int t[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) t[u] = e0 + u * 1024 < E ? ib[e0 + u * 1024] : -1;
-#pragma unroll
-        for (int u = 0; u < 8; ++u)
-            if (t[u] >= 0) atomicAdd(&cnt[t[u]], 1);
-    }
-    __syncthreads();
-    const int per = (N + 1023) / 1024;
-    const int lo = min(N, tid * per), hi = min(N, lo + per);
-    int s = 0;
-    for (int i = lo; i < hi; ++i) s += cnt[i];
-    part[tid] = s;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        const int v = tid >= o ? part[tid - o] : 0;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    int run = part[tid] - s;  // exclusive prefix of this thread's chunk
-    int32_t *ob = offs + (size_t)b * (N + 1);
-    for (int i = lo; i < hi; ++i) {
-        const int v = cnt[i];
-        cursor[i] = run;
-        ob[i] = run;
-        run += v;
-    }
-    if (tid == 1023) ob[N] = part[1023];
-    __syncthreads();
-    int2 *eb = edges + (size_t)b * E;
-    for (int e0 = tid; e0 < E; e0 += 8 * 1024) {
-        int t[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) t[u] = e0 + u * 1024 < E ? ib[e0 + u * 1024] : -1;
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            if (t[u] < 0) continue;
-            const int e = e0 + u * 1024;
-            const int pos = atomicAdd(&cursor[t[u]], 1);
-            eb[pos] = make_int2(e, e / K);
-        }
-    }
-}
-
-// Deterministic mode (dvm_set_deterministic): the reversed lists in ASCENDING EDGE ORDER without atomics between threads.
-// The edges of a cloud are cut into DET_CHUNKS contiguous chunks: (1) a histogram of targets per chunk (LDS counters, integer
-// atomics inside one workgroup: order-free), (2) per target an exclusive scan over the chunks on top of the exclusive scan
-// over the targets (= offs), (3) every chunk placed by ONE thread walking its edges in order from those bases.
-constexpr int DET_CHUNKS = 64;
-__global__ __launch_bounds__(256) void csr_det_hist_kernel(const int32_t *__restrict__ idx, int N, int K, int32_t *__restrict__ hist) {
-    extern __shared__ int csr_lds[];   // cnt[N]
-    const int b = blockIdx.y, ch = blockIdx.x;
-    const int E = N * K, per = (E + DET_CHUNKS - 1) / DET_CHUNKS, e0 = ch * per, e1 = min(E, e0 + per);
-    for (int i = threadIdx.x; i < N; i += blockDim.x) csr_lds[i] = 0;
-    __syncthreads();
-    const int32_t *ib = idx + (size_t)b * E;
-    for (int e = e0 + threadIdx.x; e < e1; e += blockDim.x) atomicAdd(&csr_lds[ib[e]], 1);
-    __syncthreads();
-    int32_t *h = hist + ((size_t)b * DET_CHUNKS + ch) * N;
-    for (int i = threadIdx.x; i < N; i += blockDim.x) h[i] = csr_lds[i];
-}
-// hist[b][ch][t] -> base position of chunk ch's first edge into target t; offs[b][0..N]
-__global__ __launch_bounds__(1024) void csr_det_scan_kernel(int32_t *__restrict__ hist, int N, int32_t *__restrict__ offs) {
-    __shared__ int part[1024];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    int32_t *h = hist + (size_t)b * DET_CHUNKS * N;
-    const int per = (N + 1023) / 1024, lo = min(N, tid * per), hi = min(N, lo + per);
-    int s = 0;
-    for (int t = lo; t < hi; ++t)
-        for (int ch = 0; ch < DET_CHUNKS; ++ch) s += h[(size_t)ch * N + t];
-    part[tid] = s;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        const int v = tid >= o ? part[tid - o] : 0;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    int run = part[tid] - s;
-    int32_t *ob = offs + (size_t)b * (N + 1);
-    for (int t = lo; t < hi; ++t) {
-        ob[t] = run;
-        for (int ch = 0; ch < DET_CHUNKS; ++ch) {
-            const int v = h[(size_t)ch * N + t];
-            h[(size_t)ch * N + t] = run;
-            run += v;
-        }
-    }
-    if (tid == 1023) ob[N] = part[1023];
-}
-__global__ __launch_bounds__(256) void csr_det_fill_kernel(const int32_t *__restrict__ idx, int N, int K, const int32_t *__restrict__ hist,
-                                                           int2 *__restrict__ edges) {
-    extern __shared__ int csr_lds[];   // cursor[N]
-    const int b = blockIdx.y, ch = blockIdx.x;
-    const int E = N * K, per = (E + DET_CHUNKS - 1) / DET_CHUNKS, e0 = ch * per, e1 = min(E, e0 + per);
-    const int32_t *h = hist + ((size_t)b * DET_CHUNKS + ch) * N;
-    for (int i = threadIdx.x; i < N; i += blockDim.x) csr_lds[i] = h[i];
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    const int32_t *ib = idx + (size_t)b * E;
-    int2 *eb = edges + (size_t)b * E;
-    for (int e = e0; e < e1; ++e) {
-        const int pos = csr_lds[ib[e]]++;
-        eb[pos] = make_int2(e, e / K);
-    }
-}
-
 template <int C>
 __global__ __launch_bounds__(256) void n2p_bwd_gather_kernel(const float *__restrict__ qkv, const float *__restrict__ attn,
                                                              const float *__restrict__ de_buf, const float *__restrict__ gout,
@@ -395,15 +226,11 @@ DVM_EXPORT int dvm_n2p_core_fwd_f32(const float *qkv, const int32_t *idx, int B,
 
 struct N2pBwdWs {
     float *de;
-    int32_t *offs, *cursor, *hist;   // hist: per-chunk histograms of the deterministic list build
-    int2 *edges;
+    RevListsT<int2> rev;   // the reversed neighbour lists (entry, source point), with the ordered build's histograms
 };
 static size_t carve_n2p_bwd(Arena &ar, int B, int N, int K, N2pBwdWs &w) {
     w.de = ar.take<float>((size_t)B * N * K * NP_H);
-    w.offs = ar.take<int32_t>((size_t)B * (N + 1));
-    w.cursor = ar.take<int32_t>((size_t)B * N);
-    w.edges = ar.take<int2>((size_t)B * N * K);
-    w.hist = ar.take<int32_t>((size_t)B * DET_CHUNKS * N);
+    w.rev.take(ar, B, N, (size_t)N * K, true);
     return ar.off;
 }
 
@@ -419,27 +246,12 @@ DVM_EXPORT int dvm_n2p_core_bwd_f32(const float *qkv, const int32_t *idx, const 
     N2pBwdWs w;
     if (!carve_ws(ws, ws_bytes, "dvm_n2p_core_bwd_f32", w, carve_n2p_bwd, B, N, K)) return DVM_ENOSPACE;
     float *const de = w.de;
-    int32_t *const offs = w.offs, *const cursor = w.cursor, *const hist = w.hist;
-    int2 *const edges = w.edges;
+    const int32_t *const offs = w.rev.offs;
+    const int2 *const edges = w.rev.edges;
     hipStream_t s = (hipStream_t)stream;
-    dim3 grid((N + 3) / 4, B), egrid((unsigned)(((long)N * K + 255) / 256), B);
-    const size_t csr_lds = (size_t)(2 * N + 1) * sizeof(int);
-    // (one workgroup per cloud: from 4 clouds on; fewer, larger clouds keep the chip busier with the three-kernel form)
-    if (deterministic() && (size_t)N * sizeof(int) <= 96 * 1024) {
-        ensure_dyn_lds((const void *)csr_det_hist_kernel, (int)(N * sizeof(int)));
-        ensure_dyn_lds((const void *)csr_det_fill_kernel, (int)(N * sizeof(int)));
-        hipLaunchKernelGGL(csr_det_hist_kernel, dim3(DET_CHUNKS, B), dim3(256), (size_t)N * sizeof(int), s, idx, N, K, hist);
-        hipLaunchKernelGGL(csr_det_scan_kernel, dim3(B), dim3(1024), 0, s, hist, N, offs);
-        hipLaunchKernelGGL(csr_det_fill_kernel, dim3(DET_CHUNKS, B), dim3(256), (size_t)N * sizeof(int), s, idx, N, K, hist, edges);
-    } else if (B >= 4 && csr_lds <= 96 * 1024 && (long)N * K < (1L << 31)) {
-        ensure_dyn_lds((const void *)csr_build_lds_kernel, (int)csr_lds);
-        hipLaunchKernelGGL(csr_build_lds_kernel, dim3(B), dim3(1024), csr_lds, s, idx, N, K, offs, edges);
-    } else {
-        (void)hipMemsetAsync(offs, 0, (size_t)B * (N + 1) * sizeof(int32_t), s);
-        hipLaunchKernelGGL(csr_count_kernel, egrid, dim3(256), 0, s, idx, N, K, offs);
-        hipLaunchKernelGGL(csr_scan_kernel, dim3(B), dim3(1024), 0, s, offs, N, cursor);
-        hipLaunchKernelGGL(csr_fill_kernel, egrid, dim3(256), 0, s, idx, N, K, cursor, edges);
-    }
+    dim3 grid((N + 3) / 4, B);
+    const long E = (long)N * K;
+    launch_rev_lists(idx, B, E, N, K, w.rev, rev_route(B, E, N), s);
     if (C == 64) {
         hipLaunchKernelGGL(n2p_bwd_point_kernel<64>, grid, dim3(256), 0, s, qkv, idx, attn, g_out, N, K, de, d_qkv);
         hipLaunchKernelGGL(n2p_bwd_gather_kernel<64>, grid, dim3(256), 0, s, qkv, attn, de, g_out, offs, edges, N, K, d_qkv);

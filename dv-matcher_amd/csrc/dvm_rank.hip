@@ -3,7 +3,7 @@
 //
 // Row form: with S = P P^T,   F^2 = sum_i [ (S_ii - 1)^2 + sum_{i' != i} S_ii'^2 ]  — every term non-negative, nothing cancels, and
 // row i of S is non-zero only at rows i' that share a column with row i.  The entries of every column come from the reversed lists
-// of launch_rev_csr (dvm_geom.hip).  One workgroup per row i:
+// of launch_rev_csr (dvm_revlist.hip).  One workgroup per row i:
 //   1. row i of S in LDS (N fp32 words): for slot t = 0..topk-1 in turn, walk the list of column pi_idx[i,t] and add
 //      pi_val[i,t] * val(e) into S[row(e)].  The rows of one column are distinct and a barrier separates the slots, so no two threads
 //      touch one word: no LDS atomics, and S[i'] takes its (at most topk) terms in slot order whatever the order of the lists.

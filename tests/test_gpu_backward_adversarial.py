@@ -26,7 +26,8 @@ apply_bwd and n2p_core_bwd: float64 autograd, per row; the bar is K 2^-24 times 
 terms that reach the row (for N2P propagated through the softmax, with the attention's own rounding).  Indices: hubs of in-degree
 95 / 96 / 97 / 150 / 400 around the gather's heavy threshold (AG_HEAVY = 96), four heavy targets in one workgroup, a heavy last
 target with M % 4 != 0, one target holding every edge, out-of-range and negative indices (no contribution, d_val = 0); N2P: a hub,
-self-loops, all slots equal, each in-edge list route by the shape that selects it.
+self-loops, all slots equal, each in-edge list route by the shape that selects it.  Both also at the edges of the list
+builder's workgroup scan (csrc/dvm_revlist.hip, block_scan_counts): 1, 1023, 1025 and 2049 targets against its 1024 threads.
 """
 import zlib
 
@@ -366,6 +367,20 @@ def test_apply_bwd_topk_channels(ops, k, C, atomics):
     apply_check(ops, val, idx, V, gout, atomics)
 
 
+@pytest.mark.parametrize("atomics", [False, True])
+@pytest.mark.parametrize("M", [1, 1023, 1025, 2049])
+def test_apply_bwd_scan_edges(ops, M, atomics):
+    """M at the edges of the list scan's 1024 threads (one target; one short of a counter per thread; 2 and 3 counters per
+    thread with trailing threads that own none); the last target holds half of the entries."""
+    B, N, k, C = 2, 64, 10, 8
+    val, V, gout, g = apply_inputs(B, N, M, k, C, M)
+    idx = torch.randint(0, M, (B, N, k), generator=g, dtype=torch.int32)
+    if M > 1:                                          # (M = 1: target 0 = M - 1 holds every entry already)
+        for e in range(B):
+            plant(idx, e, {M - 1: N * k // 2}, g, M)
+    apply_check(ops, val, idx, V, gout, atomics)
+
+
 # ------------------------------------------------------------------------------------------------------------- N2P backward
 def n2p_check(ops, qkv, idx, gout, H=4):
     """d_qkv per row against float64 autograd of models/model.py:339-350; bar: K 2^-24 times the float64 absolute terms of each
@@ -412,7 +427,7 @@ def n2p_inputs(B, N, C, Kn, family, seed):
     gout = torch.randn(B, N, C, generator=g)
     idx = torch.randint(0, N, (B, N, Kn), generator=g, dtype=torch.int32)
     if family == "hub":                       # every point lists point 5 (in-degree N), one entry also at its last point
-        idx[:, :, 0] = 5
+        idx[:, :, 0] = min(5, N - 1)
         idx[-1, :, -1] = N - 1
     elif family == "self":                    # self-loops in every list (kd = vd = 0 on that slot)
         idx[:, :, Kn // 2] = torch.arange(N, dtype=torch.int32)
@@ -444,6 +459,27 @@ def test_n2p_bwd_routes(ops, B, N, Kn, family, C):
 def test_n2p_bwd_lds_cap(ops, N, family):
     qkv, idx, gout = n2p_inputs(4, N, 64, 8, family, seed=N)
     n2p_check(ops, qkv, idx, gout)
+
+
+@pytest.mark.parametrize("family", ["random", "hub"])
+@pytest.mark.parametrize("B,N,Kn,det", [(B, N, Kn, det) for det in (False, True) for B, N, Kn in [
+    (1, 1, 1),      # one counter: every scan thread but the first owns an empty chunk
+    (1, 1025, 8),   # 2 counters per scan thread, 511 trailing threads with none; global route
+    (4, 1025, 8),   # the same on the LDS route
+    (4, 2049, 8),   # 3 counters per thread: chunk boundaries off the wave boundaries
+]] + [(4, 205, 40, False)])   # 8200 entries: one past the LDS build's 8 x 1024 stride
+def test_n2p_bwd_scan_edges(ops, B, N, Kn, det, family):
+    """The list builder's shared scan at its edges (block_scan_counts: per = ceil(N / 1024)), on every route: global and LDS by
+    B, ordered under dvm_set_deterministic (det) with two calls bit for bit."""
+    qkv, idx, gout = n2p_inputs(B, N, 64, Kn, family, seed=B * N + Kn)
+    prev = ops.set_deterministic(det)
+    try:
+        d1 = n2p_check(ops, qkv, idx, gout)
+        if det:
+            out, attn = ops.n2p_core_fwd(qkv.cuda(), idx.cuda(), 4)
+            assert torch.equal(d1, ops.n2p_core_bwd(qkv.cuda(), idx.cuda(), attn, gout.cuda(), 4))
+    finally:
+        ops.set_deterministic(prev)
 
 
 @pytest.mark.parametrize("family", ["random", "hub", "same"])
