@@ -838,17 +838,21 @@ DVM_EXPORT int dvm_softcorr_apply_f32(const float *pi_val, const int32_t *pi_idx
     DVM_REQUIRE(pi_val && pi_idx && V && out, "dvm_softcorr_apply_f32: null pointer");
     DVM_REQUIRE(B >= 1 && N >= 1 && M >= 1 && C >= 1, "dvm_softcorr_apply_f32: empty input");
     DVM_REQUIRE(topk >= 1 && topk <= 16, "dvm_softcorr_apply_f32: topk=%d unsupported (1..16)", topk);
-    long threads = (long)N * ((C + 3) / 4);
-    dim3 grid((unsigned)((threads + 255) / 256), B), block(256);
-    if (topk <= 10)
-        hipLaunchKernelGGL(apply_kernel<10>, grid, block, 0, (hipStream_t)stream, pi_val, pi_idx, V, N, M, topk, C, out);
-    else
-        hipLaunchKernelGGL(apply_kernel<16>, grid, block, 0, (hipStream_t)stream, pi_val, pi_idx, V, N, M, topk, C, out);
+    launch_apply(pi_val, pi_idx, V, B, N, M, topk, C, out, (hipStream_t)stream);
     DVM_CHECK_LAUNCH("softcorr_apply");
     return DVM_OK;
 }
 
 namespace dvm {
+// dvm_softcorr_apply_f32 without its checks (topk <= 16; every index must lie in [0, M): it becomes an address)
+void launch_apply(const float *pi_val, const int32_t *pi_idx, const float *V, int B, int N, int M, int topk, int C, float *out, hipStream_t s) {
+    long threads = (long)N * ((C + 3) / 4);
+    dim3 grid((unsigned)((threads + 255) / 256), B), block(256);
+    if (topk <= 10)
+        hipLaunchKernelGGL(apply_kernel<10>, grid, block, 0, s, pi_val, pi_idx, V, N, M, topk, C, out);
+    else
+        hipLaunchKernelGGL(apply_kernel<16>, grid, block, 0, s, pi_val, pi_idx, V, N, M, topk, C, out);
+}
 // The pieces of dvm_softcorr_apply_bwd_f32's gather form, for callers that keep the reversed lists (dvm_criterion_train.hip)
 void launch_apply_bwd_dval(const float *pi_val, const int32_t *pi_idx, const float *V, const float *g_out, int B, int N, int M, int topk, int C,
                            float *d_val, hipStream_t s) {

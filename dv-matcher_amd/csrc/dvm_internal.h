@@ -56,6 +56,8 @@ int launch_mean_grouped(const float *const *in, const int *n, float *const *out,
 int map_term_blocks(int N, int k);
 int launch_map_term(const float *verts12, const float *verts2, const int32_t *idx11, const int32_t *idx22, const float *pi_val, const int32_t *pi_idx,
                     int B, int N, int M, int k, int topk, double *partial, hipStream_t s, float *resid = nullptr);
+// out [B][N][C] = Pi V, the launches of dvm_softcorr_apply_f32 (topk <= 16; every index in [0, M))
+void launch_apply(const float *pi_val, const int32_t *pi_idx, const float *V, int B, int N, int M, int topk, int C, float *out, hipStream_t s);
 void launch_apply_bwd_dval(const float *pi_val, const int32_t *pi_idx, const float *V, const float *g_out, int B, int N, int M, int topk, int C, float
                            *d_val, hipStream_t s);
 void launch_apply_bwd_gather(const float *pi_val, const float *g_out, const int32_t *offs, const int32_t *edges, int B, int N, int M, int topk, int C,

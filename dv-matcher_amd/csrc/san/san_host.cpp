@@ -314,6 +314,10 @@ int main() {
         SHORT(dvm_rank_term_workspace_bytes(B, N, M, 10), dvm_rank_term_f32(F, I, B, N, M, 10, F, F, ws, q - 1, nullptr));
         SHORT(dvm_cycle_term_workspace_bytes(B, N, M, 10, 10), dvm_cycle_term_f32(F, I, F, I, B, N, M, 10, 10, F, F, F, ws, q - 1, nullptr));
         SHORT(dvm_distortion_term_workspace_bytes(B, N, M, 10), dvm_distortion_term_f32(F, I, F, F, B, N, M, 10, F, F, ws, q - 1, nullptr));
+        SHORT(dvm_mesh_laplacian_workspace_bytes(B, N, 2 * N), dvm_mesh_laplacian_f32(F, I, B, N, 2 * N, I, I, F, F, F, I, ws, q - 1, nullptr));
+        SHORT(dvm_knn_laplacian_workspace_bytes(B, N, 10, 0), dvm_knn_laplacian_f32(F, I, B, N, 10, 0, I, I, F, F, I, ws, q - 1, nullptr));
+        SHORT(dvm_dirichlet_term_workspace_bytes(B, N, M, 10, 3, 20 * N),
+              dvm_dirichlet_term_f32(F, I, F, I, I, F, B, N, M, 10, 3, 20 * N, F, F, ws, q - 1, nullptr));
         SHORT(dvm_pair_direction_workspace_bytes(B, N, M),
               dvm_pair_direction_fwd_f32(F, F, F, F, B, N, M, -1.f, I, F, F, F, F, F, F, F, F, F, F, 1, F, F, I, F, ws, q - 1, nullptr));
         SHORT(dvm_pair_workspace_bytes(B, N, M),

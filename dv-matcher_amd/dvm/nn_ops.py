@@ -579,7 +579,7 @@ class _SparseApply(torch.autograd.Function):
 
 class _FrobTerm(torch.autograd.Function):
     """A sparse Frobenius-norm term per batch element on its HIP kernel (dvm_rank_term_f32, dvm_cycle_term_f32,
-    dvm_distortion_term_f32): the forward call op(*args, grad=True) returns the gradients as well (the residual row is in LDS then), one
+    dvm_distortion_term_f32; dvm_dirichlet_term_f32 shares the calling pattern): the forward call op(*args, grad=True) returns the gradients as well (the residual row is in LDS then), one
     per positional input named in `diff`, and the backward only scales them.  Every other input is a constant."""
 
     @staticmethod
@@ -620,6 +620,17 @@ def distortion_term(val, idx, dist_src, dist_tgt):
     if not (torch.is_grad_enabled() and val.requires_grad):
         return ops.distortion_term(val, idx, dist_src, dist_tgt)
     return _FrobTerm.apply(ops.distortion_term, (0,), val, idx, dist_src, dist_tgt)
+
+
+def dirichlet_term(val, idx, V, op):
+    """(B,) Dirichlet energy 1/2 sum_entries w |y_i - y_j|^2 of Y = Pi V for the sparse correspondence val / idx (B,N,k), the target's
+    values V (B,M,C) and the source's ops.GraphOperator op, with autograd w.r.t. val only: V and the operator are data, and a V
+    that requires grad is refused.  Without grad it is ops.dirichlet_term: no gradient is formed."""
+    if torch.is_tensor(V) and V.requires_grad:
+        raise ValueError("dirichlet_term: V is data (the target's values); it must not require grad")
+    if not (torch.is_grad_enabled() and val.requires_grad):
+        return ops.dirichlet_term(val, idx, V, op)
+    return _FrobTerm.apply(ops.dirichlet_term, (0,), val, idx, V, op)
 
 
 class _DistLoss(torch.autograd.Function):

@@ -981,6 +981,93 @@ def distortion_term(val, idx, dist_src, dist_tgt, grad=False):
     return _frob_term("distortion", (_p(val), _p(idx), _p(dist_src), _p(dist_tgt)), (B, N, M, topk), (val,), grad)
 
 
+class GraphOperator:
+    """A weighted neighbour matrix of B source shapes in CSR (mesh_laplacian, knn_laplacian; the layout and the row order are in
+    include/dvm.h): rowptr (B,N+1) int32, col (B,Ecap) int32, w (B,Ecap), norm (B,) = the energy of the shape's own coordinates,
+    mass (B,N) or None, stats (B,4) int32 = entries' owners left out for an index out of range, for degenerate geometry, self
+    entries, entries kept.  Constants: no gradient flows into them."""
+    __slots__ = ("rowptr", "col", "w", "norm", "mass", "stats")
+
+    def __init__(self, rowptr, col, w, norm, mass, stats):
+        self.rowptr, self.col, self.w, self.norm, self.mass, self.stats = rowptr, col, w, norm, mass, stats
+
+    @property
+    def N(self):
+        return self.rowptr.shape[1] - 1
+
+    @property
+    def Ecap(self):
+        return self.col.shape[1]
+
+
+LAPLACIAN_MODES = {"stretch": 0, "uniform": 1}
+
+
+def mesh_laplacian(verts, faces):
+    """The cotangent operator of the triangle meshes (verts (B,N,3), faces (F,3) shared by the batch) -> GraphOperator with
+    Ecap = 6 F, mass = one third of the incident face areas, norm = 2 x the total area.  Faces with an index outside [0,N) or a
+    degenerate corner are left out and counted in stats (never read back here: no synchronisation).  dvm_mesh_laplacian_f32."""
+    _need_gpu(verts, faces)
+    verts, faces = _f(verts), _i(faces)
+    if verts.dim() != 3 or verts.shape[2] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError("mesh_laplacian: verts must be (B,N,3) and faces (F,3), got %s and %s" % (tuple(verts.shape), tuple(faces.shape)))
+    B, N, _ = verts.shape
+    F = faces.shape[0]
+    dev = verts.device
+    op = GraphOperator(_new(dev, B, N + 1, dtype=torch.int32), _new(dev, B, 6 * F, dtype=torch.int32), _new(dev, B, 6 * F), _new(dev, B),
+                       _new(dev, B, N), _new(dev, B, 4, dtype=torch.int32))
+    _call_ws("dvm_mesh_laplacian_f32", (_p(verts), _p(faces), B, N, F, _p(op.rowptr), _p(op.col), _p(op.w), _p(op.norm), _p(op.mass),
+                                        _p(op.stats)), dev, "laplacian", "dvm_mesh_laplacian_workspace_bytes", B, N, F)
+    return op
+
+
+def knn_laplacian(xyz, nbr, mode="stretch"):
+    """The operator W + W^T of a neighbour list (xyz (B,N,3), nbr (B,N,K) as knn_cdist returns it, self included) -> GraphOperator
+    with Ecap = 2 N K, mass None.  mode "stretch": w = 1 / |x_i - x_j|^2, norm = half the kept entries; "uniform": w = 1,
+    norm = 1/2 sum w |x_i - x_j|^2.  Self entries, indices outside [0,N) and (stretch) zero distances are left out and counted.
+    dvm_knn_laplacian_f32."""
+    if mode not in LAPLACIAN_MODES:
+        raise ValueError("knn_laplacian: mode must be 'stretch' or 'uniform', got %r" % (mode,))
+    _need_gpu(xyz, nbr)
+    xyz, nbr = _f(xyz), _i(nbr)
+    if xyz.dim() != 3 or xyz.shape[2] != 3 or nbr.dim() != 3 or tuple(nbr.shape[:2]) != tuple(xyz.shape[:2]):
+        raise ValueError("knn_laplacian: xyz must be (B,N,3) and nbr (B,N,K), got %s and %s" % (tuple(xyz.shape), tuple(nbr.shape)))
+    B, N, K = nbr.shape
+    dev = xyz.device
+    E = 2 * N * K
+    op = GraphOperator(_new(dev, B, N + 1, dtype=torch.int32), _new(dev, B, E, dtype=torch.int32), _new(dev, B, E), _new(dev, B), None,
+                       _new(dev, B, 4, dtype=torch.int32))
+    m = LAPLACIAN_MODES[mode]
+    _call_ws("dvm_knn_laplacian_f32", (_p(xyz), _p(nbr), B, N, K, m, _p(op.rowptr), _p(op.col), _p(op.w), _p(op.norm), _p(op.stats)), dev,
+             "laplacian", "dvm_knn_laplacian_workspace_bytes", B, N, K, m)
+    return op
+
+
+def dirichlet_term_takes(B, N, M, k, C, Ecap):
+    """Whether dvm_dirichlet_term_f32 takes these sizes (its workspace query answers 0 exactly when it refuses).  No device is needed."""
+    return int(_lib.load().dvm_dirichlet_term_workspace_bytes(B, N, M, k, C, Ecap)) > 0
+
+
+def dirichlet_term(val, idx, V, op, grad=False):
+    """The Dirichlet energy E = 1/2 sum_entries w |y_i - y_j|^2 of Y = Pi V per batch element, for the sparse Pi (val / idx (B,N,k),
+    columns in [0, M)), the target's values V (B,M,C), C <= 16, and the source's GraphOperator op -> loss (B,), and with grad=True
+    also g_val (B,N,k) = d loss[b] / d val.  V and op are constants.  dvm_dirichlet_term_f32: Y has ops.apply's bits, the rest is
+    float64 in CSR order, no float atomics.  Takes no part in autograd itself (nn_ops.dirichlet_term is the node)."""
+    _need_gpu(val, idx, V, op.rowptr, op.col, op.w)
+    val, idx, V = _f(val), _i(idx), _f(V)
+    rowptr, col, w = _i(op.rowptr), _i(op.col), _f(op.w)
+    if val.dim() != 3 or idx.shape != val.shape:
+        raise ValueError("dirichlet_term: val and idx must share a shape (B,N,k), got %s and %s" % (tuple(val.shape), tuple(idx.shape)))
+    B, N, topk = val.shape
+    if V.dim() != 3 or V.shape[0] != B:
+        raise ValueError("dirichlet_term: V must be (%d,M,C), got %s" % (B, tuple(V.shape)))
+    if tuple(rowptr.shape) != (B, N + 1) or col.dim() != 2 or col.shape[0] != B or col.shape != w.shape:
+        raise ValueError("dirichlet_term: the operator must have rowptr %s and col / w (%d,Ecap), got %s, %s, %s"
+                         % ((B, N + 1), B, tuple(rowptr.shape), tuple(col.shape), tuple(w.shape)))
+    M, C = V.shape[1], V.shape[2]
+    return _frob_term("dirichlet", (_p(val), _p(idx), _p(V), _p(rowptr), _p(col), _p(w)), (B, N, M, topk, C, col.shape[1]), (val,), grad)
+
+
 def _pair_out(B, n, dev):
     """One direction's outputs of the pair calls: dict(warped, verts12, T12, losses[B,6])."""
     return dict(warped=_new(dev, B, n, 3), verts12=_new(dev, B, n, 3), T12=_new(dev, B, n, dtype=torch.int32), losses=_new(dev, B, 6))

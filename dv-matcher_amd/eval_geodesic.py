@@ -97,3 +97,34 @@ def mean_geodesic_error(phi_src, phi_tgt, vts_src, vts_tgt, M_tgt, faces_tgt=Non
         face, bary = match_precise(phi_src, phi_tgt, faces_tgt)
         return float(geodesic_errors_precise(face, bary, faces_tgt, vts_src, vts_tgt, M_tgt).mean())
     return float(geodesic_errors(match(phi_src, phi_tgt), vts_src, vts_tgt, M_tgt).mean())
+
+
+def map_dirichlet_energy(verts_src, faces_src, verts_tgt, T=None, face=None, bary=None, faces_tgt=None):
+    """The smoothness of a map beside its geodesic error: the Dirichlet energy of the target coordinates pulled back to the source
+    mesh, under the source's cotangent operator, over the energy of the source's own coordinates (2 x its area) — 1 for a map
+    that preserves local lengths, larger the more neighbouring source points are torn apart on the target.  Either a vertex map
+    T (N,) (0-based: one entry of value 1 per row) or a precise map face (N,), bary (N,3) with the target's faces_tgt (three
+    entries per row, the triangle's corners; a row without a face, face < 0, contributes nothing).  On the device
+    (dvm.ops.mesh_laplacian, dvm.ops.dirichlet_term)."""
+    import torch
+    from dvm import ops
+    vs = torch.as_tensor(np.ascontiguousarray(verts_src), dtype=torch.float32).cuda()[None]
+    vt = torch.as_tensor(np.ascontiguousarray(verts_tgt), dtype=torch.float32).cuda()[None]
+    fs = torch.as_tensor(np.ascontiguousarray(np.asarray(faces_src).reshape(-1, 3)), dtype=torch.int32).cuda()
+    if (T is None) == (face is None):
+        raise ValueError("map_dirichlet_energy: give either T or (face, bary, faces_tgt)")
+    if T is not None:
+        idx = torch.as_tensor(np.asarray(T).reshape(1, -1, 1).astype(np.int32)).cuda()
+        val = torch.ones(idx.shape, dtype=torch.float32, device=idx.device)
+    else:
+        if bary is None or faces_tgt is None:
+            raise ValueError("map_dirichlet_energy: a precise map needs face, bary and faces_tgt")
+        face = np.asarray(face).reshape(-1)
+        corners = np.asarray(faces_tgt).reshape(-1, 3)[np.maximum(face, 0)]
+        idx = torch.as_tensor(np.where(face[:, None] >= 0, corners, -1).astype(np.int32)).cuda()[None]
+        val = torch.as_tensor(np.ascontiguousarray(np.asarray(bary, dtype=np.float32).reshape(-1, 3))).cuda()[None]
+    if idx.shape[1] != vs.shape[1]:
+        raise ValueError("map_dirichlet_energy: the map has %d rows, the source mesh %d vertices" % (idx.shape[1], vs.shape[1]))
+    op = ops.mesh_laplacian(vs, fs)
+    E = ops.dirichlet_term(val, idx, vt, op)
+    return float((E.double() / op.norm.double())[0])

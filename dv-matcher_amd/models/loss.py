@@ -257,6 +257,46 @@ def distortion_term(pval, pidx, dist_src, dist_tgt, symmetric=False):
     return _distortion_term_torch(pval, pidx, dist_src, dist_tgt)
 
 
+def _dirichlet_term_torch(pval, pidx, V, op):
+    """dirichlet_term's energy (not normalised) with plain torch ops, for what the kernel does not take (CPU tensors, other dtypes,
+    refused sizes): Y = Pi V and 1/2 sum_entries w |y_i - y_j|^2 in float64 over the operator's CSR entries, rounded once to fp32.
+    op: anything with rowptr (B,N+1), col / w (B,Ecap) (ops.GraphOperator).  Slots and entries with an index out of range add
+    nothing.  The used length of every batch element is read back (one synchronisation per element on a device)."""
+    B, N, _ = pval.shape
+    Vd = V.detach().double()
+    M = Vd.shape[1]
+    ix = pidx.long()
+    ok = (ix >= 0) & (ix < M)
+    rows_of_V = Vd[torch.arange(B, device=ix.device)[:, None, None], torch.where(ok, ix, torch.zeros_like(ix))]   # (B,N,k,C)
+    Y = ((pval.double() * ok).unsqueeze(-1) * rows_of_V).sum(2)
+    out = []
+    for b in range(B):
+        rp = op.rowptr[b].long()
+        used = int(rp[N])
+        rows = torch.repeat_interleave(torch.arange(N, device=pval.device), rp[1:] - rp[:-1])[:used]
+        c, w = op.col[b, :used].long(), op.w[b, :used].double()
+        keep = (c >= 0) & (c < N)
+        d = Y[b][rows[keep]] - Y[b][c[keep]]
+        out.append(0.5 * (w[keep] * (d * d).sum(-1)).sum())
+    return torch.stack(out).float()
+
+
+def dirichlet_term(pval, pidx, V, op, normalize=True):
+    """The Dirichlet energy of the pulled-back target values Y = Pi V under the source shape's neighbour operator op
+    (ops.mesh_laplacian / ops.knn_laplacian): E = 1/2 sum_entries w |y_i - y_j|^2 per batch element — the smoothness of the map
+    (not in the reference).  normalize=True returns E / op.norm, which is 1 for a map that preserves local lengths.  Differentiable
+    w.r.t. pval only (V and the operator are data).  CUDA float32 input within the kernel's limits (k, C <= 16) runs on
+    dvm_dirichlet_term_f32 (nn_ops.dirichlet_term: float64 in CSR order, no float atomics); anything else on the torch formula of
+    _dirichlet_term_torch."""
+    ts = (pval, V, op.w)
+    if (all(t.is_cuda and t.dtype == torch.float32 for t in ts) and pval.dim() == 3 and V.dim() == 3 and op.col.dim() == 2
+            and ops.dirichlet_term_takes(pval.shape[0], pval.shape[1], V.shape[1], pval.shape[2], V.shape[2], op.col.shape[1])):
+        E = nn_ops.dirichlet_term(pval, pidx, V, op)
+    else:
+        E = _dirichlet_term_torch(pval, pidx, V, op)
+    return E / op.norm.to(E.dtype) if normalize else E
+
+
 class GraphDeformLoss_Neural(nn.Module):
     partial_variant = False
 
@@ -297,6 +337,13 @@ class GraphDeformLoss_Neural(nn.Module):
         # exactly the paths above; > 0 takes the paths w_cycle > 0 takes
         self.w_distortion = 0
         self.distortion_loss = 0
+        # opt-in: weight of the Dirichlet energy of both directions' pulled-back coordinates (dirichlet_term; not in the reference):
+        # Pi12 with verts2 under the operator of verts1 built from idx11, the xyz kNN list the criterion holds anyway
+        # (ops.knn_laplacian, dirichlet_mode "stretch" or "uniform"), and the mirror image with idx22; each E / norm, 1 for a map
+        # that keeps local lengths.  0 = off, on exactly the paths above; > 0 takes the paths w_distortion > 0 takes
+        self.w_dirichlet = 0
+        self.dirichlet_mode = "stretch"
+        self.dirichlet_loss = 0
         # opt-in: "geodesic" skins every vertex to the 3 nodes nearest by the distance matrices the criterion is handed (dist1 /
         # dist2; ops.dg_build_geod — what the reference's construct_graph_euclidean does with a `geod` that is not cdist);
         # graph_ring_metric = "geodesic" takes the ARAP rings from them as well.  Nodes (Euclidean FPS) and sigma stay.
@@ -389,7 +436,7 @@ class GraphDeformLoss_Neural(nn.Module):
         instead of batch scalars (for a caller that has merged several calls into one batch)."""
         B, N, _ = verts1.shape
         M = verts2.shape[1]
-        if (self.native_train and self.sinkhorn_iters <= 0 and not per_pair and not self.dump and self.w_rank <= 0 and self.w_cycle <= 0 and self.w_distortion <= 0 and feat1.is_cuda and feat1.dtype == torch.float32
+        if (self.native_train and self.sinkhorn_iters <= 0 and not per_pair and not self.dump and self.w_rank <= 0 and self.w_cycle <= 0 and self.w_distortion <= 0 and self.w_dirichlet <= 0 and feat1.is_cuda and feat1.dtype == torch.float32
                 and feat2.dtype == torch.float32 and feat1.shape[-1] == 128 and 64 <= N <= 8192 and 64 <= M <= 8192 and self.k_deform <= 16
                 and idx11.shape[-1] == self.k_deform and all(torch.is_tensor(g1[k]) for k in ("nodes_idx", "one_ring", "infl_idx", "weights"))
                 and all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() for p in deformer.parameters())):
@@ -595,7 +642,7 @@ class GraphDeformLoss_Neural(nn.Module):
         if self.w_deform > 0 or not self.partial_variant:
             g1, g2, idx11, idx22 = geometry if geometry is not None else self.geometry(verts1, verts2, fps_starts, shape_ids, (dist1, dist2))
             merged = (train and N == M and not self.dump and not self.partial_variant and self.w_rank <= 0 and self.w_cycle <= 0
-                      and self.w_distortion <= 0 and all(torch.is_tensor(g1[k]) for k in g1))
+                      and self.w_distortion <= 0 and self.w_dirichlet <= 0 and all(torch.is_tensor(g1[k]) for k in g1))
             native = (merged and self.native_train and self.sinkhorn_iters <= 0 and feat1.is_cuda and feat1.dtype == torch.float32 and feat1.shape[-1] == 128 and N % 4 == 0
                       and 64 <= N <= 8192 and self.k_deform <= 16 and idx11.shape[-1] == self.k_deform
                       and all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() for p in deformer.parameters()))
@@ -692,6 +739,11 @@ class GraphDeformLoss_Neural(nn.Module):
                 self.distortion_loss = self._pair_mean_term(self.w_distortion, distortion_term(ex12["pval"], ex12["pidx"], sym1, sym2, symmetric=True),
                                                             distortion_term(ex21["pval"], ex21["pidx"], sym2, sym1, symmetric=True))
                 loss = loss + self.distortion_loss
+            if self.w_dirichlet > 0:
+                op1, op2 = ops.knn_laplacian(verts1, idx11, self.dirichlet_mode), ops.knn_laplacian(verts2, idx22, self.dirichlet_mode)
+                self.dirichlet_loss = self._pair_mean_term(self.w_dirichlet, dirichlet_term(ex12["pval"], ex12["pidx"], verts2, op1),
+                                                           dirichlet_term(ex21["pval"], ex21["pidx"], verts1, op2))
+                loss = loss + self.dirichlet_loss
         return loss, self.dist_loss, self.deform_loss, self.map_loss, self.self_rec_loss
 
     def _pair_mean_term(self, w, t12, t21):

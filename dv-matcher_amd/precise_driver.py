@@ -16,6 +16,7 @@ runs.
   python dv-matcher_amd/precise_driver.py --pairs pair.npz --out result/demo [--ckpt ep_val_best.pth]
 """
 import argparse
+import json
 import os
 import sys
 
@@ -28,6 +29,7 @@ if HERE not in sys.path:
 
 import test_driver  # noqa: E402
 from dvm import ops  # noqa: E402
+from eval_geodesic import map_dirichlet_energy  # noqa: E402
 
 
 def load_faces(args):
@@ -57,6 +59,21 @@ def load_faces(args):
     raise ValueError("precise maps need the triangles of every shape, and synthetic pairs have none: pass --data-root or --pairs")
 
 
+def load_verts(args):
+    """{shape name: verts (N,3) float32} of the shapes load_faces names, from the same source (for the maps' Dirichlet energy)."""
+    if args.data_root:
+        from models.dataset import testDataset
+        data = testDataset(args.data_root, name=args.data_name, train=False)
+        used = sorted({i for pair in data.combinations for i in pair})
+        return {data.used_shapes[i]: np.asarray(data.verts_list[i], dtype=np.float32) for i in used}
+    out = {}
+    for path in args.pairs:
+        d = np.load(path, allow_pickle=False)
+        for k in ("1", "2"):
+            out[str(d["name" + k])] = np.asarray(d["verts" + k], dtype=np.float32)
+    return out
+
+
 def write_precise(save_path, name_src, name_tgt, face, bary):
     pdir = os.path.join(save_path, "P")
     os.makedirs(pdir, exist_ok=True)
@@ -76,6 +93,7 @@ def main(argv=None):
     args, _ = ap.parse_known_args(argv)
     if not ({"-h", "--help"} & set(argv)):
         tris = load_faces(args)                    # (before the backbone runs: a shape without triangles is an argument error)
+        xyz = load_verts(args)
     written = test_driver.write_results
 
     def write_with_precise(save_path, name1, name2, T12, T21, feat1, feat2):
@@ -84,9 +102,14 @@ def main(argv=None):
         dev = torch.device("cuda", torch.cuda.current_device())
         f = {name1: torch.from_numpy(np.ascontiguousarray(feat1, dtype=np.float32)).to(dev)[None],
              name2: torch.from_numpy(np.ascontiguousarray(feat2, dtype=np.float32)).to(dev)[None]}
-        for src, tgt in ((name1, name2), (name2, name1)):
+        for src, tgt, T in ((name1, name2, T12), (name2, name1, T21)):
             face, bary, _, _ = ops.precise_map(f[src], f[tgt], torch.from_numpy(tris[tgt]).to(dev), want_dist=False)
-            write_precise(save_path, src, tgt, face[0].cpu().numpy(), bary[0].cpu().numpy())
+            face, bary = face[0].cpu().numpy(), bary[0].cpu().numpy()
+            write_precise(save_path, src, tgt, face, bary)
+            # the smoothness of both maps (eval_geodesic.map_dirichlet_energy: 1 = local lengths kept); printed, no file
+            print(json.dumps({"pair": [src, tgt],
+                              "dirichlet_vertex": map_dirichlet_energy(xyz[src], tris[src], xyz[tgt], T=np.asarray(T).reshape(-1) - 1),   # (the T files are 1-based)
+                              "dirichlet_precise": map_dirichlet_energy(xyz[src], tris[src], xyz[tgt], face=face, bary=bary, faces_tgt=tris[tgt])}))
 
     test_driver.write_results = write_with_precise
     try:

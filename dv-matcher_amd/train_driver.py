@@ -236,6 +236,12 @@ def main(argv=None):
                     help="weight of the geodesic distortion term ||Pi D_target Pi^T - D_source||_F of both directions (criterion.w_distortion = W, "
                          "models.loss.distortion_term on the symmetrised distance matrices; not in the reference; the criterion leaves its "
                          "native nodes for the per-op path).  0: off")
+    ap.add_argument("--w-dirichlet", type=float, default=0.0, metavar="W",
+                    help="weight of the Dirichlet energy of both directions' pulled-back coordinates, E / norm under the source's xyz kNN "
+                         "operator (criterion.w_dirichlet = W, models.loss.dirichlet_term; not in the reference; the criterion leaves its "
+                         "native nodes for the per-op path).  0: off")
+    ap.add_argument("--dirichlet-mode", choices=("stretch", "uniform"), default="stretch",
+                    help="weights of that operator (criterion.dirichlet_mode): stretch = 1 / |x_i - x_j|^2, uniform = 1")
     ap.add_argument("--graph-metric", choices=("euclidean", "geodesic"), default="euclidean",
                     help="what skins the deformation graphs (criterion.graph_metric): 'geodesic' ties every vertex to the 3 nodes nearest by "
                          "the batch's distance matrices (ops.dg_build_geod), as the reference does with a geod that is not cdist; "
@@ -353,6 +359,9 @@ def main(argv=None):
     if args.w_distortion < 0:
         ap.error("--w-distortion must not be negative")
     crit.w_distortion = args.w_distortion
+    if args.w_dirichlet < 0:
+        ap.error("--w-dirichlet must not be negative")
+    crit.w_dirichlet, crit.dirichlet_mode = args.w_dirichlet, args.dirichlet_mode
     if args.graph_ring_metric == "geodesic" and args.graph_metric != "geodesic":
         ap.error("--graph-ring-metric geodesic needs --graph-metric geodesic")
     if args.graph_metric == "geodesic" and not (getattr(train_set, "carries_dist", False) and getattr(val_set, "carries_dist", False)):
@@ -547,7 +556,7 @@ def main(argv=None):
                                            "note": "algorithmic matrix flops of the whole step per GPU over the step time; the step is "
                                                    "~900 small launches, bound by the latency of its kernel chain (network forward -> criterion -> backward), not by the matrix pipe"},
                               "points": N, "points_target": M, "criterion": type(crit).__name__, "alpha": float(alpha),
-                              "sinkhorn_iters": crit.sinkhorn_iters, "sinkhorn_tau": crit.sinkhorn_tau, "w_cycle": crit.w_cycle, "w_distortion": crit.w_distortion, "graph_metric": crit.graph_metric, "graph_ring_metric": crit.graph_ring_metric, "hip_graph": use_graph, "graph_cache": bool(args.graph_cache),
+                              "sinkhorn_iters": crit.sinkhorn_iters, "sinkhorn_tau": crit.sinkhorn_tau, "w_cycle": crit.w_cycle, "w_distortion": crit.w_distortion, "w_dirichlet": crit.w_dirichlet, "dirichlet_mode": crit.dirichlet_mode, "graph_metric": crit.graph_metric, "graph_ring_metric": crit.graph_ring_metric, "hip_graph": use_graph, "graph_cache": bool(args.graph_cache),
                               "sync_stats": (None if not (args.sync_stats and dist_on) else
                                              {"native_node": getattr(net, "sync_stats", None) is not None,
                                               "native_calls": net.__dict__.get("native_train_calls", 0),
@@ -604,7 +613,7 @@ def main(argv=None):
                 save_ckpt(net, dfm, args.ckpt_dir, cfg["expname"], "val_best")
     if rank == 0:
         print(json.dumps({"epochs": epochs, "history": history, "best_val": best_val, "criterion": type(crit).__name__,
-                          "sinkhorn_iters": crit.sinkhorn_iters, "sinkhorn_tau": crit.sinkhorn_tau, "w_cycle": crit.w_cycle, "w_distortion": crit.w_distortion, "graph_metric": crit.graph_metric, "graph_ring_metric": crit.graph_ring_metric,
+                          "sinkhorn_iters": crit.sinkhorn_iters, "sinkhorn_tau": crit.sinkhorn_tau, "w_cycle": crit.w_cycle, "w_distortion": crit.w_distortion, "w_dirichlet": crit.w_dirichlet, "dirichlet_mode": crit.dirichlet_mode, "graph_metric": crit.graph_metric, "graph_ring_metric": crit.graph_ring_metric,
                           "ckpt": list(ckpt_paths(args.ckpt_dir, cfg["expname"], "val_best"))}))
     if dist_on:
         dist.destroy_process_group()

@@ -451,6 +451,54 @@ int dvm_distortion_term_f32(const float *pi_val, const int32_t *pi_idx, const fl
                             const float *dist_tgt /* [B,M,M] */, int B, int N, int M, int topk, float *loss /* [B] */,
                             float *g_val /* [B,N,topk], may be NULL */, void *ws, size_t ws_bytes, void *stream);
 
+/* The weighted neighbour matrix of a source shape in CSR: the operator of dvm_dirichlet_term_f32 (not in the reference).  Per
+ * batch element rowptr [N+1], col [Ecap] int32, w [Ecap] fp32 — batched as [B][..] with one Ecap — norm [B] (the energy of the
+ * shape's own coordinates under the operator, closed form) and stats [B][4] int32: owners of entries left out for an index
+ * outside [0, N); for degenerate geometry; self entries (the list builder only); entries kept (= rowptr[N]).  The entries are a
+ * multiset (duplicates of (i, j) are kept) and every entry (i, j, w) has its mirror (j, i, w).  Both builders number their
+ * CANDIDATE entries in a fixed way and a row holds its kept candidates in ASCENDING CANDIDATE NUMBER (the ordered counting sort of
+ * csrc/dvm_revlist.hip: no atomic's order reaches the arrays, and nothing is sorted by value); col / w behind rowptr[N] are -1 / 0.
+ * Everything is evaluated in float64 and rounded once; tests/dirichlet_term_ref.py states the same in numpy.
+ * dvm_mesh_laplacian_f32: verts [B,N,3] fp32, faces [F,3] int32 shared by the batch, Ecap = 6 F.  Corner c of face f, at vertex
+ * v = face[c] with a = face[(c+1)%3], b = face[(c+2)%3], u = a - v, v' = b - v: candidates 6f+2c = (a, b, w) and 6f+2c+1 = (b, a, w),
+ * w = fp32(cot / 2), cot = (u . v') / |u x v'| (negative at an obtuse corner, kept).  A face with an index outside [0, N), or whose
+ * |u x v'|^2 is 0 or not finite at any corner, is left out whole and counted.  mass [B,N] = one third of the areas of the kept
+ * faces at the vertex, summed in ascending face order; norm = 2 x the total area of the kept faces (area = |u x v'| / 2 at
+ * corner 0), which is the Dirichlet energy of the embedding itself.  A vertex without faces has an empty row.
+ * dvm_knn_laplacian_f32: xyz [B,N,3], nbr [B,N,K] int32 (dvm_knn_cdist_f32's lists, self included), Ecap = 2 N K.  Slot s of
+ * point i, j = nbr[i,s]: candidates 2(iK+s) = (i, j, w) and 2(iK+s)+1 = (j, i, w) — the operator is W + W^T, a mutual pair appears
+ * twice in each row.  mode 0 ("stretch"): w = fp32(1 / |x_i - x_j|^2), norm = half the number of kept entries (E / norm is then the
+ * mean squared local stretch); mode 1 ("uniform"): w = 1, norm = 1/2 sum w |x_i - x_j|^2 (per row in row order, the rows through
+ * the fixed tree).  Left out and counted: j == i; j outside [0, N); in mode 0 a squared distance that is 0 or not finite.
+ * Limits: N <= 24576 (one counter per row in LDS), B <= 65535, 1 <= K <= 64, 6 F and 2 N K below 2^30; outside them, DVM_EINVAL and
+ * a size query of 0, before any launch.  No float atomics, no host synchronisation, capturable, the same bits from run to run. */
+size_t dvm_mesh_laplacian_workspace_bytes(int B, int N, int F);
+int dvm_mesh_laplacian_f32(const float *verts, const int32_t *faces, int B, int N, int F, int32_t *rowptr, int32_t *col, float *w,
+                           float *norm, float *mass, int32_t *stats, void *ws, size_t ws_bytes, void *stream);
+size_t dvm_knn_laplacian_workspace_bytes(int B, int N, int K, int mode);
+int dvm_knn_laplacian_f32(const float *xyz, const int32_t *nbr, int B, int N, int K, int mode, int32_t *rowptr, int32_t *col, float *w,
+                          float *norm, int32_t *stats, void *ws, size_t ws_bytes, void *stream);
+
+/* The Dirichlet energy of a correspondence under such an operator (not in the reference): with Y = P V for the sparse top-k
+ * P [N,M] given as pi_val / pi_idx [B,N,topk] and the target's values V [B,M,C] (its coordinates: C = 3),
+ *   loss[b] = E = 1/2 sum over the entries (i, j, w) of w |y_i - y_j|^2,
+ *   g_val[i,s] = dE / d pi_val[i,s] = (2 sum over the entries of row i of w (y_i - y_j)) . V[pi_idx[i,s]]   (g_val != NULL)
+ * — the gradient exactly under the operator's structural symmetry (not checked).  V and the operator are constants.  The loss
+ * is E itself (no square root); E / norm is 1 for a map that keeps local lengths.
+ * Y has the bits of dvm_softcorr_apply_f32 (its launches, into the workspace); everything after it is accumulated in float64 in CSR
+ * order: a group of 4, 8 or 16 lanes per row, one lane per channel, every lane walks the row's entries in order; the channels
+ * are joined by a fixed butterfly, the rows by the fixed-order reduction of the other loss terms.  A slot with pi_idx outside
+ * [0, M) and an entry with col outside [0, N) contribute nothing and never become an address (the slot's g_val is 0); rowptr is
+ * clamped to [0, Ecap].  No N x N or N x M array, no LDS, no float atomics, no host synchronisation, capturable, the same bits
+ * from run to run, with or without g_val, and for a batch element alone or in a batch.  Workspace: 4 B N (C + 2 topk) + 8 B N.
+ * Limits: 1 <= topk <= 16, 1 <= C <= 16, B <= 65535, N, M <= 2^24, Ecap >= 1.  Outside them dvm_dirichlet_term_workspace_bytes
+ * returns 0 and dvm_dirichlet_term_f32 DVM_EINVAL, before any launch. */
+size_t dvm_dirichlet_term_workspace_bytes(int B, int N, int M, int topk, int C, int Ecap);
+int dvm_dirichlet_term_f32(const float *pi_val, const int32_t *pi_idx, const float *V /* [B,M,C] */, const int32_t *rowptr /* [B,N+1] */,
+                           const int32_t *col /* [B,Ecap] */, const float *w /* [B,Ecap] */, int B, int N, int M, int topk, int C,
+                           int Ecap, float *loss /* [B] */, float *g_val /* [B,N,topk], may be NULL */, void *ws, size_t ws_bytes,
+                           void *stream);
+
 /* farthest_point_sample — lib/deformation_graph_point.py:18-33 with the random
  * start index made an input.  xyz [B,N,3], start [B] -> out [B,npoint].
  * Limit: N <= 12288 (the cloud is held in LDS); a larger N is DVM_EINVAL before anything is launched — as at every entry
