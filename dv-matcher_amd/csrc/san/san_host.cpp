@@ -368,6 +368,36 @@ int main() {
         EXPECT(dvm_mesh_geodesics_f64(Dd, Ii, 100, 162, nullptr, 0, Dd, Dd, mb - 1, nullptr) == DVM_ENOSPACE);
         EXPECT(dvm_mesh_geodesics_f64(Dd, Ii, 100, 162, nullptr, 0, Dd, nullptr, 0, nullptr) == DVM_ENOSPACE);
     }
+    {
+        // dvm_eigenbasis_f64 / dvm_basis_project_f64: every limit exceeded by one, and the short workspace, before a launch
+        double *Dd = (double *)0x1000;
+        int32_t *Ii = (int32_t *)0x1000;
+        float *Ff = (float *)0x1000;
+        const int mmax = dvm_eigenbasis_max_block();
+        const size_t eb = dvm_eigenbasis_workspace_bytes(2, 642, 3840, 30, 8);
+        EXPECT(mmax == 128 && eb >= 2 * 3 * 642 * 38 * sizeof(double) && dvm_eigenbasis_workspace_bytes(1, 4096, 1, 100, mmax - 100) > 0);
+        EXPECT(dvm_eigenbasis_workspace_bytes(0, 642, 3840, 30, 8) == 0 && dvm_eigenbasis_workspace_bytes(65536, 642, 3840, 30, 8) == 0 &&
+               dvm_eigenbasis_workspace_bytes(2, (1 << 24) + 1, 3840, 30, 8) == 0 && dvm_eigenbasis_workspace_bytes(2, 642, 0, 30, 8) == 0 &&
+               dvm_eigenbasis_workspace_bytes(2, 642, 3840, 0, 8) == 0 && dvm_eigenbasis_workspace_bytes(2, 642, 3840, 30, 0) == 0 &&
+               dvm_eigenbasis_workspace_bytes(2, 642, 3840, 100, mmax - 99) == 0 && dvm_eigenbasis_workspace_bytes(2, 37, 3840, 30, 8) == 0 &&
+               dvm_eigenbasis_workspace_bytes(2, 642, 3840, 2147483647, 8) == 0);
+#define EIG(k, guard, degree, iters, tol, wsb) \
+    dvm_eigenbasis_f64(Ii, Ii, Ff, Ff, 2, 642, 3840, k, guard, degree, iters, tol, Dd, Dd, Dd, Ii, Dd, wsb, nullptr)
+        EXPECT(dvm_eigenbasis_f64(nullptr, Ii, Ff, nullptr, 2, 642, 3840, 30, 8, 20, 200, 1e-10, Dd, Dd, Dd, Ii, Dd, eb, nullptr) == DVM_EINVAL);
+        EXPECT(EIG(0, 8, 20, 200, 1e-10, eb) == DVM_EINVAL && EIG(30, 0, 20, 200, 1e-10, eb) == DVM_EINVAL);
+        EXPECT(EIG(121, 8, 20, 200, 1e-10, (size_t)1 << 40) == DVM_EINVAL);
+        EXPECT(EIG(30, 8, 0, 200, 1e-10, eb) == DVM_EINVAL && EIG(30, 8, 257, 200, 1e-10, eb) == DVM_EINVAL);
+        EXPECT(EIG(30, 8, 20, 0, 1e-10, eb) == DVM_EINVAL && EIG(30, 8, 20, 200, 0.0, eb) == DVM_EINVAL);
+        EXPECT(EIG(30, 8, 20, 200, 1e-10, eb - 1) == DVM_ENOSPACE);
+#undef EIG
+        const size_t pb = dvm_basis_project_workspace_bytes(2, 642, 30, 128);
+        EXPECT(pb >= 2 * 21 * 30 * 128 * sizeof(double) && dvm_basis_project_workspace_bytes(2, 642, 129, 3) == 0 &&
+               dvm_basis_project_workspace_bytes(2, 642, 30, 129) == 0 && dvm_basis_project_workspace_bytes(2, 0, 30, 3) == 0);
+        EXPECT(dvm_basis_project_f64(Dd, nullptr, Ff, 2, 642, 30, 129, Dd, Dd, pb, nullptr) == DVM_EINVAL);
+        EXPECT(dvm_basis_project_f64(Dd, nullptr, nullptr, 2, 642, 30, 128, Dd, Dd, pb, nullptr) == DVM_EINVAL);
+        EXPECT(dvm_basis_project_f64(Dd, nullptr, Ff, 2, 642, 30, 128, Dd, Dd, pb - 1, nullptr) == DVM_ENOSPACE);
+        EXPECT(dvm_basis_project_f64(Dd, nullptr, Ff, 2, 642, 30, 128, Dd, nullptr, 0, nullptr) == DVM_ENOSPACE);
+    }
     EXPECT(dvm_profile_read(nullptr, nullptr) == DVM_EINVAL);
     EXPECT(dvm_profile_enable(0) == DVM_EINVAL);
     // context registry: destroying with nothing registered, twice, is fine; set_overlap returns the previous value

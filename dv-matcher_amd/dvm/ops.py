@@ -1068,6 +1068,77 @@ def dirichlet_term(val, idx, V, op, grad=False):
     return _frob_term("dirichlet", (_p(val), _p(idx), _p(V), _p(rowptr), _p(col), _p(w)), (B, N, M, topk, C, col.shape[1]), (val,), grad)
 
 
+class Eigenbasis:
+    """The result of eigenbasis: evals (B,k) ascending, evecs (B,N,k) with Phi^T M Phi = I (rows of inactive vertices 0, every
+    column's largest entry positive), res (B,k) = |A y - theta y| / beta of the returned pairs — all float64 — info (B,4) int32 =
+    outer iterations, converged, inactive vertices, operator applications, and mass (B,N) fp32 or None as given."""
+    __slots__ = ("evals", "evecs", "res", "info", "mass")
+
+    def __init__(self, evals, evecs, res, info, mass):
+        self.evals, self.evecs, self.res, self.info, self.mass = evals, evecs, res, info, mass
+
+    @property
+    def k(self):
+        return self.evals.shape[1]
+
+
+def eigenbasis_max_block():
+    """The widest block k + guard dvm_eigenbasis_f64 takes (one m x m float64 matrix stays in LDS)."""
+    return int(_lib.load().dvm_eigenbasis_max_block())
+
+
+def eigenbasis(op, k, guard=None, degree=20, max_iter=200, tol=1e-10):
+    """The first k eigenpairs of L phi = lambda M phi for the GraphOperator op (M = diag(op.mass), or I without a mass) by
+    Chebyshev-filtered subspace iteration on a block of k + guard columns -> Eigenbasis (the definition is in include/dvm.h).
+    guard defaults to max(8, k // 4), clipped to the entry's limits.  The call waits for its stream (it reads the convergence
+    flags back once per outer iteration) and raises DvmError when the entry fails; a basis that has not converged within max_iter
+    is RETURNED with info[:, 1] == 0 and truthful res: the caller decides.  dvm_eigenbasis_f64."""
+    _need_gpu(op.rowptr, op.col, op.w, op.mass)
+    rowptr, col, w = _i(op.rowptr), _i(op.col), _f(op.w)
+    mass = None if op.mass is None else _f(op.mass)
+    if rowptr.dim() != 2 or col.dim() != 2 or col.shape != w.shape or col.shape[0] != rowptr.shape[0]:
+        raise ValueError("eigenbasis: the operator must have rowptr (B,N+1) and col / w (B,Ecap), got %s, %s, %s"
+                         % (tuple(rowptr.shape), tuple(col.shape), tuple(w.shape)))
+    B, N, Ecap = rowptr.shape[0], rowptr.shape[1] - 1, col.shape[1]
+    if mass is not None and tuple(mass.shape) != (B, N):
+        raise ValueError("eigenbasis: mass must be %s, got %s" % ((B, N), tuple(mass.shape)))
+    k = int(k)
+    if guard is None:
+        guard = max(1, min(max(8, k // 4), min(N, eigenbasis_max_block()) - k))
+    guard = int(guard)
+    dev = rowptr.device
+    f64 = torch.float64
+    out = Eigenbasis(_new(dev, B, max(k, 0), dtype=f64), _new(dev, B, N, max(k, 0), dtype=f64), _new(dev, B, max(k, 0), dtype=f64),
+                     _new(dev, B, 4, dtype=torch.int32), op.mass)
+    _call_ws("dvm_eigenbasis_f64", (_p(rowptr), _p(col), _p(w), _p(mass), B, N, Ecap, k, guard, int(degree), int(max_iter), float(tol),
+                                    _p(out.evals), _p(out.evecs), _p(out.res), _p(out.info)), dev, "eigenbasis",
+             "dvm_eigenbasis_workspace_bytes", B, N, Ecap, k, guard)
+    return out
+
+
+def mesh_eigenbasis(verts, faces, k, **kw):
+    """mesh_laplacian followed by eigenbasis: the Laplace-Beltrami basis of the triangle meshes (verts (B,N,3), faces (F,3))."""
+    return eigenbasis(mesh_laplacian(verts, faces), k, **kw)
+
+
+def basis_project(evecs, mass, Y):
+    """Phi^T diag(mass) Y per batch element: evecs (B,N,k) float64, mass (B,N) fp32 or None (1), Y (B,N,C) fp32 -> (B,k,C) float64,
+    k, C <= 128; summed in a fixed order, no synchronisation.  dvm_basis_project_f64."""
+    _need_gpu(evecs, mass, Y)
+    evecs, Y = evecs.detach().contiguous().double(), _f(Y)
+    mass = None if mass is None else _f(mass)
+    if evecs.dim() != 3 or Y.dim() != 3 or tuple(Y.shape[:2]) != tuple(evecs.shape[:2]):
+        raise ValueError("basis_project: evecs must be (B,N,k) and Y (B,N,C), got %s and %s" % (tuple(evecs.shape), tuple(Y.shape)))
+    B, N, k = evecs.shape
+    C = Y.shape[2]
+    if mass is not None and tuple(mass.shape) != (B, N):
+        raise ValueError("basis_project: mass must be %s, got %s" % ((B, N), tuple(mass.shape)))
+    out = _new(evecs.device, B, k, C, dtype=torch.float64)
+    _call_ws("dvm_basis_project_f64", (_p(evecs), _p(mass), _p(Y), B, N, k, C, _p(out)), evecs.device, "basis_project",
+             "dvm_basis_project_workspace_bytes", B, N, k, C)
+    return out
+
+
 def _pair_out(B, n, dev):
     """One direction's outputs of the pair calls: dict(warped, verts12, T12, losses[B,6])."""
     return dict(warped=_new(dev, B, n, 3), verts12=_new(dev, B, n, 3), T12=_new(dev, B, n, dtype=torch.int32), losses=_new(dev, B, 6))

@@ -297,6 +297,21 @@ def dirichlet_term(pval, pidx, V, op, normalize=True):
     return E / op.norm.to(E.dtype) if normalize else E
 
 
+def functional_map(pi_val, pi_idx, basis_src, basis_tgt):
+    """The functional map of a sparse correspondence (not in the reference's loss): C (B,k1,k2) = Phi1^T M1 (Pi Phi2) in float64
+    for Pi (N,M) given as pi_val / pi_idx (B,N,topk) — a soft correspondence's rows or the precise map's (bary, pi_idx) — and the
+    two shapes' ops.Eigenbasis (basis_src on the N source vertices with its mass, basis_tgt on the M target vertices).  Pi Phi2 is
+    ops.apply on Phi2 cast to fp32 (dvm_softcorr_apply_f32 takes any number of channels: no slicing), the projection
+    ops.basis_project.  A slot with an index outside [0, M) adds nothing.  Forward only: no gradient flows into pi_val."""
+    phi2 = basis_tgt.evecs
+    M = phi2.shape[1]
+    ix = pi_idx.long()
+    ok = (ix >= 0) & (ix < M)
+    val = torch.where(ok, pi_val.detach().float(), torch.zeros((), dtype=torch.float32, device=pi_val.device))
+    idx = torch.where(ok, ix, torch.zeros_like(ix)).int()
+    return ops.basis_project(basis_src.evecs, basis_src.mass, ops.apply(val, idx, phi2.float()))
+
+
 class GraphDeformLoss_Neural(nn.Module):
     partial_variant = False
 

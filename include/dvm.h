@@ -499,6 +499,52 @@ int dvm_dirichlet_term_f32(const float *pi_val, const int32_t *pi_idx, const flo
                            int Ecap, float *loss /* [B] */, float *g_val /* [B,N,topk], may be NULL */, void *ws, size_t ws_bytes,
                            void *stream);
 
+/* The Laplace-Beltrami eigenbasis of such an operator: the first k eigenpairs of L phi = lambda M phi (the reference's
+ * Tools/mesh.py::mesh.spectral, which calls a sparse shift-invert solver on the host; here everything runs on the device).
+ * Inputs: the CSR operator exactly as the two builders emit it (rowptr [B,N+1], col / w [B,Ecap], a symmetric multiset of entries,
+ * duplicates kept) and mass [B,N] fp32, or NULL for a mass of 1 everywhere.
+ * Active set: a vertex is ACTIVE when its mass is finite and > 0.  An entry whose column lies outside [0, N) or is inactive
+ * contributes nothing and never becomes an address; rowptr is clamped to [0, Ecap].
+ * Operator, in float64 from the fp32 inputs, with s_i = m_i^-1/2 on active rows:
+ *   (L x)_i = sum over the entries e of row i of w_e (x_i - x_col(e))
+ *   (A y)_i = s_i sum_e w_e (s_i y_i - s_j y_j),  j = col(e)          (A = S L S, symmetric)
+ *   phi = s * y, so that Phi^T M Phi = I; the rows of inactive vertices are 0
+ *   beta = max over active i of s_i^2 (|sum_e w_e| + sum_e |w_e|)      (a Gershgorin bound of A; cotangent weights may be negative)
+ * Outputs: evals [B,k] ascending, float64; evecs [B,N,k] float64, every column's sign fixed so that its entry of largest magnitude
+ * is positive (the lowest index wins a tie); res [B,k] float64, res_j = |A y_j - theta_j y_j|_2 / beta of the RETURNED pair;
+ * info [B,4] int32 = outer iterations run, converged (1 / 0), inactive vertices, operator applications.
+ * Convergence: an element has converged when max_j res_j <= tol.  An element that reaches max_iter returns its current Ritz pairs
+ * with info[1] = 0 and truthful res: the caller decides what a basis that has not converged is worth.
+ * Method: Chebyshev-filtered subspace iteration on a block of m = k + guard columns.  Per outer iteration: Rayleigh-Ritz (H = X^T A X,
+ * a parallel-ordered cyclic Jacobi eigensolver, eigenvalues ascending with ties by column number, X <- X Q, residuals from a fresh
+ * A X); a degree-`degree` Chebyshev filter that damps [theta_m, 1.01 beta], scaled at theta_1 (one launch per degree:
+ * Y' = a (A Y - c Y) - b X, a row's entries walked in CSR order); Cholesky-QR twice, each on the Gram matrix scaled to a unit
+ * diagonal.  A Cholesky pivot that is not a positive finite number fails the call (DVM_ELAUNCH), it does not produce NaNs.  The
+ * start block is a counter-based hash of (vertex, column) alone.  Every sum has one fixed order and there are no float atomics:
+ * an element gives the same bits alone or in a batch, and from run to run; the workgroups of a converged element leave at once.
+ * Slow case: when lambda_k and lambda_{k+guard} lie in one near-degenerate cluster the filter cannot separate them and many outer
+ * iterations are needed; move k or guard off the cluster, or raise degree / max_iter.
+ * THE ENTRY WAITS FOR ITS STREAM: like dvm_mesh_geodesics_f64 it is a dataset-time call.  It reads the B state rows back once per
+ * outer iteration and stops launching when every element is done, so it is NOT capturable.  This is its only synchronisation.
+ * An element with fewer than k + guard active vertices, or whose beta is 0 or not finite, fails the call (DVM_EINVAL) at the first
+ * read-back; the outputs are then not written.
+ * Limits: 1 <= k, guard >= 1, k + guard <= min(N, dvm_eigenbasis_max_block() = 128), 1 <= degree <= 256, max_iter >= 1, tol > 0,
+ * N <= 2^24, B <= 65535, Ecap >= 1.  Outside them DVM_EINVAL (and a size query of 0 for the sizes it takes), before any launch.
+ * Workspace: three [B,N,m] float64 blocks, 16 B N bytes of row data, min(64, ceil(N / 32)) + 3 m x m matrices per element.
+ *
+ * dvm_basis_project_f64: out[b] = Phi[b]^T diag(mass[b]) Y[b] for Phi [B,N,k] float64, Y [B,N,C] fp32, out [B,k,C] float64 (mass
+ * NULL: 1; a mass that is not a positive finite number counts as 0) — the solver's weighted tall-skinny product: rows added in
+ * ascending order within min(64, ceil(N / 32)) chunks, the chunks in ascending order.  Capturable, no synchronisation, no float
+ * atomics.  Limits: k, C <= 128, N <= 2^24, B <= 65535; outside them DVM_EINVAL and a size query of 0. */
+int    dvm_eigenbasis_max_block(void);
+size_t dvm_eigenbasis_workspace_bytes(int B, int N, int Ecap, int k, int guard);
+int    dvm_eigenbasis_f64(const int32_t *rowptr, const int32_t *col, const float *w, const float *mass /* or NULL */,
+                          int B, int N, int Ecap, int k, int guard, int degree, int max_iter, double tol,
+                          double *evals, double *evecs, double *res, int32_t *info, void *ws, size_t ws_bytes, void *stream);
+size_t dvm_basis_project_workspace_bytes(int B, int N, int k, int C);
+int    dvm_basis_project_f64(const double *evecs, const float *mass /* or NULL */, const float *Y, int B, int N, int k, int C,
+                             double *out, void *ws, size_t ws_bytes, void *stream);
+
 /* farthest_point_sample — lib/deformation_graph_point.py:18-33 with the random
  * start index made an input.  xyz [B,N,3], start [B] -> out [B,npoint].
  * Limit: N <= 12288 (the cloud is held in LDS); a larger N is DVM_EINVAL before anything is launched — as at every entry
