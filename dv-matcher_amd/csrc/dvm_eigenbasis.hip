@@ -11,36 +11,28 @@
 //
 // Kernels.  eig_op_kernel: one thread per (row, column), lanes along the contiguous 8 m-byte row; a row's entries are walked in
 // CSR order and the neighbour rows are read as whole rows: Y' = a (A Y - c Y) - b X, one launch per filter degree.
-// eig_tn_kernel: P^T diag(wt) R over a chunk of rows, a 16 x 16 thread grid with an 8 x 8 register tile each, rows staged
-// through LDS and added in ascending row order; eig_reduce_kernel adds the chunks in ascending order (the chunking depends on N
+// eig_tn_kernel (dvm_dense64.h, shared with dvm_zoomout.hip): P^T diag(wt) R over a chunk of rows, a 16 x 16 thread grid with an
+// 8 x 8 register tile each, rows staged through LDS and added in ascending row order; eig_reduce_kernel adds the chunks in ascending order (the chunking depends on N
 // alone).  eig_update_kernel: X T for an m x m T.  These two are plain FMA forms (profiles/notes_eigenbasis.md).  The dense m x m
 // steps run in one workgroup per batch element with one matrix in LDS (m <= 128: 128 KB) and the second in global memory:
 // eig_jacobi_kernel (parallel-ordered cyclic Jacobi, round-robin pairs; eigenvalues ascending, ties by column number) and
-// eig_chol_kernel (scaled Gram -> Cholesky factor with a pivot check -> the inverse factor, applied to the block by
-// eig_update_kernel).  No float atomics anywhere: every sum has one order, so an element gives the same bits alone or in a batch.
+// eig_chol_kernel (scaled Gram -> Cholesky factor with a pivot check, chol_scaled_lds of dvm_dense64.h -> the inverse factor,
+// applied to the block by eig_update_kernel).  No float atomics anywhere: every sum has one order, so an element gives the same bits alone or in a batch.
 //
 // state [B][8] int32: done, error, outer iterations, converged, inactive vertices, operator applications.  Every kernel of the
 // loop leaves at once when its element's `done` is set, so a finished element's pairs (always in block 2 after step (1)) stay.
 // The host reads the state back once per outer iteration: the entry waits for its stream and is not capturable.
-#include "dvm_common.h"
-#include <math.h>
+#include "dvm_dense64.h"
 #include <vector>
 
 namespace dvm {
 namespace {
 
-constexpr int EIG_THREADS = 256;
-constexpr int EIG_MAX_M = 128;        // block width: one m x m float64 matrix in LDS
-constexpr int EIG_MAX_N = 1 << 24;
 constexpr int EIG_MAX_DEGREE = 256;
-constexpr int EIG_MAX_CHUNKS = 64;    // row chunks of the tall-skinny products
-constexpr int EIG_TR = 8;             // rows staged per step of eig_tn_kernel
 constexpr int EIG_UR = 16;            // rows per workgroup of eig_update_kernel
 constexpr int EIG_SWEEPS = 40;
 enum { ST_DONE = 0, ST_ERR = 1, ST_ITER = 2, ST_CONV = 3, ST_INACTIVE = 4, ST_NOPS = 5, ST_WORDS = 8 };
 enum { EIG_ERR_ACTIVE = 1, EIG_ERR_PIVOT = 2, EIG_ERR_SCALE = 3 };
-
-__device__ __forceinline__ bool mass_active(float m) { return m > 0.f && m < INFINITY; }
 
 // s_i and the row's Gershgorin term (-1 on an inactive row)
 __global__ __launch_bounds__(EIG_THREADS) void eig_rows_kernel(const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
@@ -168,80 +160,6 @@ __global__ __launch_bounds__(EIG_THREADS) void eig_op_kernel(const int32_t *__re
     Yout[(size_t)b * N * m + t] = out;
 }
 
-// part[b][chunk] [ma][mb] = sum over the chunk's rows, ascending, of wt_r P[r][:]^T R[r][:]   (P [N][ma] float64, R [N][mb])
-template <typename TR_>
-__global__ __launch_bounds__(EIG_THREADS) void eig_tn_kernel(const double *__restrict__ P, const TR_ *__restrict__ R, const float *__restrict__ wt,
-                                                             int N, int ma, int mb, int rows_per_chunk, double *__restrict__ part,
-                                                             const int32_t *__restrict__ state) {
-    const int b = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x;
-    if (state && state[(size_t)b * ST_WORDS + ST_DONE]) return;
-    __shared__ double sP[EIG_TR][EIG_MAX_M], sR[EIG_TR][EIG_MAX_M];
-    const int tp = tid / 16, tq = tid % 16;
-    const int nu = (ma + 15) / 16, nv = (mb + 15) / 16;
-    double acc[8][8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u)
-#pragma unroll
-        for (int v = 0; v < 8; ++v) acc[u][v] = 0.0;
-    const int r0 = chunk * rows_per_chunk, r1 = min(r0 + rows_per_chunk, N);
-    const double *Pb = P + (size_t)b * N * ma;
-    const TR_ *Rb = R + (size_t)b * N * mb;
-    for (int base = r0; base < r1; base += EIG_TR) {
-        __syncthreads();
-        for (int e = tid; e < EIG_TR * EIG_MAX_M; e += EIG_THREADS) {
-            const int r = base + e / EIG_MAX_M, c = e % EIG_MAX_M;
-            double pv = 0.0, rv = 0.0;
-            if (r < r1) {
-                if (c < ma) {
-                    pv = Pb[(size_t)r * ma + c];
-                    if (wt) {
-                        const float mv = wt[(size_t)b * N + r];
-                        pv = mass_active(mv) ? pv * (double)mv : 0.0;
-                    }
-                }
-                if (c < mb) rv = (double)Rb[(size_t)r * mb + c];
-            }
-            sP[e / EIG_MAX_M][c] = pv;
-            sR[e / EIG_MAX_M][c] = rv;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < EIG_TR; ++r) {
-            double pv[8], rv[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) pv[u] = sP[r][tp + 16 * u];
-#pragma unroll
-            for (int v = 0; v < 8; ++v) rv[v] = sR[r][tq + 16 * v];
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-                if (u < nu) {
-#pragma unroll
-                    for (int v = 0; v < 8; ++v)
-                        if (v < nv) acc[u][v] = fma(pv[u], rv[v], acc[u][v]);
-                }
-        }
-    }
-    double *out = part + ((size_t)b * gridDim.x + chunk) * ma * mb;
-#pragma unroll
-    for (int u = 0; u < 8; ++u)
-#pragma unroll
-        for (int v = 0; v < 8; ++v) {
-            const int p = tp + 16 * u, q = tq + 16 * v;
-            if (p < ma && q < mb) out[(size_t)p * mb + q] = acc[u][v];
-        }
-}
-
-// out[b][e] = part[b][0][e] + part[b][1][e] + ..   (e < mm)
-__global__ __launch_bounds__(EIG_THREADS) void eig_reduce_kernel(const double *__restrict__ part, int nchunks, int mm, double *__restrict__ out,
-                                                                 const int32_t *__restrict__ state) {
-    const int b = blockIdx.y, e = blockIdx.x * EIG_THREADS + threadIdx.x;
-    if (state && state[(size_t)b * ST_WORDS + ST_DONE]) return;
-    if (e >= mm) return;
-    double acc = 0.0;
-    for (int c = 0; c < nchunks; ++c) acc += part[((size_t)b * nchunks + c) * mm + e];
-    out[(size_t)b * mm + e] = acc;
-}
-
 // Xout = Xin T for T [m][m]: 16 rows per workgroup in LDS, a thread owns 4 rows x columns (tq, tq + 64)
 __global__ __launch_bounds__(EIG_THREADS) void eig_update_kernel(const double *__restrict__ Xin, const double *__restrict__ T,
                                                                  double *__restrict__ Xout, int N, int m, const int32_t *__restrict__ state) {
@@ -288,45 +206,7 @@ __global__ __launch_bounds__(EIG_THREADS) void eig_chol_kernel(const double *__r
     if (state[(size_t)b * ST_WORDS + ST_DONE]) return;
     const double *Gb = G + (size_t)b * m * m;
     double *Tb = T + (size_t)b * m * m;
-    if (tid == 0) bad = 0;
-    __syncthreads();
-    if (tid < m) {
-        const double d = Gb[(size_t)tid * m + tid];
-        if (d > 0.0 && d <= 1.79e308)
-            dsc[tid] = 1.0 / sqrt(d);
-        else {
-            dsc[tid] = 0.0;
-            bad = 1;
-        }
-    }
-    __syncthreads();
-    for (int e = tid; e < m * m; e += EIG_THREADS) {
-        const int i = e / m, j = e % m;
-        // the lower triangle is used; both halves of G are averaged
-        lds[e] = 0.5 * (Gb[e] + Gb[(size_t)j * m + i]) * dsc[i] * dsc[j];
-    }
-    __syncthreads();
-    for (int j = 0; j < m; ++j) {   // (`bad` is tested behind a barrier only: every thread leaves at the same j)
-        if (tid == 0) {
-            const double p = lds[j * m + j];
-            if (p > 0.0 && p <= 1.79e308)
-                lds[j * m + j] = sqrt(p);
-            else
-                bad = 1;
-        }
-        __syncthreads();
-        if (bad) break;
-        const double piv = lds[j * m + j];
-        for (int i = j + 1 + tid; i < m; i += EIG_THREADS) lds[i * m + j] /= piv;
-        __syncthreads();
-        const int n = m - j - 1;
-        for (int e = tid; e < n * n; e += EIG_THREADS) {
-            const int i = j + 1 + e / n, c = j + 1 + e % n;
-            if (c <= i) lds[i * m + c] -= lds[i * m + j] * lds[c * m + j];
-        }
-        __syncthreads();
-    }
-    if (bad) {
+    if (!chol_scaled_lds(Gb, m, lds, dsc, &bad, 0.0)) {
         if (tid == 0) {
             state[(size_t)b * ST_WORDS + ST_ERR] = EIG_ERR_PIVOT;
             state[(size_t)b * ST_WORDS + ST_DONE] = 1;
@@ -573,11 +453,6 @@ __global__ __launch_bounds__(EIG_THREADS) void eig_output_kernel(const double *_
     }
 }
 
-static int tn_chunks(int N) {
-    const int c = (N + 4 * EIG_TR - 1) / (4 * EIG_TR);
-    return c < EIG_MAX_CHUNKS ? c : EIG_MAX_CHUNKS;
-}
-
 }  // namespace
 }  // namespace dvm
 
@@ -629,15 +504,6 @@ static const char *project_limits(int B, int N, int k, int C) {
 }
 #undef EIG_LIMIT
 
-// out [B][ma][mb] = P^T diag(wt) R through `part`
-template <typename TR_>
-static void launch_tn(const double *P, const TR_ *R, const float *wt, int B, int N, int ma, int mb, double *part, double *out, const int32_t *state,
-                      hipStream_t s) {
-    const int nch = tn_chunks(N), rpc = (N + nch - 1) / nch;
-    hipLaunchKernelGGL((eig_tn_kernel<TR_>), dim3(nch, B), dim3(EIG_THREADS), 0, s, P, R, wt, N, ma, mb, rpc, part, state);
-    hipLaunchKernelGGL(eig_reduce_kernel, dim3((ma * mb + EIG_THREADS - 1) / EIG_THREADS, B), dim3(EIG_THREADS), 0, s, part, nch, ma * mb, out, state);
-}
-
 DVM_EXPORT int dvm_eigenbasis_max_block(void) { return EIG_MAX_M; }
 
 DVM_EXPORT size_t dvm_eigenbasis_workspace_bytes(int B, int N, int Ecap, int k, int guard) {
@@ -675,7 +541,7 @@ DVM_EXPORT int dvm_eigenbasis_f64(const int32_t *rowptr, const int32_t *col, con
         const int mid = src == 0 ? 1 : 3 - src;
         const int path[3] = {src, mid, 0};
         for (int pass = 0; pass < 2; ++pass) {
-            launch_tn<double>(z.blk[path[pass]], z.blk[path[pass]], nullptr, B, N, m, m, z.part, z.H, z.state, s);
+            launch_tn<double>(z.blk[path[pass]], m, z.blk[path[pass]], m, N, nullptr, nullptr, B, N, m, m, z.part, z.H, z.state, ST_WORDS, s);
             hipLaunchKernelGGL(eig_chol_kernel, dim3(B), dim3(EIG_THREADS), lds, s, z.H, z.T, m, z.state);
             update(z.blk[path[pass]], z.T, z.blk[path[pass + 1]]);
         }
@@ -691,7 +557,7 @@ DVM_EXPORT int dvm_eigenbasis_f64(const int32_t *rowptr, const int32_t *col, con
     for (int it = 1; it <= max_iter; ++it) {
         // Rayleigh-Ritz: X in block 0 -> the rotated X in block 2, A X in block 1
         op(z.blk[0], z.blk[0], z.blk[1], -1);
-        launch_tn<double>(z.blk[0], z.blk[1], nullptr, B, N, m, m, z.part, z.H, z.state, s);
+        launch_tn<double>(z.blk[0], m, z.blk[1], m, N, nullptr, nullptr, B, N, m, m, z.part, z.H, z.state, ST_WORDS, s);
         hipLaunchKernelGGL(eig_jacobi_kernel, dim3(B), dim3(EIG_THREADS), lds, s, z.H, z.T, z.Q, z.theta, m, z.state);
         update(z.blk[0], z.Q, z.blk[2]);
         op(z.blk[2], z.blk[2], z.blk[1], -1);
@@ -753,7 +619,7 @@ DVM_EXPORT int dvm_basis_project_f64(const double *evecs, const float *mass, con
         set_error("%s: workspace too small (%zu < %zu)", who, ws ? ws_bytes : (size_t)0, need);
         return DVM_ENOSPACE;
     }
-    launch_tn<float>(evecs, Y, mass, B, N, k, C, (double *)ws, out, nullptr, (hipStream_t)stream);
+    launch_tn<float>(evecs, k, Y, C, N, nullptr, mass, B, N, k, C, (double *)ws, out, nullptr, 0, (hipStream_t)stream);
     DVM_CHECK_LAUNCH("basis_project");
     return DVM_OK;
 }

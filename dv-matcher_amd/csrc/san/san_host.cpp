@@ -398,6 +398,53 @@ int main() {
         EXPECT(dvm_basis_project_f64(Dd, nullptr, Ff, 2, 642, 30, 128, Dd, Dd, pb - 1, nullptr) == DVM_ENOSPACE);
         EXPECT(dvm_basis_project_f64(Dd, nullptr, Ff, 2, 642, 30, 128, Dd, nullptr, 0, nullptr) == DVM_ENOSPACE);
     }
+    {
+        // the ZoomOut entries (dvm_zoomout.hip): workspace carves at the largest sizes, every limit exceeded by one, null pointers
+        // and the short workspace, before a launch
+        double *Dd = (double *)0x1000;
+        int32_t *Ii = (int32_t *)0x1000;
+        float *Ff = (float *)0x1000;
+        const size_t big = (size_t)1 << 40;
+        const size_t fb0 = dvm_fmap_from_pmap_workspace_bytes(2, 642, 600, 30, 0), fb1 = dvm_fmap_from_pmap_workspace_bytes(2, 642, 600, 30, 1);
+        const size_t nb = dvm_spectral_nn_workspace_bytes(2, 642, 600, 30), tb = dvm_fmap_to_pmap_workspace_bytes(2, 642, 600, 30);
+        const size_t zb = dvm_zoomout_workspace_bytes(2, 642, 600, 6, 30, 2, 1, 1);
+        EXPECT(fb0 >= 2 * 21 * 900 * sizeof(double) && fb1 >= fb0 + 2 * 900 * sizeof(double));
+        EXPECT(nb >= 2 * 642 * 12 && tb >= nb + 2 * 600 * 30 * sizeof(double) && zb >= fb1 + tb + 2 * 900 * sizeof(double));
+        EXPECT(dvm_zoomout_workspace_bytes(65535, 1 << 24, 1 << 24, 1, 128, 1, 1, 1) > dvm_zoomout_workspace_bytes(1, 1 << 24, 1 << 24, 1, 128, 1, 1, 1));
+        int32_t plan[4] = {0, 0, 0, 0};
+        EXPECT(dvm_spectral_nn_plan(1, 4096, 4096, 128, plan) == DVM_OK && plan[0] == 64 && plan[1] == 64 && plan[2] >= 1 &&
+               plan[3] % plan[1] == 0 && (long long)plan[2] * plan[3] >= 4096 && (long long)(plan[2] - 1) * plan[3] < 4096);
+        EXPECT(dvm_spectral_nn_plan(65535, 1 << 24, 1 << 24, 128, plan) == DVM_OK && plan[2] == 1 && plan[3] >= (1 << 24));
+        EXPECT(dvm_spectral_nn_plan(1, 4096, 4096, 129, plan) == DVM_EINVAL && dvm_spectral_nn_plan(1, 4096, 4096, 30, nullptr) == DVM_EINVAL);
+        EXPECT(dvm_fmap_from_pmap_workspace_bytes(0, 642, 600, 30, 0) == 0 && dvm_fmap_from_pmap_workspace_bytes(2, 642, 600, 129, 0) == 0 &&
+               dvm_fmap_from_pmap_workspace_bytes(2, 642, 600, 30, 2) == 0 && dvm_fmap_from_pmap_workspace_bytes(2, (1 << 24) + 1, 600, 30, 0) == 0);
+        EXPECT(dvm_spectral_nn_workspace_bytes(65536, 642, 600, 30) == 0 && dvm_spectral_nn_workspace_bytes(2, 0, 600, 30) == 0 &&
+               dvm_spectral_nn_workspace_bytes(2, 642, (1 << 24) + 1, 30) == 0 && dvm_spectral_nn_workspace_bytes(2, 642, 600, 0) == 0);
+        EXPECT(dvm_fmap_to_pmap_workspace_bytes(2, 642, 0, 30) == 0 && dvm_fmap_to_pmap_workspace_bytes(2, 642, 600, 129) == 0);
+        EXPECT(dvm_zoomout_workspace_bytes(2, 642, 600, 0, 30, 2, 1, 0) == 0 && dvm_zoomout_workspace_bytes(2, 642, 600, 31, 30, 2, 1, 0) == 0 &&
+               dvm_zoomout_workspace_bytes(2, 642, 600, 6, 129, 2, 1, 0) == 0 && dvm_zoomout_workspace_bytes(2, 642, 600, 6, 30, 0, 1, 0) == 0 &&
+               dvm_zoomout_workspace_bytes(2, 642, 600, 6, 30, 2, 0, 0) == 0 && dvm_zoomout_workspace_bytes(2, 642, 600, 6, 30, 2, 1, 2) == 0);
+#define FROM(ldx, ldy, k, mode, info, wsb) dvm_fmap_from_pmap_f64(Dd, ldx, Ff, Dd, ldy, Ii, 2, 642, 600, k, mode, Dd, info, Dd, wsb, nullptr)
+        EXPECT(FROM(40, 40, 0, 0, Ii, big) == DVM_EINVAL && FROM(40, 40, 129, 0, Ii, big) == DVM_EINVAL && FROM(29, 40, 30, 0, Ii, big) == DVM_EINVAL);
+        EXPECT(FROM(40, 29, 30, 0, Ii, big) == DVM_EINVAL && FROM(40, 40, 30, 2, Ii, big) == DVM_EINVAL && FROM(40, 40, 30, 1, nullptr, big) == DVM_EINVAL);
+        EXPECT(FROM(40, 40, 30, 1, Ii, fb1 - 1) == DVM_ENOSPACE && FROM(40, 40, 30, 0, Ii, fb0 - 1) == DVM_ENOSPACE);
+#undef FROM
+        EXPECT(dvm_fmap_embed_f64(Dd, 40, Dd, 2, 600, 30, Dd, 29, nullptr) == DVM_EINVAL && dvm_fmap_embed_f64(Dd, 29, Dd, 2, 600, 30, Dd, 30, nullptr) == DVM_EINVAL);
+        EXPECT(dvm_fmap_embed_f64(Dd, 40, nullptr, 2, 600, 30, Dd, 30, nullptr) == DVM_EINVAL && dvm_fmap_embed_f64(Dd, 40, Dd, 0, 600, 30, Dd, 30, nullptr) == DVM_EINVAL);
+        EXPECT(dvm_spectral_nn_f64(Dd, 29, Dd, 40, 2, 642, 600, 30, Ii, nullptr, Dd, big, nullptr) == DVM_EINVAL);
+        EXPECT(dvm_spectral_nn_f64(Dd, 40, Dd, 40, 2, 642, 600, 30, nullptr, nullptr, Dd, big, nullptr) == DVM_EINVAL);
+        EXPECT(dvm_spectral_nn_f64(Dd, 40, Dd, 40, 2, 642, 600, 30, Ii, nullptr, Dd, nb - 1, nullptr) == DVM_ENOSPACE);
+        EXPECT(dvm_spectral_nn_f64(Dd, 40, Dd, 40, 2, 642, 600, 30, Ii, nullptr, nullptr, 0, nullptr) == DVM_ENOSPACE);
+        EXPECT(dvm_fmap_to_pmap_f64(Dd, 40, Dd, 40, nullptr, 2, 642, 600, 30, Ii, nullptr, nullptr, Dd, big, nullptr) == DVM_EINVAL);
+        EXPECT(dvm_fmap_to_pmap_f64(Dd, 40, Dd, 29, Dd, 2, 642, 600, 30, Ii, nullptr, nullptr, Dd, big, nullptr) == DVM_EINVAL);
+        EXPECT(dvm_fmap_to_pmap_f64(Dd, 40, Dd, 40, Dd, 2, 642, 600, 30, Ii, nullptr, nullptr, Dd, tb - 1, nullptr) == DVM_ENOSPACE);
+#define ZOOM(ki, kf, ks, ni, mode, wsb) dvm_zoomout_f64(Dd, 40, Ff, Dd, 40, Ii, 2, 642, 600, ki, kf, ks, ni, mode, Dd, Ii, Ii, Dd, wsb, nullptr)
+        EXPECT(ZOOM(0, 30, 2, 1, 1, big) == DVM_EINVAL && ZOOM(31, 30, 2, 1, 1, big) == DVM_EINVAL && ZOOM(6, 41, 2, 1, 1, big) == DVM_EINVAL);
+        EXPECT(ZOOM(6, 30, 0, 1, 1, big) == DVM_EINVAL && ZOOM(6, 30, 2, 0, 1, big) == DVM_EINVAL && ZOOM(6, 30, 2, 1, -1, big) == DVM_EINVAL);
+        EXPECT(dvm_zoomout_f64(Dd, 40, nullptr, Dd, 40, nullptr, 2, 642, 600, 6, 30, 2, 1, 1, Dd, Ii, Ii, Dd, big, nullptr) == DVM_EINVAL);
+        EXPECT(ZOOM(6, 30, 2, 1, 1, zb - 1) == DVM_ENOSPACE && strstr(dvm_last_error(), "dvm_zoomout_f64") != nullptr);
+#undef ZOOM
+    }
     EXPECT(dvm_profile_read(nullptr, nullptr) == DVM_EINVAL);
     EXPECT(dvm_profile_enable(0) == DVM_EINVAL);
     // context registry: destroying with nothing registered, twice, is fine; set_overlap returns the previous value

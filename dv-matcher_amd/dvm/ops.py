@@ -1139,6 +1139,169 @@ def basis_project(evecs, mass, Y):
     return out
 
 
+_FMAP_MODES = {"adjoint": 0, "lstsq": 1}
+
+
+def _f64(t):
+    """A contiguous float64 tensor without autograd history (the same object when it already is one)."""
+    if t.dtype is torch.float64 and not t.requires_grad and t.is_contiguous():
+        return t
+    return t.detach().contiguous().double()
+
+
+def _fmap_mode(solve, who):
+    if solve not in _FMAP_MODES:
+        raise ValueError("%s: solve must be 'adjoint' or 'lstsq', got %r" % (who, solve))
+    return _FMAP_MODES[solve]
+
+
+def _basis_pair(phi_src, phi_tgt, who):
+    """The two bases as contiguous float64 (B,N,K1) / (B,M,K2): a truncation to k columns is the same buffer with its row stride."""
+    phi_src, phi_tgt = _f64(phi_src), _f64(phi_tgt)
+    if phi_src.dim() != 3 or phi_tgt.dim() != 3 or phi_src.shape[0] != phi_tgt.shape[0]:
+        raise ValueError("%s: the bases must be (B,N,K) and (B,M,K), got %s and %s" % (who, tuple(phi_src.shape), tuple(phi_tgt.shape)))
+    return phi_src, phi_tgt
+
+
+def _ws_arg(lib, size_query, size_args, dev, tag, workspace_buf):
+    """(buffer, bytes) of an entry's workspace: the caller's own buffer (a capture must not allocate) or the cached one."""
+    nb = getattr(lib, size_query)(*size_args)
+    ws = workspace(nb, dev, tag) if workspace_buf is None else workspace_buf
+    return ws, (nb if workspace_buf is None else workspace_buf.numel())
+
+
+def spectral_nn_plan(B, N, M, k):
+    """How dvm_spectral_nn_f64 tiles a search: dict(tile_n, tile_m, segments, seg_len) — source rows per workgroup, target rows per
+    tile, the number of target segments and their length.  The result of a search does not depend on it."""
+    plan = (ctypes.c_int32 * 4)()
+    check(_lib.load().dvm_spectral_nn_plan(int(B), int(N), int(M), int(k), plan), "dvm_spectral_nn_plan")
+    return dict(tile_n=plan[0], tile_m=plan[1], segments=plan[2], seg_len=plan[3])
+
+
+def spectral_nn(A, E, k=None, want_dist=False):
+    """T (B,N) int32 = argmin_j |E[j,:k] - A[i,:k]|^2 in float64, every pair in the exact sequential form (sub, mul, add rounded
+    separately, coordinates ascending), ties to the lowest j, NaN distances never win; with want_dist also the winning distances
+    (B,N) float64.  A (B,N,K1), E (B,M,K2) float64; k defaults to min(K1, K2) and is at most 128.  dvm_spectral_nn_f64."""
+    _need_gpu(A, E)
+    A, E = _basis_pair(A, E, "spectral_nn")
+    B, N, M = A.shape[0], A.shape[1], E.shape[1]
+    k = min(A.shape[2], E.shape[2]) if k is None else int(k)
+    T = _new(A.device, B, N, dtype=torch.int32)
+    dmin = _new(A.device, B, N, dtype=torch.float64) if want_dist else None
+    _call_ws("dvm_spectral_nn_f64", (_p(A), A.shape[2], _p(E), E.shape[2], B, N, M, k, _p(T), _p(dmin)), A.device, "spectral_nn",
+             "dvm_spectral_nn_workspace_bytes", B, N, M, k)
+    return (T, dmin) if want_dist else T
+
+
+def fmap_from_pmap(phi_src, mass_src, phi_tgt, T, k=None, solve="adjoint", want_info=False):
+    """The functional map of a point map T (B,N) int32 into the target: C (B,k,k) float64 with phi_src[:, :k] C ~ phi_tgt[T, :k].
+    solve="adjoint": C = phi_src[:, :k]^T diag(mass_src) phi_tgt[T, :k] (mass_src (B,N) fp32 or None for 1), the weighted
+    least-squares solution for a mass-orthonormal basis; solve="lstsq": pinv(phi_src[:, :k]) phi_tgt[T, :k] by Cholesky on the normal
+    equations (the reference's pMap2fMap; mass_src is not used).  An entry of T outside [0, M) adds nothing.  want_info also returns
+    info (B,4) int32 = status (1: a Cholesky pivot was not positive and finite, C is NaN), that k, the entries of T outside
+    [0, M), 0.  No synchronisation.  dvm_fmap_from_pmap_f64."""
+    _need_gpu(phi_src, mass_src, phi_tgt, T)
+    mode = _fmap_mode(solve, "fmap_from_pmap")
+    phi_src, phi_tgt = _basis_pair(phi_src, phi_tgt, "fmap_from_pmap")
+    T = _i(T)
+    mass = None if mass_src is None else _f(mass_src)
+    B, N, M = phi_src.shape[0], phi_src.shape[1], phi_tgt.shape[1]
+    if tuple(T.shape) != (B, N) or (mass is not None and tuple(mass.shape) != (B, N)):
+        raise ValueError("fmap_from_pmap: T and mass_src must be %s, got %s and %s"
+                         % ((B, N), tuple(T.shape), None if mass is None else tuple(mass.shape)))
+    k = min(phi_src.shape[2], phi_tgt.shape[2]) if k is None else int(k)
+    C = _new(phi_src.device, B, max(k, 0), max(k, 0), dtype=torch.float64)
+    info = _new(phi_src.device, B, 4, dtype=torch.int32)
+    _call_ws("dvm_fmap_from_pmap_f64", (_p(phi_src), phi_src.shape[2], _p(mass), _p(phi_tgt), phi_tgt.shape[2], _p(T), B, N, M, k, mode,
+                                        _p(C), _p(info)), phi_src.device, "fmap_from_pmap", "dvm_fmap_from_pmap_workspace_bytes", B, N, M, k, mode)
+    return (C, info) if want_info else C
+
+
+def fmap_embed(phi_tgt, C):
+    """E (B,M,k) float64 = phi_tgt[:, :k] C^T for C (B,k,k): the target's vertices in the source's spectral coordinates (what the
+    nearest-neighbour search of fmap_to_pmap runs against).  dvm_fmap_embed_f64."""
+    _need_gpu(phi_tgt, C)
+    phi_tgt, C = _f64(phi_tgt), _f64(C)
+    if phi_tgt.dim() != 3 or C.dim() != 3 or C.shape[0] != phi_tgt.shape[0] or C.shape[1] != C.shape[2]:
+        raise ValueError("fmap_embed: phi_tgt must be (B,M,K) and C (B,k,k), got %s and %s" % (tuple(phi_tgt.shape), tuple(C.shape)))
+    B, M, k = phi_tgt.shape[0], phi_tgt.shape[1], C.shape[1]
+    E = _new(phi_tgt.device, B, M, k, dtype=torch.float64)
+    _call("dvm_fmap_embed_f64", _p(phi_tgt), phi_tgt.shape[2], _p(C), B, M, k, _p(E), k)
+    return E
+
+
+def fmap_to_pmap(phi_src, phi_tgt, C, want_dist=False, want_embedding=False):
+    """The point map of a functional map C (B,k,k): T (B,N) int32, T[i] = the target vertex whose embedded row (fmap_embed) is
+    nearest to phi_src[i, :k] (spectral_nn; the reference's fMap2pMap).  Returns T, then the winning squared distances (B,N)
+    with want_dist, then the embedding (B,M,k) with want_embedding.  No synchronisation.  dvm_fmap_to_pmap_f64."""
+    _need_gpu(phi_src, phi_tgt, C)
+    phi_src, phi_tgt = _basis_pair(phi_src, phi_tgt, "fmap_to_pmap")
+    C = _f64(C)
+    if C.dim() != 3 or C.shape[0] != phi_src.shape[0] or C.shape[1] != C.shape[2]:
+        raise ValueError("fmap_to_pmap: C must be (%d,k,k), got %s" % (phi_src.shape[0], tuple(C.shape)))
+    B, N, M, k = phi_src.shape[0], phi_src.shape[1], phi_tgt.shape[1], C.shape[1]
+    dev = phi_src.device
+    T = _new(dev, B, N, dtype=torch.int32)
+    dmin = _new(dev, B, N, dtype=torch.float64) if want_dist else None
+    E = _new(dev, B, M, k, dtype=torch.float64) if want_embedding else None
+    _call_ws("dvm_fmap_to_pmap_f64", (_p(phi_src), phi_src.shape[2], _p(phi_tgt), phi_tgt.shape[2], _p(C), B, N, M, k, _p(T), _p(dmin), _p(E)),
+             dev, "fmap_to_pmap", "dvm_fmap_to_pmap_workspace_bytes", B, N, M, k)
+    out = (T,) + ((dmin,) if want_dist else ()) + ((E,) if want_embedding else ())
+    return out if len(out) > 1 else T
+
+
+class ZoomOut:
+    """The result of zoomout: C (B,k_final,k_final) float64, T (B,N) int32 — the map that produced C — and info (B,4) int32 =
+    status (0 ok, 1 a Cholesky pivot that was not positive and finite), the k at which it failed, the entries of T0 outside
+    [0, M), the nearest-neighbour steps run.  Unpacks as (C, T, info)."""
+    __slots__ = ("C", "T", "info")
+
+    def __init__(self, C, T, info):
+        self.C, self.T, self.info = C, T, info
+
+    def __iter__(self):
+        return iter((self.C, self.T, self.info))
+
+
+def zoomout_workspace_bytes(B, N, M, k_init, k_final, k_step=1, n_inter=1, solve="adjoint"):
+    """The bytes of scratch zoomout takes for these sizes (0 outside the entry's limits): for a caller that brings its own."""
+    return int(_lib.load().dvm_zoomout_workspace_bytes(int(B), int(N), int(M), int(k_init), int(k_final), int(k_step), int(n_inter),
+                                                       _fmap_mode(solve, "zoomout")))
+
+
+def zoomout(phi_src, mass_src, phi_tgt, T0, k_init, k_final, k_step=1, n_inter=1, solve="adjoint", check=True, workspace_buf=None):
+    """ZoomOut spectral refinement of a point map T0 (B,N) int32 (the reference's zo_fmap): for k = k_init, k_init + k_step, ..
+    below k_final, n_inter times { C = fmap_from_pmap(T, k); T = fmap_to_pmap(C) }, then C = fmap_from_pmap(T, k_final) -> ZoomOut
+    (C, T, info), bit for bit what those calls give in that order.  The bases are (B,N,K) / (B,M,K) float64 with K >= k_final
+    (ops.eigenbasis' evecs); mass_src (B,N) fp32 or None.  The entry only enqueues launches (capturable with check=False and a
+    workspace_buf of zoomout_workspace_bytes bytes).  check=True reads info back (one synchronisation) and raises DvmError when an
+    element's Cholesky failed (solve="lstsq" on a rank-deficient basis); with check=False such an element returns NaN in C, its
+    last T and info[:, 0] == 1.  dvm_zoomout_f64."""
+    _need_gpu(phi_src, mass_src, phi_tgt, T0, workspace_buf)
+    mode = _fmap_mode(solve, "zoomout")
+    phi_src, phi_tgt = _basis_pair(phi_src, phi_tgt, "zoomout")
+    T0 = _i(T0)
+    mass = None if mass_src is None else _f(mass_src)
+    B, N, M = phi_src.shape[0], phi_src.shape[1], phi_tgt.shape[1]
+    if tuple(T0.shape) != (B, N) or (mass is not None and tuple(mass.shape) != (B, N)):
+        raise ValueError("zoomout: T0 and mass_src must be %s, got %s and %s"
+                         % ((B, N), tuple(T0.shape), None if mass is None else tuple(mass.shape)))
+    k_init, k_final, k_step, n_inter = int(k_init), int(k_final), int(k_step), int(n_inter)
+    dev = phi_src.device
+    out = ZoomOut(_new(dev, B, max(k_final, 0), max(k_final, 0), dtype=torch.float64), _new(dev, B, N, dtype=torch.int32),
+                  _new(dev, B, 4, dtype=torch.int32))
+    lib = _lib.load()
+    ws, nb = _ws_arg(lib, "dvm_zoomout_workspace_bytes", (B, N, M, k_init, k_final, k_step, n_inter, mode), dev, "zoomout", workspace_buf)
+    _lib.check(lib.dvm_zoomout_f64(_p(phi_src), phi_src.shape[2], _p(mass), _p(phi_tgt), phi_tgt.shape[2], _p(T0), B, N, M, k_init, k_final,
+                                   k_step, n_inter, mode, _p(out.C), _p(out.T), _p(out.info), _p(ws), nb, _stream()), "dvm_zoomout_f64")
+    if check:
+        bad = out.info[:, 0].nonzero().flatten().tolist()
+        if bad:
+            raise DvmError("zoomout: a Cholesky pivot of Phi^T Phi was not positive and finite in element(s) %s at k = %s: the truncated "
+                           "source basis is rank-deficient" % (bad, [int(out.info[b, 1]) for b in bad]))
+    return out
+
+
 def _pair_out(B, n, dev):
     """One direction's outputs of the pair calls: dict(warped, verts12, T12, losses[B,6])."""
     return dict(warped=_new(dev, B, n, 3), verts12=_new(dev, B, n, 3), T12=_new(dev, B, n, dtype=torch.int32), losses=_new(dev, B, 6))

@@ -9,6 +9,7 @@ geodesic matrices are preprocessing on the host, like the reference's own script
 `M_*.mat`) are not shipped with the reference: this module takes arrays.
 
   err = mean_geodesic_error(phi_src, phi_tgt, vts_src, vts_tgt, M_tgt)
+  err = mean_geodesic_error(.., zoomout=dict(basis_src=.., basis_tgt=.., k_init=20, k_final=100))   # ZoomOut-refined map
 """
 import numpy as np
 
@@ -91,8 +92,25 @@ def geodesic_errors_precise(face, bary, faces_tgt, vts_src, vts_tgt, M_tgt):
     return (bary[vts_src] * np.asarray(M_tgt)[corners, vts_tgt[:, None]]).sum(axis=1)
 
 
-def mean_geodesic_error(phi_src, phi_tgt, vts_src, vts_tgt, M_tgt, faces_tgt=None):
-    """The vertex map's mean error; with faces_tgt the precise map's (match_precise, geodesic_errors_precise)."""
+def match_zoomout(phi_src, phi_tgt, basis_src, basis_tgt, k_init, k_final, k_step=1, n_inter=1, solve="adjoint"):
+    """match() refined by ZoomOut (the reference's Tools/utils.py::zo_fmap as a post-process): the features' nearest-neighbour map
+    is the start map, models.loss.zoomout grows the functional map from k_init to k_final over the two shapes' Laplace-Beltrami
+    bases (dvm.ops.Eigenbasis of one shape each, e.g. ops.mesh_eigenbasis), and the returned map is the point map of the final C
+    (models.loss.pointwise_map) -> T (N,) int64, 0-based."""
+    import torch
+    from models.loss import pointwise_map, zoomout
+    T0 = torch.as_tensor(match(phi_src, phi_tgt).astype(np.int32)).cuda()[None]
+    zo = zoomout(T0, basis_src, basis_tgt, k_init, k_final, k_step=k_step, n_inter=n_inter, solve=solve)
+    return pointwise_map(zo.C, basis_src, basis_tgt)[0].cpu().numpy().astype(np.int64)
+
+
+def mean_geodesic_error(phi_src, phi_tgt, vts_src, vts_tgt, M_tgt, faces_tgt=None, zoomout=None):
+    """The vertex map's mean error; with faces_tgt the precise map's (match_precise, geodesic_errors_precise); with zoomout — a dict
+    of match_zoomout's arguments after the features (basis_src, basis_tgt, k_init, k_final, ..) — the refined vertex map's."""
+    if zoomout is not None:
+        if faces_tgt is not None:
+            raise ValueError("mean_geodesic_error: zoomout refines the vertex map; it cannot be combined with faces_tgt")
+        return float(geodesic_errors(match_zoomout(phi_src, phi_tgt, **zoomout), vts_src, vts_tgt, M_tgt).mean())
     if faces_tgt is not None:
         face, bary = match_precise(phi_src, phi_tgt, faces_tgt)
         return float(geodesic_errors_precise(face, bary, faces_tgt, vts_src, vts_tgt, M_tgt).mean())

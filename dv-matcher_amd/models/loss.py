@@ -312,6 +312,25 @@ def functional_map(pi_val, pi_idx, basis_src, basis_tgt):
     return ops.basis_project(basis_src.evecs, basis_src.mass, ops.apply(val, idx, phi2.float()))
 
 
+def zoomout(T, basis_src, basis_tgt, k_init, k_final=None, k_step=1, n_inter=1, solve="adjoint", check=True):
+    """ZoomOut spectral refinement of a hard map T (B,N) int32 into the target (the reference's Tools/utils.py::zo_fmap; not in its
+    loss) over the two shapes' ops.Eigenbasis: for k = k_init, k_init + k_step, .. below k_final the map is turned into a k x k
+    functional map (ops.fmap_from_pmap, with basis_src's mass for solve="adjoint") and back into a map (ops.fmap_to_pmap) ->
+    ops.ZoomOut (C (B,k_final,k_final) float64, the map T that produced it, info).  k_final defaults to the smaller basis.  The point
+    map of the returned C is pointwise_map(C, basis_src, basis_tgt).  Forward only.  dvm_zoomout_f64."""
+    if k_final is None:
+        k_final = min(basis_src.k, basis_tgt.k)
+    return ops.zoomout(basis_src.evecs, basis_src.mass, basis_tgt.evecs, T, k_init, k_final, k_step=k_step, n_inter=n_inter, solve=solve,
+                       check=check)
+
+
+def pointwise_map(C, basis_src, basis_tgt, want_dist=False):
+    """The point map of a functional map C (B,k,k) between two ops.Eigenbasis (the reference's fMap2pMap): T (B,N) int32, the target
+    vertex whose row of Phi_tgt[:, :k] C^T lies nearest to the source vertex's row of Phi_src[:, :k]; with want_dist also the
+    squared distances.  ops.fmap_to_pmap."""
+    return ops.fmap_to_pmap(basis_src.evecs, basis_tgt.evecs, C, want_dist=want_dist)
+
+
 class GraphDeformLoss_Neural(nn.Module):
     partial_variant = False
 

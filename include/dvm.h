@@ -545,6 +545,65 @@ size_t dvm_basis_project_workspace_bytes(int B, int N, int k, int C);
 int    dvm_basis_project_f64(const double *evecs, const float *mass /* or NULL */, const float *Y, int B, int N, int k, int C,
                              double *out, void *ws, size_t ws_bytes, void *stream);
 
+/* ZoomOut spectral refinement: maps to and from a basis (the reference's Tools/utils.py: pMap2fMap, fMap2pMap, zo_fmap /
+ * func_zm_fmap, there a cKDTree query and pinv(B1) @ B2[T] on the host per step).  float64 throughout.
+ * The source shape X has N vertices, the target Y has M.  The bases are Phi_X [B,N,K] and Phi_Y [B,M,K] float64 as
+ * dvm_eigenbasis_f64 returns them; a truncated basis Phi[:, :k] is the same buffer with its row stride (ldx, ldy = K) given as a
+ * leading dimension, so nothing is copied (element b starts at b * rows * ld).  A point map is T [B,N] int32 into Y.  C is
+ * [B,k,k] float64, row-major, with Phi_X[:, :k] C ~ Phi_Y[T, :k] (the reference's C21 = pinv(B1) @ B2[T12]).
+ *
+ * dvm_fmap_from_pmap_f64 (pMap2fMap).  G = Phi_Y[T, :k]; a row with T[i] outside [0, M) is a zero row and is counted.
+ *   mode 0 (adjoint): C = Phi_X[:, :k]^T diag(m) G, m = mass [B,N] fp32 or NULL for 1; a mass that is not positive and finite
+ *     counts as 0, as in dvm_basis_project_f64.  For an M-orthonormal basis this is the weighted least-squares solution (the form of
+ *     the ZoomOut paper).
+ *   mode 1 (lstsq): pinv(Phi_X[:, :k]) @ G through the normal equations (Phi_X^T Phi_X) C = Phi_X^T G (mass is not used).  Both
+ *     products come from the tall-skinny kernel; one workgroup per element then averages the Gram matrix' triangles, scales it to
+ *     a unit diagonal, factorises it (Cholesky, the matrix in LDS) and does two triangular solves.
+ *   The gather is fused into the product (no [N,k] copy of G is made).  Sums run in one fixed order: rows ascending within
+ *   min(64, ceil(N / 32)) chunks, the chunks ascending; no float atomics.
+ *   info [B,4] int32 = status (0 ok, 1 a Cholesky pivot that is not positive and finite: a diagonal entry of the Gram matrix
+ *   that is not positive and finite, or a pivot of the unit-diagonal matrix that is not a finite number above k 2^-52, which is
+ *   where two equal columns land), the k at which that happened, the entries of T outside [0, M), 0.  A failed element's C is
+ *   filled with NaN.
+ * dvm_fmap_embed_f64.  E [B,M,k] (row stride lde) = Phi_Y[:, :k] C^T: E_jc = sum_a Phi_Y[j,a] C[c,a], a ascending, one accumulator.
+ * dvm_spectral_nn_f64 (the k-d tree query of fMap2pMap).  A [B,N,k] with row stride lda, E [B,M,k] with row stride lde ->
+ *   T[i] = argmin_j d(i,j), d(i,j) = (..((t_0 t_0) + t_1 t_1) + ..) with t_c = E[j,c] - A[i,c], c ascending; every subtraction,
+ *   product and sum is rounded separately (no fused multiply-add), so the distance can be reproduced bit for bit.  Every pair is
+ *   evaluated in this form; there is no screen.  Ties go to the lowest j; a NaN distance counts as +inf; a row whose every
+ *   distance is +inf returns 0.  dmin [B,N] (may be NULL) is the winning d.
+ *   Tiling: a workgroup takes 64 source rows and one segment of the target, in tiles of 64 target rows; the target is cut into
+ *   `segments` segments of `seg_len` rows (a multiple of 64) and the segment winners are merged by the total order (d, j) in a
+ *   second launch.  dvm_spectral_nn_plan writes plan [4] (host memory) = source tile, target tile, segments, seg_len.  The result
+ *   does not depend on the plan.
+ * dvm_fmap_to_pmap_f64 (fMap2pMap): the two steps above with A = Phi_X[:, :k] and E in the workspace; dmin [B,N] and
+ *   E_out [B,M,k] (contiguous) may be NULL.
+ * dvm_zoomout_f64 (zo_fmap): T = T0; for k = k_init, k_init + k_step, .. < k_final: n_inter times { C = from_pmap(T, k);
+ *   T = to_pmap(C, k) }; C = from_pmap(T, k_final).  Outputs C [B,k_final,k_final], T [B,N] (the map that produced C, as in the
+ *   reference; may be T0's buffer) and info [B,4] = status, the failing k, the entries of T0 outside [0, M), the NN steps run.
+ *   The schedule is the host's and the entry only enqueues launches: no synchronisation, capturable.  An element whose Cholesky
+ *   fails sets its status, skips its remaining steps and returns C filled with NaN together with its last T; the call itself
+ *   still returns DVM_OK (the caller reads info).  The outputs are, bit for bit, those of the stage entries called in that order;
+ *   an element gives the same bits alone or in a batch, and from run to run.
+ * Limits: 1 <= k_init <= k_final <= 128 (k <= 128 at the stage entries), k <= every leading dimension, k_step >= 1, n_inter >= 1,
+ * N, M <= 2^24, B <= 65535, mode 0 or 1.  Outside them DVM_EINVAL and a size query of 0, before any launch. */
+size_t dvm_fmap_from_pmap_workspace_bytes(int B, int N, int M, int k, int mode);
+int    dvm_fmap_from_pmap_f64(const double *phi_x, int ldx, const float *mass /* or NULL */, const double *phi_y, int ldy,
+                              const int32_t *T, int B, int N, int M, int k, int mode, double *C, int32_t *info, void *ws,
+                              size_t ws_bytes, void *stream);
+int    dvm_fmap_embed_f64(const double *phi_y, int ldy, const double *C, int B, int M, int k, double *E, int lde, void *stream);
+int    dvm_spectral_nn_plan(int B, int N, int M, int k, int32_t *plan /* host, [4] */);
+size_t dvm_spectral_nn_workspace_bytes(int B, int N, int M, int k);
+int    dvm_spectral_nn_f64(const double *A, int lda, const double *E, int lde, int B, int N, int M, int k, int32_t *T,
+                           double *dmin /* or NULL */, void *ws, size_t ws_bytes, void *stream);
+size_t dvm_fmap_to_pmap_workspace_bytes(int B, int N, int M, int k);
+int    dvm_fmap_to_pmap_f64(const double *phi_x, int ldx, const double *phi_y, int ldy, const double *C, int B, int N, int M, int k,
+                            int32_t *T, double *dmin /* or NULL */, double *E_out /* or NULL */, void *ws, size_t ws_bytes,
+                            void *stream);
+size_t dvm_zoomout_workspace_bytes(int B, int N, int M, int k_init, int k_final, int k_step, int n_inter, int mode);
+int    dvm_zoomout_f64(const double *phi_x, int ldx, const float *mass /* or NULL */, const double *phi_y, int ldy, const int32_t *T0,
+                       int B, int N, int M, int k_init, int k_final, int k_step, int n_inter, int mode, double *C, int32_t *T,
+                       int32_t *info, void *ws, size_t ws_bytes, void *stream);
+
 /* farthest_point_sample — lib/deformation_graph_point.py:18-33 with the random
  * start index made an input.  xyz [B,N,3], start [B] -> out [B,npoint].
  * Limit: N <= 12288 (the cloud is held in LDS); a larger N is DVM_EINVAL before anything is launched — as at every entry
